@@ -9,12 +9,19 @@ timed region starts.  Metric = BASELINE.json's "sender query-eval ms" on the 16M
 (lower is better; strong scaling: the query is fixed, BinBundles are sharded over ranks).
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  Synthetic data: ciphertext / key limbs are uniform
-residues, BinBundle plaintexts come from the engine's documented GPU generator.
-The CPU oracle (oracle/) is used ONLY in the cpu_baseline leg (rank 0, N=1) as the timed CPU
+residues, BinBundle plaintexts come from the engine's documented GPU generator; the seeds are fixed, so
+the same arguments give the same inputs on every run.
+A plain run sets up, warms up, times the K steps and prints the line (`value` = `ms_per_step`).  `--full`
+adds every other measurement and check: the queued rate, per-kernel event profiles and the roofline,
+phase timers, one-stream ComputePowers, NTT streaming, host / adapter / wire I/O, the multi-rank gather
+check and the CPU baseline.
+`--dump-outputs DIR` writes the result ciphertexts of the last timed step to DIR (see dump_outputs).
+The CPU oracle (oracle/) is used ONLY in the cpu_baseline leg (rank 0, N=1, --full) as the timed CPU
 restatement and as the bit-exactness checker of the GPU result; it is never on the measured path.
 """
 import argparse
@@ -31,6 +38,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 GOLD = 0x9E3779B97F4A7C15
 SEED0 = 0x41505355             # "APSU"
+MAX_DUMP_BYTES = 64 << 20      # --dump-outputs: at most this many bytes of .npy data
 
 # synthetic DB shape per parameter set: BinBundles per bundle index, degrees
 WORKLOADS = {
@@ -59,12 +67,20 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="16M-4096", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-io", action="store_true", help="skip the host-input / host-output measurement (apsu_he_eval_all_ex)")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check (queued rate, profiles, roofline, phase "
+                         "timers, one-stream, NTT streaming, host / adapter / wire I/O, gather check, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result ciphertexts of the last timed step to DIR/*.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-io", action="store_true", help="with --full: skip the host-input / host-output measurement (apsu_he_eval_all_ex)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not record per-kernel HIP events in untimed steps")
     ap.add_argument("--profile-steps", type=int, default=2,
-                    help="untimed steps after the timed region whose NTT launches are bracketed by HIP events (roofline sample)")
+                    help="with --full: untimed steps after the timed region whose NTT launches are bracketed by HIP events (roofline sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    profiling = args.full and not args.no_profile
 
     import torch
     import apsu_amd
@@ -113,7 +129,7 @@ def main():
             proc_ntt["limbs"] += p[k][2]
         return p
 
-    if not args.no_profile:
+    if profiling:
         ctx.profile_enable(2)                      # HIP events around the NTT launches only (the roofline kernel)
     n, t, K, first = ctx.n, ctx.t, ctx.K, ctx.first_chain_idx
     Lf = first + 1
@@ -204,7 +220,7 @@ def main():
     # round 3 it ran with the NTT event sampling of the setup still on -- the one-stream walk -- so the first timed step was the
     # first two-stream walk ever: second-lane arena growth, job-table uploads and event creation landed inside the timed
     # region, 0.03-0.17 ms per step of `value` depending on the box, while latency_ms_sync and the phase timers were clean.)
-    if not args.no_profile:
+    if profiling:
         take_profile()                             # setup launches go to the process totals only
         ctx.profile_enable(0)
     # Setup, not warm-up: the engine builds its steady state lazily -- up to three pooled powers buffers of this shape (one is being
@@ -221,7 +237,7 @@ def main():
     # run K queries back to back): a sampled step runs ComputePowers on one stream, carries an event pair per launch
     # (~10 us of stream time each) and ends with a host wait -- +0.9 ms per step (profiles/r02_bench_sampling.txt), which
     # round 2 still charged to one timed step.
-    if not args.no_profile:
+    if profiling:
         ctx.profile_enable(0)
     if step_no[0] & 1:
         step()                                     # the timed region starts with query kind 0
@@ -238,32 +254,39 @@ def main():
         lat.append((time.perf_counter() - tl) * 1e3)
     fence()
     elapsed = time.perf_counter() - t0
-    # one result of each query kind, as the TIMED steps wrote it (the loops below overwrite the buffers)
-    timed_results = {k: out_bufs[k].clone() for k in range(min(2, args.steps))}
     latency_median_ms = sorted(lat)[len(lat) // 2]
-    # ---- the rate of QUEUED queries (never `value`): K queries back to back, nothing waited for until the end; query k + 1's
-    # ComputePowers runs on the engine's second stream next to query k's evaluation (apsu_he_set_query_overlap)
-    q_steps = max(args.steps, 10) & ~1
-    for _ in range(2):
-        step()
-    fence()
-    pipelined0 = ctx.debug_counters()["pipelined"]
-    t1 = time.perf_counter()
-    for i in range(q_steps):
-        step()
-    fence()
-    throughput_ms = (time.perf_counter() - t1) * 1e3 / q_steps
-    pipelined_steps = ctx.debug_counters()["pipelined"] - pipelined0
-    queued_results = {k: out_bufs[k].clone() for k in range(2)}     # written by the last two QUEUED (pipelined) steps
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the result table (gathered over the ranks when N > 1), before anything below
+        # reuses the buffers
+        dump_outputs(args.dump_outputs, gathered if world > 1 else out_dev, [_rows[(u[0], u[1])] for u in units])
+    timed_results = queued_results = None
+    throughput_ms = q_steps = pipelined_steps = None
+    if args.full:
+        # one result of each query kind, as the TIMED steps wrote it (the loops below overwrite the buffers)
+        timed_results = {k: out_bufs[k].clone() for k in range(min(2, args.steps))}
+        # ---- the rate of QUEUED queries (never `value`): K queries back to back, nothing waited for until the end; query k + 1's
+        # ComputePowers runs on the engine's second stream next to query k's evaluation (apsu_he_set_query_overlap)
+        q_steps = max(args.steps, 10) & ~1
+        for _ in range(2):
+            step()
+        fence()
+        pipelined0 = ctx.debug_counters()["pipelined"]
+        t1 = time.perf_counter()
+        for i in range(q_steps):
+            step()
+        fence()
+        throughput_ms = (time.perf_counter() - t1) * 1e3 / q_steps
+        pipelined_steps = ctx.debug_counters()["pipelined"] - pipelined0
+        queued_results = {k: out_bufs[k].clone() for k in range(2)}     # written by the last two QUEUED (pipelined) steps
     sampled = 0
-    if not args.no_profile:
+    if profiling:
         ctx.profile_enable(2)
         for _ in range(max(1, args.profile_steps)):
             step()
             sampled += 1
         fence()
     prof = prof_all = None
-    if not args.no_profile:
+    if profiling:
         prof = take_profile()
         # per-kernel-class breakdown from two extra, untimed steps with events around every launch
         ctx.profile_enable(1)
@@ -274,7 +297,7 @@ def main():
         ctx.profile_enable(2)
     # phase timers under the reference's STOPWATCH names (apsu_he_phase_*), default scheduling policy, untimed steps
     phases = None
-    if not args.no_profile:
+    if profiling:
         ctx.profile_enable(0)
         ctx.phase_enable(True)
         for _ in range(5):
@@ -286,7 +309,7 @@ def main():
     # the same query with ComputePowers forced onto ONE stream (untimed extra steps; `value` above is the default policy:
     # the high-power chain of the PowersDag on a second stream)
     two_stream_ms = None
-    if not args.no_profile:
+    if profiling:
         ctx.profile_enable(0)
         ctx.set_two_stream(0)
         for _ in range(2):
@@ -317,13 +340,14 @@ def main():
         "dtype": "u64", "data": "synthetic",
         "step_issue": "device-resident inputs, masks and results; a step is ONE query with a host wait at its end (query latency: the "
                       "reference serves one query per dispatcher run), consecutive steps alternate between two different queries; "
-                      "`value` = `ms_per_step` = wall time of the K timed steps / K.  `throughput_ms_per_query` is the rate of queued "
-                      "queries (K back to back, no host wait in between, query k+1's ComputePowers pipelined next to query k's "
+                      "`value` = `ms_per_step` = wall time of the K timed steps / K.  `throughput_ms_per_query` (--full) is the rate of "
+                      "queued queries (K back to back, no host wait in between, query k+1's ComputePowers pipelined next to query k's "
                       "evaluation: apsu_he_set_async_results + apsu_he_set_query_overlap) -- rounds 2-4 reported THAT as `value`",
         "latency_ms_median": round(latency_median_ms, 4),
-        "throughput_ms_per_query": round(throughput_ms, 4),
-        "throughput_steps": int(q_steps),
-        "pipelined_steps": int(pipelined_steps),             # queued steps whose ComputePowers ran next to the evaluation in front of it
+        **({"throughput_ms_per_query": round(throughput_ms, 4),
+            "throughput_steps": int(q_steps),
+            "pipelined_steps": int(pipelined_steps),         # queued steps whose ComputePowers ran next to the evaluation in front of it
+            } if args.full else {}),
         "config": {"workload": "%s: n=%d, %d bundle indices x %d BinBundles (degrees %s), %d source -> %d target powers, "
                                "ps_low_degree=%d" % (args.config, n, ctx.bundle_idx_count, wl["bundles_per_idx"],
                                                      sorted(set(wl["degrees"](D)), reverse=True), ns,
@@ -428,7 +452,7 @@ def main():
                                         "round 4: 7 bytes per coefficient of a 56-bit prime) / launch time (HIP events, the two untimed profiling steps)"}
 
     # ---- NTT streaming micro-measurement: >= 1 GiB of distinct limbs (HBM, not cache) -----------
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and profiling:
         try:
             limbs = max(1, (1 << 30) // (n * 8))
             polys = limbs // Lf
@@ -447,7 +471,7 @@ def main():
         except Exception as e:                                          # never lose the main line
             result["ntt_stream"] = {"error": str(e)}
 
-    if not args.no_profile and "roofline" in result:
+    if profiling and "roofline" in result:
         ctx.profile_enable(0)
         result["roofline"]["process_avg_launch_us"] = round(proc_ntt["ms"] * 1e3 / max(1, proc_ntt["launches"]), 2)
         result["roofline"]["process_launches"] = proc_ntt["launches"]
@@ -469,7 +493,7 @@ def main():
     # ---- the same query with HOST inputs and outputs (rank 0, N=1 only; never `value`) ----------
     # apsu_he_eval_all_ex: the in-process entry the reference's one-process caller would use (receiver_osn.cpp:290-364); the query
     # ciphertexts, masks and results cross PCIe inside the timed call.  Own copy of the DB on the same GPU (same seeds).
-    if rank == 0 and world == 1 and not args.no_profile and not args.no_host_io:
+    if rank == 0 and world == 1 and profiling and not args.no_host_io:
         try:
             M = apsu_amd.MultiContext(params_json, [local_rank])
             if rk_host is not None:
@@ -511,7 +535,7 @@ def main():
     # call from host memory into host memory with its own wait.  integration/receiver_run_query.cpp is the batched form: the sources of all
     # bundle indices in ONE apsu_he_compute_powers, all BinBundles in ONE apsu_he_eval_bundles into one host buffer.  Both are issued here
     # exactly as those files issue them (incl. the per-query upload of the relinearisation keys, HeGpu::relin_keys), host wall clock.
-    if rank == 0 and world == 1 and not args.no_profile and not args.no_host_io:
+    if rank == 0 and world == 1 and profiling and not args.no_host_io:
         try:
             from concurrent.futures import ThreadPoolExecutor
             srcs_h = [[np.ascontiguousarray(src_host[b, s]) for s in range(ns)] for b in range(ctx.bundle_idx_count)]
@@ -559,7 +583,7 @@ def main():
     # apsu_he_run_query_request: the framed QueryRequest as the reference's querier sends it (SEAL objects: seeded ciphertexts + seeded
     # RelinKeys; query.cpp:44-80) in, one framed ResultPackage per BinBundle out; parse, inflate, seed expansion on the device, the query,
     # serialise -- host wall clock.  The same source ciphertexts as above (c0 from src_host; c1 = the seed's expansion), same masks.
-    if rank == 0 and world == 1 and not args.no_profile and not args.no_host_io and rk_host is not None:
+    if rank == 0 and world == 1 and profiling and not args.no_host_io and rk_host is not None:
         try:
             from apsu_amd import seal as _seal, wire as _wire
             sc = _seal.SealContext(params_json)
@@ -599,10 +623,10 @@ def main():
             result["wire_io"] = {"error": str(e)}
 
     # ---- CPU baseline + bit-exactness (rank 0, N=1 only) --------------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(ctx, params_json, units, mine, bundles, src_hosts, rk_host, mask_hosts,
                                               unit_pos, {"timed": timed_results, "queued": queued_results}, n, t)
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and args.full:
         g = gathered.cpu()
         mine_ok = bool((g[:len(mine)] == out_dev[:len(mine)].cpu()).all())
         filled = all(bool(g[row].any()) for row in _rows.values())
@@ -612,6 +636,18 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, table, rows):
+    """Writes the result ciphertexts of one step, as the caller of the path receives them, to out_dir: row rows[i] of `table`
+    ([rows][2 polynomials][n] 64-bit residues) for the workload's i-th BinBundle.  float64 holds integers only up to 2^53, so
+    each 64-bit word is stored exactly as two halves: result = result_hi32 * 2^32 + result_lo32, each [BinBundle][2][n]."""
+    res = table[rows].cpu().numpy().view(np.uint64)
+    if 2 * res.size * 8 > MAX_DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of results exceed the %d-byte limit" % (2 * res.size * 8, MAX_DUMP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "result_hi32.npy"), (res >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(out_dir, "result_lo32.npy"), (res & np.uint64(0xFFFFFFFF)).astype(np.float64))
 
 
 def cpu_baseline(ctx, params_json, units, mine, bundles, src_hosts, rk_host, mask_hosts, unit_pos, gpu_results, n, t):

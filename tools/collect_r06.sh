@@ -19,11 +19,11 @@ if [ "$part" = base ] || [ "$part" = after ]; then
   timeout -k 10 200 python3 tools/ntt_latency.py 16M-4096 > $O/ntt_latency_16M_$tag.txt 2>&1 || { echo "ntt_latency 16M failed"; tail -3 $O/ntt_latency_16M_$tag.txt; exit 1; }
   timeout -k 10 200 python3 tools/ntt_latency.py 1M-1024-com > $O/ntt_latency_1M_$tag.txt 2>&1 || { echo "ntt_latency 1M failed"; tail -3 $O/ntt_latency_1M_$tag.txt; exit 1; }
   echo "latency tables done"
-  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_1M_$tag -- python3 bench.py --config 1M-1024-com --steps 6 --warmup 2 --no-cpu-baseline --no-host-io --no-profile > $O/trace_1M_$tag.log 2>&1 || { echo "1M trace failed"; tail -3 $O/trace_1M_$tag.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_1M_$tag -- python3 bench.py --full --config 1M-1024-com --steps 6 --warmup 2 --no-cpu-baseline --no-host-io --no-profile > $O/trace_1M_$tag.log 2>&1 || { echo "1M trace failed"; tail -3 $O/trace_1M_$tag.log; exit 1; }
   python3 tools/launch_gaps.py $O/trace_1M_$tag > $O/launch_gaps_1M_$tag.txt 2>&1
   python3 tools/query_timeline.py $O/trace_1M_$tag > $O/query_timeline_1M_$tag.txt 2>&1
   rm -rf $O/trace_1M_$tag
-  timeout -k 10 200 python3 bench.py --config 1M-1024-com --no-cpu-baseline > $O/bench_1M_$tag.json 2> $O/bench_1M_$tag.err || { echo "1M bench failed"; tail -3 $O/bench_1M_$tag.err; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --config 1M-1024-com --no-cpu-baseline > $O/bench_1M_$tag.json 2> $O/bench_1M_$tag.err || { echo "1M bench failed"; tail -3 $O/bench_1M_$tag.err; exit 1; }
   echo "1M done"
   if [ "$part" = after ]; then
     RANK_COST_REPEAT=3 timeout -k 10 400 python3 tools/rank_cost.py 16M-4096 > $O/rank_cost_16M_$tag.txt 2>&1 || { echo "rank_cost 16M failed"; tail -3 $O/rank_cost_16M_$tag.txt; exit 1; }
@@ -122,7 +122,7 @@ if [ "$part" = place2 ]; then
 fi
 if [ "$part" = bench ]; then
   bash tools/collect_profiles.sh r06 || exit 1
-  APSU_HE_SPLIT=0 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_one_stream -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-io --no-profile > $O/trace_one_stream.log 2>&1 || exit 1
+  APSU_HE_SPLIT=0 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_one_stream -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-host-io --no-profile > $O/trace_one_stream.log 2>&1 || exit 1
   python3 tools/ntt_launch_table.py $O/trace_one_stream > $O/ntt_launch_table_one_stream.txt 2>&1 || exit 1
   rm -rf $O/trace_one_stream
 fi
