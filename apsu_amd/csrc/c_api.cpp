@@ -99,6 +99,9 @@ int apsu_he_create_raw(uint64_t n, const uint64_t *coeff_modulus, int k, uint64_
 {
     return guarded([&] {
         REQUIRE(coeff_modulus && out && k > 0, "null argument");
+        // SEAL_USER_MOD_BIT_COUNT_MAX: coefficient primes of at most 60 bits (the JSON path refuses wider coeff_modulus_bits; k_mac's
+        // operand split assumes s = ceil(bits / 2) <= 30).  The 61-bit BEHZ primes are internal and never pass through here.
+        for (int j = 0; j < k; j++) REQUIRE(!(coeff_modulus[j] >> 60), "coeff_modulus prime has more than 60 bits");
         HeParams hp = HeParams::Create((size_t)n, std::vector<u64>(coeff_modulus, coeff_modulus + k), plain_modulus);
         auto c = new apsu_he_ctx;
         try { c->eng = std::make_unique<Engine>(hp, nullptr, device); } catch (...) { delete c; throw; }

@@ -739,6 +739,23 @@ void Engine::check_level(int chain_idx) const
     if (chain_idx < 0 || chain_idx > hp_.first_chain_idx) throw std::invalid_argument("chain_idx is not a data level");
 }
 
+// seal::is_data_valid_for on tier-1 ciphertext data: the kernels take canonical residues (the product-free inverse butterflies
+// wrap mod 2^64 on a word >= q, the lazy loaders bound their sums by q), so a word outside [0, q_j) is refused rather than turned
+// into a silently wrong limb.  Device operands (apsu_he_set_tier1_on_device) are not read back: keeping them canonical is the
+// caller's precondition (include/apsu_he.h).
+void Engine::check_tier1_residues(const u64 *ct, size_t polys, int chain_idx, const char *what) const
+{
+    if (tier1_device_) return;
+    const size_t n = hp_.n, L = (size_t)chain_idx + 1;
+    for (size_t p = 0; p < polys; p++)
+        for (size_t j = 0; j < L; j++) {
+            const u64 *row = ct + (p * L + j) * n, qj = hp_.key_q[j];
+            u64 bad = 0;
+            for (size_t k = 0; k < n; k++) bad |= (u64)(row[k] >= qj);
+            if (bad) throw std::invalid_argument(what);
+        }
+}
+
 // ============================================================================ arena
 u64 *Engine::ws(size_t words)
 {
@@ -938,6 +955,7 @@ void Engine::transform_to_ntt(u64 *ct, int polys, int chain_idx)
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(ct, polys, chain_idx, "transform_to_ntt: operand holds a coefficient outside [0, q)");
     const size_t w = (size_t)polys * (chain_idx + 1) * hp_.n;
     WITH_ARENA({
         u64 *d = ws(w);
@@ -953,6 +971,7 @@ void Engine::transform_from_ntt(u64 *ct, int polys, int chain_idx)
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(ct, polys, chain_idx, "transform_from_ntt: operand holds a coefficient outside [0, q)");
     const size_t w = (size_t)polys * (chain_idx + 1) * hp_.n;
     WITH_ARENA({
         u64 *d = ws(w);
@@ -968,6 +987,8 @@ void Engine::multiply_plain_ntt(const u64 *ct, const u64 *pt_ntt, u64 *out, int 
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(ct, polys, chain_idx, "multiply_plain_ntt: operand holds a coefficient outside [0, q)");
+    check_tier1_residues(pt_ntt, 1, chain_idx, "multiply_plain_ntt: NTT-form plaintext holds a coefficient outside [0, q)");
     const size_t n = hp_.n, L = chain_idx + 1, w = polys * L * n;
     WITH_ARENA({
         u64 *d = ws(w), *p = ws(L * n), *o = ws(w);
@@ -1011,6 +1032,7 @@ void Engine::multiply_plain(const u64 *ct, const u64 *pt, size_t pt_coeffs, u64 
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(ct, polys, chain_idx, "multiply_plain: operand holds a coefficient outside [0, q)");
     const size_t n = hp_.n, L = chain_idx + 1, w = polys * L * n;
     if (pt_coeffs > n) throw std::invalid_argument("plaintext has too many coefficients");
     const unsigned char mono = !tier1_device_ && is_monomial(pt, pt_coeffs) ? 1 : 0;      // (device operands: flagged by a kernel below)
@@ -1036,6 +1058,8 @@ void Engine::add(u64 *acc, const u64 *x, int polys, int chain_idx)
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(acc, polys, chain_idx, "add: operand holds a coefficient outside [0, q)");
+    check_tier1_residues(x, polys, chain_idx, "add: operand holds a coefficient outside [0, q)");
     const size_t w = (size_t)polys * (chain_idx + 1) * hp_.n;
     WITH_ARENA({
         u64 *a = ws(w), *b = ws(w);
@@ -1052,6 +1076,7 @@ void Engine::add_plain(u64 *ct, const u64 *pt, size_t pt_coeffs, int chain_idx)
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(ct, 1, chain_idx, "add_plain: operand holds a coefficient outside [0, q)");
     const size_t n = hp_.n, L = chain_idx + 1;
     if (pt_coeffs > n) throw std::invalid_argument("plaintext has too many coefficients");
     WITH_ARENA({
@@ -1071,6 +1096,8 @@ void Engine::multiply(const u64 *a, const u64 *b, u64 *out3, int chain_idx)
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(a, 2, chain_idx, "multiply: operand holds a coefficient outside [0, q)");
+    if (b != a) check_tier1_residues(b, 2, chain_idx, "multiply: operand holds a coefficient outside [0, q)");
     const size_t n = hp_.n, L = chain_idx + 1;
     const int E = hlevel(chain_idx).L + hlevel(chain_idx).nB + 1;
     const bool square = (a == b);
@@ -1098,6 +1125,7 @@ void Engine::relinearize(u64 *ct3, const RelinKeys &rk, int chain_idx)
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(ct3, 3, chain_idx, "relinearize: operand holds a coefficient outside [0, q)");
     if (!hp_.using_keyswitching) throw std::logic_error("parameters do not support key switching");
     const size_t n = hp_.n, L = chain_idx + 1;
     WITH_ARENA({
@@ -1114,6 +1142,7 @@ void Engine::mod_switch_to_next(u64 *ct, int polys, int chain_idx)
     Enter g(this);
     TIER1_SLOTS();
     check_level(chain_idx);
+    check_tier1_residues(ct, polys, chain_idx, "mod_switch_to_next: operand holds a coefficient outside [0, q)");
     if (chain_idx == 0) throw std::invalid_argument("end of modulus switching chain reached");
     const size_t n = hp_.n, L = chain_idx + 1;
     WITH_ARENA({
@@ -2755,6 +2784,8 @@ void Engine::multiply_sized(const u64 *a, int sa, const u64 *b, int sb, u64 *out
     TIER1_SLOTS();
     check_level(chain_idx);
     if (sa < 2 || sb < 2 || sa + sb - 1 > (int)CT_SIZE_MAX) throw std::invalid_argument("invalid size");      // Ciphertext::resize
+    check_tier1_residues(a, (size_t)sa, chain_idx, "multiply_sized: operand holds a coefficient outside [0, q)");
+    if (b != a) check_tier1_residues(b, (size_t)sb, chain_idx, "multiply_sized: operand holds a coefficient outside [0, q)");
     const size_t n = hp_.n, L = chain_idx + 1;
     const size_t E = hlevel(chain_idx).L + hlevel(chain_idx).nB + 1;
     const bool square = (a == b && sa == sb);

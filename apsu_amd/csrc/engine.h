@@ -265,6 +265,8 @@ private:
                        u64 **defer_moddown = nullptr);
     bool fuse_tail_ = true;           // eval_patstock: the last key switch's mod-down inside the epilogue kernel (APSU_HE_FUSE_TAIL=0: its own launch)
     void check_level(int chain_idx) const;
+    // tier-1 caller data (host operands): every word of limb j of each of `polys` polynomials at chain_idx below q_j, else invalid_argument
+    void check_tier1_residues(const u64 *ct, size_t polys, int chain_idx, const char *what) const;
     // BEHZ steps 4-8 for operands given as ext-NTT polynomials [size][E][n]; out: [sa + sb - 1][L][n], coefficient form
     void d_multiply_sized(const u64 *ea, int sa, const u64 *eb, int sb, u64 *out, int chain_idx);
     // ComputePowers / eval / eval_patstock without key switching and with products (ciphertexts of any size): plain

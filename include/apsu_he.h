@@ -86,7 +86,8 @@ int apsu_he_abi_version(void);
 /* ---- lifetime ------------------------------------------------------------------------------ */
 /* PSUParams::Load(json) + CryptoContext(params) (psu_params.cpp:290-374, crypto_context.h:32-37) */
 int apsu_he_create(const char *psu_params_json, int device, apsu_he_ctx **out);
-/* SEALContext from explicit primes (tests / tier-1 use without PSUParams) */
+/* SEALContext from explicit primes (tests / tier-1 use without PSUParams).  Each prime has at most 60 bits
+ * (SEAL_USER_MOD_BIT_COUNT_MAX), as coeff_modulus_bits of the JSON form: a wider one is APSU_HE_INVALID_ARGUMENT. */
 int apsu_he_create_raw(uint64_t poly_modulus_degree, const uint64_t *coeff_modulus, int coeff_modulus_size,
                        uint64_t plain_modulus, int device, apsu_he_ctx **out);
 int apsu_he_destroy(apsu_he_ctx *ctx);
@@ -344,7 +345,10 @@ int apsu_he_set_query_overlap(apsu_he_ctx *ctx, int mode);
  * addresses -- and the calls return with their work queued on the context's stream instead of copying in, waiting and copying out:
  * a caller that replaces Evaluator methods one by one (receiver_osn.cpp:422-478, bin_bundle.cpp:143-170) keeps its ciphertexts in
  * HBM across calls and pays no host round trip per method.  Ordering and completion as for apsu_he_set_async_results:
- * calls on one context execute in call order; apsu_he_sync / apsu_he_stream give the completion point.  Default off. */
+ * calls on one context execute in call order; apsu_he_sync / apsu_he_stream give the completion point.  Default off.
+ * Precondition: host operands of the tier-1 calls are checked like seal::is_data_valid_for (every word of limb j below q_j, else
+ * APSU_HE_INVALID_ARGUMENT); device operands are NOT read back for that check -- every word the caller hands over must already be a
+ * canonical residue of its limb's prime, or the result is undefined (the kernels take canonical input). */
 int apsu_he_set_tier1_on_device(apsu_he_ctx *ctx, int on);
 int apsu_he_sync(apsu_he_ctx *ctx);
 int apsu_he_stream(apsu_he_ctx *ctx, void **hip_stream);

@@ -21,6 +21,12 @@ FAMILIES = [
     (8192, [50, 50, 50, 38, 30], 0, 26),    # 256M-4096
     (16384, [58, 58, 50, 40], 0, 22),       # beyond the shipped sets: one 1024-thread workgroup per limb, 144 KiB of LDS
     (32768, [58, 56, 50, 44], 0, 20),       # SEAL's largest ring: a limb is two LDS-resident halves around one global radix-2 stage
+    # the generic BEHZ kernels (k_behz_ext<0, 0>, k_behz_finish<0, 0>, k_behz_finish_sum<0, false>): nB = L + 1 (a 41-bit t next to
+    # 60-bit primes: 32 + bits(t) + bits(Q) >= 61 (L + 1), params.cpp make_level), and L >= 5 data limbs up to the largest chain the
+    # context accepts (8 primes: 7 data limbs)
+    (8192, [60, 60, 60], 0, 41),
+    (16384, [50, 50, 50, 50, 50, 50], 0, 22),
+    (16384, [48, 48, 48, 48, 48, 48, 48, 48], 0, 22),
 ]
 
 
@@ -41,6 +47,30 @@ def pair(request):
     G = apsu_amd.HeContext(n=n, coeff_modulus=C.q, plain_modulus=C.t)
     yield C, G
     G.close()
+
+
+def test_generic_behz_families_take_the_generic_shapes():
+    """the three families above do reach the generic BEHZ shapes at their first data level (the oracle's nB is that level's)"""
+    C = ref.RefContext(8192, [60, 60, 60], 0, 41)
+    assert C.first + 1 == 2 and C.nB == C.first + 2
+    C = ref.RefContext(16384, [50] * 6, 0, 22)
+    assert C.first + 1 == 5
+    C = ref.RefContext(16384, [48] * 8, 0, 22)
+    assert C.first + 1 == 7 and C.nB == 7
+
+
+def test_too_many_limbs_are_refused():
+    """more primes than the engine's limb arrays hold: ValueError at context creation, never a device error"""
+    for K in (9, 10):
+        q = ref.RefContext(16384, [48] * 8, 0, 22).q
+        extra = []
+        cand = min(q) - 2 * 16384
+        while len(extra) < K - 8:
+            if all(pow(w, cand - 1, cand) == 1 for w in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37)) and cand not in q:
+                extra.append(cand)
+            cand -= 2 * 16384
+        with pytest.raises(ValueError):
+            apsu_amd.HeContext(n=16384, coeff_modulus=list(q) + extra, plain_modulus=ref.RefContext(16384, [48] * 8, 0, 22).t)
 
 
 def test_ntt_roundtrip_and_order(pair):

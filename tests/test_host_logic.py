@@ -721,3 +721,69 @@ def test_database_file_reader_refuses_malformed_files_without_a_gpu(tmp_path):
             opened(data, name)
     with pytest.raises(apsu_amd.ApsuHeError):
         apsu_amd.DbFile(str(tmp_path / "missing"))
+
+
+def _eighth_61_bit_prime(n):
+    """a 61-bit NTT prime of the BEHZ base's shape (the first hits of the downward scan are the context's own auxiliary primes)"""
+    q, found = ((1 << 61) - 1) // (2 * n) * (2 * n) + 1, 0
+    while True:
+        if all(pow(w, q - 1, q) == 1 for w in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37)):
+            found += 1
+            if found == 8:
+                return q
+        q -= 2 * n
+
+
+@pytest.mark.parametrize("n,bits", [(4096, 36), (4096, 50), (4096, 60), (8192, 50), (8192, 56), (8192, 58), (8192, 59), (8192, 60),
+                                    (4096, 61), (8192, 61), (16384, 60)])
+def test_workgroup_emulation_at_whole_polynomial_extremes(emu, n, bits):
+    """the pass functions on polynomials whose EVERY residue is an extreme (q - 1, both k_mac halves at their maximum, alternating
+    extremes), in both per-lane forms where the ring has two, for every modulus class (narrow, the 58 / 59 boundary at n = 8192, wide,
+    the 61-bit wide-near BEHZ primes): forward and inverse against the oracle (or, for 61 bits, against the other form and the round
+    trip), and the tensor loader with lazy input (ntt_lazy_bound_q) against canonical input and the exact product"""
+    import edge_values as ev
+    logn = n.bit_length() - 1
+    emu.emu_ntt_limb_c.argtypes = [C.c_int, C.c_int, C.c_uint64, u64p, C.c_int, C.c_int]
+    emu.emu_intt_tensor_limb_c.argtypes = [C.c_int, C.c_uint64, u64p, u64p, u64p, u64p, u64p, C.c_int, C.c_int]
+    if bits == 61:
+        q, c = _eighth_61_bit_prime(n), None
+    else:
+        c = ref.RefContext(n, [bits], 65537 if (65537 - 1) % (2 * n) == 0 else 0, 0 if (65537 - 1) % (2 * n) == 0 else 20)
+        q = c.q[0]
+    forms = [16] + ([8] if n in (4096, 8192) else [])
+    lazy_runs = 0
+    for kind in ("q-1", "max_halves", "alternating"):
+        x = ev.fill(kind, q, n)
+        for inverse in (0, 1):
+            want = None
+            if c is not None:
+                want = x.copy().reshape(1, 1, n)
+                (c.transform_from_ntt if inverse else c.transform_to_ntt)(want, 0)
+                want = want.reshape(-1)
+            for co in forms:
+                a = x.copy()
+                assert emu.emu_ntt_limb_c(logn, inverse, q, a.ctypes.data_as(u64p), n // co, co) == 0, emu.emu_last_error()
+                assert int(a.max()) < q, (kind, inverse, co)
+                if want is None:
+                    want = a
+                assert (a == want).all(), (hex(q), kind, inverse, co)
+                back = a.copy()
+                assert emu.emu_ntt_limb_c(logn, 1 - inverse, q, back.ctypes.data_as(u64p), n // co, co) == 0
+                assert (back == x).all(), (hex(q), kind, inverse, co)
+        # tensor loader: every operand word at the extreme, one product and the two-product cross term
+        for cross in (False, True):
+            null = C.POINTER(C.c_uint64)()
+            exact = (np.array([(int(v) * int(v) * (2 if cross else 1)) % q for v in x], dtype=np.uint64))
+            assert emu.emu_ntt_limb(logn, 1, C.c_uint64(q), exact.ctypes.data_as(u64p), n // 16) == 0
+            for co in forms:
+                for lazy in (0, 0x100):
+                    out = np.zeros(n, dtype=np.uint64)
+                    rc = emu.emu_intt_tensor_limb_c(logn, q, x.ctypes.data_as(u64p), x.ctypes.data_as(u64p),
+                                                    x.ctypes.data_as(u64p) if cross else null, x.ctypes.data_as(u64p) if cross else null,
+                                                    out.ctypes.data_as(u64p), n // co, co | lazy)
+                    if rc in (-2, -3):                    # no fold reduction for q / no room for lazy input: the engine does not take it
+                        continue
+                    assert rc == 0, emu.emu_last_error()
+                    lazy_runs += 1 if lazy else 0
+                    assert (out == exact).all(), (hex(q), kind, cross, co, lazy)
+    assert lazy_runs > 0 or bits in (36, 58, 59, 60)
