@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include "modmath.h"
 #include "ntt_core.h"
+#include "ntt_form.h"
 #include "blake2x.h"
 
 namespace apsu_he {
@@ -115,18 +116,14 @@ struct MacJob {
 // tabs[modmap[g % period] & NTT_MAP_MASK].  An inverse transform of a limb whose map entry carries NTT_MAP_RAW writes its
 // result WITHOUT the final twist n^-1 psi^-k and without the final reduction (consumers: the unrolled BEHZ finish kernels).
 constexpr int NTT_MAP_RAW = 1 << 30, NTT_MAP_MASK = NTT_MAP_RAW - 1;
-// latency_limbs (round 6): a launch of at most that many limbs takes the LATENCY form of the transform (8 coefficients per lane, twice the
-// waves per limb; ntt_core.h plan_k) where the ring size has one (n = 8192, 4096); 0 = always the throughput form; NTT_FORM_AUTO = the
-// measured crossover per ring size and kind of launch (kernels.hip, ntt_use_latency_form).  Same bits.
-constexpr size_t NTT_FORM_AUTO = ~(size_t)0;
-// narrow_only: the caller knows that every modulus of the launch is narrow (ntt_is_narrow: the data primes of every shipped parameter set) --
-// large forward launches then take the 8-coefficient form compiled for 8 waves per SIMD (NTT_FORM_AUTO only).
+// latency_limbs (NTT_FORM_AUTO, 0 or a limb count) and narrow (every modulus of the launch is a narrow data prime) choose the form of
+// the transform through ntt_form (ntt_form.h).  Same bits in every form.
 void launch_ntt(int logn, bool inverse, u64 *data, size_t count, const NttTable *tabs, const int *modmap,
-                int period, hipStream_t st, size_t latency_limbs = 0, bool narrow_only = false);
+                int period, hipStream_t st, size_t latency_limbs, bool narrow);
 // forward NTT of limbs gathered from src[g] (reduced into the table's modulus on load), written to data + g*n.
 // nored: the caller has checked ntt_gather_nored_ok for every (source, target) pair of the launch: no reduction on load
 void launch_ntt_gather(int logn, const u64 *const *src, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
-                       hipStream_t st, bool nored = false, size_t latency_limbs = 0);
+                       hipStream_t st, bool nored, size_t latency_limbs, bool narrow);
 // out = a (.) b per limb; a:[batch][polys][L][n], b:[batch][L][n] (b_batch_stride may be 0)
 void launch_dyadic_plain(const DevLevel *lv, const u64 *ct, const u64 *pt, u64 *out, int polys, size_t n, int batch,
                          size_t pt_batch_stride, hipStream_t st);

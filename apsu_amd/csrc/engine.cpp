@@ -179,7 +179,7 @@ Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), 
         if (const char *v = std::getenv("APSU_HE_SEED_EXPAND_HOST")) seed_expand_host_ = std::atoi(v) != 0;
         // The latency form of the LDS-resident transform (ntt_core.h plan_k, c = 8): a limb's workgroup has twice the waves, so a launch
         // that gives a CU at most one limb hides that limb's LDS turnarounds and table loads behind three other waves per SIMD.
-        // Crossovers: kernels.hip, ntt_use_latency_form (tools/microbench/ntt_forms.hip, profiles/r06_ntt_forms_n8192.txt / _n4096.txt).
+        // Crossovers: ntt_form.h, ntt_form (tools/microbench/ntt_forms.hip, profiles/r06_ntt_forms_n8192.txt / _n4096.txt).
         ntt_latency_limbs_ = NTT_FORM_AUTO;
         data_primes_narrow_ = true;
         for (int j = 0; j < hp_.K; j++) data_primes_narrow_ = data_primes_narrow_ && ntt_is_narrow(hp_.key_q[j], hp_.logn);
@@ -898,12 +898,10 @@ bool Engine::mac_kara(int lvl, uint32_t mean_cnt) const
     return true;
 }
 
-void Engine::d_ntt(u64 *data, size_t count, const int *modmap, int period, bool inverse)
+void Engine::d_ntt(u64 *data, size_t count, const int *modmap, int period, bool inverse, bool narrow)
 {
     PROF(inverse ? P_NTT_INV : P_NTT_FWD, count);
-    // (launches over the data primes alone -- map_ct() and its suffixes -- may take the narrow-moduli build, kernels.hip launch_ntt)
-    const bool narrow_only = data_primes_narrow_ && modmap >= map_ct() && (modmap - map_ct()) + period <= hp_.K;
-    launch_ntt(hp_.logn, inverse, data, count, tabs(), modmap, period, st_, ntt_latency_limbs_, narrow_only);
+    launch_ntt(hp_.logn, inverse, data, count, tabs(), modmap, period, st_, ntt_latency_limbs_, narrow);
 }
 
 bool Engine::d_relinearize(u64 *ct3, size_t ct_stride, int batch, const RelinKeys &rk, int chain_idx, u64 *ext_out, int n_ext, u64 **defer_moddown)
@@ -923,7 +921,7 @@ bool Engine::d_relinearize(u64 *ct3, size_t ct_stride, int batch, const RelinKey
         bool nored = hp_.logn <= 14;
         for (int I = 0; I <= L && nored; I++) nored = ntt_gather_nored_ok(hp_.key_q[I < L ? I : hp_.K - 1], max_src, hp_.logn);
         PROF(P_NTT_FWD, src.size());
-        launch_ntt_gather(hp_.logn, upload_jobs(src), tdec, src.size(), tabs(), map_ks(chain_idx), (L + 1) * L, st_, nored, ntt_latency_limbs_);
+        launch_ntt_gather(hp_.logn, upload_jobs(src), tdec, src.size(), tabs(), map_ks(chain_idx), (L + 1) * L, st_, nored, ntt_latency_limbs_, data_primes_narrow_);
     }
     u64 *acc = ws((size_t)batch * 2 * (L + 1) * n);
     // the inverse transform leaves its twist to the mod-down kernel, whose own constants absorb it (unrolled sizes)
@@ -932,7 +930,7 @@ bool Engine::d_relinearize(u64 *ct3, size_t ct_stride, int batch, const RelinKey
     // (the inner product formed by the inverse transform's load, the way the BEHZ tensor product is, was measured in round 3:
     //  2 % SLOWER on the whole query -- six operand streams per output and tdec read twice; tools/microbench/intt_ks_experiment.hip)
     { PROFW(P_KEYSWITCH, (size_t)batch * n * ((size_t)L * (L + 1) + 2 * (L + 1))); launch_ks_inner(dkey(), L, tdec, rk.data.u(), acc, n, batch, st_); }
-    d_ntt(acc, (size_t)batch * 2 * (L + 1), amap, L + 1, true);
+    d_ntt(acc, (size_t)batch * 2 * (L + 1), amap, L + 1, true, false);
     if (defer_moddown) {
         *defer_moddown = raw ? acc : nullptr;
         if (raw) return false;                                   // the caller's epilogue kernel takes it from here
@@ -1108,11 +1106,11 @@ void Engine::multiply(const u64 *a, const u64 *b, u64 *out3, int chain_idx)
         if (!square) H2D(in + 2 * L * n, b, 2 * L * n);
         u64 *ext = ws((size_t)nop * 2 * E * n);
         { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, in, L * n, 1, ext, n, nop * 2, st_); }
-        d_ntt(ext, (size_t)nop * 2 * E, map_ext(chain_idx), E, false);
+        d_ntt(ext, (size_t)nop * 2 * E, map_ext(chain_idx), E, false, false);
         u64 *d = ws((size_t)3 * E * n), *o = ws(3 * L * n);
         std::vector<TensorJob> tj{ TensorJob{ ext, square ? ext : ext + (size_t)2 * E * n, d } };
         { PROF(P_TENSOR, 0); launch_tensor(dlevel(chain_idx), upload_jobs(tj), n, 1, st_); }
-        d_ntt(d, (size_t)3 * E, map_ext_fin(chain_idx), E, true);        // the finish below applies the twist where it can
+        d_ntt(d, (size_t)3 * E, map_ext_fin(chain_idx), E, true, false);        // the finish below applies the twist where it can
         std::vector<FinishJob> fj{ FinishJob{ d, o, 1, 0 } };
         { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, upload_jobs(fj), false, n, 1, st_); }
         D2H(out3, o, 3 * L * n);
@@ -1451,7 +1449,7 @@ void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *
                 if (npar > 0) {
                     // (parents that came out of a key switch were extended by its mod-down kernel: run.ext_done)
                     if (run.ext_done != (int)d - 1) { PROFW(P_BEHZ_EXT, (size_t)npar * nb * 2 * n * (Lf + Ef)); launch_behz_ext(dlevel(first), hlevel(first).L, hlevel(first).nB, slot_ptr(pl.s0, 0), slot_w, 2, ext_ptr(pl.s0, 0), n, npar * nb, st_); }
-                    d_ntt(ext_ptr(pl.s0, 0), (size_t)npar * nb * 2 * Ef, map_ext(first), (int)Ef, false);
+                    d_ntt(ext_ptr(pl.s0, 0), (size_t)npar * nb * 2 * Ef, map_ext(first), (int)Ef, false, false);
                 }
                 const auto &cl = s.levels[d];
                 const int nn = cl.s1 - cl.s0;
@@ -1471,7 +1469,7 @@ void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *
                     launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Ef, Ef * n, nullptr, 0, tabs(), map_ext_fin(first), (int)Ef, st_, ntt_latency_limbs_);
                 } else {
                     { PROF(P_TENSOR, 0); launch_tensor(dlevel(first), upload_jobs(tj), n, (int)tj.size(), st_); }
-                    d_ntt(dbuf, (size_t)nn * nb * 3 * Ef, map_ext_fin(first), (int)Ef, true);
+                    d_ntt(dbuf, (size_t)nn * nb * 3 * Ef, map_ext_fin(first), (int)Ef, true, false);
                 }
                 { PROFW(P_BEHZ_FINISH, fj.size() * 3 * n * (Ef + Lf)); launch_behz_finish(dlevel(first), hlevel(first).L, hlevel(first).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
                 if (hp_.using_keyswitching && nn > 0) {                                                                          // :431
@@ -1525,7 +1523,7 @@ void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *
             bool nored = hp_.logn <= 14;
             for (size_t j = 0; j < Lf && nored; j++) nored = ntt_gather_nored_ok(hp_.key_q[j], hp_.key_q[j], hp_.logn);
             PROF(P_NTT_FWD, srcp.size());
-            launch_ntt_gather(hp_.logn, upload_jobs(srcp), pw->low.u(), srcp.size(), tabs(), map_ct(), (int)Lf, st_, nored, ntt_latency_limbs_);
+            launch_ntt_gather(hp_.logn, upload_jobs(srcp), pw->low.u(), srcp.size(), tabs(), map_ct(), (int)Lf, st_, nored, ntt_latency_limbs_, data_primes_narrow_);
         } else if (do_low) {
             convert(s.low_powers, low_target, pw->low.u());
             d_ntt_ct(pw->low.u(), (size_t)pw->n_low * nb * 2, low_target, false);                      // :467,475
@@ -1534,7 +1532,7 @@ void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *
             convert(s.high_powers, high, pw->high.u());
             // derived form used by eval_patstock's ct x ct products and coefficient-form plaintext products
             { PROFW(P_BEHZ_EXT, (size_t)pw->n_high * nb * 2 * n * (Lh + Eh)); launch_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, pw->high.u(), Lh * n, 1, pw->hext.u(), n, (int)(pw->n_high * nb * 2), st_); }
-            d_ntt(pw->hext.u(), (size_t)pw->n_high * nb * 2 * Eh, map_ext(high), (int)Eh, false);
+            d_ntt(pw->hext.u(), (size_t)pw->n_high * nb * 2 * Eh, map_ext(high), (int)Eh, false, false);
         }
     }
 }
@@ -1830,7 +1828,7 @@ std::unique_ptr<Bundle> Engine::build_bundle(uint32_t bundle_idx, uint32_t cache
         // BatchEncoder::encode (bin_bundle.cpp:409): slot permutation, then inverse negacyclic NTT mod t
         u64 *raw = ws((size_t)(degree + 1) * n);
         launch_scatter_slots(poly, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), raw, n, (int)degree + 1, st_);
-        d_ntt(raw, degree + 1, map_ct() + tid, 1, true);
+        d_ntt(raw, degree + 1, map_ct() + tid, 1, true, false);
         finish_bundle(*b, raw);
         sync();
     });
@@ -2104,7 +2102,7 @@ void Engine::mask_generate_impl(uint32_t count, u64 *masks_dev, u64 *values_host
         { PROF(P_OTHER, 0); fill(vals, (size_t)count * n); }                                                       // :248-251
         // BatchEncoder::encode (:271): slot permutation, inverse negacyclic NTT mod t
         { PROF(P_OTHER, 0); launch_scatter_slots(vals, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), masks_dev, n, (int)count, st_); }
-        d_ntt(masks_dev, count, map_ct() + tid, 1, true);
+        d_ntt(masks_dev, count, map_ct() + tid, 1, true, false);
         if (blocks_host) {                                                                                        // :256-266
             u64 *blk = ws((size_t)count * items * 2);
             { PROF(P_OTHER, 0); launch_pack_blocks(vals, n, items, felts, plain_modulus_len(hp_.t), blk, (int)count, st_); }
@@ -2141,14 +2139,14 @@ void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_devi
         std::vector<CtJob> cj;
         for (uint32_t i = 0; i < count; i++) cj.push_back(CtJob{ ct + ((size_t)i * 2 + 1) * n, v + (size_t)i * n });
         { PROF(P_OTHER, 0); launch_copy_jobs(upload_jobs(cj), n, (int)count, st_); }
-        d_ntt(v, count, map_ct(), 1, false);
+        d_ntt(v, count, map_ct(), 1, false, data_primes_narrow_);
         { PROF(P_OTHER, 0); launch_dyadic_plain(dlevel(0), v, sk, v, 1, n, (int)count, 0, st_); }
-        d_ntt(v, count, map_ct(), 1, true);
+        d_ntt(v, count, map_ct(), 1, true, data_primes_narrow_);
         // x = c0 + v; m = round(t x / q_0) mod t
         u64 *pt = ws((size_t)count * n);
         { PROF(P_OTHER, 0); launch_decrypt_round(ct, 2 * n, v, hp_.key_q[0], hp_.t, pt, n, (int)count, st_); }
         // BatchEncoder::decode: forward NTT mod t, slot gather
-        d_ntt(pt, count, map_ct() + tid, 1, false);
+        d_ntt(pt, count, map_ct() + tid, 1, false, false);
         u64 *vals = ws((size_t)count * n);
         { PROF(P_OTHER, 0); launch_gather_slots(pt, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), vals, n, (int)count, st_); }
         if (blocks_host) {                                                                      // sender_osn.cpp:684-690
@@ -2403,7 +2401,7 @@ void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
     const int *imap_dev = upload_jobs(g.imap);
     if (side_tp) HIP_CHECK(hipEventRecord(ev_fork_, st_));    // behind k_mac (the powers and the database are read-only from here on)
     else if (g.n_term) { PROF(P_MAC, (uint64_t)g.n_term * (g.term_packed ? packed_row_bits(hp_.key_q[Ll - 1]) : 64)); launch_term_product(dlevel(low), g.term_jobs, g.n_term, n, (int)Ll - 1, (u32)(Ll * n), (u32)n, g.term_packed, st_); }
-    d_ntt(inner, g.imap.size() - n_vlast, imap_dev, (int)g.imap.size(), true);               // :268,297,320,333
+    d_ntt(inner, g.imap.size() - n_vlast, imap_dev, (int)g.imap.size(), true, false);               // :268,297,320,333
     if (side_tp) HIP_CHECK(hipEventRecord(ev_intt_, st_));
 
     // Side lane (round 4).  Two pieces of the evaluation hang off nothing that follows on the main stream: the sums of the
@@ -2437,7 +2435,7 @@ void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
         HIP_CHECK(hipStreamWaitEvent(st_, ev_fork_, 0));
         if (side_tp) {
             launch_term_product(dlevel(low), g.term_jobs, g.n_term, n, (int)Ll - 1, (u32)(Ll * n), (u32)n, g.term_packed, st_);
-            d_ntt(vlast, n_vlast, imap_dev + (g.imap.size() - n_vlast), (int)n_vlast, true);
+            d_ntt(vlast, n_vlast, imap_dev + (g.imap.size() - n_vlast), (int)n_vlast, true, false);
         }
         if (async_high) HIP_CHECK(hipStreamWaitEvent(st_, pw.high_ready, 0));   // the cf sums read the high powers (second stream)
         { auto mj = group_mac(cs); launch_mac(dlevel(high), (int)Lh, upload_jobs(mj), n, (int)mj.size(), st_, mac_kara(high, mac_mean_cnt(mj)), mac_packed(mj)); }
@@ -2468,7 +2466,7 @@ void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
         }
         { PROFW(P_BEHZ_EXT, (size_t)NI * 2 * n * (Lh + Eh)); launch_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, innerh, Lh * n, 1, ext, n, NI * 2, st_); }
     }
-    d_ntt(ext, (size_t)NI * 2 * Eh, map_ext(high), (int)Eh, false);
+    d_ntt(ext, (size_t)NI * 2 * Eh, map_ext(high), (int)Eh, false, false);
     if (async_high) HIP_CHECK(hipStreamWaitEvent(st_, pw.high_ready, 0));
     u64 *result = ws((size_t)Bs * 3 * Lh * n);                                                  // :238-240
     // The products of one BinBundle are summed (:273,303).  Each keeps its own rounding (note N1), but only
@@ -2523,7 +2521,7 @@ void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
                                tabs(), upload_jobs(dmap), (int)dmap.size(), st_, ntt_latency_limbs_);
         } else {
             { PROFW(P_TENSOR, ((size_t)NI * 4 * Eh + (size_t)NI * 3 * Lh + (size_t)Bs * 3 * (Eh - Lh)) * n); launch_tensor_sum(dlevel(high), (int)Eh, upload_jobs(tj), n, (int)tj.size(), 0, st_); }
-            d_ntt(dq, dmap.size(), upload_jobs(dmap), (int)dmap.size(), true);
+            d_ntt(dq, dmap.size(), upload_jobs(dmap), (int)dmap.size(), true, false);
         }
         { PROFW(P_BEHZ_FINISH, ((size_t)NI * 3 * Lh + (size_t)Bs * 3 * (Eh - Lh) + (size_t)Bs * 3 * Lh) * n); launch_behz_finish_sum(dlevel(high), hlevel(high).L, hlevel(high).nB, upload_jobs(fj), n, (int)fj.size(), st_); }
     } else {
@@ -2555,7 +2553,7 @@ void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
             launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Eh, Eh * n, nullptr, 0, tabs(), map_ext_fin(high), (int)Eh, st_, ntt_latency_limbs_);
         } else {
             if (!tj.empty()) { PROF(P_TENSOR, 0); launch_tensor(dlevel(high), upload_jobs(tj), n, (int)tj.size(), st_); }
-            d_ntt(dbuf, (size_t)NI * 3 * Eh, map_ext_fin(high), (int)Eh, true);
+            d_ntt(dbuf, (size_t)NI * 3 * Eh, map_ext_fin(high), (int)Eh, true, false);
         }
         { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(high), hlevel(high).L, hlevel(high).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
         { PROF(P_BEHZ_FINISH, 0); launch_sum_jobs(dlevel(high), (int)Lh, upload_jobs(sj), 3, n, Bs, st_); }
@@ -2771,7 +2769,7 @@ void Engine::d_multiply_sized(const u64 *ea, int sa, const u64 *eb, int sb, u64 
     if (so3 > so) HIP_CHECK(hipMemsetAsync(d + (size_t)so * E * n, 0, (size_t)(so3 - so) * E * n * sizeof(u64), st_));
     std::vector<TensorConvJob> tj{ TensorConvJob{ ea, eb, d, sa, sb } };
     { PROF(P_TENSOR, 0); launch_tensor_conv(dlevel(chain_idx), upload_jobs(tj), n, 1, st_); }
-    d_ntt(d, (size_t)so3 * E, map_ext_fin(chain_idx), (int)E, true);
+    d_ntt(d, (size_t)so3 * E, map_ext_fin(chain_idx), (int)E, true, false);
     std::vector<FinishJob> fj;
     for (int t = 0; t < so3 / 3; t++) fj.push_back(FinishJob{ d + (size_t)3 * t * E * n, o + (size_t)3 * t * L * n, 1, 0 });
     { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
@@ -2796,7 +2794,7 @@ void Engine::multiply_sized(const u64 *a, int sa, const u64 *b, int sb, u64 *out
         const int np = sa + (square ? 0 : sb);
         u64 *ext = ws((size_t)np * E * n);
         { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, in, L * n, 1, ext, n, np, st_); }
-        d_ntt(ext, (size_t)np * E, map_ext(chain_idx), (int)E, false);
+        d_ntt(ext, (size_t)np * E, map_ext(chain_idx), (int)E, false, false);
         u64 *o = ws((size_t)(sa + sb - 1) * L * n);
         d_multiply_sized(ext, sa, square ? ext : ext + (size_t)sa * E * n, sb, o, chain_idx);
         D2H(out, o, (size_t)(sa + sb - 1) * L * n);
@@ -2859,7 +2857,7 @@ std::unique_ptr<Powers> Engine::compute_powers_nks(const uint32_t *bundle_indice
         auto extend = [&](int s0, int s1) {
             if (s1 <= s0) return;
             { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(0), hlevel(0).L, hlevel(0).nB, coef_ptr(s0, 0), S * n, (int)S, ext_ptr(s0, 0), n, (s1 - s0) * nb, st_); }
-            d_ntt(ext_ptr(s0, 0), (size_t)(s1 - s0) * nb * S * E, map_ext(0), (int)E, false);
+            d_ntt(ext_ptr(s0, 0), (size_t)(s1 - s0) * nb * S * E, map_ext(0), (int)E, false, false);
         };
         extend(s.levels[0].s0, s.levels[0].s1);
         for (size_t d = 1; d < s.levels.size(); d++) {
@@ -2971,7 +2969,7 @@ void Engine::eval_bundles_nks(const Bundle *const *bundles, int count, const Pow
                     const int sa = (int)s_in[i], sb = (int)sz(i * h), so = sa + sb - 1;
                     u64 *iext = ws((size_t)sa * E * n), *prod = ws((size_t)so * n);
                     { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(0), hlevel(0).L, hlevel(0).nB, inner[i], n, 1, iext, n, sa, st_); }
-                    d_ntt(iext, (size_t)sa * E, map_ext(0), (int)E, false);
+                    d_ntt(iext, (size_t)sa * E, map_ext(0), (int)E, false, false);
                     d_multiply_sized(iext, sa, hext_ptr(i, bs), sb, prod, 0);
                     { PROF(P_OTHER, 0); launch_add(dlevel(0), result, prod, so, n, 1, st_); }
                     arena_off_ = mark;

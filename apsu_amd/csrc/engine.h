@@ -253,8 +253,9 @@ private:
     const int *map_ksacc_raw(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ksacc_raw_.p()) + chain_idx * (DMAXL + 1); }
 
     // device-pointer building blocks
-    void d_ntt(u64 *data, size_t count, const int *modmap, int period, bool inverse);
-    void d_ntt_ct(u64 *data, size_t polys, int chain_idx, bool inverse) { d_ntt(data, polys * (chain_idx + 1), map_ct(), chain_idx + 1, inverse); }
+    // narrow: all moduli named by the map are data primes and all of them are narrow (ntt_form takes the launch's form from it)
+    void d_ntt(u64 *data, size_t count, const int *modmap, int period, bool inverse, bool narrow);
+    void d_ntt_ct(u64 *data, size_t polys, int chain_idx, bool inverse) { d_ntt(data, polys * (chain_idx + 1), map_ct(), chain_idx + 1, inverse, data_primes_narrow_); }
     // BFV multiply of `njobs` (a, b) pairs given as ext-NTT operands; writes size-3 results
     // ext_out / n_ext: the first n_ext ciphertexts also get their BEHZ extension written to ext_out[b][2][E][n] (fused into
     // the mod-down; returns false when the level has no unrolled extension and the caller must run launch_behz_ext itself)

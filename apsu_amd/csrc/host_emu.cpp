@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ntt_core.h"
+#include "ntt_form.h"
 #include "blake2x.h"
 #include "params.h"
 #include "powers_dag.h"
@@ -209,6 +210,13 @@ int emu_pick_pooled_buffer(const unsigned char *entries, int count, int inputs_r
     std::vector<PoolEntryState> st(count);
     for (int i = 0; i < count; i++) st[i] = PoolEntryState{ (entries[i] & 1) != 0, (entries[i] & 2) != 0, (entries[i] & 4) != 0 };
     return pick_pooled_buffer(st.data(), st.size(), inputs_ready != 0);
+}
+
+// The launch form of the transform (ntt_form.h), for tabulation by tests/test_host_logic.py: out = threads, coeffs_per_lane, min_waves, split
+void emu_ntt_form(int logn, int kind, size_t limbs, size_t latency_limbs, int narrow, int *out)
+{
+    const NttForm f = ntt_form(logn, (NttKind)kind, limbs, latency_limbs, narrow != 0);
+    out[0] = f.threads; out[1] = f.coeffs_per_lane; out[2] = f.min_waves; out[3] = f.split;
 }
 
 // PSUParams::Load + HeParams: returns derived numbers for comparison with the oracle

@@ -26,9 +26,8 @@ void throw_hip(hipError_t e, const char *file, int line);
 // twiddles are the big transform's for that half (W_h[2^s + b] = W[2^(s+1) + h 2^s + b]); the first Cooley-Tukey stage runs in
 // front (k_ntt_first_stage), the inverse's last stage and twist behind (k_ntt_last_stage), so the inverse halves are always RAW.
 // C: coefficients per lane -- 16 (T = n / 16 threads per limb: the throughput form) or 8 (T = n / 8: the latency form of round 6 for
-// launches that leave CUs idle, ntt_core.h plan_k; chosen by the launch wrappers from the number of limbs, same bits).
-// MINW: waves per SIMD the register budget must admit (8: <= 64 VGPRs, two 1024-thread workgroups per CU at n = 8192 -- large forward launches
-// over narrow moduli only: -4 ... -7 %, tools/microbench/ntt_forms.hip; slower on 61-bit limbs and on every inverse)
+// launches that leave CUs idle, ntt_core.h plan_k; same bits).  MINW: waves per SIMD the register budget must admit (8: <= 64 VGPRs, two
+// 1024-thread workgroups per CU at n = 8192).  Which form a launch takes: ntt_form (ntt_form.h).
 template <int LOGN, bool INV, int T, int C = 16, int MINW = 4>
 __global__ __launch_bounds__(T, MINW) void k_ntt(u64 *__restrict__ data, const NttTable *__restrict__ tabs,
                                            const int *__restrict__ modmap, int period, int split)
@@ -57,7 +56,6 @@ constexpr int EW_T = 256;                                         // threads per
 // ---- poly_modulus_degree 32768: one radix-2 stage over global memory around two half-size LDS-resident transforms.
 // Tables: entry 2 m (+ 1) of `tabs`; its ninv / ninv_q fields carry the first stage's twiddle psi^brv(1) (the twist comes
 // from the scale table), dit and scale are the full-size tables.
-constexpr int SPLIT_LOGN = 15;
 // forward, first Cooley-Tukey stage: (x_j, x_{j + n/2}) -> (x + w y, x - w y), canonical; src != nullptr: limb g is gathered from
 // src[g] (residues of another modulus, reduced on load: the key switch's decomposition)
 __global__ __launch_bounds__(EW_T) void k_ntt_first_stage(const u64 *const *__restrict__ src, u64 *__restrict__ data, size_t n,
@@ -102,8 +100,7 @@ __global__ __launch_bounds__(EW_T) void k_ntt_last_stage(u64 *__restrict__ data,
 
 // Forward NTT of gathered limbs: limb g is read from src[g] (residues of another modulus, reduced on load) and written
 // to data + g*N.  Replaces the decompose kernel of the key switch (App. B10): out[I][J] = NTT_I(c2_J mod m_I).
-// MINW: waves per SIMD the register budget must admit (8: <= 64 VGPRs, two 1024-thread workgroups per CU at n = 8192 -- the form large
-// gathered launches take since round 6: -1 ... -5 %, tools/microbench/ntt_forms.hip)
+// C, MINW: as k_ntt (ntt_form picks them)
 template <int LOGN, int T, int C = 16, int MINW = 4>
 __global__ __launch_bounds__(T, MINW) void k_ntt_gather(const u64 *const *__restrict__ src, u64 *__restrict__ data,
                                                   const NttTable *__restrict__ tabs, const int *__restrict__ modmap, int period, int nored)
@@ -121,52 +118,6 @@ __global__ __launch_bounds__(T, MINW) void k_ntt_gather(const u64 *const *__rest
         else ntt_body<LOGN, false, NTT_NARROW, T, 1, false, SrcPlain, true, false, 0, -1, C>(lds, p, tab, tid, src[g]);
     } else if (tab.wide_d4) ntt_body<LOGN, false, NTT_WIDE_NEAR, T, 1, false, SrcPlain, true, false, 0, -1, C>(lds, p, tab, tid, src[g]);
     else ntt_body<LOGN, false, NTT_WIDE, T, 1, false, SrcPlain, true, false, 0, -1, C>(lds, p, tab, tid, src[g]);
-}
-
-// Which form of the workgroup does a launch of `count` limbs take?  latency_limbs: 0 = always 16 coefficients per lane; NTT_FORM_AUTO = the
-// crossovers measured with tools/microbench/ntt_forms.hip (profiles/r06_ntt_forms_n8192.txt, _n4096.txt): at n = 8192 a limb's
-// 1024-thread workgroup wins while a CU gets at most one limb (<= 256 limbs: -3 ... -16 %) and loses above (+2 ... +20 %); at n = 4096
-// (512 threads, registers for 7-8 waves per SIMD) the forward, gathered and tensor-on-load transforms win at every size (-2 ... -24 %), the
-// plain inverse up to 1 024 limbs; any other value = that threshold for every kind (tests force either form with it).
-enum NttKind { NTT_KIND_FORWARD, NTT_KIND_INVERSE, NTT_KIND_GATHER, NTT_KIND_TENSOR };
-static bool ntt_use_latency_form(int logn, NttKind kind, size_t count, size_t latency_limbs)
-{
-    if (!plan_has_latency_form(logn) || latency_limbs == 0) return false;
-    if (latency_limbs != NTT_FORM_AUTO) return count <= latency_limbs;
-    if (logn == 13) return count <= 256;
-    return kind != NTT_KIND_INVERSE || count <= 1024;
-}
-
-void launch_ntt_gather(int logn, const u64 *const *src, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
-                       hipStream_t st, bool nored, size_t latency_limbs)
-{
-    const int nr = nored ? 1 : 0;
-    if (!count) return;
-    if (ntt_use_latency_form(logn, NTT_KIND_GATHER, count, latency_limbs)) {
-        if (logn == 13) hipLaunchKernelGGL((k_ntt_gather<13, 1024, 8>), dim3((unsigned)count), dim3(1024), 0, st, src, data, tabs, modmap, period, nr);
-        else hipLaunchKernelGGL((k_ntt_gather<12, 512, 8>), dim3((unsigned)count), dim3(512), 0, st, src, data, tabs, modmap, period, nr);
-        KERNEL_CHECK();
-        return;
-    }
-    if (latency_limbs == NTT_FORM_AUTO && logn == 13) {          // large gathered launches at n = 8192: 8 coefficients per lane at 8 waves per SIMD
-        hipLaunchKernelGGL((k_ntt_gather<13, 1024, 8, 8>), dim3((unsigned)count), dim3(1024), 0, st, src, data, tabs, modmap, period, nr);
-        KERNEL_CHECK();
-        return;
-    }
-    if (logn == 15) {                                            // first stage gathers and reduces, the halves are plain transforms
-        const size_t n = (size_t)1 << 15;
-        hipLaunchKernelGGL(k_ntt_first_stage, dim3((unsigned)((n / 2 + EW_T - 1) / EW_T), (unsigned)count), dim3(EW_T), 0, st, src, data, n, tabs, modmap, period);
-        hipLaunchKernelGGL((k_ntt<14, false, 1024>), dim3((unsigned)(count * 2)), dim3(1024), 0, st, data, tabs, modmap, period, 1);
-        KERNEL_CHECK();
-        return;
-    }
-#define G_CASE(LN, T) case LN: hipLaunchKernelGGL((k_ntt_gather<LN, T>), dim3((unsigned)count), dim3(T), 0, st, src, data, tabs, modmap, period, nr); break;
-    switch (logn) {
-    G_CASE(14, 1024) G_CASE(13, 512) G_CASE(12, 256) G_CASE(11, 128) G_CASE(10, 64) G_CASE(8, 64) G_CASE(6, 64)
-    default: throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
-    }
-#undef G_CASE
-    KERNEL_CHECK();
 }
 
 // Inverse NTT of dyadic tensor products (BEHZ steps 4 + 5 in one launch): workgroup g < n_tensor owns output limb
@@ -235,77 +186,83 @@ __global__ __launch_bounds__(T, 4) void k_intt_tensor(const TensorJob *__restric
     }
 }
 
+// ---- launch forms: ntt_form (ntt_form.h) picks the form, one instantiation table per kernel family holds the kernels it may pick
+// (inverse / forward kernel of each form; the tables' order is the kernels' order in the code object)
+template <class K> struct NttFormRow { int logn, threads, coeffs_per_lane, min_waves; K inv, fwd; };
+template <class K, size_t R> static K form_kernel(const NttFormRow<K> (&rows)[R], int logn, const NttForm &f, bool inverse)
+{
+    for (const NttFormRow<K> &r : rows)
+        if (r.logn == logn && r.threads == f.threads && r.coeffs_per_lane == f.coeffs_per_lane && r.min_waves == f.min_waves && (inverse ? r.inv : r.fwd))
+            return inverse ? r.inv : r.fwd;
+    throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
+    return nullptr;
+}
+
+using GatherKernel = void (*)(const u64 *const *, u64 *, const NttTable *, const int *, int, int);
+#define ROW(LN, T, C, W) { LN, T, C, W, nullptr, k_ntt_gather<LN, T, C, W> },
+static const NttFormRow<GatherKernel> k_ntt_gather_forms[] = {
+    ROW(13, 1024, 8, 4) ROW(12, 512, 8, 4) ROW(13, 1024, 8, 8)
+    ROW(14, 1024, 16, 4) ROW(13, 512, 16, 4) ROW(12, 256, 16, 4) ROW(11, 128, 16, 4) ROW(10, 64, 16, 4) ROW(8, 64, 16, 4) ROW(6, 64, 16, 4)
+};
+#undef ROW
+using TensorKernel = void (*)(const TensorJob *, int, size_t, size_t, u64 *, const NttTable *, const int *, int);
+#define ROW(LN, T, C) { LN, T, C, 4, k_intt_tensor<LN, T, C>, nullptr },
+static const NttFormRow<TensorKernel> k_intt_tensor_forms[] = {
+    ROW(13, 1024, 8) ROW(12, 512, 8)
+    ROW(14, 1024, 16) ROW(13, 512, 16) ROW(12, 256, 16) ROW(11, 128, 16) ROW(10, 64, 16) ROW(8, 64, 16) ROW(6, 64, 16)
+};
+#undef ROW
+using NttKernel = void (*)(u64 *, const NttTable *, const int *, int, int);
+#define ROW(LN, T, C, W) { LN, T, C, W, k_ntt<LN, true, T, C, W>, k_ntt<LN, false, T, C, W> },
+static const NttFormRow<NttKernel> k_ntt_forms[] = {
+    ROW(14, 1024, 16, 4)
+    { 13, 1024, 8, 8, nullptr, k_ntt<13, false, 1024, 8, 8> },
+    ROW(13, 1024, 8, 4) ROW(12, 512, 8, 4)
+    ROW(13, 512, 16, 4) ROW(12, 256, 16, 4) ROW(11, 128, 16, 4) ROW(10, 64, 16, 4) ROW(8, 64, 16, 4) ROW(6, 64, 16, 4)
+};
+#undef ROW
+
+// n = 32768 (f.split): the halves run in f's form at n = 16384; src != nullptr: the first stage gathers and reduces
+static void launch_ntt_split(bool inverse, const u64 *const *src, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
+                             hipStream_t st, const NttForm &f)
+{
+    const size_t n = (size_t)1 << SPLIT_LOGN;
+    const dim3 g((unsigned)((n / 2 + EW_T - 1) / EW_T), (unsigned)count);
+    if (!inverse) hipLaunchKernelGGL(k_ntt_first_stage, g, dim3(EW_T), 0, st, src, data, n, tabs, modmap, period);
+    hipLaunchKernelGGL(form_kernel(k_ntt_forms, SPLIT_LOGN - 1, f, inverse), dim3((unsigned)(count * 2)), dim3(f.threads), 0, st,
+                       data, tabs, modmap, period, 1);
+    if (inverse) hipLaunchKernelGGL(k_ntt_last_stage, g, dim3(EW_T), 0, st, data, n, tabs, modmap, period);
+}
+
+void launch_ntt(int logn, bool inverse, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
+                hipStream_t st, size_t latency_limbs, bool narrow)
+{
+    if (!count) return;
+    const NttForm f = ntt_form(logn, inverse ? NTT_KIND_INVERSE : NTT_KIND_FORWARD, count, latency_limbs, narrow);
+    if (f.split) launch_ntt_split(inverse, nullptr, data, count, tabs, modmap, period, st, f);
+    else hipLaunchKernelGGL(form_kernel(k_ntt_forms, logn, f, inverse), dim3((unsigned)count), dim3(f.threads), 0, st, data, tabs, modmap, period, 0);
+    KERNEL_CHECK();
+}
+
+void launch_ntt_gather(int logn, const u64 *const *src, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
+                       hipStream_t st, bool nored, size_t latency_limbs, bool narrow)
+{
+    if (!count) return;
+    const NttForm f = ntt_form(logn, NTT_KIND_GATHER, count, latency_limbs, narrow);
+    if (f.split) launch_ntt_split(false, src, data, count, tabs, modmap, period, st, f);
+    else hipLaunchKernelGGL(form_kernel(k_ntt_gather_forms, logn, f, false), dim3((unsigned)count), dim3(f.threads), 0, st, src, data, tabs, modmap, period, nored ? 1 : 0);
+    KERNEL_CHECK();
+}
+
 void launch_intt_tensor(int logn, const TensorJob *jobs, int njobs, int limbs, size_t src_ps, u64 *plain, size_t n_plain,
                         const NttTable *tabs, const int *modmap, int period, hipStream_t st, size_t latency_limbs)
 {
     const size_t n_tensor = (size_t)njobs * 3 * limbs;
     const size_t count = (n_tensor / 3 + 7) / 8 * 24 + n_plain;                 // the XCD-aware order pads the pairs to blocks of eight
     if (!(n_tensor + n_plain)) return;
-    if (ntt_use_latency_form(logn, NTT_KIND_TENSOR, n_tensor + n_plain, latency_limbs)) {
-        if (logn == 13) hipLaunchKernelGGL((k_intt_tensor<13, 1024, 8>), dim3((unsigned)count), dim3(1024), 0, st, jobs, limbs, src_ps, n_tensor, plain, tabs, modmap, period);
-        else hipLaunchKernelGGL((k_intt_tensor<12, 512, 8>), dim3((unsigned)count), dim3(512), 0, st, jobs, limbs, src_ps, n_tensor, plain, tabs, modmap, period);
-        KERNEL_CHECK();
-        return;
-    }
-#define T_CASE(LN, T) case LN: hipLaunchKernelGGL((k_intt_tensor<LN, T>), dim3((unsigned)count), dim3(T), 0, st, jobs, limbs, src_ps, n_tensor, plain, tabs, modmap, period); break;
-    switch (logn) {
-    T_CASE(14, 1024) T_CASE(13, 512) T_CASE(12, 256) T_CASE(11, 128) T_CASE(10, 64) T_CASE(8, 64) T_CASE(6, 64)
-    default: throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
-    }
-#undef T_CASE
-    KERNEL_CHECK();
-}
-
-template <int LOGN, int T>
-static void launch_ntt_t(bool inverse, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
-                         hipStream_t st, int split = 0)
-{
-    if (inverse) hipLaunchKernelGGL((k_ntt<LOGN, true, T>), dim3((unsigned)count), dim3(T), 0, st, data, tabs, modmap, period, split);
-    else hipLaunchKernelGGL((k_ntt<LOGN, false, T>), dim3((unsigned)count), dim3(T), 0, st, data, tabs, modmap, period, split);
-}
-
-static void launch_ntt_split(bool inverse, const u64 *const *src, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
-                             hipStream_t st)
-{
-    const size_t n = (size_t)1 << SPLIT_LOGN;
-    const dim3 g((unsigned)((n / 2 + EW_T - 1) / EW_T), (unsigned)count);
-    if (!inverse) hipLaunchKernelGGL(k_ntt_first_stage, g, dim3(EW_T), 0, st, src, data, n, tabs, modmap, period);
-    launch_ntt_t<SPLIT_LOGN - 1, 1024>(inverse, data, count * 2, tabs, modmap, period, st, 1);
-    if (inverse) hipLaunchKernelGGL(k_ntt_last_stage, g, dim3(EW_T), 0, st, data, n, tabs, modmap, period);
-}
-
-void launch_ntt(int logn, bool inverse, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
-                hipStream_t st, size_t latency_limbs, bool narrow_only)
-{
-    if (!count) return;
-    if (latency_limbs == NTT_FORM_AUTO && logn == 13 && !inverse && narrow_only && count > 256) {
-        // large forward launches whose moduli are all narrow (the data primes): 8 coefficients per lane at 8 waves per SIMD
-        hipLaunchKernelGGL((k_ntt<13, false, 1024, 8, 8>), dim3((unsigned)count), dim3(1024), 0, st, data, tabs, modmap, period, 0);
-        KERNEL_CHECK();
-        return;
-    }
-    if (ntt_use_latency_form(logn, inverse ? NTT_KIND_INVERSE : NTT_KIND_FORWARD, count, latency_limbs)) {   // 8 coefficients per lane
-        if (logn == 13) {
-            if (inverse) hipLaunchKernelGGL((k_ntt<13, true, 1024, 8>), dim3((unsigned)count), dim3(1024), 0, st, data, tabs, modmap, period, 0);
-            else hipLaunchKernelGGL((k_ntt<13, false, 1024, 8>), dim3((unsigned)count), dim3(1024), 0, st, data, tabs, modmap, period, 0);
-        } else {
-            if (inverse) hipLaunchKernelGGL((k_ntt<12, true, 512, 8>), dim3((unsigned)count), dim3(512), 0, st, data, tabs, modmap, period, 0);
-            else hipLaunchKernelGGL((k_ntt<12, false, 512, 8>), dim3((unsigned)count), dim3(512), 0, st, data, tabs, modmap, period, 0);
-        }
-        KERNEL_CHECK();
-        return;
-    }
-    switch (logn) {
-    case SPLIT_LOGN: launch_ntt_split(inverse, nullptr, data, count, tabs, modmap, period, st); break;
-    case 14: launch_ntt_t<14, 1024>(inverse, data, count, tabs, modmap, period, st); break;
-    case 13: launch_ntt_t<13, 512>(inverse, data, count, tabs, modmap, period, st); break;
-    case 12: launch_ntt_t<12, 256>(inverse, data, count, tabs, modmap, period, st); break;
-    case 11: launch_ntt_t<11, 128>(inverse, data, count, tabs, modmap, period, st); break;
-    case 10: launch_ntt_t<10, 64>(inverse, data, count, tabs, modmap, period, st); break;
-    case 8: launch_ntt_t<8, 64>(inverse, data, count, tabs, modmap, period, st); break;
-    case 6: launch_ntt_t<6, 64>(inverse, data, count, tabs, modmap, period, st); break;
-    default: throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
-    }
+    const NttForm f = ntt_form(logn, NTT_KIND_TENSOR, n_tensor + n_plain, latency_limbs, false);
+    hipLaunchKernelGGL(form_kernel(k_intt_tensor_forms, logn, f, true), dim3((unsigned)count), dim3(f.threads), 0, st,
+                       jobs, limbs, src_ps, n_tensor, plain, tabs, modmap, period);
     KERNEL_CHECK();
 }
 

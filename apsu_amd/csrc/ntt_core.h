@@ -236,7 +236,7 @@ HD u64 mul_lazy4(u64 x, u64 w, u64 wq, u64 nq)
 // the register-only butterfly loop 10 % faster (tools/microbench/bfly.hip, profiles/r04_bfly_mad_chain.txt).  The compiler
 // narrows the same chain written in C back to 32-bit multiplies, hence the instruction by name.  UNI: the twiddle is
 // wave-uniform (scalar registers; one scalar source per instruction is what gfx9 allows); nq always is.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(APSU_NTT_NO_MAD_CHAIN)
+#if defined(__HIP_DEVICE_COMPILE__)
 template <bool SB> __device__ __forceinline__ u64 ntt_mad64(u32 a, u32 b, u64 c)
 {
     u64 d;
@@ -245,27 +245,10 @@ template <bool SB> __device__ __forceinline__ u64 ntt_mad64(u32 a, u32 b, u64 c)
     else asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "v"(c));
     return d;
 }
-#define NTT_MAD_CHAIN 1
 #endif
-// where the chain pays (measured per direction, profiles/r04_ntt_mad_chain.txt); APSU_NTT_MAD_CHAIN_MODE: 1 forward passes
-// (default), 2 forward passes with wave-uniform twiddles only, 3 every pass of both directions, 4 forward as 1 + inverse with the
-// chain started from zero, 5 both directions from zero, 6 forward as 1 + the inverse's contiguous pass (constant twiddle indices) only,
-// 7 both directions with the chain in C behind opaque sums, 8 forward as 1 + inverse as 7
-#ifndef APSU_NTT_MAD_CHAIN_MODE
-#define APSU_NTT_MAD_CHAIN_MODE 1
-#endif
-#if defined(NTT_MAD_CHAIN)
-template <bool SB> __device__ __forceinline__ u64 ntt_mul64(u32 a, u32 b)         // a * b as the head of a chain (addend 0)
-{
-    u64 d;
-    unsigned long long carry;
-    if constexpr (SB) asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(d), "=s"(carry) : "v"(a), "s"(b));
-    else asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(d), "=s"(carry) : "v"(a), "v"(b));
-    return d;
-}
-#endif
-// CHAIN: 0 the compiler's form; 1 chain on top of the low product's high word; 2 chain from zero, joined by one 64-bit shift-add
-template <bool UNI = false, int CHAIN = 0>
+// CHAIN: the chain above, taken by the forward passes and not by the inverse ones (measured per direction,
+// profiles/r04_ntt_mad_chain.txt); otherwise, and in the host emulation, the compiler's form
+template <bool UNI = false, bool CHAIN = false>
 HD void bfly_lazy4(u64 &x, u64 &y, u64 w, u64 wq, u64 nq, u64 q4)
 {
     const u32 y0 = (u32)y, y1 = (u32)(y >> 32), a0 = (u32)wq, a1 = (u32)(wq >> 32);
@@ -274,21 +257,8 @@ HD void bfly_lazy4(u64 &x, u64 &y, u64 w, u64 wq, u64 nq, u64 q4)
     const u32 h0 = (u32)h, h1 = (u32)(h >> 32), w0 = (u32)w, w1 = (u32)(w >> 32), n0 = (u32)nq, n1 = (u32)(nq >> 32);
     const u64 lo = (u64)h0 * n0 + ((u64)y0 * w0 + x);
     u64 s;
-#if defined(NTT_MAD_CHAIN)
-    if constexpr (CHAIN == 2) {
-        u64 acc = ntt_mul64<UNI>(y0, w1);
-        acc = ntt_mad64<UNI>(y1, w0, acc);
-        acc = ntt_mad64<true>(h0, n1, acc);
-        acc = ntt_mad64<true>(h1, n0, acc);
-        s = lo + (acc << 32);
-    } else if constexpr (CHAIN == 3) {                           // the chain in C; an empty statement keeps every sum whole (64 bits), so the
-        u64 acc = lo >> 32;                                        // compiler takes v_mad_u64_u32 but picks registers and operand kinds itself
-        acc = (u64)y0 * w1 + acc; asm("" : "+v"(acc));
-        acc = (u64)y1 * w0 + acc; asm("" : "+v"(acc));
-        acc = (u64)h0 * n1 + acc; asm("" : "+v"(acc));
-        acc = (u64)h1 * n0 + acc; asm("" : "+v"(acc));
-        s = (u64)(u32)lo | (acc << 32);
-    } else if constexpr (CHAIN == 1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (CHAIN) {
         u64 acc = lo >> 32;
         acc = ntt_mad64<UNI>(y0, w1, acc);
         acc = ntt_mad64<UNI>(y1, w0, acc);
@@ -502,7 +472,7 @@ HD void ntt_pass16(u64 *lds, u64 *__restrict__ glob, int w, const NttTable &tab,
                         }
                         if (MODE == NTT_WIDE) x = csub_top(x, n4);
                     if (MODE == NTT_WIDE_NEAR) x = csub_top_near(x, d4);
-                        bfly_lazy4<(!COLS && !PRE), (APSU_NTT_MAD_CHAIN_MODE == 3 ? 1 : (APSU_NTT_MAD_CHAIN_MODE == 4 || APSU_NTT_MAD_CHAIN_MODE == 5) ? 2 : (APSU_NTT_MAD_CHAIN_MODE == 6 && !COLS && !PRE) ? 1 : (APSU_NTT_MAD_CHAIN_MODE == 7 || APSU_NTT_MAD_CHAIN_MODE == 8) ? 3 : 0)>(x, y, tv[0], tv[1], nq, q4);   // !COLS: the twiddle index is a compile-time constant
+                        bfly_lazy4(x, y, tv[0], tv[1], nq, q4);
                     }
                     continue;
                 }
@@ -518,7 +488,7 @@ HD void ntt_pass16(u64 *lds, u64 *__restrict__ glob, int w, const NttTable &tab,
                     u64 &x = r[gg][j], &y = r[gg][j | bit];
                     if (MODE == NTT_WIDE) x = csub_top(x, n4);
                     if (MODE == NTT_WIDE_NEAR) x = csub_top_near(x, d4);
-                    bfly_lazy4<UNIFORM_TW && !PRE, (APSU_NTT_MAD_CHAIN_MODE == 2 ? ((UNIFORM_TW && !PRE) ? 1 : 0) : APSU_NTT_MAD_CHAIN_MODE == 5 ? 2 : APSU_NTT_MAD_CHAIN_MODE == 7 ? 3 : 1)>(x, y, t.w, t.wq, nq, q4);
+                    bfly_lazy4<UNIFORM_TW && !PRE, true>(x, y, t.w, t.wq, nq, q4);
                 }
             }
         }

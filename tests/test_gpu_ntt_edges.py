@@ -3,7 +3,7 @@
 Modulus classes at n = 8192: narrow (50, 56), the narrow boundary (58 is narrow, 59 is wide: ntt_is_narrow), wide (59, 60), and
 the 61-bit auxiliary primes behind multiply (NTT_WIDE_NEAR included).  Forms: every launch forced to 16 coefficients per lane
 (APSU_HE_NTT_LATENCY_LIMBS=0), every launch forced to 8 per lane, and the default selection (switch unset), at limb counts on both
-sides of each switch-over of kernels.hip (ntt_use_latency_form, launch_ntt, launch_ntt_gather): 256 / 257 limbs at n = 8192,
+sides of each switch-over of ntt_form (apsu_amd/csrc/ntt_form.h): 256 / 257 limbs at n = 8192,
 1024 / 1025 for the inverse at n = 4096.  Inputs: every residue q - 1, both operand halves at their maximum, alternating extremes,
 random with extremes sprinkled in (tests/edge_values.py).
 """

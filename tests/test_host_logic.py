@@ -380,6 +380,46 @@ def test_scheduler_pool_pick_rule(emu):
                 assert got == want, (pool, ready, got, want)
 
 
+NTT_FORM_AUTO = 2 ** 64 - 1
+FWD, INV, GATHER, TENSOR = range(4)
+FORM_LIMBS = (1, 256, 257, 1024, 1025, 6840)
+# the throughput form (threads, coefficients per lane, waves per SIMD, split) per logn; the latency form where the ring size has one
+FORM_T = {15: (1024, 16, 4, 1), 14: (1024, 16, 4, 0), 13: (512, 16, 4, 0), 12: (256, 16, 4, 0), 11: (128, 16, 4, 0),
+          10: (64, 16, 4, 0), 8: (64, 16, 4, 0), 6: (64, 16, 4, 0)}
+FORM_L = {13: (1024, 8, 4, 0), 12: (512, 8, 4, 0)}
+FORM_W = (1024, 8, 8, 0)                                          # n = 8192: 8 coefficients per lane built for 8 waves per SIMD
+# (latency_limbs, logn, kind) -> form per limb count of FORM_LIMBS as T / L / W, for narrow False and True; every other case: all T
+NTT_FORM_TABLE = {
+    (256, 13, FWD): ("LLTTTT", "LLTTTT"), (256, 13, INV): ("LLTTTT", "LLTTTT"),
+    (256, 13, GATHER): ("LLTTTT", "LLTTTT"), (256, 13, TENSOR): ("LLTTTT", "LLTTTT"),
+    (256, 12, FWD): ("LLTTTT", "LLTTTT"), (256, 12, INV): ("LLTTTT", "LLTTTT"),
+    (256, 12, GATHER): ("LLTTTT", "LLTTTT"), (256, 12, TENSOR): ("LLTTTT", "LLTTTT"),
+    (NTT_FORM_AUTO, 13, FWD): ("LLTTTT", "LLWWWW"), (NTT_FORM_AUTO, 13, INV): ("LLTTTT", "LLTTTT"),
+    (NTT_FORM_AUTO, 13, GATHER): ("LLWWWW", "LLWWWW"), (NTT_FORM_AUTO, 13, TENSOR): ("LLTTTT", "LLTTTT"),
+    (NTT_FORM_AUTO, 12, FWD): ("LLLLLL", "LLLLLL"), (NTT_FORM_AUTO, 12, INV): ("LLLLTT", "LLLLTT"),
+    (NTT_FORM_AUTO, 12, GATHER): ("LLLLLL", "LLLLLL"), (NTT_FORM_AUTO, 12, TENSOR): ("LLLLLL", "LLLLLL"),
+}
+
+
+def test_ntt_launch_form_table(emu):
+    """ntt_form (apsu_amd/csrc/ntt_form.h), the one place that picks the form of every transform launch, against today's policy written
+    out: latency_limbs 0 = the throughput form; a limb count = the latency form up to it where the ring size has one; NTT_FORM_AUTO = up to
+    256 limbs at n = 8192 (above: the 8-wave build for narrow forward and for every gathered launch), at n = 4096 always but the inverse
+    above 1 024 limbs.  Every form gives the same bits, so the GPU parity tests cannot see this choice."""
+    emu.emu_ntt_form.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int)]
+    emu.emu_ntt_form.restype = None
+    out = (C.c_int * 4)()
+    for logn in (6, 8, 10, 11, 12, 13, 14, 15):
+        for kind in (FWD, INV, GATHER, TENSOR):
+            for narrow in (0, 1):
+                for latency in (0, 256, NTT_FORM_AUTO):
+                    row = NTT_FORM_TABLE.get((latency, logn, kind), ("TTTTTT", "TTTTTT"))[narrow]
+                    for limbs, f in zip(FORM_LIMBS, row):
+                        want = {"T": FORM_T[logn], "L": FORM_L.get(logn), "W": FORM_W}[f]
+                        emu.emu_ntt_form(logn, kind, limbs, latency, narrow, out)
+                        assert tuple(out) == want, (logn, kind, narrow, latency, limbs, tuple(out), want)
+
+
 def test_c_abi_exports_every_declared_symbol():
     """the shared library loads and exports exactly the functions include/apsu_he.h declares"""
     import apsu_amd
