@@ -78,6 +78,17 @@ template <class F> static int guarded(F &&fn)
 
 #define REQUIRE(cond, msg) do { if (!(cond)) throw std::invalid_argument(msg); } while (0)
 
+// The auxiliary BEHZ base of an engine context (params.cpp, narrow_aux_base): the engine's own narrow primes wherever they meet SEAL's
+// size bound with SEAL's prime count, else SEAL's.  APSU_HE_AUX_BASE=seal forces SEAL's 61-bit base (the A/B and the tests of the wide
+// transform paths); the results are the same bits either way.
+static AuxBase aux_base_from_env()
+{
+    const char *v = std::getenv("APSU_HE_AUX_BASE");
+    if (!v || !*v || !std::strcmp(v, "narrow")) return AuxBase::Narrow;
+    if (!std::strcmp(v, "seal")) return AuxBase::Seal;
+    throw std::invalid_argument("APSU_HE_AUX_BASE must be 'seal' or 'narrow'");
+}
+
 extern "C" {
 
 const char *apsu_he_last_error(void) { return g_last_error.c_str(); }
@@ -88,7 +99,7 @@ int apsu_he_create(const char *json, int device, apsu_he_ctx **out)
     return guarded([&] {
         REQUIRE(json && out, "null argument");
         PSUParams p = PSUParams::Load(json);
-        HeParams hp = HeParams::FromPSUParams(p);
+        HeParams hp = HeParams::FromPSUParams(p, aux_base_from_env());
         auto c = new apsu_he_ctx;
         try { c->eng = std::make_unique<Engine>(hp, &p, device); } catch (...) { delete c; throw; }
         *out = c;
@@ -100,9 +111,9 @@ int apsu_he_create_raw(uint64_t n, const uint64_t *coeff_modulus, int k, uint64_
     return guarded([&] {
         REQUIRE(coeff_modulus && out && k > 0, "null argument");
         // SEAL_USER_MOD_BIT_COUNT_MAX: coefficient primes of at most 60 bits (the JSON path refuses wider coeff_modulus_bits; k_mac's
-        // operand split assumes s = ceil(bits / 2) <= 30).  The 61-bit BEHZ primes are internal and never pass through here.
+        // operand split assumes s = ceil(bits / 2) <= 30).  The auxiliary BEHZ primes are internal and never pass through here.
         for (int j = 0; j < k; j++) REQUIRE(!(coeff_modulus[j] >> 60), "coeff_modulus prime has more than 60 bits");
-        HeParams hp = HeParams::Create((size_t)n, std::vector<u64>(coeff_modulus, coeff_modulus + k), plain_modulus);
+        HeParams hp = HeParams::Create((size_t)n, std::vector<u64>(coeff_modulus, coeff_modulus + k), plain_modulus, aux_base_from_env());
         auto c = new apsu_he_ctx;
         try { c->eng = std::make_unique<Engine>(hp, nullptr, device); } catch (...) { delete c; throw; }
         *out = c;
@@ -464,7 +475,7 @@ int apsu_he_multi_create(const char *json, const int *devices, int n_devices, ap
     return guarded([&] {
         REQUIRE(json && devices && out && n_devices > 0, "null argument");
         PSUParams p = PSUParams::Load(json);
-        HeParams hp = HeParams::FromPSUParams(p);
+        HeParams hp = HeParams::FromPSUParams(p, aux_base_from_env());
         auto m = new apsu_he_multi;
         try { m->m = std::make_unique<MultiEngine>(hp, p, std::vector<int>(devices, devices + n_devices)); } catch (...) { delete m; throw; }
         *out = m;

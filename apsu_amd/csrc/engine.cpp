@@ -162,6 +162,7 @@ Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), 
         //   APSU_HE_EVAL_PER_TERM=1    eval_patstock's products finished one by one (the fallback of the summed finish)
         //   APSU_HE_MAC_KARA=0/1       three-product k_mac forced off / on (default: by chain length)
         //   APSU_HE_SEED_EXPAND_HOST=1 seeded objects expanded by the host codec (the fallback of the device sampler)
+        //   APSU_HE_AUX_BASE=seal      SEAL's 61-bit auxiliary BEHZ base instead of the narrow one (read by c_api.cpp before HeParams; round 7)
         //   APSU_HE_FUSE_TAIL=0        eval_patstock's last mod-down as its own launch instead of inside the epilogue kernel (round 6)
         //   APSU_HE_NTT_LATENCY_LIMBS=n transform launches of at most n limbs take the latency form (8 coefficients per lane; round 6);
         //                              0 = always the throughput form.  Default: the measured crossover per ring size and kind of launch.
@@ -183,6 +184,10 @@ Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), 
         ntt_latency_limbs_ = NTT_FORM_AUTO;
         data_primes_narrow_ = true;
         for (int j = 0; j < hp_.K; j++) data_primes_narrow_ = data_primes_narrow_ && ntt_is_narrow(hp_.key_q[j], hp_.logn);
+        // launches over the extended base (map_ext / map_ext_fin) state narrowness with this flag: with the engine's own auxiliary base
+        // (params.cpp, narrow_aux_base) the largest forward launch of a query, the extension transform, takes the 8-wave form
+        ext_primes_narrow_ = data_primes_narrow_;
+        for (u64 m : hp_.aux_primes) ext_primes_narrow_ = ext_primes_narrow_ && ntt_is_narrow(m, hp_.logn);
         if (const char *v = std::getenv("APSU_HE_FUSE_TAIL")) fuse_tail_ = std::atoi(v) != 0;
         if (const char *v = std::getenv("APSU_HE_NTT_LATENCY_LIMBS")) ntt_latency_limbs_ = std::strtoull(v, nullptr, 10);
     }
@@ -1106,11 +1111,11 @@ void Engine::multiply(const u64 *a, const u64 *b, u64 *out3, int chain_idx)
         if (!square) H2D(in + 2 * L * n, b, 2 * L * n);
         u64 *ext = ws((size_t)nop * 2 * E * n);
         { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, in, L * n, 1, ext, n, nop * 2, st_); }
-        d_ntt(ext, (size_t)nop * 2 * E, map_ext(chain_idx), E, false, false);
+        d_ntt(ext, (size_t)nop * 2 * E, map_ext(chain_idx), E, false, ext_primes_narrow_);
         u64 *d = ws((size_t)3 * E * n), *o = ws(3 * L * n);
         std::vector<TensorJob> tj{ TensorJob{ ext, square ? ext : ext + (size_t)2 * E * n, d } };
         { PROF(P_TENSOR, 0); launch_tensor(dlevel(chain_idx), upload_jobs(tj), n, 1, st_); }
-        d_ntt(d, (size_t)3 * E, map_ext_fin(chain_idx), E, true, false);        // the finish below applies the twist where it can
+        d_ntt(d, (size_t)3 * E, map_ext_fin(chain_idx), E, true, ext_primes_narrow_);        // the finish below applies the twist where it can
         std::vector<FinishJob> fj{ FinishJob{ d, o, 1, 0 } };
         { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, upload_jobs(fj), false, n, 1, st_); }
         D2H(out3, o, 3 * L * n);
@@ -1449,7 +1454,7 @@ void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *
                 if (npar > 0) {
                     // (parents that came out of a key switch were extended by its mod-down kernel: run.ext_done)
                     if (run.ext_done != (int)d - 1) { PROFW(P_BEHZ_EXT, (size_t)npar * nb * 2 * n * (Lf + Ef)); launch_behz_ext(dlevel(first), hlevel(first).L, hlevel(first).nB, slot_ptr(pl.s0, 0), slot_w, 2, ext_ptr(pl.s0, 0), n, npar * nb, st_); }
-                    d_ntt(ext_ptr(pl.s0, 0), (size_t)npar * nb * 2 * Ef, map_ext(first), (int)Ef, false, false);
+                    d_ntt(ext_ptr(pl.s0, 0), (size_t)npar * nb * 2 * Ef, map_ext(first), (int)Ef, false, ext_primes_narrow_);
                 }
                 const auto &cl = s.levels[d];
                 const int nn = cl.s1 - cl.s0;
@@ -1469,7 +1474,7 @@ void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *
                     launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Ef, Ef * n, nullptr, 0, tabs(), map_ext_fin(first), (int)Ef, st_, ntt_latency_limbs_);
                 } else {
                     { PROF(P_TENSOR, 0); launch_tensor(dlevel(first), upload_jobs(tj), n, (int)tj.size(), st_); }
-                    d_ntt(dbuf, (size_t)nn * nb * 3 * Ef, map_ext_fin(first), (int)Ef, true, false);
+                    d_ntt(dbuf, (size_t)nn * nb * 3 * Ef, map_ext_fin(first), (int)Ef, true, ext_primes_narrow_);
                 }
                 { PROFW(P_BEHZ_FINISH, fj.size() * 3 * n * (Ef + Lf)); launch_behz_finish(dlevel(first), hlevel(first).L, hlevel(first).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
                 if (hp_.using_keyswitching && nn > 0) {                                                                          // :431
@@ -1532,7 +1537,7 @@ void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *
             convert(s.high_powers, high, pw->high.u());
             // derived form used by eval_patstock's ct x ct products and coefficient-form plaintext products
             { PROFW(P_BEHZ_EXT, (size_t)pw->n_high * nb * 2 * n * (Lh + Eh)); launch_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, pw->high.u(), Lh * n, 1, pw->hext.u(), n, (int)(pw->n_high * nb * 2), st_); }
-            d_ntt(pw->hext.u(), (size_t)pw->n_high * nb * 2 * Eh, map_ext(high), (int)Eh, false, false);
+            d_ntt(pw->hext.u(), (size_t)pw->n_high * nb * 2 * Eh, map_ext(high), (int)Eh, false, ext_primes_narrow_);
         }
     }
 }
@@ -2466,7 +2471,7 @@ void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
         }
         { PROFW(P_BEHZ_EXT, (size_t)NI * 2 * n * (Lh + Eh)); launch_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, innerh, Lh * n, 1, ext, n, NI * 2, st_); }
     }
-    d_ntt(ext, (size_t)NI * 2 * Eh, map_ext(high), (int)Eh, false, false);
+    d_ntt(ext, (size_t)NI * 2 * Eh, map_ext(high), (int)Eh, false, ext_primes_narrow_);
     if (async_high) HIP_CHECK(hipStreamWaitEvent(st_, pw.high_ready, 0));
     u64 *result = ws((size_t)Bs * 3 * Lh * n);                                                  // :238-240
     // The products of one BinBundle are summed (:273,303).  Each keeps its own rounding (note N1), but only
@@ -2553,7 +2558,7 @@ void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
             launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Eh, Eh * n, nullptr, 0, tabs(), map_ext_fin(high), (int)Eh, st_, ntt_latency_limbs_);
         } else {
             if (!tj.empty()) { PROF(P_TENSOR, 0); launch_tensor(dlevel(high), upload_jobs(tj), n, (int)tj.size(), st_); }
-            d_ntt(dbuf, (size_t)NI * 3 * Eh, map_ext_fin(high), (int)Eh, true, false);
+            d_ntt(dbuf, (size_t)NI * 3 * Eh, map_ext_fin(high), (int)Eh, true, ext_primes_narrow_);
         }
         { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(high), hlevel(high).L, hlevel(high).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
         { PROF(P_BEHZ_FINISH, 0); launch_sum_jobs(dlevel(high), (int)Lh, upload_jobs(sj), 3, n, Bs, st_); }
@@ -2769,7 +2774,7 @@ void Engine::d_multiply_sized(const u64 *ea, int sa, const u64 *eb, int sb, u64 
     if (so3 > so) HIP_CHECK(hipMemsetAsync(d + (size_t)so * E * n, 0, (size_t)(so3 - so) * E * n * sizeof(u64), st_));
     std::vector<TensorConvJob> tj{ TensorConvJob{ ea, eb, d, sa, sb } };
     { PROF(P_TENSOR, 0); launch_tensor_conv(dlevel(chain_idx), upload_jobs(tj), n, 1, st_); }
-    d_ntt(d, (size_t)so3 * E, map_ext_fin(chain_idx), (int)E, true, false);
+    d_ntt(d, (size_t)so3 * E, map_ext_fin(chain_idx), (int)E, true, ext_primes_narrow_);
     std::vector<FinishJob> fj;
     for (int t = 0; t < so3 / 3; t++) fj.push_back(FinishJob{ d + (size_t)3 * t * E * n, o + (size_t)3 * t * L * n, 1, 0 });
     { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
@@ -2794,7 +2799,7 @@ void Engine::multiply_sized(const u64 *a, int sa, const u64 *b, int sb, u64 *out
         const int np = sa + (square ? 0 : sb);
         u64 *ext = ws((size_t)np * E * n);
         { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(chain_idx), hlevel(chain_idx).L, hlevel(chain_idx).nB, in, L * n, 1, ext, n, np, st_); }
-        d_ntt(ext, (size_t)np * E, map_ext(chain_idx), (int)E, false, false);
+        d_ntt(ext, (size_t)np * E, map_ext(chain_idx), (int)E, false, ext_primes_narrow_);
         u64 *o = ws((size_t)(sa + sb - 1) * L * n);
         d_multiply_sized(ext, sa, square ? ext : ext + (size_t)sa * E * n, sb, o, chain_idx);
         D2H(out, o, (size_t)(sa + sb - 1) * L * n);
@@ -2857,7 +2862,7 @@ std::unique_ptr<Powers> Engine::compute_powers_nks(const uint32_t *bundle_indice
         auto extend = [&](int s0, int s1) {
             if (s1 <= s0) return;
             { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(0), hlevel(0).L, hlevel(0).nB, coef_ptr(s0, 0), S * n, (int)S, ext_ptr(s0, 0), n, (s1 - s0) * nb, st_); }
-            d_ntt(ext_ptr(s0, 0), (size_t)(s1 - s0) * nb * S * E, map_ext(0), (int)E, false, false);
+            d_ntt(ext_ptr(s0, 0), (size_t)(s1 - s0) * nb * S * E, map_ext(0), (int)E, false, ext_primes_narrow_);
         };
         extend(s.levels[0].s0, s.levels[0].s1);
         for (size_t d = 1; d < s.levels.size(); d++) {
@@ -2969,7 +2974,7 @@ void Engine::eval_bundles_nks(const Bundle *const *bundles, int count, const Pow
                     const int sa = (int)s_in[i], sb = (int)sz(i * h), so = sa + sb - 1;
                     u64 *iext = ws((size_t)sa * E * n), *prod = ws((size_t)so * n);
                     { PROF(P_BEHZ_EXT, 0); launch_behz_ext(dlevel(0), hlevel(0).L, hlevel(0).nB, inner[i], n, 1, iext, n, sa, st_); }
-                    d_ntt(iext, (size_t)sa * E, map_ext(0), (int)E, false, false);
+                    d_ntt(iext, (size_t)sa * E, map_ext(0), (int)E, false, ext_primes_narrow_);
                     d_multiply_sized(iext, sa, hext_ptr(i, bs), sb, prod, 0);
                     { PROF(P_OTHER, 0); launch_add(dlevel(0), result, prod, so, n, 1, st_); }
                     arena_off_ = mark;

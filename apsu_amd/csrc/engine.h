@@ -253,7 +253,7 @@ private:
     const int *map_ksacc_raw(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ksacc_raw_.p()) + chain_idx * (DMAXL + 1); }
 
     // device-pointer building blocks
-    // narrow: all moduli named by the map are data primes and all of them are narrow (ntt_form takes the launch's form from it)
+    // narrow: all moduli named by the map are narrow (data_primes_narrow_ / ext_primes_narrow_; ntt_form takes the launch's form from it)
     void d_ntt(u64 *data, size_t count, const int *modmap, int period, bool inverse, bool narrow);
     void d_ntt_ct(u64 *data, size_t polys, int chain_idx, bool inverse) { d_ntt(data, polys * (chain_idx + 1), map_ct(), chain_idx + 1, inverse, data_primes_narrow_); }
     // BFV multiply of `njobs` (a, b) pairs given as ext-NTT operands; writes size-3 results
@@ -306,6 +306,7 @@ private:
     bool pipe_cp_ = true;             // queued queries: the whole ComputePowers on the second stream, next to the evaluation in front (set_query_overlap 1 / 3)
     bool force_pipe_ = false;         // ... whether or not an evaluation is still running (set_query_overlap 3)
     bool data_primes_narrow_ = false; // every key prime runs the transform without range control (ntt_is_narrow)
+    bool ext_primes_narrow_ = false;  // ... and so does every modulus of the extended base q u Bsk (HeParams::aux_narrow)
     size_t ntt_latency_limbs_ = 0;    // transform launches of at most this many limbs take the 8-coefficient-per-lane form (APSU_HE_NTT_LATENCY_LIMBS)
     bool eval_side_ = true;           // cf sums + i = 0 finish of eval_patstock on a side stream (APSU_HE_EVAL_SIDE=0: on the main stream)
     bool async_results_ = false;      // eval_bundles with device masks + device output returns once the work is queued

@@ -240,6 +240,26 @@ int emu_params_info(const char *json, uint64_t *out, int cap)
     } catch (const std::exception &e) { g_err = e.what(); return -2; }
 }
 
+// The auxiliary BEHZ base HeParams picks for a parameter file (narrow = 1: AuxBase::Narrow, the engine's default; 0: SEAL's).
+// out = aux_narrow, aux_bits, logn, levels, then per level L, nB, m_sk, gamma, B_0 .. B_{nB-1}.  aux_note (why SEAL's base was kept)
+// is left in emu_last_error.
+int emu_aux_base(const char *json, int narrow, uint64_t *out, int cap)
+{
+    try {
+        PSUParams p = PSUParams::Load(json);
+        HeParams hp = HeParams::FromPSUParams(p, narrow ? AuxBase::Narrow : AuxBase::Seal);
+        std::vector<u64> v;
+        v.push_back(hp.aux_narrow); v.push_back((u64)hp.aux_bits); v.push_back((u64)hp.logn); v.push_back(hp.level.size());
+        for (const LevelConstants &lv : hp.level) {
+            v.push_back(lv.L); v.push_back(lv.nB); v.push_back(lv.m_sk); v.push_back(lv.gamma);
+            for (u64 b : lv.B) v.push_back(b);
+        }
+        g_err = hp.aux_note;
+        for (size_t i = 0; i < v.size() && (int)i < cap; i++) out[i] = v[i];
+        return (int)v.size();
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
 // PowersDag::configure on explicit sets; nodes: [power, depth, p1, p2] ascending by power
 int emu_powers_dag(const uint32_t *sources, int ns, const uint32_t *targets, int nt, uint32_t *nodes)
 {

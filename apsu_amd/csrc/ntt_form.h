@@ -22,7 +22,7 @@ struct NttForm {
     bool split;            // SPLIT_LOGN: threads .. min_waves describe the two half transforms
 };
 
-// limbs: of the launch (tensor launches: products' limbs + plain limbs).  narrow: every modulus of the launch is a narrow data prime.
+// limbs: of the launch (tensor launches: products' limbs + plain limbs).  narrow: every modulus of the launch is narrow (ntt_is_narrow).
 // NTT_FORM_AUTO at n = 8192: a limb's 1024-thread workgroup wins while a CU gets at most one limb (<= 256 limbs: -3 ... -16 %) and loses
 // above (+2 ... +20 %), where forward launches over narrow moduli and every gathered launch take the 8-coefficient build for 8 waves per
 // SIMD instead (<= 64 VGPRs, two workgroups per CU: -4 ... -7 % and -1 ... -5 %; slower on 61-bit limbs and on every inverse).

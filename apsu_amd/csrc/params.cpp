@@ -2,6 +2,7 @@
 // :290-374 (Load from JSON), common/apsu/util/utils.cpp:146-177 (create_powers_set).
 // SEAL-defined constants follow SURVEY.md App. B ([SEAL-recall]: SEAL is not in the image).
 #include "params.h"
+#include "ntt_core.h"
 
 #include <algorithm>
 #include <cctype>
@@ -434,6 +435,70 @@ struct Big {
     }
 };
 
+// SEAL's |B| at a level (rns.cpp RNSTool: one more prime than q has when 61-bit primes could fall short of the size bound)
+int seal_nB(int L, int t_bits, int q_bits) { return L + ((32 + t_bits + q_bits >= 61 * L + 61) ? 1 : 0); }
+
+int prod_bits(const std::vector<u64> &a)
+{
+    Big P(1);
+    for (u64 x : a) P.mul(x);
+    return P.bits();
+}
+
+// The engine's own auxiliary BEHZ base (AuxBase::Narrow).  The product's bits do not depend on WHICH primes Bsk u {m_sk} and gamma
+// are, only on SEAL's size bound 32 + bits(t) + bits(Q) < bits(prod(B) m_sk) at every level.  SEAL's 61-bit primes
+// are wide for the transforms (range control in every butterfly, product-free psi^0 butterflies in stage 1 only, no 8-wave forward
+// form); this base takes primes = 1 mod 2n of the largest bit size k whose primes are narrow for the context's ring (ntt_is_narrow)
+// AND take the tensor loader's lazy input (ntt_lazy_input_ok, computed per prime from its fold word bound, not assumed), skipping
+// coefficient and plain moduli: 57 bits at n = 8192 and 4096, 58 at n = 2048.  The scan runs down from 2^k, so every prime is
+// 2^k - c with a small c (the one-multiply fold of ntt_reduce_any and the 2^k - c 128-bit fold).  |B| stays SEAL's at every level;
+// where the narrow primes miss the bound with that count at some level, the context keeps SEAL's base (an extra limb in every
+// extension costs more than narrowness saves) and aux_note says why.  Returns false then.
+bool narrow_aux_base(HeParams &hp)
+{
+    const size_t n = hp.n;
+    const int maxL = hp.first_chain_idx + 1;
+    const size_t count = (size_t)maxL + 3;
+    auto usable = [&](u64 q) {
+        NttTable tab{};
+        tab.q = q;
+        tab.narrow = ntt_is_narrow(q, hp.logn) ? 1 : 0;
+        ntt_fold_params(q, tab.fold_k, tab.fold_c);
+        return tab.narrow && ntt_lazy_input_ok(tab, hp.logn);
+    };
+    std::vector<u64> primes;
+    int bits = 0;
+    for (int k = 60; k >= 44 && !bits; k--) {
+        primes.clear();
+        const u64 lower = (u64)1 << (k - 1), f = 2 * (u64)n;
+        bool ok = true;
+        for (u64 v = (((u64)1 << k) - 1) / f * f + 1; primes.size() < count && v > lower && ok; v -= f) {
+            if (!is_prime_u64(v) || v == hp.t || std::find(hp.key_q.begin(), hp.key_q.end(), v) != hp.key_q.end()) continue;
+            ok = usable(v);
+            primes.push_back(v);
+        }
+        if (ok && primes.size() == count) bits = k;
+    }
+    if (!bits) { hp.aux_note = "no bit size gives enough narrow primes with lazy tensor input"; return false; }
+    const int t_bits = 64 - __builtin_clzll(hp.t);
+    for (int L = 1; L <= maxL; L++) {
+        const int q_bits = prod_bits(std::vector<u64>(hp.key_q.begin(), hp.key_q.begin() + L));
+        const int nB = seal_nB(L, t_bits, q_bits);
+        std::vector<u64> bsk(primes.begin() + 2, primes.begin() + 2 + nB);
+        bsk.push_back(primes[0]);
+        const int have = prod_bits(bsk), need = 32 + t_bits + q_bits;
+        if (!(need < have)) {
+            hp.aux_note = "level L = " + std::to_string(L) + ": " + std::to_string(nB + 1) + " primes of " + std::to_string(bits) +
+                          " bits give " + std::to_string(have) + " bits, the size bound needs more than " + std::to_string(need);
+            return false;
+        }
+    }
+    hp.aux_primes = primes;
+    hp.aux_bits = bits;
+    hp.aux_narrow = true;
+    return true;
+}
+
 LevelConstants make_level(const HeParams &hp, int L)
 {
     LevelConstants lv;
@@ -453,8 +518,7 @@ LevelConstants make_level(const HeParams &hp, int L)
     }
     for (int j = 0; j + 1 < L; j++) lv.inv_q_last.push_back(ModulusInfo(lv.q[j]).inv(lv.q[L - 1] % lv.q[j]));
 
-    int t_bits = 64 - __builtin_clzll(t);
-    lv.nB = L + ((32 + t_bits + q_bits >= 61 * L + 61) ? 1 : 0);
+    lv.nB = seal_nB(L, 64 - __builtin_clzll(t), q_bits);
     if ((size_t)lv.nB + 2 > hp.aux_primes.size()) throw std::logic_error("auxiliary prime list too short");
     lv.m_sk = hp.aux_primes[0];
     lv.gamma = hp.aux_primes[1];
@@ -499,7 +563,7 @@ LevelConstants make_level(const HeParams &hp, int L)
 
 } // namespace
 
-HeParams HeParams::Create(size_t n, const std::vector<u64> &coeff_modulus, u64 plain_modulus)
+HeParams HeParams::Create(size_t n, const std::vector<u64> &coeff_modulus, u64 plain_modulus, AuxBase aux)
 {
     HeParams hp;
     if (n < 2 || (n & (n - 1))) throw std::invalid_argument("poly_modulus_degree must be a power of two");
@@ -514,7 +578,8 @@ HeParams HeParams::Create(size_t n, const std::vector<u64> &coeff_modulus, u64 p
     for (u64 q : hp.key_q)
         if (q >> 61 || (q - 1) % (2 * n) || !is_prime_u64(q)) throw std::invalid_argument("coeff_modulus prime is not NTT-friendly");
     int maxL = hp.first_chain_idx + 1;
-    hp.aux_primes = get_primes(2 * (u64)n, 61, (size_t)maxL + 3);
+    hp.aux_primes = get_primes(2 * (u64)n, 61, (size_t)maxL + 3);   // SEAL's base (rns.cpp), kept unless the narrow one applies
+    if (aux == AuxBase::Narrow) narrow_aux_base(hp);
     for (u64 q : hp.key_q) hp.ntt.push_back(make_ntt_tables(q, n, hp.logn));
     for (u64 q : hp.aux_primes) hp.ntt.push_back(make_ntt_tables(q, n, hp.logn));
     if (plain_modulus > 1 && (plain_modulus - 1) % (2 * (u64)n) == 0 && is_prime_u64(plain_modulus)) {
@@ -543,11 +608,11 @@ HeParams HeParams::Create(size_t n, const std::vector<u64> &coeff_modulus, u64 p
     return hp;
 }
 
-HeParams HeParams::FromPSUParams(const PSUParams &p)
+HeParams HeParams::FromPSUParams(const PSUParams &p, AuxBase aux)
 {
     return Create(p.seal_params.poly_modulus_degree,
                   coeff_modulus_create(p.seal_params.poly_modulus_degree, p.seal_params.coeff_modulus_bits),
-                  p.seal_params.plain_modulus);
+                  p.seal_params.plain_modulus, aux);
 }
 
 } // namespace apsu_he

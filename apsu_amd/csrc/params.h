@@ -70,6 +70,10 @@ struct NttTablesHost {                  // one modulus
     u64 ninv = 0, ninv_q = 0;
 };
 
+// Which primes form the auxiliary BEHZ base Bsk u {m_sk} and gamma (HeParams::Create, params.cpp): SEAL's 61-bit ones, or the
+// engine's own narrow ones where they meet SEAL's size bound with SEAL's prime count at every level.
+enum class AuxBase { Seal, Narrow };
+
 constexpr int MAXL = 8;                 // limbs of q at a data level (<= K-1)
 constexpr int MAXB = MAXL + 2;          // |Bsk| <= L + 2
 
@@ -105,7 +109,10 @@ struct HeParams {
     bool using_keyswitching = false;
     u64 t = 0;
     std::vector<u64> key_q;             // q_0 .. q_{K-1}; q_{K-1} = special prime when K>1
-    std::vector<u64> aux_primes;        // get_primes(2n, 61, .): [0]=m_sk, [1]=gamma, [2..]=B
+    std::vector<u64> aux_primes;        // [0]=m_sk, [1]=gamma, [2..]=B: SEAL's get_primes(2n, 61, .) or the narrow base (aux_narrow)
+    bool aux_narrow = false;            // aux_primes is the engine's narrow base (AuxBase::Narrow and the bound held)
+    int aux_bits = 61;                  // bit size of the aux primes
+    std::string aux_note;               // AuxBase::Narrow and SEAL's base kept: why
     // modulus ids: 0..K-1 = key_q ; K + i = aux_primes[i]
     std::vector<NttTablesHost> ntt;     // indexed by modulus id
     std::vector<LevelConstants> level;  // indexed by chain_idx, 0..first_chain_idx
@@ -116,8 +123,8 @@ struct HeParams {
     std::vector<uint32_t> slot_map;     // matrix_reps_index_map
     int plain_id() const { return K + (int)aux_primes.size(); }
 
-    static HeParams Create(size_t n, const std::vector<u64> &coeff_modulus, u64 plain_modulus);
-    static HeParams FromPSUParams(const PSUParams &p);
+    static HeParams Create(size_t n, const std::vector<u64> &coeff_modulus, u64 plain_modulus, AuxBase aux = AuxBase::Seal);
+    static HeParams FromPSUParams(const PSUParams &p, AuxBase aux = AuxBase::Seal);
     int clamp_chain_idx(int chain_idx) const { return chain_idx > first_chain_idx ? first_chain_idx : chain_idx; }
     int aux_id(int i) const { return K + i; }             // modulus id of aux_primes[i]
     int bsk_id(int level_nB, int i) const { return i < level_nB ? K + 2 + i : K + 0; }   // Bsk_i -> modulus id
