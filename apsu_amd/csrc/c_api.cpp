@@ -305,6 +305,36 @@ int apsu_he_mask_generate_blake2xb(apsu_he_ctx *c, const uint64_t *seed, uint64_
 int apsu_he_decrypt_decode(apsu_he_ctx *c, const uint64_t *sk_ntt, const uint64_t *cts, int cts_on_device, uint32_t count,
                            uint64_t *values, uint64_t *blocks)
 { return guarded([&] { REQUIRE(c && sk_ntt && (cts || !count), "null argument"); c->eng->decrypt_decode(sk_ntt, cts, cts_on_device != 0, count, values, blocks); }); }
+int apsu_he_decrypt_decode_budget(apsu_he_ctx *c, const uint64_t *sk_ntt, const uint64_t *cts, int cts_on_device, uint32_t count,
+                                  uint64_t *values, uint64_t *blocks, int32_t *budget_bits)
+{
+    return guarded([&] {
+        REQUIRE(c && sk_ntt && ((cts && budget_bits) || !count), "null argument");
+        static_assert(sizeof(int) == sizeof(int32_t), "budget_bits is an int array inside the engine");
+        c->eng->decrypt_decode(sk_ntt, cts, cts_on_device != 0, count, values, blocks, reinterpret_cast<int *>(budget_bits));
+    });
+}
+// ---- N5: the querier's side
+int apsu_he_keygen(apsu_he_ctx *c, const uint64_t *seed, uint64_t *sk_ntt)
+{ return guarded([&] { REQUIRE(c && seed && sk_ntt, "null argument"); c->eng->keygen(seed, sk_ntt); }); }
+int apsu_he_relin_keygen(apsu_he_ctx *c, const uint64_t *sk_ntt, const uint64_t *seed, uint64_t *ksk, uint64_t *key_seeds, apsu_he_relin **out)
+{
+    return guarded([&] {
+        REQUIRE(c && sk_ntt && seed, "null argument");
+        std::unique_ptr<RelinKeys> rk;
+        c->eng->relin_keygen(sk_ntt, seed, ksk, key_seeds, out ? &rk : nullptr);
+        if (out) { auto r = new apsu_he_relin; r->rk = std::move(rk); *out = r; }
+    });
+}
+int apsu_he_query_create(apsu_he_ctx *c, const uint64_t *sk_ntt, const uint64_t *seed, const uint32_t *bundle_indices, int n_bundle_idx,
+                         const uint64_t *values, int values_on_device, uint64_t *cts_dev, uint64_t *ct_seeds)
+{
+    return guarded([&] {
+        REQUIRE(c && sk_ntt && seed && n_bundle_idx >= 0, "null argument");
+        REQUIRE(!n_bundle_idx || (bundle_indices && values && cts_dev && ct_seeds), "null argument");
+        c->eng->query_create(sk_ntt, seed, bundle_indices, n_bundle_idx, values, values_on_device != 0, cts_dev, ct_seeds);
+    });
+}
 int apsu_he_bundle_degree(const apsu_he_bundle *b, uint32_t *degree)
 { return guarded([&] { REQUIRE(b && degree, "null argument"); *degree = b->b->degree; }); }
 int apsu_he_bundle_result_size(const apsu_he_ctx *c, const apsu_he_bundle *b, uint32_t *polys)

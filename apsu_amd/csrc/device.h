@@ -8,6 +8,7 @@
 #include "ntt_core.h"
 #include "ntt_form.h"
 #include "blake2x.h"
+#include "query_side.h"
 
 namespace apsu_he {
 
@@ -166,6 +167,22 @@ void launch_algebraize(const unsigned char *items, size_t count, u32 felts, u32 
 // N4: item -> 128-bit block packing for PEQT, and the rounding step of the querier's decryption
 void launch_pack_blocks(const u64 *values, size_t n, u32 items, u32 felts, u32 len, u64 *out, int batch, hipStream_t st);
 void launch_decrypt_round(const u64 *ct, size_t ct_stride, const u64 *v, u64 q0, u64 t, u64 *out, size_t n, int batch, hipStream_t st);
+// ... with the invariant noise budget's numerator: worst[b] (zeroed by the caller) = max over k of the centred |t x mod q0|
+void launch_decrypt_round_budget(const u64 *ct, size_t ct_stride, const u64 *v, u64 q0, u64 t, u64 *out, size_t n, int batch, u64 *worst,
+                                 hipStream_t st);
+// N5: the querier's side (query_side.h has the stream layout and the value maps).  Small signed polynomials are int8 arrays.
+constexpr u32 QS_FLAG_VALUE = 1;                     // k_plain_powers met a slot value >= t
+// out[b * S + s][slot_map[i]] = vals[b][i]^exps[s] mod t  (BatchEncoder's pre-transform order; the inverse NTT mod t follows)
+void launch_plain_powers(const u64 *vals, const u32 *slot_map, const u32 *exps, int S, Mod t, u64 *out, size_t n, int batch, u32 *flags, hipStream_t st);
+void launch_sample_ternary(const Blake2xbSeed &seed, signed char *out, size_t n, hipStream_t st);
+// out[c][n] = noise polynomial of object first_object + c
+void launch_sample_cbd(const Blake2xbSeed &seed, u64 first_object, signed char *out, size_t n, int count, hipStream_t st);
+// dst[c][j][k] = small[c][k] mod key prime j, j < limbs
+void launch_small_lift(const DevKey *key, const signed char *small, u64 *dst, int limbs, size_t n, int count, hipStream_t st);
+// c0 = Delta(pt) - e - v per limb, written into cts[c][0]  (cts: [count][2][L][n]; v: [count][L][n]; pt: [count][n]; e: [count][n])
+void launch_enc_finish(const DevLevel *lv, const u64 *pt, const u64 *v, const signed char *e, u64 *cts, size_t n, int count, hipStream_t st);
+// ksk[i][0][j] = -(ksk[i][1][j] s_j + e[i][j]) + [j == i] (p mod q_i) s_i^2  over the K key limbs, NTT domain
+void launch_rlk_finish(const DevKey *key, int K, const u64 *s, const u64 *e, u64 *ksk, size_t n, hipStream_t st);
 void launch_flag_monomial(const u64 *pt, size_t n, int batch, unsigned char *flag, hipStream_t st);
 // BEHZ
 // ct c at in + c*in_stride holds `polys` polys [L][n]; out packed [c][polys][E][n]

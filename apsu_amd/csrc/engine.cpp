@@ -2118,7 +2118,7 @@ void Engine::mask_generate_impl(uint32_t count, u64 *masks_dev, u64 *values_host
     });
 }
 
-void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_device, uint32_t count, u64 *values_host, u64 *blocks_host)
+void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_device, uint32_t count, u64 *values_host, u64 *blocks_host, int *budget_bits)
 {
     Enter g(this);
     if (!has_psu_) throw std::logic_error("context was created without PSUParams");
@@ -2149,6 +2149,14 @@ void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_devi
         d_ntt(v, count, map_ct(), 1, true, data_primes_narrow_);
         // x = c0 + v; m = round(t x / q_0) mod t
         u64 *pt = ws((size_t)count * n);
+        std::vector<u64> worst_host;
+        if (budget_bits) {
+            u64 *worst = ws(count);
+            worst_host.resize(count);
+            HIP_CHECK(hipMemsetAsync(worst, 0, count * sizeof(u64), st_));
+            { PROF(P_OTHER, 0); launch_decrypt_round_budget(ct, 2 * n, v, hp_.key_q[0], hp_.t, pt, n, (int)count, worst, st_); }
+            D2H(worst_host.data(), worst, count);
+        } else
         { PROF(P_OTHER, 0); launch_decrypt_round(ct, 2 * n, v, hp_.key_q[0], hp_.t, pt, n, (int)count, st_); }
         // BatchEncoder::decode: forward NTT mod t, slot gather
         d_ntt(pt, count, map_ct() + tid, 1, false, false);
@@ -2161,7 +2169,216 @@ void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_devi
         }
         if (values_host) D2H(values_host, vals, (size_t)count * n);
         sync();
+        // Decryptor::invariant_noise_budget: floor(log2(q_0 / (2 |t x mod q_0|))), the whole of q_0 for a noiseless result
+        for (uint32_t i = 0; budget_bits && i < count; i++) {
+            const unsigned __int128 q0 = hp_.key_q[0], w = worst_host[i];
+            int bits = 0;
+            while (w && (w << (bits + 1)) < q0) bits++;
+            budget_bits[i] = w ? bits : 64 - __builtin_clzll(hp_.key_q[0]);
+        }
     });
+}
+
+// ============================================================================ N5: the querier's side (query_side.h)
+void Engine::check_key_residues(const u64 *sk, int limbs) const
+{
+    for (int j = 0; j < limbs; j++)
+        for (size_t k = 0; k < hp_.n; k++)
+            if (sk[(size_t)j * hp_.n + k] >= hp_.key_q[j]) throw std::invalid_argument("secret key is not reduced modulo its limb's prime");
+}
+
+static Blake2xbSeed master_seed(const u64 seed[8])
+{
+    Blake2xbSeed sd;
+    for (int i = 0; i < 8; i++) sd.w[i] = seed[i];
+    return sd;
+}
+
+void Engine::host_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst)
+{
+    const int L = key_level ? hp_.K : hp_.first_chain_idx + 1;
+    std::vector<u64> q(hp_.key_q.begin(), hp_.key_q.begin() + L), buf((size_t)L * hp_.n);
+    for (int i = 0; i < count; i++) {
+        sealio::sample_poly_uniform(seeds + (size_t)i * 8, q.data(), (size_t)L, hp_.n, buf.data());
+        HIP_CHECK(hipMemcpyAsync(dst[i], buf.data(), buf.size() * sizeof(u64), hipMemcpyHostToDevice, st_));
+        sync();                                                  // buf is reused
+    }
+}
+
+bool Engine::queue_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst)
+{
+    const int L = key_level ? hp_.K : hp_.first_chain_idx + 1;
+    if (L > DMAXL || seed_expand_host_) return false;
+    const DevLevel *lv = nullptr;
+    if (key_level && hp_.K - 1 > hp_.first_chain_idx) {
+        if (!d_key_level_.p()) {                                 // the DevLevel-shaped view of the key level (as in seed_expand)
+            std::vector<unsigned char> raw(sizeof(DevLevel), 0);
+            DevLevel *d = reinterpret_cast<DevLevel *>(raw.data());
+            d->L = hp_.K;
+            for (int j = 0; j < hp_.K; j++) d->q[j] = make_mod(hp_.key_q[j]);
+            d_key_level_.alloc(sizeof(DevLevel));
+            HIP_CHECK(hipMemcpy(d_key_level_.p(), raw.data(), sizeof(DevLevel), hipMemcpyHostToDevice));
+        }
+        lv = reinterpret_cast<const DevLevel *>(d_key_level_.p());
+    } else lv = dlevel(key_level ? hp_.K - 1 : hp_.first_chain_idx);
+    std::vector<u64> mm(L);
+    for (int j = 0; j < L; j++) mm[j] = ~(u64)0 - (~(u64)0 % hp_.key_q[j]) - 1;          // util/rlwe.cpp: max_multiple
+    std::vector<SeedJob> jobs(count);
+    for (int i = 0; i < count; i++) {
+        for (int k = 0; k < 8; k++) jobs[i].seed.w[k] = seeds[(size_t)i * 8 + k];
+        jobs[i].dst = dst[i];
+    }
+    const size_t need = ((size_t)count * (1 + 8192) + 1) * sizeof(u32);
+    if (d_seed_rej_.bytes() < need) {
+        sync();
+        d_seed_rej_.alloc(need * 2);
+        HIP_CHECK(hipMemsetAsync(d_seed_rej_.p(), 0, d_seed_rej_.bytes(), st_));
+    }
+    u32 *rej = reinterpret_cast<u32 *>(d_seed_rej_.p());
+    int *overflow = reinterpret_cast<int *>(rej + (size_t)count * (1 + 8192));
+    HIP_CHECK(hipMemsetAsync(overflow, 0, sizeof(int), st_));
+    { PROF(P_OTHER, 0); launch_seed_expand(upload_jobs(jobs), count, lv, L, upload_jobs(mm), hp_.n, rej, overflow, st_); }
+    return true;
+}
+
+// after a sync: did some object reject more words than the device lists hold?  (then the lists are cleared for their next use)
+bool Engine::seeds_overflowed(int count)
+{
+    int h = 0;
+    HIP_CHECK(hipMemcpy(&h, reinterpret_cast<u32 *>(d_seed_rej_.p()) + (size_t)count * (1 + 8192), sizeof(int), hipMemcpyDeviceToHost));
+    if (h) {
+        HIP_CHECK(hipMemsetAsync(d_seed_rej_.p(), 0, d_seed_rej_.bytes(), st_));
+        sync();
+    }
+    return h != 0;
+}
+
+void Engine::keygen(const u64 seed[8], u64 *sk_ntt_host)
+{
+    Enter g(this);
+    const size_t n = hp_.n;
+    const int K = hp_.K;
+    TIER1_SLOTS();
+    WITH_ARENA({
+        signed char *small = reinterpret_cast<signed char *>(ws(n / 8));
+        u64 *sk = ws((size_t)K * n);
+        { PROF(P_OTHER, 0); launch_sample_ternary(master_seed(seed), small, n, st_); }
+        { PROF(P_OTHER, 0); launch_small_lift(dkey(), small, sk, K, n, 1, st_); }
+        d_ntt(sk, K, map_ct(), K, false, data_primes_narrow_);
+        HIP_CHECK(hipMemcpyAsync(sk_ntt_host, sk, (size_t)K * n * sizeof(u64), hipMemcpyDeviceToHost, st_));
+        sync();
+    });
+}
+
+void Engine::relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_host, u64 *seeds_host, std::unique_ptr<RelinKeys> *resident)
+{
+    Enter g(this);
+    if (!hp_.using_keyswitching) throw std::invalid_argument("parameters do not support key switching: the reference creates no relinearisation keys");
+    const size_t n = hp_.n;
+    const int K = hp_.K, nk = K - 1;
+    check_key_residues(sk_ntt_host, K);
+    const Blake2xbSeed master = master_seed(seed);
+    std::vector<u64> seeds((size_t)nk * 8);
+    for (int i = 0; i < nk; i++) blake2xb_stream_block(master, qs_seed_block((u64)i), seeds.data() + (size_t)i * 8);
+    auto rk = std::make_unique<RelinKeys>();
+    const size_t words = (size_t)nk * 2 * K * n;
+    rk->data.alloc(words * sizeof(u64));
+    std::vector<u64 *> a(nk);
+    for (int i = 0; i < nk; i++) a[i] = rk->data.u() + ((size_t)i * 2 + 1) * K * n;
+    TIER1_SLOTS();
+    WITH_ARENA({
+        u64 *sk = ws((size_t)K * n);
+        HIP_CHECK(hipMemcpyAsync(sk, sk_ntt_host, (size_t)K * n * sizeof(u64), hipMemcpyHostToDevice, st_));
+        signed char *small = reinterpret_cast<signed char *>(ws((size_t)nk * n / 8));
+        u64 *e = ws((size_t)nk * K * n);
+        bool on_device = queue_seed_expand(true, nk, seeds.data(), a.data());
+        if (!on_device) host_seed_expand(true, nk, seeds.data(), a.data());
+        auto rest = [&] {
+            { PROF(P_OTHER, 0); launch_sample_cbd(master, 0, small, n, nk, st_); }
+            { PROF(P_OTHER, 0); launch_small_lift(dkey(), small, e, K, n, nk, st_); }
+            d_ntt(e, (size_t)nk * K, map_ct(), K, false, data_primes_narrow_);
+            { PROF(P_OTHER, 0); launch_rlk_finish(dkey(), K, sk, e, rk->data.u(), n, st_); }
+            sync();
+        };
+        rest();
+        if (on_device && seeds_overflowed(nk)) {                 // (seed_expand's fallback: the host redoes the public halves)
+            host_seed_expand(true, nk, seeds.data(), a.data());
+            rest();
+        }
+    });
+    if (ksk_host) HIP_CHECK(hipMemcpy(ksk_host, rk->data.p(), words * sizeof(u64), hipMemcpyDeviceToHost));
+    if (seeds_host) std::memcpy(seeds_host, seeds.data(), seeds.size() * sizeof(u64));
+    if (resident) *resident = std::move(rk);
+}
+
+void Engine::query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint32_t *bundle_indices, int nb, const u64 *values, bool values_on_device,
+                          u64 *cts_dev, u64 *seeds_host)
+{
+    Enter g(this);
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!hp_.batching) throw std::logic_error("plain_modulus does not support batching");
+    if (nb <= 0) return;
+    const size_t n = hp_.n;
+    const int first = hp_.first_chain_idx, L = first + 1, tid = hp_.plain_id();
+    std::vector<u32> exps(psu_.query_params.query_powers.begin(), psu_.query_params.query_powers.end());   // ascending (std::set)
+    const int S = (int)exps.size(), count = nb * S;
+    if ((size_t)nb * S > 65535) throw std::invalid_argument("more than 65535 ciphertexts in one call");
+    for (int b = 0; b < nb; b++)
+        if (bundle_indices[b] >= psu_.bundle_idx_count) throw std::invalid_argument("bundle index out of range");
+    check_key_residues(sk_ntt_host, L);
+    if (!values_on_device)
+        for (size_t i = 0; i < (size_t)nb * n; i++)
+            if (values[i] >= hp_.t) throw std::invalid_argument("slot value is not reduced modulo the plain modulus");
+    const Blake2xbSeed master = master_seed(seed);
+    std::vector<u64> seeds((size_t)count * 8);
+    for (int c = 0; c < count; c++) blake2xb_stream_block(master, qs_seed_block(QS_KEY_OBJECTS + (u64)c), seeds.data() + (size_t)c * 8);
+    std::vector<u64 *> c1(count);
+    for (int c = 0; c < count; c++) c1[c] = cts_dev + ((size_t)c * 2 + 1) * L * n;
+    u32 flags_host = 0;
+    TIER1_SLOTS();
+    WITH_ARENA({
+        u64 *sk = ws((size_t)L * n);
+        HIP_CHECK(hipMemcpyAsync(sk, sk_ntt_host, (size_t)L * n * sizeof(u64), hipMemcpyHostToDevice, st_));
+        const u64 *vals = values;
+        if (!values_on_device) {
+            u64 *staged = ws((size_t)nb * n);
+            HIP_CHECK(hipMemcpyAsync(staged, values, (size_t)nb * n * sizeof(u64), hipMemcpyHostToDevice, st_));
+            vals = staged;
+        }
+        u32 *flags = reinterpret_cast<u32 *>(ws(1));
+        HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(u64), st_));
+        u64 *pt = ws((size_t)count * n);
+        signed char *small = reinterpret_cast<signed char *>(ws((size_t)count * n / 8));
+        u64 *v = ws((size_t)count * L * n);
+        // PlaintextPowers + BatchEncoder::encode (plaintext_powers.cpp:41-46,51-99)
+        { PROF(P_OTHER, 0); launch_plain_powers(vals, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), upload_jobs(exps), S, make_mod(hp_.t), pt, n, nb, flags, st_); }
+        d_ntt(pt, count, map_ct() + tid, 1, true, false);
+        { PROF(P_OTHER, 0); launch_sample_cbd(master, QS_KEY_OBJECTS, small, n, count, st_); }
+        // Encryptor::encrypt_symmetric: c1 from its public seed, v = c1 s, c0 = Delta(m) - e - v
+        bool on_device = queue_seed_expand(false, count, seeds.data(), c1.data());
+        if (!on_device) host_seed_expand(false, count, seeds.data(), c1.data());
+        auto rest = [&] {
+            std::vector<const u64 *> src((size_t)count * L);
+            for (int c = 0; c < count; c++)
+                for (int j = 0; j < L; j++) src[(size_t)c * L + j] = c1[c] + (size_t)j * n;
+            bool nored = hp_.logn <= 14;                         // (limb j of c1 is a canonical residue of q_j: nothing to reduce)
+            for (int j = 0; j < L && nored; j++) nored = ntt_gather_nored_ok(hp_.key_q[j], hp_.key_q[j], hp_.logn);
+            { PROF(P_NTT_FWD, src.size());
+              launch_ntt_gather(hp_.logn, upload_jobs(src), v, src.size(), tabs(), map_ct(), L, st_, nored, ntt_latency_limbs_, data_primes_narrow_); }
+            { PROF(P_OTHER, 0); launch_dyadic_plain(dlevel(first), v, sk, v, 1, n, count, 0, st_); }
+            d_ntt(v, (size_t)count * L, map_ct(), L, true, data_primes_narrow_);
+            { PROF(P_OTHER, 0); launch_enc_finish(dlevel(first), pt, v, small, cts_dev, n, count, st_); }
+            HIP_CHECK(hipMemcpyAsync(&flags_host, flags, sizeof(u32), hipMemcpyDeviceToHost, st_));
+            sync();
+        };
+        rest();
+        if (on_device && seeds_overflowed(count)) {
+            host_seed_expand(false, count, seeds.data(), c1.data());
+            rest();
+        }
+    });
+    if (flags_host & QS_FLAG_VALUE) throw std::invalid_argument("slot value is not reduced modulo the plain modulus");
+    if (seeds_host) std::memcpy(seeds_host, seeds.data(), seeds.size() * sizeof(u64));
 }
 
 // ============================================================================ tier 2: BinBundle evaluation

@@ -152,7 +152,16 @@ public:
     void mask_generate(u64 seed, uint32_t count, u64 *masks_dev, u64 *values_host, u64 *blocks_host);
     // the same with the reference's generator: SEAL's Blake2xb PRNG under `seed`, starting at its first_value-th 32-bit output
     void mask_generate_blake2xb(const u64 seed[8], u64 first_value, uint32_t count, u64 *masks_dev, u64 *values_host, u64 *blocks_host);
-    void decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_device, uint32_t count, u64 *values_host, u64 *blocks_host);
+    // budget_bits (may be null): SEAL's invariant noise budget of every result
+    void decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_device, uint32_t count, u64 *values_host, u64 *blocks_host,
+                        int *budget_bits = nullptr);
+    // N5, the querier's side (query_side.h): Sender::reset_keys and create_query's HE half (sender/apsu/sender_osn.cpp:215-229,426-484)
+    void keygen(const u64 seed[8], u64 *sk_ntt_host);                                       // [K][n]
+    // ksk_host [K-1][2][K][n], seeds_host [K-1][8] and resident may each be null
+    void relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_host, u64 *seeds_host, std::unique_ptr<RelinKeys> *resident);
+    // cts_dev: [nb * S][2][L][n] device words; seeds_host: [nb * S][8]
+    void query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint32_t *bundle_indices, int nb, const u64 *values, bool values_on_device,
+                      u64 *cts_dev, u64 *seeds_host);
     // N3 on the device: c1 of `count` seeded objects at chain_idx (-1 / K - 1: the key level) = util::sample_poly_uniform under
     // SEAL's Blake2xb generator seeded with seeds[i][8], written to the DEVICE buffers dst[i] ([L][n] words each)
     void seed_expand(int chain_idx, int count, const u64 *seeds, u64 *const *dst);
@@ -392,6 +401,12 @@ private:
     void ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g);
     void finish_bundle(Bundle &b, const u64 *raw);     // raw: [degree+1][n] coefficient-form plaintexts mod t (device)
     DevBuf d_slot_map_;
+    // seed expansion queued on the stream without a host wait (query_create, relin_keygen): false = the objects need the host's
+    // sampler (seed_expand's rule) and nothing was queued; seeds_overflowed() after the final sync tells whether the device lists sufficed
+    bool queue_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst);
+    bool seeds_overflowed(int count);
+    void host_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst);
+    void check_key_residues(const u64 *sk_ntt_host, int limbs) const;
     DevBuf d_seed_rej_, d_seed_mm_, d_key_level_;   // seed expansion: rejection lists, max_multiple per (level, limb), DevLevel-shaped view of the key level
 
     // profiling state

@@ -374,13 +374,10 @@ void launch_sum_jobs(const DevLevel *lv, int L, const SumJob *jobs, int polys, s
     KERNEL_CHECK();
 }
 
-// K8: add_plain_inplace (bin_bundle.cpp:159,162,345,346): c0 += round(m*Q/t) in RNS  (App. B7)
-__global__ __launch_bounds__(EW_T) void k_add_plain(const DevLevel *__restrict__ lv, const PlainJob *__restrict__ jobs, size_t n)
+// Delta(m) of SEAL's BFV scaling (App. B7): round(m*Q/t) = m*floor(Q/t) + fix in RNS, fix = floor((m*(Q mod t) + floor((t+1)/2)) / t).
+// Shared by add_plain and the querier's encryption (k_enc_finish).
+__device__ __forceinline__ u64 plain_scale_fix(const DevLevel *__restrict__ lv, u64 m)
 {
-    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
-    if (k >= n) return;
-    const PlainJob job = jobs[blockIdx.y];
-    const u64 m = job.pt[k];
     // fix = floor((m * (Q mod t) + floor((t+1)/2)) / t), exact 128-by-64 division (m < t < 2^61)
     u128p num = mul128(m, lv->q_mod_t);
     add128(num, u128p{ lv->threshold, 0 });
@@ -396,13 +393,27 @@ __global__ __launch_bounds__(EW_T) void k_add_plain(const DevLevel *__restrict__
             if (rem >= t) { rem -= t; fix |= 1; }
         }
     }
+    return fix;
+}
+__device__ __forceinline__ u64 plain_scale_limb(const DevLevel *__restrict__ lv, int j, u64 m, u64 fix)
+{
+    u128p s = mul128(m, lv->coeff_div_plain[j]);
+    add128(s, u128p{ fix, 0 });
+    return barrett128(s, lv->q[j]);
+}
+
+// K8: add_plain_inplace (bin_bundle.cpp:159,162,345,346): c0 += round(m*Q/t) in RNS  (App. B7)
+__global__ __launch_bounds__(EW_T) void k_add_plain(const DevLevel *__restrict__ lv, const PlainJob *__restrict__ jobs, size_t n)
+{
+    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (k >= n) return;
+    const PlainJob job = jobs[blockIdx.y];
+    const u64 m = job.pt[k];
+    const u64 fix = plain_scale_fix(lv, m);
     u64 *c0 = job.ct;
     for (int j = 0; j < lv->L; j++) {
-        const Mod mq = lv->q[j];
-        u128p s = mul128(m, lv->coeff_div_plain[j]);
-        add128(s, u128p{ fix, 0 });
-        const u64 scaled = barrett128(s, mq);
-        c0[j * n + k] = addmod(c0[j * n + k], scaled, mq.q);
+        const u64 scaled = plain_scale_limb(lv, j, m, fix);
+        c0[j * n + k] = addmod(c0[j * n + k], scaled, lv->q[j].q);
     }
 }
 
@@ -827,17 +838,14 @@ void launch_pack_blocks(const u64 *values, size_t n, u32 items, u32 felts, u32 l
 
 // N4: the querier's decryption of a result at the last level (result_package.cpp:175-213, Decryptor::decrypt):
 // x = c0 + v (v = INTT(NTT(c1) . s), one limb q0), m = round(t x / q0) mod t.
-__global__ __launch_bounds__(EW_T) void k_decrypt_round(const u64 *__restrict__ ct, size_t ct_stride, const u64 *__restrict__ v,
-                                                        u64 q0, u64 t, u64 *__restrict__ out, size_t n)
+// rem receives (t x + floor(q0 / 2)) mod q0
+__device__ __forceinline__ u64 decrypt_round_coeff(u64 x, u64 q0, u64 t, u64 &rem)
 {
-    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
-    if (k >= n) return;
-    const size_t b = blockIdx.y;
-    const u64 x = addmod(ct[b * ct_stride + k], v[b * n + k], q0);
     u128p num = mul128(x, t);
     add128(num, u128p{ q0 >> 1, 0 });
     // floor(num / q0) mod t by restoring division, the quotient folded mod t on the fly (num < 2^124)
-    u64 rem = 0, quo = 0;
+    u64 quo = 0;
+    rem = 0;
     for (int i = 127; i >= 0; i--) {
         const u64 bit = i >= 64 ? (num.hi >> (i - 64)) & 1 : (num.lo >> i) & 1;
         rem = (rem << 1) | bit;                                   // rem < q0 < 2^62 before the shift
@@ -845,13 +853,194 @@ __global__ __launch_bounds__(EW_T) void k_decrypt_round(const u64 *__restrict__ 
         if (rem >= q0) { rem -= q0; quo |= 1; }
         if (quo >= t) quo -= t;
     }
-    out[b * n + k] = quo;
+    return quo;
+}
+
+__global__ __launch_bounds__(EW_T) void k_decrypt_round(const u64 *__restrict__ ct, size_t ct_stride, const u64 *__restrict__ v,
+                                                        u64 q0, u64 t, u64 *__restrict__ out, size_t n)
+{
+    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (k >= n) return;
+    const size_t b = blockIdx.y;
+    const u64 x = addmod(ct[b * ct_stride + k], v[b * n + k], q0);
+    u64 rem;
+    out[b * n + k] = decrypt_round_coeff(x, q0, t, rem);
+}
+
+// The same with SEAL's invariant noise budget (result_package.cpp:175-213, Decryptor::invariant_noise_budget): worst[b] = the
+// largest centred |t x mod q0| over ciphertext b's coefficients; budget = floor(log2(q0 / (2 worst))) is formed on the host.
+// Wave maximum, then the workgroup's four waves through LDS and one atomic per workgroup.
+__global__ __launch_bounds__(EW_T) void k_decrypt_round_budget(const u64 *__restrict__ ct, size_t ct_stride, const u64 *__restrict__ v,
+                                                               u64 q0, u64 t, u64 *__restrict__ out, size_t n, unsigned long long *__restrict__ worst)
+{
+    __shared__ u64 wave_max[EW_T / 64];
+    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    const size_t b = blockIdx.y;
+    u64 dist = 0;
+    if (k < n) {
+        const u64 x = addmod(ct[b * ct_stride + k], v[b * n + k], q0);
+        u64 rem;
+        out[b * n + k] = decrypt_round_coeff(x, q0, t, rem);
+        const u64 r = submod(rem, q0 >> 1, q0);                   // t x mod q0
+        dist = r > (q0 >> 1) ? q0 - r : r;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const u64 o = (u64)__shfl_xor((unsigned long long)dist, off, 64);
+        dist = o > dist ? o : dist;
+    }
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = dist;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < EW_T / 64; w++) dist = wave_max[w] > dist ? wave_max[w] : dist;
+        atomicMax(worst + b, (unsigned long long)dist);
+    }
 }
 
 void launch_decrypt_round(const u64 *ct, size_t ct_stride, const u64 *v, u64 q0, u64 t, u64 *out, size_t n, int batch, hipStream_t st)
 {
     if (!batch) return;
     hipLaunchKernelGGL(k_decrypt_round, ew_grid(n, batch), dim3(EW_T), 0, st, ct, ct_stride, v, q0, t, out, n);
+    KERNEL_CHECK();
+}
+
+void launch_decrypt_round_budget(const u64 *ct, size_t ct_stride, const u64 *v, u64 q0, u64 t, u64 *out, size_t n, int batch, u64 *worst,
+                                 hipStream_t st)
+{
+    if (!batch) return;
+    hipLaunchKernelGGL(k_decrypt_round_budget, ew_grid(n, batch), dim3(EW_T), 0, st, ct, ct_stride, v, q0, t, out, n,
+                       reinterpret_cast<unsigned long long *>(worst));
+    KERNEL_CHECK();
+}
+
+// ============================================================================ N5: the querier's side (query_side.h)
+// PlaintextPowers (sender/apsu/plaintext_powers.cpp:51-99) + the slot permutation of BatchEncoder::encode: for bundle index b
+// (blockIdx.y) and slot i, out[b * S + s][slot_map[i]] = x[b][i]^exps[s] mod t; the inverse NTT mod t follows.  The exponent bits
+// are wave-uniform.  A value >= t raises QS_FLAG_VALUE (and counts as 0).
+__global__ __launch_bounds__(EW_T) void k_plain_powers(const u64 *__restrict__ vals, const u32 *__restrict__ slot_map, const u32 *__restrict__ exps,
+                                                       int S, Mod t, u64 *__restrict__ out, size_t n, u32 *__restrict__ flags)
+{
+    const size_t i = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (i >= n) return;
+    const size_t b = blockIdx.y;
+    u64 x = vals[b * n + i];
+    if (x >= t.q) { atomicOr(flags, QS_FLAG_VALUE); x = 0; }
+    const u32 dst = slot_map[i];
+    for (int s = 0; s < S; s++) out[(b * S + s) * n + dst] = qs_pow_mod(x, exps[s], t);
+}
+
+void launch_plain_powers(const u64 *vals, const u32 *slot_map, const u32 *exps, int S, Mod t, u64 *out, size_t n, int batch, u32 *flags, hipStream_t st)
+{
+    if (!batch || !S) return;
+    hipLaunchKernelGGL(k_plain_powers, ew_grid(n, batch), dim3(EW_T), 0, st, vals, slot_map, exps, S, t, out, n, flags);
+    KERNEL_CHECK();
+}
+
+// The two samplers: one lane per 64-byte stream block (as k_fill_blake2xb) = eight coefficients, written once as eight signed
+// bytes; the residues modulo each prime are formed by the consumers.  out: [n] resp. [count][n] int8, n a multiple of 8.
+__global__ __launch_bounds__(EW_T) void k_sample_ternary(Blake2xbSeed seed, u64 *__restrict__ out, size_t n)
+{
+    const size_t g = (size_t)blockIdx.x * EW_T + threadIdx.x;     // group of eight coefficients
+    if (g * 8 >= n) return;
+    u64 blk[8], packed = 0;
+    blake2xb_stream_block(seed, qs_secret_block(g * 8), blk);
+#pragma unroll
+    for (int i = 0; i < 8; i++) packed |= (u64)(unsigned char)(signed char)qs_ternary(blk[i]) << (8 * i);
+    out[g] = packed;
+}
+
+__global__ __launch_bounds__(EW_T) void k_sample_cbd(Blake2xbSeed seed, u64 first_object, u64 *__restrict__ out, size_t n)
+{
+    const size_t g = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (g * 8 >= n) return;
+    const size_t c = blockIdx.y;
+    u64 blk[8], packed = 0;
+    blake2xb_stream_block(seed, qs_noise_block(first_object + c, g * 8), blk);
+#pragma unroll
+    for (int i = 0; i < 8; i++) packed |= (u64)(unsigned char)(signed char)qs_cbd(blk[i]) << (8 * i);
+    out[c * (n / 8) + g] = packed;
+}
+
+void launch_sample_ternary(const Blake2xbSeed &seed, signed char *out, size_t n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_sample_ternary, dim3((unsigned)((n / 8 + EW_T - 1) / EW_T)), dim3(EW_T), 0, st, seed, reinterpret_cast<u64 *>(out), n);
+    KERNEL_CHECK();
+}
+
+void launch_sample_cbd(const Blake2xbSeed &seed, u64 first_object, signed char *out, size_t n, int count, hipStream_t st)
+{
+    if (!count) return;
+    hipLaunchKernelGGL(k_sample_cbd, ew_grid(n / 8, count), dim3(EW_T), 0, st, seed, first_object, reinterpret_cast<u64 *>(out), n);
+    KERNEL_CHECK();
+}
+
+// small signed polynomials as residues of the key primes: dst[c][j][k] = small[c][k] mod q_j, j < limbs  (blockIdx.y = c * limbs + j)
+__global__ __launch_bounds__(EW_T) void k_small_lift(const DevKey *__restrict__ key, const signed char *__restrict__ small, u64 *__restrict__ dst,
+                                                     int limbs, size_t n)
+{
+    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (k >= n) return;
+    const size_t c = blockIdx.y / limbs;
+    const int j = (int)(blockIdx.y % limbs);
+    dst[(size_t)blockIdx.y * n + k] = qs_residue(small[c * n + k], key->q[j].q);
+}
+
+void launch_small_lift(const DevKey *key, const signed char *small, u64 *dst, int limbs, size_t n, int count, hipStream_t st)
+{
+    if (!count) return;
+    hipLaunchKernelGGL(k_small_lift, ew_grid(n, count * limbs), dim3(EW_T), 0, st, key, small, dst, limbs, n);
+    KERNEL_CHECK();
+}
+
+// Encryptor::encrypt_symmetric's closing step for ciphertext c = blockIdx.y, one lane per coefficient across the limbs:
+// c0_j = Delta(m)_j - e - (c1 s)_j, canonical.  cts: [count][2][L][n] (c1 already in place), v: [count][L][n] = c1 s in coefficient
+// form, pt: [count][n] mod t, e: [count][n] int8.
+__global__ __launch_bounds__(EW_T) void k_enc_finish(const DevLevel *__restrict__ lv, const u64 *__restrict__ pt, const u64 *__restrict__ v,
+                                                     const signed char *__restrict__ e, u64 *__restrict__ cts, size_t n)
+{
+    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (k >= n) return;
+    const size_t c = blockIdx.y;
+    const int L = lv->L;
+    const u64 m = pt[c * n + k];
+    const u64 fix = plain_scale_fix(lv, m);
+    const int ek = e[c * n + k];
+    const u64 *vc = v + c * L * n;
+    u64 *c0 = cts + c * 2 * L * n;
+    for (int j = 0; j < L; j++) {
+        const u64 q = lv->q[j].q;
+        const u64 x = submod(plain_scale_limb(lv, j, m, fix), qs_residue(ek, q), q);
+        c0[j * n + k] = submod(x, vc[j * n + k], q);
+    }
+}
+
+void launch_enc_finish(const DevLevel *lv, const u64 *pt, const u64 *v, const signed char *e, u64 *cts, size_t n, int count, hipStream_t st)
+{
+    if (!count) return;
+    hipLaunchKernelGGL(k_enc_finish, ew_grid(n, count), dim3(EW_T), 0, st, lv, pt, v, e, cts, n);
+    KERNEL_CHECK();
+}
+
+// KeyGenerator::create_relin_keys' closing step in the NTT domain, key i and limb j = blockIdx.y / K, % K:
+// ksk[i][0][j] = -(a s + e) + [j == i] (p mod q_i) s^2, a = ksk[i][1][j], e: [K-1][K][n] (NTT form), s: [K][n], p = the special prime
+__global__ __launch_bounds__(EW_T) void k_rlk_finish(const DevKey *__restrict__ key, const u64 *__restrict__ s, const u64 *__restrict__ e,
+                                                     u64 *__restrict__ ksk, size_t n)
+{
+    const size_t k = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (k >= n) return;
+    const int K = key->K;
+    const int i = (int)(blockIdx.y / K), j = (int)(blockIdx.y % K);
+    const Mod mq = key->q[j];
+    const u64 sk = s[(size_t)j * n + k];
+    u64 *c0 = ksk + ((size_t)i * 2 * K + j) * n, *a = c0 + (size_t)K * n;
+    u64 r = submod(0, addmod(mulmod(a[k], sk, mq), e[((size_t)i * K + j) * n + k], mq.q), mq.q);
+    if (j == i) r = addmod(r, mulmod(mulmod(sk, sk, mq), barrett64(key->q[K - 1].q, mq), mq), mq.q);
+    c0[k] = r;
+}
+
+void launch_rlk_finish(const DevKey *key, int K, const u64 *s, const u64 *e, u64 *ksk, size_t n, hipStream_t st)
+{
+    if (K < 2) return;
+    hipLaunchKernelGGL(k_rlk_finish, ew_grid(n, (K - 1) * K), dim3(EW_T), 0, st, key, s, e, ksk, n);
     KERNEL_CHECK();
 }
 

@@ -453,9 +453,10 @@ class HeContext:
                                                              _p(blks) if want_blocks else None))
         return vals, blks
 
-    def decrypt_decode(self, sk_ntt, cts, count=None, on_device=False, want_blocks=True):
+    def decrypt_decode(self, sk_ntt, cts, count=None, on_device=False, want_blocks=True, want_budget=False):
         """N4: the querier's decrypt + decode + packing of `count` results (result_package.cpp:175-213).
-        sk_ntt: secret key mod q_0 in NTT form [n]; cts: [count][2][1][n] array, or a device pointer with on_device."""
+        sk_ntt: secret key mod q_0 in NTT form [n]; cts: [count][2][1][n] array, or a device pointer with on_device.
+        want_budget: a third return value, SEAL's invariant noise budget (bits, int32) of every result."""
         if not on_device:
             cts = np.ascontiguousarray(cts, dtype=np.uint64)
             count = cts.size // (2 * self.n)
@@ -465,9 +466,72 @@ class HeContext:
         vals = np.empty((count, self.n), dtype=np.uint64)
         blks = np.empty((count, self.info.items_per_bundle, 2), dtype=np.uint64) if want_blocks else None
         sk = np.ascontiguousarray(sk_ntt, dtype=np.uint64)
+        if want_budget:
+            bits = np.zeros(count, dtype=np.int32)
+            _check(load_library().apsu_he_decrypt_decode_budget(self.h, _p(sk), ptr, 1 if on_device else 0, C.c_uint32(count), _p(vals),
+                                                                _p(blks) if want_blocks else None, C.c_void_p(bits.ctypes.data)))
+            return vals, blks, bits
         _check(load_library().apsu_he_decrypt_decode(self.h, _p(sk), ptr, 1 if on_device else 0, C.c_uint32(count), _p(vals),
                                                      _p(blks) if want_blocks else None))
         return vals, blks
+
+    # ---- N5: the querier's side (Sender::reset_keys, Sender::create_query; sender/apsu/sender_osn.cpp:215-229,426-484)
+    @staticmethod
+    def _seed_words(seed):
+        """64 bytes or eight 64-bit words; None: fresh from the operating system (the seed is key material)"""
+        if seed is None:
+            seed = os.urandom(64)
+        if isinstance(seed, (bytes, bytearray)):
+            if len(seed) != 64:
+                raise ValueError("seed must be 64 bytes")
+            return np.frombuffer(bytes(seed), dtype="<u8").astype(np.uint64)
+        sd = np.ascontiguousarray(seed, dtype=np.uint64)
+        if sd.size != 8:
+            raise ValueError("seed must be eight 64-bit words")
+        return sd
+
+    def keygen(self, seed=None):
+        """-> sk_ntt [K][n]: a uniform ternary secret modulo every key prime, NTT form (sk_ntt[0] is what decrypt_decode takes)"""
+        sd = self._seed_words(seed)
+        sk = np.empty((self.K, self.n), dtype=np.uint64)
+        _check(load_library().apsu_he_keygen(self.h, _p(sd), _p(sk)))
+        return sk
+
+    def relin_keygen(self, sk_ntt, seed=None, want_host=True, want_resident=True):
+        """-> (ksk [K-1][2][K][n] or None, public seeds [K-1][8], RelinKeys resident on the device or None)"""
+        sd = self._seed_words(seed)
+        sk = np.ascontiguousarray(sk_ntt, dtype=np.uint64)
+        if sk.size != self.K * self.n:
+            raise ValueError("sk_ntt must hold K * n words")
+        nk = max(self.K - 1, 0)
+        ksk = np.empty((nk, 2, self.K, self.n), dtype=np.uint64) if want_host else None
+        seeds = np.empty((nk, 8), dtype=np.uint64)
+        h = C.c_void_p()
+        _check(load_library().apsu_he_relin_keygen(self.h, _p(sk), _p(sd), _p(ksk) if want_host else None, _p(seeds),
+                                                   C.byref(h) if want_resident else None))
+        return ksk, seeds, (RelinKeys(self, h) if want_resident else None)
+
+    def query_create(self, sk_ntt, bundle_indices, values, cts_dev, seed=None, values_on_device=False):
+        """Encrypted source powers of a query.  values: [len(bundle_indices)][n] slot values (< t), or a device pointer with
+        values_on_device; cts_dev: device pointer to len(bundle_indices) * source_power_count * 2 * (first_chain_idx + 1) * n words,
+        ciphertext b * source_power_count + s = source power s (ascending) of bundle_indices[b], as compute_powers(on_device=True)
+        reads them.  -> public seeds [count][8] of the ciphertexts' c1."""
+        sd = self._seed_words(seed)
+        sk = np.ascontiguousarray(sk_ntt, dtype=np.uint64)
+        if sk.size < (self.first_chain_idx + 1) * self.n:
+            raise ValueError("sk_ntt must hold the limbs of the first data level")
+        idx = np.array(bundle_indices, dtype=np.uint32)
+        if values_on_device:
+            vp = C.c_void_p(int(values))
+        else:
+            values = np.ascontiguousarray(values, dtype=np.uint64)
+            if values.size != len(idx) * self.n:
+                raise ValueError("values must hold n slot values per bundle index")
+            vp = _p(values)
+        seeds = np.empty((len(idx) * self.source_power_count, 8), dtype=np.uint64)
+        _check(load_library().apsu_he_query_create(self.h, _p(sk), _p(sd), C.c_void_p(idx.ctypes.data), len(idx), vp,
+                                                   1 if values_on_device else 0, C.c_void_p(int(cts_dev)), _p(seeds)))
+        return seeds
 
     def bundle_coeff(self, bundle, degree):
         """test hook -> (array, kind): kind 0 raw mod t, 1 NTT form [L][n], 2 pre-lifted NTT at the high level"""

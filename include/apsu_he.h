@@ -185,6 +185,48 @@ int apsu_he_mask_generate_blake2xb(apsu_he_ctx *ctx, const uint64_t seed[8], uin
                                    uint64_t *values, uint64_t *blocks);
 int apsu_he_decrypt_decode(apsu_he_ctx *ctx, const uint64_t *sk_ntt, const uint64_t *cts, int cts_on_device, uint32_t count,
                            uint64_t *values, uint64_t *blocks);
+/* ---- N5 (added after ABI 7, additive): the querier's side of the HE path -- APSU's *sender*  -----------------------
+ * apsu_he_keygen + apsu_he_relin_keygen replace Sender::reset_keys (sender/apsu/sender_osn.cpp:215-229: KeyGenerator, secret key,
+ * create_relin_keys); apsu_he_query_create replaces the prepare_data / encrypt_data blocks of Sender::create_query (:426-484:
+ * PlaintextPowers, BatchEncoder::encode, Encryptor::encrypt_symmetric; plaintext_powers.cpp:41-46,51-99);
+ * apsu_he_decrypt_decode_budget is apsu_he_decrypt_decode with the invariant noise budget ResultPackage::extract also reports
+ * (common/apsu/network/result_package.cpp:175-213).  Cuckoo hashing, OPRF and algebraization (apsu_he_algebraize_items) stay with the caller.
+ *
+ * Randomness.  SEAL draws through std::uniform_int_distribution and its bootstrap generator, which no restatement can pin; the
+ * streams here are the engine's own.  Every draw of a call is a function of u[0], u[1], ...: the 32-bit outputs of SEAL's Blake2xb
+ * generator (blake2x.h; the generator of apsu_he_mask_generate_blake2xb) under the caller's 64-byte seed[8].  A 64-bit draw at an
+ * even position p is w = u[p] + 2^32 u[p + 1].  With B = 16 outputs per 64-byte stream block:
+ *   secret s             coefficient k:  w at p = 2k                                        (blocks [0, 4096))
+ *                        s_k = floor(3 w / 2^64) - 1, uniform over {-1, 0, 1} up to 2^-64
+ *   public seed          of object o:    the 16 outputs u[B (4096 + o)], ... as eight 64-bit words   (blocks [4096, 4096 + 2^20))
+ *   noise e of object o  coefficient k:  w at p = B (2^21 + 4096 o) + 2k                    (blocks 2^21 + 4096 o + [0, 4096))
+ *                        e_k = popcount(bits 0..20 of w) - popcount(bits 21..41 of w): SEAL's centred binomial, |e| <= 21, variance 10.5
+ * Objects: o = i for relinearisation key i (i < 16); o = 16 + c for ciphertext c of apsu_he_query_create.  One noise polynomial per
+ * object, shared by its limbs.  The ranges are disjoint for every poly_modulus_degree <= 32768 and o < 2^20 (apsu_amd/csrc/query_side.h
+ * holds the constants).  The public seeds are outputs of the secret stream; nothing secret is drawn from a public seed.
+ * The seed is key material and must come from the operating system's generator.  The three calls of one querier may share a seed
+ * (their ranges are disjoint); two queries must not -- a second apsu_he_query_create needs a fresh seed.
+ *
+ * apsu_he_keygen: sk_ntt[K][n] = s modulo every key prime, NTT form; sk_ntt[0] is what apsu_he_decrypt_decode takes.
+ * apsu_he_relin_keygen: key i = (-(a_i s + e_i) + [limb == i] (p mod q_i) s^2, a_i) over the K limbs in NTT form, p = the special
+ * prime, a_i = the expansion of its public seed at the key level as apsu_he_seed_expand(chain_idx = -1) gives it.  ksk (host,
+ * [K-1][2][K][n], the layout of apsu_he_relin_upload), key_seeds (host, [K-1][8], what apsu_he_seal_relin_keys_save takes) and out (the
+ * keys resident on the device, no host round trip) may each be NULL.  A parameter set without key switching: APSU_HE_INVALID_ARGUMENT.
+ * apsu_he_query_create: values[b][n] (host, or device with values_on_device) = the slot values (algebraized items, < plain_modulus) of
+ * bundle index bundle_indices[b].  cts_dev (DEVICE memory, n_bundle_idx * source_power_count * 2 * L * n words, L = first_chain_idx + 1):
+ * ciphertext b * source_power_count + s = encryption of BatchEncoder::encode(x^e mod t per slot), e = the s-th source power (ascending);
+ * size 2, coefficient form, first data level -- the order apsu_he_compute_powers(src_on_device = 1) reads.  ct_seeds (host, [count][8]):
+ * the public seed of every c1, so that apsu_he_seal_ct_save(seed) writes the seeded object: c1 = apsu_he_seal_sample_poly_uniform(seed),
+ * c0 = Delta(m) - e - c1 s with the scaling of apsu_he_add_plain.  Every word is a canonical residue.  At most 65535 ciphertexts per call.
+ * A value >= plain_modulus, a secret-key word >= its prime, a bundle index out of range: APSU_HE_INVALID_ARGUMENT.  Synchronous.
+ * apsu_he_decrypt_decode_budget: budget_bits[count] = Decryptor::invariant_noise_budget of each result,
+ * floor(log2(q_0 / (2 max_k |t x_k mod q_0|))) with x the phase c0 + c1 s (the bit count of q_0 for a noiseless result). */
+int apsu_he_keygen(apsu_he_ctx *ctx, const uint64_t seed[8], uint64_t *sk_ntt);
+int apsu_he_relin_keygen(apsu_he_ctx *ctx, const uint64_t *sk_ntt, const uint64_t seed[8], uint64_t *ksk, uint64_t *key_seeds, apsu_he_relin **out);
+int apsu_he_query_create(apsu_he_ctx *ctx, const uint64_t *sk_ntt, const uint64_t seed[8], const uint32_t *bundle_indices, int n_bundle_idx,
+                         const uint64_t *values, int values_on_device, uint64_t *cts_dev, uint64_t *ct_seeds);
+int apsu_he_decrypt_decode_budget(apsu_he_ctx *ctx, const uint64_t *sk_ntt, const uint64_t *cts, int cts_on_device, uint32_t count,
+                                  uint64_t *values, uint64_t *blocks, int32_t *budget_bits);
 /* N1, one step earlier: util::algebraize_item (common/apsu/util/db_encoding.cpp:209-256,360-366; called at
  * receiver_db.cpp:296-298 on every OPRF'd item) for `count` hashed items of 16 bytes each: felts[i * felts_per_item + j] =
  * bits [j*b, (j+1)*b) of item i's first item_bit_count bits, read as a little-endian bit string, b = bit_count(plain_modulus) - 1.
