@@ -1225,7 +1225,7 @@ void decode_query(Engine &E, const apsu_he_seal_ctx *sc, const uint8_t *request,
             ct.coeff_modulus_size != Lf || ct.data.size() != ct_words)
             throw std::invalid_argument("query ciphertext is not a fresh size-2 ciphertext at the first data level");
         // ... and every coefficient a canonical residue of its limb's prime (seal::is_data_valid_for, part of is_valid_for): the engine's
-        // lazy transforms take source limbs as they are (Engine::run_dag, ntt_gather_nored_ok), a word >= q_j would overflow their range
+        // lazy transforms take source limbs as they are (Engine::dag_outputs, ntt_gather_nored_ok), a word >= q_j would overflow their range
         check_residues(ct.data.data(), ct.seeded ? 1 : 2, hp.key_q.data(), Lf, n, "query ciphertext holds a coefficient outside [0, q)");
         std::memcpy(host + k * ct_words, ct.data.data(), (ct.seeded ? ct_words / 2 : ct_words) * sizeof(u64));
         seeded[k] = ct.seeded ? 1 : 0;

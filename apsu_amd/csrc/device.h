@@ -7,6 +7,7 @@
 #include "modmath.h"
 #include "ntt_core.h"
 #include "ntt_form.h"
+#include "eval_plan.h"
 #include "blake2x.h"
 #include "query_side.h"
 

@@ -1393,153 +1393,166 @@ void Engine::build_schedule()
     split_ok_ = true;
 }
 
-// One walk over a (sub)schedule of the PowersDag on the current lane: sources, the level-synchronous products, and the
-// final per-power conversions (receiver_osn.cpp:395-488).
-//   stage 0: workspace + sources;  stage d >= 1: the products of depth d;  stage -1: final conversions.
-// The stages of one walk must run in order on one lane; `run` carries the walk's buffers between them, so two walks
+// One walk over a (sub)schedule of the PowersDag on the current lane: sources (dag_sources), the level-synchronous products
+// (dag_level(d), d = 1 ..), and the final per-power conversions (dag_outputs) (receiver_osn.cpp:395-488).
+// The steps of one walk must run in order on one lane; DagRun carries the walk's buffers between them, so two walks
 // (the halves of a split DAG) can be interleaved level by level on two lanes.
-struct Engine::DagRun { u64 *pwf = nullptr, *ext = nullptr, *dbuf = nullptr; size_t arena_mark = 0; int ext_done = -1; };   // ext_done: level whose parents are already extended
+struct Engine::DagRun {
+    const Sched &s; int nb; size_t n, Lf, Ef, slot_w;       // slot_w: (c0, c1, c2 scratch) per power and bundle index
+    u64 *pwf = nullptr, *ext = nullptr, *dbuf = nullptr; size_t arena_mark = 0; int ext_done = -1;   // ext_done: level whose parents are already extended
+    DagRun(const Engine &e, const Sched &s_, int nb_)
+        : s(s_), nb(nb_), n(e.hp_.n), Lf(e.hp_.first_chain_idx + 1),
+          Ef(e.dlevel(e.hp_.first_chain_idx) ? (size_t)(e.hlevel(e.hp_.first_chain_idx).L + e.hlevel(e.hp_.first_chain_idx).nB + 1) : 0), slot_w(3 * Lf * n) {}
+    u64 *slot_ptr(int slot, int b) const { return pwf + ((size_t)slot * nb + b) * slot_w; }
+    u64 *ext_ptr(int slot, int b) const { return ext + ((size_t)slot * nb + b) * 2 * Ef * n; }
+};
 
-void Engine::run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *const *src, bool on_device, const RelinKeys *rk,
-                     Powers &pwr, bool do_low, bool do_high)
+// workspace + sources (receiver_osn.cpp:304-317)
+void Engine::dag_sources(DagRun &run, const u64 *const *src, bool on_device)
 {
-    Powers *pw = &pwr;
-    const size_t n = hp_.n;
-    const int first = hp_.first_chain_idx, high = hp_.clamp_chain_idx(1);
-    const int low_target = pw->low_level;
-    const size_t Lf = first + 1, Ef = dlevel(first) ? (size_t)(hlevel(first).L + hlevel(first).nB + 1) : 0;
-    const size_t P = s.slot_power.size();
-    const size_t slot_w = 3 * Lf * n;                       // (c0, c1, c2 scratch) per power and bundle index
-    const size_t Lh = high + 1, Eh = hlevel(high).L + hlevel(high).nB + 1;
-    auto slot_ptr = [&](int slot, int b) { return run.pwf + ((size_t)slot * nb + b) * slot_w; };
-    auto ext_ptr = [&](int slot, int b) { return run.ext + ((size_t)slot * nb + b) * 2 * Ef * n; };
-    {
-        // sources (receiver_osn.cpp:304-317)
-        if (stage == 0) {
-            run.pwf = ws(P * nb * slot_w);
-            int si = 0;
-            std::vector<CtJob> cj;                               // device-resident sources: one gather launch
-            for (auto &kv : dag_.nodes()) {
-                if (!kv.second.is_source()) continue;
-                if (s.slot_of[kv.first] < 0) { si++; continue; }        // belongs to the other half of a split DAG
-                for (int b = 0; b < nb; b++) {
-                    const u64 *sp = src[(size_t)b * dag_.source_count() + si];
-                    if (on_device) cj.push_back(CtJob{ sp, slot_ptr(s.slot_of[kv.first], b) });
-                    else {                                       // host sources: a plain copy, then the same check in place (round 6)
-                        H2D(slot_ptr(s.slot_of[kv.first], b), sp, 2 * Lf * n);
-                        cj.push_back(CtJob{ slot_ptr(s.slot_of[kv.first], b), slot_ptr(s.slot_of[kv.first], b) });
-                    }
-                }
-                si++;
+    const Sched &s = run.s;
+    const size_t n = run.n, Lf = run.Lf, P = s.slot_power.size();
+    const int first = hp_.first_chain_idx, nb = run.nb;
+    run.pwf = ws(P * nb * run.slot_w);
+    int si = 0;
+    std::vector<CtJob> cj;                               // device-resident sources: one gather launch
+    for (auto &kv : dag_.nodes()) {
+        if (!kv.second.is_source()) continue;
+        if (s.slot_of[kv.first] < 0) { si++; continue; }        // belongs to the other half of a split DAG
+        for (int b = 0; b < nb; b++) {
+            const u64 *sp = src[(size_t)b * dag_.source_count() + si];
+            u64 *slot = run.slot_ptr(s.slot_of[kv.first], b);
+            if (on_device) cj.push_back(CtJob{ sp, slot });
+            else {                                       // host sources: a plain copy, then the same check in place (round 6)
+                H2D(slot, sp, 2 * Lf * n);
+                cj.push_back(CtJob{ slot, slot });
             }
-            if (!cj.empty()) { PROF(P_OTHER, 0); launch_copy_sources(upload_jobs(cj), 2 * Lf * n, (int)cj.size(), dlevel(first), (int)Lf, n, bad_source_ + query_seq_ % BAD_SLOTS, query_seq_, st_); }
-            if (s.levels.size() > 1) {
-                run.ext = ws(P * nb * 2 * Ef * n);
-                size_t max_nodes = 0;
-                for (size_t d = 1; d < s.levels.size(); d++) max_nodes = std::max(max_nodes, (size_t)(s.levels[d].s1 - s.levels[d].s0));
-                run.dbuf = ws(max_nodes * nb * 3 * Ef * n);
-            }
-            run.arena_mark = arena_off_;
-            return;
         }
-        if (stage > 0) {
-            if ((size_t)stage >= s.levels.size()) return;
-            u64 *dbuf = run.dbuf;
-            {
-                const size_t d = (size_t)stage;
-                arena_off_ = run.arena_mark;
-                // extend + NTT the parents that became available at depth d-1
-                const auto &pl = s.levels[d - 1];
-                const int npar = pl.sp - pl.s0;
-                if (npar > 0) {
-                    // (parents that came out of a key switch were extended by its mod-down kernel: run.ext_done)
-                    if (run.ext_done != (int)d - 1) { PROFW(P_BEHZ_EXT, (size_t)npar * nb * 2 * n * (Lf + Ef)); launch_behz_ext(dlevel(first), hlevel(first).L, hlevel(first).nB, slot_ptr(pl.s0, 0), slot_w, 2, ext_ptr(pl.s0, 0), n, npar * nb, st_); }
-                    d_ntt(ext_ptr(pl.s0, 0), (size_t)npar * nb * 2 * Ef, map_ext(first), (int)Ef, false, ext_primes_narrow_);
-                }
-                const auto &cl = s.levels[d];
-                const int nn = cl.s1 - cl.s0;
-                if (nn <= 0) return;
-                std::vector<TensorJob> tj;
-                std::vector<FinishJob> fj;
-                for (auto &nd : s.nodes) {
-                    if (nd[0] < cl.s0 || nd[0] >= cl.s1) continue;
-                    for (int b = 0; b < nb; b++) {
-                        u64 *dd = dbuf + ((size_t)(nd[0] - cl.s0) * nb + b) * 3 * Ef * n;
-                        tj.push_back(TensorJob{ ext_ptr(nd[1], b), ext_ptr(nd[2], b), dd });
-                        fj.push_back(FinishJob{ dd, slot_ptr(nd[0], b), 1, 0 });
-                    }
-                }
-                if (fuse_tensor_) {                                                                                              // :422/:424
-                    PROF(P_NTT_FUSED, tj.size() * 3 * Ef);
-                    launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Ef, Ef * n, nullptr, 0, tabs(), map_ext_fin(first), (int)Ef, st_, ntt_latency_limbs_);
-                } else {
-                    { PROF(P_TENSOR, 0); launch_tensor(dlevel(first), upload_jobs(tj), n, (int)tj.size(), st_); }
-                    d_ntt(dbuf, (size_t)nn * nb * 3 * Ef, map_ext_fin(first), (int)Ef, true, ext_primes_narrow_);
-                }
-                { PROFW(P_BEHZ_FINISH, fj.size() * 3 * n * (Ef + Lf)); launch_behz_finish(dlevel(first), hlevel(first).L, hlevel(first).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
-                if (hp_.using_keyswitching && nn > 0) {                                                                          // :431
-                    const int npar_here = ((size_t)d + 1 < s.levels.size()) ? (cl.sp - cl.s0) : 0;
-                    if (d_relinearize(slot_ptr(cl.s0, 0), slot_w, nn * nb, *rk, first, npar_here ? ext_ptr(cl.s0, 0) : nullptr, npar_here * nb))
-                        run.ext_done = (int)d;
-                }
-            }
-            return;
-        }
-        arena_off_ = run.arena_mark;
-        // final per-power conversions (receiver_osn.cpp:459-487)
-        auto convert = [&](const std::vector<uint32_t> &powers, int target, u64 *out) {
-            if (powers.empty()) return;
-            const int cnt = (int)powers.size() * nb;
-            std::vector<CtJob> jobs;
-            int lvl = first;
-            u64 *cur = nullptr;
-            auto dst_for = [&](int level_after) -> u64 * {
-                return level_after == target ? out : ws((size_t)cnt * 2 * (level_after + 1) * n);
-            };
-            if (first == target) {
-                for (size_t i = 0; i < powers.size(); i++)
-                    for (int b = 0; b < nb; b++)
-                        jobs.push_back(CtJob{ slot_ptr(s.slot_of[powers[i]], b), out + ((size_t)b * powers.size() + i) * 2 * Lf * n });
-                { PROF(P_OTHER, 0); launch_copy_jobs(upload_jobs(jobs), 2 * Lf * n, cnt, st_); }
-                return;
-            }
-            cur = dst_for(first - 1);
-            for (size_t i = 0; i < powers.size(); i++)
-                for (int b = 0; b < nb; b++)
-                    jobs.push_back(CtJob{ slot_ptr(s.slot_of[powers[i]], b), cur + ((size_t)b * powers.size() + i) * 2 * (Lf - 1) * n });
-            { PROFW(P_MODSWITCH, (size_t)cnt * 2 * n * (2 * Lf - 1)); launch_modswitch_jobs(dlevel(first), upload_jobs(jobs), 2, n, cnt, st_); }                     // :463,471,478
-            lvl = first - 1;
-            while (lvl > target) {
-                u64 *nxt = dst_for(lvl - 1);
-                { PROFW(P_MODSWITCH, (size_t)cnt * 2 * n * (2 * lvl + 1)); launch_modswitch(dlevel(lvl), cur, (size_t)2 * (lvl + 1) * n, 2, nxt, n, cnt, st_); }
-                cur = nxt;
-                lvl--;
-            }
-        };
-        if (do_low && first == low_target && !s.low_powers.empty()) {
-            // no level change: the forward NTT (:467,475) reads the slots and writes the packed output directly
-            const size_t np = s.low_powers.size();
-            std::vector<const u64 *> srcp(np * nb * 2 * Lf);
-            for (int b = 0; b < nb; b++)
-                for (size_t i = 0; i < np; i++)
-                    for (size_t pl = 0; pl < 2 * Lf; pl++)
-                        srcp[(((size_t)b * np + i) * 2 * Lf) + pl] = slot_ptr(s.slot_of[s.low_powers[i]], b) + pl * n;
-            // (limb j of a slot is already a canonical residue of q_j: nothing to reduce)
-            bool nored = hp_.logn <= 14;
-            for (size_t j = 0; j < Lf && nored; j++) nored = ntt_gather_nored_ok(hp_.key_q[j], hp_.key_q[j], hp_.logn);
-            PROF(P_NTT_FWD, srcp.size());
-            launch_ntt_gather(hp_.logn, upload_jobs(srcp), pw->low.u(), srcp.size(), tabs(), map_ct(), (int)Lf, st_, nored, ntt_latency_limbs_, data_primes_narrow_);
-        } else if (do_low) {
-            convert(s.low_powers, low_target, pw->low.u());
-            d_ntt_ct(pw->low.u(), (size_t)pw->n_low * nb * 2, low_target, false);                      // :467,475
-        }
-        if (do_high && pw->n_high) {
-            convert(s.high_powers, high, pw->high.u());
-            // derived form used by eval_patstock's ct x ct products and coefficient-form plaintext products
-            { PROFW(P_BEHZ_EXT, (size_t)pw->n_high * nb * 2 * n * (Lh + Eh)); launch_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, pw->high.u(), Lh * n, 1, pw->hext.u(), n, (int)(pw->n_high * nb * 2), st_); }
-            d_ntt(pw->hext.u(), (size_t)pw->n_high * nb * 2 * Eh, map_ext(high), (int)Eh, false, ext_primes_narrow_);
+        si++;
+    }
+    if (!cj.empty()) { PROF(P_OTHER, 0); launch_copy_sources(upload_jobs(cj), 2 * Lf * n, (int)cj.size(), dlevel(first), (int)Lf, n, bad_source_ + query_seq_ % BAD_SLOTS, query_seq_, st_); }
+    if (s.levels.size() > 1) {
+        run.ext = ws(P * nb * 2 * run.Ef * n);
+        size_t max_nodes = 0;
+        for (size_t d = 1; d < s.levels.size(); d++) max_nodes = std::max(max_nodes, (size_t)(s.levels[d].s1 - s.levels[d].s0));
+        run.dbuf = ws(max_nodes * nb * 3 * run.Ef * n);
+    }
+    run.arena_mark = arena_off_;
+}
+
+// the products of depth d >= 1 (nothing when the schedule is shallower)
+void Engine::dag_level(DagRun &run, size_t d, const RelinKeys *rk)
+{
+    const Sched &s = run.s;
+    if (d >= s.levels.size()) return;
+    const size_t n = run.n, Lf = run.Lf, Ef = run.Ef;
+    const int first = hp_.first_chain_idx, nb = run.nb;
+    arena_off_ = run.arena_mark;
+    // extend + NTT the parents that became available at depth d-1
+    const auto &pl = s.levels[d - 1];
+    const int npar = pl.sp - pl.s0;
+    if (npar > 0) {
+        // (parents that came out of a key switch were extended by its mod-down kernel: run.ext_done)
+        if (run.ext_done != (int)d - 1) { PROFW(P_BEHZ_EXT, (size_t)npar * nb * 2 * n * (Lf + Ef)); launch_behz_ext(dlevel(first), hlevel(first).L, hlevel(first).nB, run.slot_ptr(pl.s0, 0), run.slot_w, 2, run.ext_ptr(pl.s0, 0), n, npar * nb, st_); }
+        d_ntt(run.ext_ptr(pl.s0, 0), (size_t)npar * nb * 2 * Ef, map_ext(first), (int)Ef, false, ext_primes_narrow_);
+    }
+    const auto &cl = s.levels[d];
+    const int nn = cl.s1 - cl.s0;
+    if (nn <= 0) return;
+    std::vector<TensorJob> tj;
+    std::vector<FinishJob> fj;
+    for (auto &nd : s.nodes) {
+        if (nd[0] < cl.s0 || nd[0] >= cl.s1) continue;
+        for (int b = 0; b < nb; b++) {
+            u64 *dd = run.dbuf + ((size_t)(nd[0] - cl.s0) * nb + b) * 3 * Ef * n;
+            tj.push_back(TensorJob{ run.ext_ptr(nd[1], b), run.ext_ptr(nd[2], b), dd });
+            fj.push_back(FinishJob{ dd, run.slot_ptr(nd[0], b), 1, 0 });
         }
     }
+    if (fuse_tensor_) {                                                                                              // :422/:424
+        PROF(P_NTT_FUSED, tj.size() * 3 * Ef);
+        launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Ef, Ef * n, nullptr, 0, tabs(), map_ext_fin(first), (int)Ef, st_, ntt_latency_limbs_);
+    } else {
+        { PROF(P_TENSOR, 0); launch_tensor(dlevel(first), upload_jobs(tj), n, (int)tj.size(), st_); }
+        d_ntt(run.dbuf, (size_t)nn * nb * 3 * Ef, map_ext_fin(first), (int)Ef, true, ext_primes_narrow_);
+    }
+    { PROFW(P_BEHZ_FINISH, fj.size() * 3 * n * (Ef + Lf)); launch_behz_finish(dlevel(first), hlevel(first).L, hlevel(first).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
+    if (hp_.using_keyswitching) {                                                                                    // :431
+        const int npar_here = (d + 1 < s.levels.size()) ? (cl.sp - cl.s0) : 0;
+        if (d_relinearize(run.slot_ptr(cl.s0, 0), run.slot_w, nn * nb, *rk, first, npar_here ? run.ext_ptr(cl.s0, 0) : nullptr, npar_here * nb))
+            run.ext_done = (int)d;
+    }
+}
+
+// final per-power conversions (receiver_osn.cpp:459-487)
+void Engine::dag_outputs(DagRun &run, Powers &pw, bool do_low, bool do_high)
+{
+    const Sched &s = run.s;
+    const size_t n = run.n, Lf = run.Lf;
+    const int first = hp_.first_chain_idx, high = hp_.clamp_chain_idx(1), nb = run.nb;
+    const size_t Lh = high + 1, Eh = hlevel(high).L + hlevel(high).nB + 1;
+    arena_off_ = run.arena_mark;
+    auto convert = [&](const std::vector<uint32_t> &powers, int target, u64 *out) {
+        if (powers.empty()) return;
+        const int cnt = (int)powers.size() * nb;
+        std::vector<CtJob> jobs;
+        int lvl = first;
+        u64 *cur = nullptr;
+        auto dst_for = [&](int level_after) -> u64 * {
+            return level_after == target ? out : ws((size_t)cnt * 2 * (level_after + 1) * n);
+        };
+        if (first == target) {
+            for (size_t i = 0; i < powers.size(); i++)
+                for (int b = 0; b < nb; b++)
+                    jobs.push_back(CtJob{ run.slot_ptr(s.slot_of[powers[i]], b), out + ((size_t)b * powers.size() + i) * 2 * Lf * n });
+            { PROF(P_OTHER, 0); launch_copy_jobs(upload_jobs(jobs), 2 * Lf * n, cnt, st_); }
+            return;
+        }
+        cur = dst_for(first - 1);
+        for (size_t i = 0; i < powers.size(); i++)
+            for (int b = 0; b < nb; b++)
+                jobs.push_back(CtJob{ run.slot_ptr(s.slot_of[powers[i]], b), cur + ((size_t)b * powers.size() + i) * 2 * (Lf - 1) * n });
+        { PROFW(P_MODSWITCH, (size_t)cnt * 2 * n * (2 * Lf - 1)); launch_modswitch_jobs(dlevel(first), upload_jobs(jobs), 2, n, cnt, st_); }                     // :463,471,478
+        lvl = first - 1;
+        while (lvl > target) {
+            u64 *nxt = dst_for(lvl - 1);
+            { PROFW(P_MODSWITCH, (size_t)cnt * 2 * n * (2 * lvl + 1)); launch_modswitch(dlevel(lvl), cur, (size_t)2 * (lvl + 1) * n, 2, nxt, n, cnt, st_); }
+            cur = nxt;
+            lvl--;
+        }
+    };
+    if (do_low && first == pw.low_level && !s.low_powers.empty()) {
+        // no level change: the forward NTT (:467,475) reads the slots and writes the packed output directly
+        const size_t np = s.low_powers.size();
+        std::vector<const u64 *> srcp(np * nb * 2 * Lf);
+        for (int b = 0; b < nb; b++)
+            for (size_t i = 0; i < np; i++)
+                for (size_t pl = 0; pl < 2 * Lf; pl++)
+                    srcp[(((size_t)b * np + i) * 2 * Lf) + pl] = run.slot_ptr(s.slot_of[s.low_powers[i]], b) + pl * n;
+        // (limb j of a slot is already a canonical residue of q_j: nothing to reduce)
+        bool nored = hp_.logn <= 14;
+        for (size_t j = 0; j < Lf && nored; j++) nored = ntt_gather_nored_ok(hp_.key_q[j], hp_.key_q[j], hp_.logn);
+        PROF(P_NTT_FWD, srcp.size());
+        launch_ntt_gather(hp_.logn, upload_jobs(srcp), pw.low.u(), srcp.size(), tabs(), map_ct(), (int)Lf, st_, nored, ntt_latency_limbs_, data_primes_narrow_);
+    } else if (do_low) {
+        convert(s.low_powers, pw.low_level, pw.low.u());
+        d_ntt_ct(pw.low.u(), (size_t)pw.n_low * nb * 2, pw.low_level, false);                         // :467,475
+    }
+    if (do_high && pw.n_high) {
+        convert(s.high_powers, high, pw.high.u());
+        // derived form used by eval_patstock's ct x ct products and coefficient-form plaintext products
+        { PROFW(P_BEHZ_EXT, (size_t)pw.n_high * nb * 2 * n * (Lh + Eh)); launch_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, pw.high.u(), Lh * n, 1, pw.hext.u(), n, (int)(pw.n_high * nb * 2), st_); }
+        d_ntt(pw.hext.u(), (size_t)pw.n_high * nb * 2 * Eh, map_ext(high), (int)Eh, false, ext_primes_narrow_);
+    }
+}
+
+// the whole of one walk on the current lane
+void Engine::dag_walk(const Sched &s, int nb, const u64 *const *src, bool on_device, const RelinKeys *rk, Powers &pw)
+{
+    DagRun r(*this, s, nb);
+    dag_sources(r, src, on_device);
+    for (size_t d = 1; d < s.levels.size(); d++) dag_level(r, d, rk);
+    dag_outputs(r, pw, true, true);
 }
 
 std::unique_ptr<Powers> Engine::compute_powers(const uint32_t *bundle_indices, int nb, const u64 *const *src, bool on_device,
@@ -1651,23 +1664,17 @@ std::unique_ptr<Powers> Engine::compute_powers(const uint32_t *bundle_indices, i
         if (pipe) {
             switch_lane(1);
             if (plan.side_waits_last_use) HIP_CHECK(hipStreamWaitEvent(st_, pw->last_use, 0));
-            DagRun r;
-            run_dag(sched_, r, 0, nb, src, on_device, rk, *pw, true, true);
-            for (int d = 1; d < (int)sched_.levels.size(); d++) run_dag(sched_, r, d, nb, src, on_device, rk, *pw, true, true);
-            run_dag(sched_, r, -1, nb, src, on_device, rk, *pw, true, true);
+            dag_walk(sched_, nb, src, on_device, rk, *pw);
             HIP_CHECK(hipEventRecord(pw->high_ready, st_));
             switch_lane(0);
         } else if (!split) {
-            DagRun r;
-            run_dag(sched_, r, 0, nb, src, on_device, rk, *pw, true, true);
-            for (int d = 1; d < (int)sched_.levels.size(); d++) run_dag(sched_, r, d, nb, src, on_device, rk, *pw, true, true);
-            run_dag(sched_, r, -1, nb, src, on_device, rk, *pw, true, true);
+            dag_walk(sched_, nb, src, on_device, rk, *pw);
         } else {
             // everything queued so far on the main stream (the previous query's evaluation may still read a pooled
             // Powers buffer) precedes the second stream's work; the two walks are queued level by level so that
             // both streams have work from the start
-            DagRun rl, rh;
-            const int depth = (int)std::max(sched_low_.levels.size(), sched_high_.levels.size());
+            DagRun rl(*this, sched_low_, nb), rh(*this, sched_high_, nb);
+            const size_t depth = std::max(sched_low_.levels.size(), sched_high_.levels.size());
             // (round 4: with device-resident inputs that the caller has declared complete -- apsu_he_set_query_overlap; lane 1 reads
             //  the sources and the relinearisation keys, which a caller may otherwise still be producing on the main stream -- the
             //  second stream waits for the LAST READER of this powers buffer -- the
@@ -1675,21 +1682,21 @@ std::unique_ptr<Powers> Engine::compute_powers(const uint32_t *bundle_indices, i
             //  query's high-power chain then runs next to the tail of the query in front of it, whose launches leave CUs idle)
             //  (plan.side_waits_main / side_waits_last_use; a pooled buffer whose reader left no mark waits for all)
             if (plan.side_waits_main) HIP_CHECK(hipEventRecord(ev_main_, st_));
-            run_dag(sched_low_, rl, 0, nb, src, on_device, rk, *pw, true, false);
+            dag_sources(rl, src, on_device);
             switch_lane(1);
             if (plan.side_waits_main) HIP_CHECK(hipStreamWaitEvent(st_, ev_main_, 0));
             else if (plan.side_waits_last_use) HIP_CHECK(hipStreamWaitEvent(st_, pw->last_use, 0));
-            run_dag(sched_high_, rh, 0, nb, src, on_device, rk, *pw, false, true);
-            for (int d = 1; d < depth; d++) {
+            dag_sources(rh, src, on_device);
+            for (size_t d = 1; d < depth; d++) {
                 switch_lane(0);
-                run_dag(sched_low_, rl, d, nb, src, on_device, rk, *pw, true, false);
+                dag_level(rl, d, rk);
                 switch_lane(1);
-                run_dag(sched_high_, rh, d, nb, src, on_device, rk, *pw, false, true);
+                dag_level(rh, d, rk);
             }
             switch_lane(0);
-            run_dag(sched_low_, rl, -1, nb, src, on_device, rk, *pw, true, false);
+            dag_outputs(rl, *pw, true, false);
             switch_lane(1);
-            run_dag(sched_high_, rh, -1, nb, src, on_device, rk, *pw, false, true);
+            dag_outputs(rh, *pw, false, true);
             // (starting the high-power chain only when the low-power chain -- the evaluation's critical path -- has finished was
             //  measured in round 3: level on the whole query, 21 % slower on the N = 8 shard; profiles/r03_ab_fusions.txt)
             HIP_CHECK(hipEventRecord(pw->high_ready, st_));
@@ -2396,10 +2403,9 @@ struct Engine::EvalCall {
     const u64 *hext_ptr(uint32_t i, int b) const { return pw.hext.u() + (((size_t)b * pw.n_high + (i - 1)) * 2) * Eh * n; }
     u64 *res_ptr(int i) const { return out_rows ? out_rows[c0 + i] : res + (size_t)i * 2 * n; }
     const u64 *mask_ptr(int i) const { return masks_on_device ? masks[c0 + i] : mask_d + (size_t)i * n; }
+    const Bundle &bundle(int i) const { return *bundles[c0 + i]; }   // i: position in the chunk
+    int slot(int i) const { return bslot[c0 + i]; }
 };
-// which forms of the Paterson-Stockmeyer steps this call takes (decided once per chunk in eval_patstock)
-struct Engine::PsPlan { bool i0_fast, need_vlast, raw_drop, raw_i0, async_high, late_high; };
-
 // One batch: every Paterson-Stockmeyer BinBundle of the chunk, ordered by bundle index (the shared powers of
 // one index then stay in the same L2).  (Cutting the batch into groups whose database scans overlap the previous
 // group's VALU-bound tail on a second stream was built and measured in rounds 2 and 3, also with an LDS-DMA
@@ -2408,117 +2414,104 @@ struct Engine::PsPlan { bool i0_fast, need_vlast, raw_drop, raw_i0, async_high, 
 struct PsBatch {
     std::vector<int> ids;                               // positions in this chunk
     std::vector<int> nin, in_off;                       // inner polynomials per BinBundle, prefix offsets
-    int NI = 0;
+    int Bs = 0, NI = 0;
     u64 *inner = nullptr, *ssum = nullptr, *vlast = nullptr, *term = nullptr, *cf = nullptr;
     std::vector<int> imap;                              // modulus of every limb polynomial of the merged block
+    const int *imap_dev = nullptr;
+    size_t n_vlast_side = 0;                            // limb polynomials at the end of the block that the side lane transforms back
     const MacJob *mac_jobs = nullptr;
     int n_mac = 0;
     uint64_t units = 0; uint32_t mean_cnt = 0; bool mac_is_packed = false;
     const TermJob *term_jobs = nullptr;                 // the i = 0 block's per-term products on the dropped limb (k_term_product)
     size_t n_term = 0; bool term_packed = false;
+    // what the steps of ps_run hand on: the extended inner polynomials, the summed products, the deferred mod-down of the last
+    // key switch (or nullptr), the side lane's i = 0 addend
+    u64 *ext = nullptr, *result = nullptr, *ks_acc = nullptr, *i0_side = nullptr;
 };
 
 // BatchedPlaintextPolyn::eval (bin_bundle.cpp:106-174) for the BinBundles pl_ids of the chunk
 void Engine::eval_plain(EvalCall &c, const std::vector<int> &pl_ids)
 {
-    const size_t n = c.n, Ll = c.Ll;
-    const int low = c.low, c0 = c.c0;
-    const Bundle *const *bundles = c.bundles;
-    const std::vector<int> &bslot = c.bslot;
-    const u32 low_term_stride = c.low_term_stride;
-    auto low_ptr = [&](uint32_t power, int b) { return c.low_ptr(power, b); };
-    auto res_ptr = [&](int i) { return c.res_ptr(i); };
-    auto mask_ptr = [&](int i) { return c.mask_ptr(i); };
     const int Bp = (int)pl_ids.size();
-    const int lvl = low;                                   // level of powers[1]
+    const int lvl = c.low;                                 // level of powers[1]
     const size_t Lv = lvl + 1;
-    u64 *acc = ws((size_t)Bp * 2 * Lv * n);
+    u64 *acc = ws((size_t)Bp * 2 * Lv * c.n);
     std::vector<MacStream> ms;
     std::vector<EpiJob> ej;
     for (int x = 0; x < Bp; x++) {
-        const Bundle &b = *bundles[c0 + pl_ids[x]];
-        u64 *o = acc + (size_t)x * 2 * Lv * n;
-        if (b.degree) ms.push_back(MacStream{ bundle_slot(b, false, 0, Lv * n), low_ptr(1, bslot[c0 + pl_ids[x]]), o, b.degree,
-                                              bundle_stride(b, false, Lv * n), low_term_stride, (u32)(Ll * n), (u32)(Lv * n), 0, (u32)Lv,
+        const Bundle &b = c.bundle(pl_ids[x]);
+        u64 *o = acc + (size_t)x * 2 * Lv * c.n;
+        if (b.degree) ms.push_back(MacStream{ bundle_slot(b, false, 0, Lv * c.n), c.low_ptr(1, c.slot(pl_ids[x])), o, b.degree,
+                                              bundle_stride(b, false, Lv * c.n), c.low_term_stride, (u32)(c.Ll * c.n), (u32)(Lv * c.n), 0, (u32)Lv,
                                               (u32)b.packed });   // :140-149
-        else HIP_CHECK(hipMemsetAsync(o, 0, 2 * Lv * n * sizeof(u64), st_));
-        ej.push_back(EpiJob{ o, nullptr, nullptr, b.a0.u(), mask_ptr(pl_ids[x]), res_ptr(pl_ids[x]) });
+        else HIP_CHECK(hipMemsetAsync(o, 0, 2 * Lv * c.n * sizeof(u64), st_));
+        ej.push_back(EpiJob{ o, nullptr, nullptr, b.a0.u(), c.mask_ptr(pl_ids[x]), c.res_ptr(pl_ids[x]) });
     }
-    { auto mj = group_mac(ms); PROF(P_MAC, mac_units(mj)); launch_mac(dlevel(lvl), (int)Lv, upload_jobs(mj), n, (int)mj.size(), st_, mac_kara(lvl, mac_mean_cnt(mj)), mac_packed(mj)); }
+    { auto mj = group_mac(ms); PROF(P_MAC, mac_units(mj)); launch_mac(dlevel(lvl), (int)Lv, upload_jobs(mj), c.n, (int)mj.size(), st_, mac_kara(lvl, mac_mean_cnt(mj)), mac_packed(mj)); }
     d_ntt_ct(acc, (size_t)Bp * 2, lvl, true);                                                 // :154
     // :159 add_plain(a_0), :162 add_plain(mask), :168-170 mod switch to the last level, :171 clear bits
-    { PROFW(P_MODSWITCH, (size_t)Bp * n * (2 * Lv + 4)); launch_eval_epilogue(dlevel(0), lvl, upload_jobs(ej), Lv * n, hp_.irrelevant_bit_count, n, Bp, st_); }
+    { PROFW(P_MODSWITCH, (size_t)Bp * c.n * (2 * Lv + 4)); launch_eval_epilogue(dlevel(0), lvl, upload_jobs(ej), Lv * c.n, hp_.irrelevant_bit_count, c.n, Bp, st_); }
 }
 
 // the sums of the pre-lifted coefficient-form plaintexts, sum_i lift(a_{i*h}) (.) C^{i*h} (bin_bundle.cpp:328-337), as MAC streams
 void Engine::ps_cf_streams(const EvalCall &c, const PsBatch &g, std::vector<MacStream> &out)
 {
-    const size_t n = c.n, Lh = c.Lh, Eh = c.Eh;
-    const int c0 = c.c0;
-    const Bundle *const *bundles = c.bundles;
-    const std::vector<int> &bslot = c.bslot;
-    auto hext_ptr = [&](uint32_t i, int b) { return c.hext_ptr(i, b); };
-    for (size_t x = 0; x < g.ids.size(); x++) {
-        const Bundle &b = *bundles[c0 + g.ids[x]];
-        out.push_back(MacStream{ bundle_slot(b, true, 0, Lh * n), hext_ptr(1, bslot[c0 + g.ids[x]]), g.cf + x * 2 * Lh * n, b.H,
-                                 bundle_stride(b, true, Lh * n), (u32)((size_t)2 * Eh * n), (u32)(Eh * n), (u32)(Lh * n), 0, (u32)Lh,
+    for (int x = 0; x < g.Bs; x++) {
+        const Bundle &b = c.bundle(g.ids[x]);
+        out.push_back(MacStream{ bundle_slot(b, true, 0, c.Lh * c.n), c.hext_ptr(1, c.slot(g.ids[x])), g.cf + (size_t)x * 2 * c.Lh * c.n, b.H,
+                                 bundle_stride(b, true, c.Lh * c.n), (u32)((size_t)2 * c.Eh * c.n), (u32)(c.Eh * c.n), (u32)(c.Lh * c.n), 0, (u32)c.Lh,
                                  (u32)b.packed });
     }
 }
+// ... as a launch of their own on the current stream, where they did not join the main multiply-accumulate (CF_SIDE_LANE, CF_BEHIND_HIGH_READY)
+void Engine::ps_cf_mac(const EvalCall &c, const PsBatch &g)
+{
+    std::vector<MacStream> cs;
+    ps_cf_streams(c, g, cs);
+    auto mj = group_mac(cs);
+    PROF(P_MAC, mac_units(mj));
+    launch_mac(dlevel(c.high), (int)c.Lh, upload_jobs(mj), c.n, (int)mj.size(), st_, mac_kara(c.high, mac_mean_cnt(mj)), mac_packed(mj));
+}
 
-// BatchedPlaintextPolyn::eval_patstock (bin_bundle.cpp:192-360) for the BinBundles ps_ids of the chunk: the plan, the batch, its
-// job tables (ps_tables) and the launch sequence (ps_run)
+// BatchedPlaintextPolyn::eval_patstock (bin_bundle.cpp:192-360) for the BinBundles ps_ids of the chunk: the batch, the plan
+// (eval_plan.h, plan_eval: every form decision, enumerated on the CPU tier), the job tables (ps_tables) and the launch sequence (ps_run)
 void Engine::eval_patstock(EvalCall &c, const std::vector<int> &ps_ids)
 {
-    const size_t Ll = c.Ll;
-    const uint32_t l = c.l;
-    const int high = c.high, low = c.low, c0 = c.c0;
-    const Powers &pw = c.pw;
-    const std::vector<int> &bslot = c.bslot;
-    // i = 0 block (:314-324): every term C^j (.) a_j is INTT'd and rounded to the high level ON ITS OWN before
-    // the sum (note N1).  With one dropped limb the sum of the rounded terms is
-    //   (sum_j c_j[m] + l*half - sum_j ((c_j[last] + half) mod q_last)) * q_last^-1  mod q_m,
-    // where the first sum is exact and may be taken in the NTT domain.  So only the LAST limb of each term
-    // needs its own inverse transform (2 per term instead of 2*L_low), bit-identical to the reference.
-    const bool i0_fast = (low - high <= 1) && ((unsigned __int128)(l + 1) * hlevel(low).q[Ll - 1] < ((unsigned __int128)1 << 64));
-    const bool need_vlast = i0_fast && low > high;
-    // RAW inverse transforms (no twist, no final reduction) where the consumer's own constants absorb the twist:
-    // the inner polynomials when the fused drop + extension kernel takes them, the i = 0 block's sums and last limbs
-    const bool raw_drop = low == high + 1 && hlevel(high).L == hlevel(high).nB && hlevel(high).L <= 3;
-    const bool raw_i0 = need_vlast;
+    if (c.low < c.high) throw std::logic_error("the low powers lie below the high powers");
     PsBatch g;
     g.ids = ps_ids;
-    std::stable_sort(g.ids.begin(), g.ids.end(), [&](int a, int b) { return bslot[c0 + a] < bslot[c0 + b]; });
-    // high powers still in flight on the second stream (split ComputePowers): everything that needs only the low
-    // powers goes first, the cf products (which read the high powers) come later
-    const bool async_high = pw.high_async && pw.high_ready;
-    const bool late_high = async_high;
-    const PsPlan plan{ i0_fast, need_vlast, raw_drop, raw_i0, async_high, late_high };
+    std::stable_sort(g.ids.begin(), g.ids.end(), [&](int a, int b) { return c.slot(a) < c.slot(b); });
+    g.Bs = (int)g.ids.size();
+    // inner polynomials i = 1..H (block H only if r > 0)                     :248-304
+    g.nin.resize(g.Bs); g.in_off.resize(g.Bs);
+    EvalState s{};
+    for (int x = 0; x < g.Bs; x++) {
+        const Bundle &b = c.bundle(g.ids[x]);
+        g.nin[x] = (int)b.H - (b.r == 0 ? 1 : 0);
+        g.in_off[x] = g.NI;
+        g.NI += g.nin[x];
+        s.max_terms = std::max(s.max_terms, g.nin[x]);
+    }
+    s.low = c.low; s.high = c.high;
+    s.L = hlevel(c.high).L; s.nB = hlevel(c.high).nB;
+    s.l = c.l; s.q_last = hlevel(c.low).q[c.Ll - 1];
+    for (size_t j = 0; j < c.Lh; j++) s.q_widest = std::max(s.q_widest, hlevel(c.high).q[j]);
+    s.Bs = g.Bs;
+    s.high_in_flight = c.pw.high_async && c.pw.high_ready;
+    s.eval_side = eval_side_; s.prof_on = prof_on_; s.force_per_term = force_per_term_; s.fuse_tensor = fuse_tensor_; s.fuse_tail = fuse_tail_;
+    s.lane2 = lanes_[2].st != nullptr; s.on_lane0 = cur_lane_ == 0;
+    const EvalPlan plan = plan_eval(s);
     ps_tables(c, plan, g);
     ps_run(c, plan, g);
 }
 
 // phase A: workspace and the job array of the multiply-accumulate
-void Engine::ps_tables(EvalCall &c, const PsPlan &plan, PsBatch &g)
+void Engine::ps_tables(EvalCall &c, const EvalPlan &plan, PsBatch &g)
 {
     const size_t n = c.n, Ll = c.Ll, Lh = c.Lh;
     const uint32_t l = c.l;
-    const int c0 = c.c0;
-    const Bundle *const *bundles = c.bundles;
-    const std::vector<int> &bslot = c.bslot;
-    const u32 low_term_stride = c.low_term_stride;
-    auto low_ptr = [&](uint32_t power, int b) { return c.low_ptr(power, b); };
-    const bool i0_fast = plan.i0_fast, need_vlast = plan.need_vlast, raw_drop = plan.raw_drop, raw_i0 = plan.raw_i0;
-    const bool late_high = plan.late_high;
-    const int Bs = (int)g.ids.size();
-    // inner polynomials i = 1..H (block H only if r > 0)                     :248-304
-    g.nin.resize(Bs); g.in_off.resize(Bs);
-    for (int x = 0; x < Bs; x++) {
-        const Bundle &b = *bundles[c0 + g.ids[x]];
-        g.nin[x] = (int)b.H - (b.r == 0 ? 1 : 0);
-        g.in_off[x] = g.NI;
-        g.NI += g.nin[x];
-    }
+    const int Bs = g.Bs;
+    const bool cf_here = plan.cf == CF_WITH_MAC;
     // Every dyadic multiply-accumulate of the evaluation reads only the query powers and the database, so
     // all of a group run as ONE launch, and their results share ONE inverse-NTT launch:
     //   inner [NI][2][Ll]   sum_j C^j (.) a_{i*h+j}                                  :258-264
@@ -2526,63 +2519,63 @@ void Engine::ps_tables(EvalCall &c, const PsPlan &plan, PsBatch &g)
     //   vlast [Bs*l][2][1]  C^j (.) a_j on the dropped limb, per term               (i = 0 block, fast form)
     //   term  [Bs*l][2][Ll] C^j (.) a_j, per term                                   (i = 0 block, general form)
     //   cf    [Bs][2][Lh]   sum_i lift(a_{i*h}) (.) C^{i*h}                          :328-337 (exact)
-    const size_t w_inner = (size_t)g.NI * 2 * Ll * n, w_ssum = i0_fast ? (size_t)Bs * 2 * Lh * n : 0;
-    const size_t w_vlast = need_vlast ? (size_t)Bs * l * 2 * n : 0, w_term = i0_fast ? 0 : (size_t)Bs * l * 2 * Ll * n;
+    const size_t w_inner = (size_t)g.NI * 2 * Ll * n, w_ssum = plan.i0_fast ? (size_t)Bs * 2 * Lh * n : 0;
+    const size_t w_vlast = plan.need_vlast ? (size_t)Bs * l * 2 * n : 0, w_term = plan.i0_fast ? 0 : (size_t)Bs * l * 2 * Ll * n;
     const size_t w_cf = (size_t)Bs * 2 * Lh * n;
-    g.inner = ws(w_inner + w_ssum + w_vlast + w_term + (late_high ? 0 : w_cf));
+    g.inner = ws(w_inner + w_ssum + w_vlast + w_term + (cf_here ? w_cf : 0));
     g.ssum = g.inner + w_inner; g.vlast = g.ssum + w_ssum; g.term = g.vlast + w_vlast;
-    g.cf = late_high ? nullptr : g.term + w_term;
+    g.cf = cf_here ? g.term + w_term : nullptr;
     std::vector<MacStream> ms;
     auto map_push = [&](size_t polys, int first_limb, int limbs) {
         for (size_t p = 0; p < polys; p++) for (int j = 0; j < limbs; j++) g.imap.push_back(first_limb + j);
     };
     for (int x = 0; x < Bs; x++) {
-        const Bundle &b = *bundles[c0 + g.ids[x]];
-        const int bs = bslot[c0 + g.ids[x]];
+        const Bundle &b = c.bundle(g.ids[x]);
         for (int i = 1; i <= g.nin[x]; i++) {
             const u32 cnt = (u32)i < b.H ? l : b.r;
-            ms.push_back(MacStream{ bundle_slot(b, false, (size_t)i * l, Ll * n), low_ptr(1, bs),
+            ms.push_back(MacStream{ bundle_slot(b, false, (size_t)i * l, Ll * n), c.low_ptr(1, c.slot(g.ids[x])),
                                     g.inner + ((size_t)g.in_off[x] + i - 1) * 2 * Ll * n, cnt,
-                                    bundle_stride(b, false, Ll * n), low_term_stride, (u32)(Ll * n), (u32)(Ll * n), 0, (u32)Ll,
+                                    bundle_stride(b, false, Ll * n), c.low_term_stride, (u32)(Ll * n), (u32)(Ll * n), 0, (u32)Ll,
                                     (u32)b.packed });
         }
     }
     map_push((size_t)g.NI * 2, 0, (int)Ll);
-    if (raw_drop) for (int &v : g.imap) v |= NTT_MAP_RAW;          // consumed by the fused drop + extension only
-    if (i0_fast) {
+    if (plan.raw_drop) for (int &v : g.imap) v |= NTT_MAP_RAW;     // consumed by the fused drop + extension only
+    if (plan.i0_fast) {
         for (int x = 0; x < Bs; x++) {
-            const Bundle &b = *bundles[c0 + g.ids[x]];
-            ms.push_back(MacStream{ bundle_slot(b, false, 0, Ll * n), low_ptr(1, bslot[c0 + g.ids[x]]), g.ssum + (size_t)x * 2 * Lh * n, l,
-                                    bundle_stride(b, false, Ll * n), low_term_stride, (u32)(Ll * n), (u32)(Lh * n), 0, (u32)Lh,
+            const Bundle &b = c.bundle(g.ids[x]);
+            ms.push_back(MacStream{ bundle_slot(b, false, 0, Ll * n), c.low_ptr(1, c.slot(g.ids[x])), g.ssum + (size_t)x * 2 * Lh * n, l,
+                                    bundle_stride(b, false, Ll * n), c.low_term_stride, (u32)(Ll * n), (u32)(Lh * n), 0, (u32)Lh,
                                     (u32)b.packed });
         }
         map_push((size_t)Bs * 2, 0, (int)Lh);
-        if (raw_i0) for (size_t x = g.imap.size() - (size_t)Bs * 2 * Lh; x < g.imap.size(); x++) g.imap[x] |= NTT_MAP_RAW;
+        if (plan.raw_i0) for (size_t x = g.imap.size() - (size_t)Bs * 2 * Lh; x < g.imap.size(); x++) g.imap[x] |= NTT_MAP_RAW;
     }
     std::vector<TermJob> tj;
-    if (need_vlast || !i0_fast) {
+    if (plan.need_vlast || !plan.i0_fast) {
         for (int x = 0; x < Bs; x++) {
-            const Bundle &b = *bundles[c0 + g.ids[x]];
-            const int bs = bslot[c0 + g.ids[x]];
-            if (i0_fast) {
+            const Bundle &b = c.bundle(g.ids[x]);
+            const int bs = c.slot(g.ids[x]);
+            if (plan.i0_fast) {
                 if (x == 0) g.term_packed = b.packed;
                 else if (g.term_packed != (bool)b.packed) throw std::logic_error("BinBundles of one evaluation differ in their row format");
             }
             for (u32 j = 1; j <= l; j++) {
-                if (i0_fast)                                 // the dropped limb of every term by itself: k_term_product (not k_mac chains of length one)
-                    tj.push_back(TermJob{ bundle_slot(b, false, j - 1, Ll * n), low_ptr(j, bs), g.vlast + ((size_t)x * l + j - 1) * 2 * n });
+                if (plan.i0_fast)                            // the dropped limb of every term by itself: k_term_product (not k_mac chains of length one)
+                    tj.push_back(TermJob{ bundle_slot(b, false, j - 1, Ll * n), c.low_ptr(j, bs), g.vlast + ((size_t)x * l + j - 1) * 2 * n });
                 else
-                    ms.push_back(MacStream{ bundle_slot(b, false, j - 1, Ll * n), low_ptr(j, bs),
-                                            g.term + ((size_t)x * l + j - 1) * 2 * Ll * n, 1, bundle_stride(b, false, Ll * n), low_term_stride,
+                    ms.push_back(MacStream{ bundle_slot(b, false, j - 1, Ll * n), c.low_ptr(j, bs),
+                                            g.term + ((size_t)x * l + j - 1) * 2 * Ll * n, 1, bundle_stride(b, false, Ll * n), c.low_term_stride,
                                             (u32)(Ll * n), (u32)(Ll * n), 0, (u32)Ll, (u32)b.packed });
             }
         }
-        if (i0_fast) {
+        if (plan.i0_fast) {
             map_push((size_t)Bs * l * 2, (int)Ll - 1, 1);
-            if (raw_i0) for (size_t x = g.imap.size() - (size_t)Bs * l * 2; x < g.imap.size(); x++) g.imap[x] |= NTT_MAP_RAW;
+            if (plan.raw_i0) for (size_t x = g.imap.size() - (size_t)Bs * l * 2; x < g.imap.size(); x++) g.imap[x] |= NTT_MAP_RAW;
         } else map_push((size_t)Bs * l * 2, 0, (int)Ll);
     }
-    if (!late_high) { ps_cf_streams(c, g, ms); map_push((size_t)Bs * 2, 0, (int)Lh); }
+    if (plan.side_i0) g.n_vlast_side = (size_t)Bs * l * 2;
+    if (cf_here) { ps_cf_streams(c, g, ms); map_push((size_t)Bs * 2, 0, (int)Lh); }
     auto mj = group_mac(ms);
     g.mac_jobs = upload_jobs(mj);
     g.n_mac = (int)mj.size();
@@ -2592,235 +2585,228 @@ void Engine::ps_tables(EvalCall &c, const PsPlan &plan, PsBatch &g)
     if (!tj.empty()) { g.term_jobs = upload_jobs(tj); g.n_term = tj.size(); }
 }
 
-// ---- phase B: the multiply-accumulate (the level-`low` constants serve every limb: levels share their leading
-// primes) and everything behind it
-void Engine::ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g)
+// ---- phase B: the launch sequence.  The steps below, in the order ps_run takes them; each reads the call (c), the plan and what the
+// steps before it left in the batch (g).
+// the i = 0 block's per-term products on the dropped limb, on the current stream
+void Engine::ps_term_product(const EvalCall &c, const PsBatch &g)
 {
-    const size_t n = c.n, Ll = c.Ll, Lh = c.Lh, Eh = c.Eh;
-    const uint32_t l = c.l;
-    const int high = c.high, low = c.low, c0 = c.c0;
-    const Powers &pw = c.pw;
-    const Bundle *const *bundles = c.bundles;
-    const std::vector<int> &bslot = c.bslot;
-    auto hext_ptr = [&](uint32_t i, int b) { return c.hext_ptr(i, b); };
-    auto res_ptr = [&](int i) { return c.res_ptr(i); };
-    auto mask_ptr = [&](int i) { return c.mask_ptr(i); };
-    const bool i0_fast = plan.i0_fast, raw_drop = plan.raw_drop, raw_i0 = plan.raw_i0;
-    const bool async_high = plan.async_high, late_high = plan.late_high;
-    auto cf_streams = [&](const PsBatch &gg, std::vector<MacStream> &out) { ps_cf_streams(c, gg, out); };
-    const RelinKeys *rk = c.rk;
-    const int Bs = (int)g.ids.size(), NI = g.NI;
-    const std::vector<int> &nin = g.nin, &in_off = g.in_off;
-    u64 *inner = g.inner, *ssum = g.ssum, *vlast = g.vlast, *term = g.term;
-    { PROF(P_MAC, g.units); launch_mac(dlevel(low), (int)Ll, g.mac_jobs, n, g.n_mac, st_, mac_kara(low, g.mean_cnt), g.mac_is_packed); }
-    // Side lane (rounds 4, 5): see below.  side_tp (round 5): the i = 0 block's per-term products and THEIR inverse transforms leave the main
-    // stream too -- they feed only the i = 0 finish, which runs on the side lane anyway -- so the main chain behind k_mac starts with the
-    // inner polynomials alone: -0.017 ms (-0.5 %) on the latency of the 16M-4096 query over four order-balanced A/B runs, -1.7 % on the
-    // N = 8 shard, same bits (profiles/r05_ab_side_term_product.txt)
-    const bool side_tp = eval_side_ && plan.late_high && !prof_on_ && i0_fast && low != high && lanes_[2].st && cur_lane_ == 0 &&
-                         (size_t)Bs * l <= 4096 && g.n_term && plan.need_vlast;
-    const size_t n_vlast = side_tp ? (size_t)Bs * l * 2 : 0;
-    const int *imap_dev = upload_jobs(g.imap);
-    if (side_tp) HIP_CHECK(hipEventRecord(ev_fork_, st_));    // behind k_mac (the powers and the database are read-only from here on)
-    else if (g.n_term) { PROF(P_MAC, (uint64_t)g.n_term * (g.term_packed ? packed_row_bits(hp_.key_q[Ll - 1]) : 64)); launch_term_product(dlevel(low), g.term_jobs, g.n_term, n, (int)Ll - 1, (u32)(Ll * n), (u32)n, g.term_packed, st_); }
-    d_ntt(inner, g.imap.size() - n_vlast, imap_dev, (int)g.imap.size(), true, false);               // :268,297,320,333
-    if (side_tp) HIP_CHECK(hipEventRecord(ev_intt_, st_));
+    PROF(P_MAC, (uint64_t)g.n_term * (g.term_packed ? packed_row_bits(hp_.key_q[c.Ll - 1]) : 64));
+    launch_term_product(dlevel(c.low), g.term_jobs, g.n_term, c.n, (int)c.Ll - 1, (u32)(c.Ll * c.n), (u32)c.n, g.term_packed, st_);
+}
+// the i = 0 block's finish with one dropped limb (launch_i0_finish), on the current stream: one exact [2][Lh][n] addend per BinBundle
+void Engine::ps_i0_finish(const EvalCall &c, const EvalPlan &plan, const PsBatch &g, u64 *i0)
+{
+    std::vector<I0Job> ij;
+    for (int x = 0; x < g.Bs; x++)
+        ij.push_back(I0Job{ g.ssum + (size_t)x * 2 * c.Lh * c.n, g.vlast + (size_t)x * c.l * 2 * c.n, i0 + (size_t)x * 2 * c.Lh * c.n, (int)c.l, 1 });
+    PROFW(P_MODSWITCH, (size_t)g.Bs * c.n * (4 * c.Lh + 2 * c.l));
+    launch_i0_finish(dlevel(c.low), upload_jobs(ij), c.n, g.Bs, st_, plan.raw_i0);
+}
 
-    // Side lane (round 4).  Two pieces of the evaluation hang off nothing that follows on the main stream: the sums of the
-    // coefficient-form products (they read the high powers and the database, :328-337) and the i = 0 block's finish (it reads the
-    // inverse transforms above).  Both are launches that cannot fill the chip (224 workgroups of 28-term chains; one pass over
-    // the per-term last limbs) and used to sit in the tail of the main stream, where nothing could hide them.  They run on a
-    // third stream (lane 2; the first of them waits for the high-power chain's event) next to the drop / extension / transform
-    // launches, and the epilogue waits for them.  (With pipelined queries the next query's ComputePowers fills the same holes and the
-    // lane is level, profiles/r04_ab_eval_side.txt; it still serves a query that runs alone.)
-    const bool side = eval_side_ && late_high && !prof_on_ && i0_fast && low != high && lanes_[2].st && cur_lane_ == 0;
-    // (the i = 0 finish only while it is small: 256M-4096's reads 4 GB of per-term limbs, a bandwidth-bound pass that gains nothing
-    //  from running next to the transforms -- measured +0.9 % there, -1.2 % at 16M-4096, -4.2 % on its N = 8 shard; profiles/r04_ab_eval_side.txt)
-    const bool side_i0 = side && (size_t)Bs * l <= 4096;
-    u64 *i0_side = nullptr;
-    if (side) {
-        g.cf = ws((size_t)Bs * 2 * Lh * n);
-        if (side_i0) i0_side = ws((size_t)Bs * 2 * Lh * n);
-    }
-    bool side_ran = false;
-    auto run_side = [&]() {
-        side_ran = true;
-        std::vector<MacStream> cs;
-        cf_streams(g, cs);
-        std::vector<I0Job> ij;
-        if (side_i0)
-            for (int x = 0; x < Bs; x++)
-                ij.push_back(I0Job{ ssum + (size_t)x * 2 * Lh * n, vlast + (size_t)x * l * 2 * n, i0_side + (size_t)x * 2 * Lh * n, (int)l, 1 });
-        if (!side_tp) HIP_CHECK(hipEventRecord(ev_fork_, st_));
-        switch_lane(2);
-        struct Back { Engine *e; ~Back() { e->switch_lane(0); } } back{ this };
-        HIP_CHECK(hipStreamWaitEvent(st_, ev_fork_, 0));
-        if (side_tp) {
-            launch_term_product(dlevel(low), g.term_jobs, g.n_term, n, (int)Ll - 1, (u32)(Ll * n), (u32)n, g.term_packed, st_);
-            d_ntt(vlast, n_vlast, imap_dev + (g.imap.size() - n_vlast), (int)n_vlast, true, false);
-        }
-        if (async_high) HIP_CHECK(hipStreamWaitEvent(st_, pw.high_ready, 0));   // the cf sums read the high powers (second stream)
-        { auto mj = group_mac(cs); launch_mac(dlevel(high), (int)Lh, upload_jobs(mj), n, (int)mj.size(), st_, mac_kara(high, mac_mean_cnt(mj)), mac_packed(mj)); }
-        d_ntt_ct(g.cf, (size_t)Bs * 2, high, true);
-        if (side_tp) HIP_CHECK(hipStreamWaitEvent(st_, ev_intt_, 0));            // the i = 0 finish also reads the sums the main stream transforms back
-        if (side_i0) launch_i0_finish(dlevel(low), upload_jobs(ij), n, Bs, st_, raw_i0);
-        HIP_CHECK(hipEventRecord(ev_side_, st_));
-    };
-    // the side lane starts behind the inverse transforms above, next to the drop / extension / transform launches (starting it behind the
-    // tensor-on-load transform instead, next to the finish and the key switch of the sums, measured level: profiles/r04_ab_eval_side.txt)
-    if (side) run_side();
-    const bool late_cf = late_high && !side;                 // the cf sums on the main stream, behind the wait for the high powers
+// 1. the multiply-accumulate (the level-`low` constants serve every limb: levels share their leading primes), the i = 0 block's term
+// products and the merged inverse transform.  With I0_SIDE the term products and their transforms are left to the side lane:
+// ev_fork_ marks the end of k_mac (the powers and the database are read-only from here on), ev_intt_ the end of the transforms.
+void Engine::ps_mac(EvalCall &c, const EvalPlan &plan, PsBatch &g)
+{
+    { PROF(P_MAC, g.units); launch_mac(dlevel(c.low), (int)c.Ll, g.mac_jobs, c.n, g.n_mac, st_, mac_kara(c.low, g.mean_cnt), g.mac_is_packed); }
+    g.imap_dev = upload_jobs(g.imap);
+    if (plan.side_i0) HIP_CHECK(hipEventRecord(ev_fork_, st_));
+    else if (g.n_term) ps_term_product(c, g);
+    d_ntt(g.inner, g.imap.size() - g.n_vlast_side, g.imap_dev, (int)g.imap.size(), true, false);    // :268,297,320,333
+    if (plan.side_i0) HIP_CHECK(hipEventRecord(ev_intt_, st_));
+}
 
-    // mod switch to the high level (:269,298), then ct x ct with the high powers (:272,301): extend, NTT,
-    // tensor, INTT, finish (+ sum over i, :273,303).  A single drop is folded into the extension's pass.
-    u64 *ext = ws((size_t)NI * 2 * Eh * n);
-    bool fused_drop = false;
-    if (low == high + 1) {
-        PROFW(P_BEHZ_EXT, (size_t)NI * 2 * n * (Ll + Eh));
-        fused_drop = launch_drop_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, inner, Ll * n, 1, ext, n, NI * 2, st_, raw_drop);
+// 2. the side lane (plan.side; why and what: eval_plan.h): the cf sums and, with I0_SIDE, the whole i = 0 block behind k_mac.  It starts
+// behind the inverse transforms above, next to the drop / extension / transform launches (starting it behind the tensor-on-load
+// transform instead, next to the finish and the key switch of the sums, measured level: profiles/r04_ab_eval_side.txt), and ends
+// with ev_side_.
+void Engine::ps_side(EvalCall &c, const EvalPlan &plan, PsBatch &g)
+{
+    g.cf = ws((size_t)g.Bs * 2 * c.Lh * c.n);
+    if (plan.side_i0) g.i0_side = ws((size_t)g.Bs * 2 * c.Lh * c.n);
+    else HIP_CHECK(hipEventRecord(ev_fork_, st_));
+    switch_lane(2);
+    struct Back { Engine *e; ~Back() { e->switch_lane(0); } } back{ this };
+    HIP_CHECK(hipStreamWaitEvent(st_, ev_fork_, 0));
+    if (plan.side_i0) {
+        ps_term_product(c, g);
+        d_ntt(g.vlast, g.n_vlast_side, g.imap_dev + (g.imap.size() - g.n_vlast_side), (int)g.n_vlast_side, true, false);
     }
-    if (!fused_drop) {
-        u64 *innerh = inner;
-        for (int lv = low; lv > high; lv--) {
+    if (plan.wait_high_ready) HIP_CHECK(hipStreamWaitEvent(st_, c.pw.high_ready, 0));   // the cf sums read the high powers (second stream)
+    ps_cf_mac(c, g);
+    d_ntt_ct(g.cf, (size_t)g.Bs * 2, c.high, true);
+    if (plan.side_i0) {
+        HIP_CHECK(hipStreamWaitEvent(st_, ev_intt_, 0));     // the i = 0 finish also reads the sums the main stream transforms back
+        ps_i0_finish(c, plan, g, g.i0_side);
+    }
+    HIP_CHECK(hipEventRecord(ev_side_, st_));
+}
+
+// 3. the inner polynomials: mod switch to the high level (:269,298), extension to q u Bsk and forward transform, ready for the
+// ct x ct products.  A single drop is folded into the extension's pass (plan.fused_drop), which then reads RAW transforms.
+void Engine::ps_drop_ext(EvalCall &c, const EvalPlan &plan, PsBatch &g)
+{
+    const size_t n = c.n;
+    const int NI = g.NI;
+    const LevelConstants &h = hlevel(c.high);
+    g.ext = ws((size_t)NI * 2 * c.Eh * n);
+    if (plan.fused_drop) {
+        PROFW(P_BEHZ_EXT, (size_t)NI * 2 * n * (c.Ll + c.Eh));
+        if (!launch_drop_behz_ext(dlevel(c.high), h.L, h.nB, g.inner, c.Ll * n, 1, g.ext, n, NI * 2, st_, plan.raw_drop))
+            throw std::logic_error("the plan takes the fused drop + extension, the kernel table has none for this level");
+    } else {
+        u64 *innerh = g.inner;
+        for (int lv = c.low; lv > c.high; lv--) {
             u64 *nxt = ws((size_t)NI * 2 * lv * n);
             { PROFW(P_MODSWITCH, (size_t)NI * 2 * n * (2 * lv + 1)); launch_modswitch(dlevel(lv), innerh, (size_t)2 * (lv + 1) * n, 2, nxt, n, NI, st_); }
             innerh = nxt;
         }
-        { PROFW(P_BEHZ_EXT, (size_t)NI * 2 * n * (Lh + Eh)); launch_behz_ext(dlevel(high), hlevel(high).L, hlevel(high).nB, innerh, Lh * n, 1, ext, n, NI * 2, st_); }
+        { PROFW(P_BEHZ_EXT, (size_t)NI * 2 * n * (c.Lh + c.Eh)); launch_behz_ext(dlevel(c.high), h.L, h.nB, innerh, c.Lh * n, 1, g.ext, n, NI * 2, st_); }
     }
-    d_ntt(ext, (size_t)NI * 2 * Eh, map_ext(high), (int)Eh, false, ext_primes_narrow_);
-    if (async_high) HIP_CHECK(hipStreamWaitEvent(st_, pw.high_ready, 0));
-    u64 *result = ws((size_t)Bs * 3 * Lh * n);                                                  // :238-240
-    // The products of one BinBundle are summed (:273,303).  Each keeps its own rounding (note N1), but only
-    // the q limbs are needed per term for that: the Bsk limbs are summed in the NTT domain by the tensor
-    // kernel and finished once per BinBundle (see behz_finish_coeff).  Bit-identical, 6 instead of 15
-    // inverse transforms per term at L = 2.
-    int max_terms = 0;
-    for (int x = 0; x < Bs; x++) max_terms = std::max(max_terms, nin[x]);
-    // the summed finish adds per-term canonical residues of EVERY q limb as plain integers: the widest limb bounds it
-    u64 q_widest = 0;
-    for (size_t j = 0; j < Lh; j++) q_widest = std::max(q_widest, hlevel(high).q[j]);
-    const bool summed = !force_per_term_ && Lh <= 4 &&
-                        (unsigned __int128)max_terms * q_widest < ((unsigned __int128)1 << 63);
-    const size_t w_cf = (size_t)Bs * 2 * Lh * n;
-    if (summed) {
-        const size_t nBskh = Eh - Lh;
-        u64 *dq = ws((size_t)NI * 3 * Lh * n + (size_t)Bs * 3 * nBskh * n + (late_cf ? w_cf : 0));
-        u64 *bsum = dq + (size_t)NI * 3 * Lh * n;
-        if (late_cf) {                                      // the cf sums join this inverse-NTT launch
-            g.cf = bsum + (size_t)Bs * 3 * nBskh * n;
-            std::vector<MacStream> cs;
-            cf_streams(g, cs);
-            auto mj = group_mac(cs); PROF(P_MAC, mac_units(mj)); launch_mac(dlevel(high), (int)Lh, upload_jobs(mj), n, (int)mj.size(), st_, mac_kara(high, mac_mean_cnt(mj)), mac_packed(mj));
-        }
-        std::vector<TensorSumJob> tj;
-        std::vector<FinishSumJob> fj;
-        std::vector<int> dmap;
-        for (int x = 0; x < Bs; x++) {
-            if (!nin[x]) { HIP_CHECK(hipMemsetAsync(result + (size_t)x * 3 * Lh * n, 0, 3 * Lh * n * sizeof(u64), st_)); continue; }
-            const size_t job = (size_t)in_off[x];
-            tj.push_back(TensorSumJob{ ext + job * 2 * Eh * n, hext_ptr(1, bslot[c0 + g.ids[x]]), dq + job * 3 * Lh * n,
-                                       bsum + (size_t)x * 3 * nBskh * n, nin[x], 0 });
-            fj.push_back(FinishSumJob{ dq + job * 3 * Lh * n, bsum + (size_t)x * 3 * nBskh * n, result + (size_t)x * 3 * Lh * n, nin[x], 0 });
-        }
-        // (the finish applies the inverse transform's twist itself where it is the unrolled kernel: raw output)
-        const int rawf = fast_finish(high) ? NTT_MAP_RAW : 0;
-        for (size_t p = 0; p < (size_t)NI * 3; p++) for (size_t j = 0; j < Lh; j++) dmap.push_back((int)j | rawf);
-        for (size_t p = 0; p < (size_t)Bs * 3; p++) for (size_t i = 0; i < nBskh; i++) dmap.push_back(hp_.bsk_id(hlevel(high).nB, (int)i) | rawf);
-        if (late_cf) for (size_t p = 0; p < (size_t)Bs * 2; p++) for (size_t j = 0; j < Lh; j++) dmap.push_back((int)j);
-        if (fuse_tensor_) {
-            // per-term q limbs: product formed by the inverse transform's load; the Bsk sums (and cf) join the launch
-            std::vector<TensorJob> pj;
-            for (int x = 0; x < Bs; x++)
-                for (int i = 0; i < nin[x]; i++) {
-                    const size_t job = (size_t)in_off[x] + i;
-                    pj.push_back(TensorJob{ ext + job * 2 * Eh * n, hext_ptr(1 + i, bslot[c0 + g.ids[x]]), dq + job * 3 * Lh * n });
-                }
-            // (only the Bsk limbs: four operand limbs per term in, three sums per BinBundle out)
-            { PROFW(P_TENSOR, ((size_t)NI * 4 + (size_t)Bs * 3) * (Eh - Lh) * n); launch_tensor_sum(dlevel(high), (int)Eh, upload_jobs(tj), n, (int)tj.size(), (int)Lh, st_); }
-            PROF(P_NTT_FUSED, dmap.size());
-            launch_intt_tensor(hp_.logn, upload_jobs(pj), (int)pj.size(), (int)Lh, Eh * n, bsum, dmap.size() - pj.size() * 3 * Lh,
-                               tabs(), upload_jobs(dmap), (int)dmap.size(), st_, ntt_latency_limbs_);
-        } else {
-            { PROFW(P_TENSOR, ((size_t)NI * 4 * Eh + (size_t)NI * 3 * Lh + (size_t)Bs * 3 * (Eh - Lh)) * n); launch_tensor_sum(dlevel(high), (int)Eh, upload_jobs(tj), n, (int)tj.size(), 0, st_); }
-            d_ntt(dq, dmap.size(), upload_jobs(dmap), (int)dmap.size(), true, false);
-        }
-        { PROFW(P_BEHZ_FINISH, ((size_t)NI * 3 * Lh + (size_t)Bs * 3 * (Eh - Lh) + (size_t)Bs * 3 * Lh) * n); launch_behz_finish_sum(dlevel(high), hlevel(high).L, hlevel(high).nB, upload_jobs(fj), n, (int)fj.size(), st_); }
-    } else {
-        if (late_cf) {
-            g.cf = ws(w_cf);
-            std::vector<MacStream> cs;
-            cf_streams(g, cs);
-            { auto mj = group_mac(cs); PROF(P_MAC, mac_units(mj)); launch_mac(dlevel(high), (int)Lh, upload_jobs(mj), n, (int)mj.size(), st_, mac_kara(high, mac_mean_cnt(mj)), mac_packed(mj)); }
-            d_ntt_ct(g.cf, (size_t)Bs * 2, high, true);
-        }
-        u64 *dbuf = ws((size_t)NI * 3 * Eh * n);
-        // every (BinBundle, block) product is finished (x t, floor, Bsk -> q) by its own threads, then the
-        // per-term results are summed per BinBundle (:273,303): the roundings stay per term (note N1)
-        u64 *tbuf = ws((size_t)NI * 3 * Lh * n);
-        std::vector<TensorJob> tj;
-        std::vector<FinishJob> fj;
-        std::vector<SumJob> sj;
-        for (int x = 0; x < Bs; x++) {
-            const int bs = bslot[c0 + g.ids[x]];
-            for (int i = 1; i <= nin[x]; i++) {
-                const size_t job = (size_t)in_off[x] + i - 1;
-                tj.push_back(TensorJob{ ext + job * 2 * Eh * n, hext_ptr(i, bs), dbuf + job * 3 * Eh * n });
-                fj.push_back(FinishJob{ dbuf + job * 3 * Eh * n, tbuf + job * 3 * Lh * n, 1, 0 });
-            }
-            sj.push_back(SumJob{ tbuf + (size_t)in_off[x] * 3 * Lh * n, result + (size_t)x * 3 * Lh * n, nin[x], 0 });
-        }
-        if (fuse_tensor_ && tj.size() == (size_t)NI) {
-            PROF(P_NTT_FUSED, tj.size() * 3 * Eh);
-            launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Eh, Eh * n, nullptr, 0, tabs(), map_ext_fin(high), (int)Eh, st_, ntt_latency_limbs_);
-        } else {
-            if (!tj.empty()) { PROF(P_TENSOR, 0); launch_tensor(dlevel(high), upload_jobs(tj), n, (int)tj.size(), st_); }
-            d_ntt(dbuf, (size_t)NI * 3 * Eh, map_ext_fin(high), (int)Eh, true, ext_primes_narrow_);
-        }
-        { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(high), hlevel(high).L, hlevel(high).nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
-        { PROF(P_BEHZ_FINISH, 0); launch_sum_jobs(dlevel(high), (int)Lh, upload_jobs(sj), 3, n, Bs, st_); }
-    }
-    // (round 6: the mod-down of this last key switch is performed by the epilogue kernel below, on the way in: one launch fewer at the
-    //  end of every query, the updated (c0, c1) never go to memory; APSU_HE_FUSE_TAIL=0 keeps the launch)
-    u64 *ks_acc = nullptr;
-    d_relinearize(result, 3 * Lh * n, Bs, *rk, high, nullptr, 0, fuse_tail_ ? &ks_acc : nullptr);   // :308-310
+    d_ntt(g.ext, (size_t)NI * 2 * c.Eh, map_ext(c.high), (int)c.Eh, false, ext_primes_narrow_);
+}
 
-    // i = 0 block, reduced to one exact [2][Lh][n] addend per BinBundle
-    u64 *i0 = nullptr;
-    if (side && !side_ran) run_side();                        // (paths without the fused tensor launch)
-    if (side) HIP_CHECK(hipStreamWaitEvent(st_, ev_side_, 0));
-    if (side_i0) {
-        i0 = i0_side;
-    } else if (i0_fast && low == high) {
-        i0 = ssum;
-    } else if (i0_fast) {
-        i0 = ws((size_t)Bs * 2 * Lh * n);
-        std::vector<I0Job> ij;
+// 4. ct x ct with the high powers (:272,301) and the sum over i (:273,303), summed finish (plan.summed; why it is bit-identical:
+// eval_plan.h): tensor, INTT, one finish per BinBundle.  With CF_BEHIND_HIGH_READY the cf sums join the inverse-NTT launch.
+void Engine::ps_products_summed(EvalCall &c, const EvalPlan &plan, PsBatch &g)
+{
+    const size_t n = c.n, Lh = c.Lh, Eh = c.Eh, nBskh = Eh - Lh;
+    const int Bs = g.Bs, NI = g.NI;
+    const LevelConstants &h = hlevel(c.high);
+    const bool late_cf = plan.cf == CF_BEHIND_HIGH_READY;
+    g.result = ws((size_t)Bs * 3 * Lh * n);                                                     // :238-240
+    u64 *dq = ws((size_t)NI * 3 * Lh * n + (size_t)Bs * 3 * nBskh * n + (late_cf ? (size_t)Bs * 2 * Lh * n : 0));
+    u64 *bsum = dq + (size_t)NI * 3 * Lh * n;
+    if (late_cf) {
+        g.cf = bsum + (size_t)Bs * 3 * nBskh * n;
+        ps_cf_mac(c, g);
+    }
+    std::vector<TensorSumJob> tj;
+    std::vector<FinishSumJob> fj;
+    std::vector<int> dmap;
+    for (int x = 0; x < Bs; x++) {
+        if (!g.nin[x]) { HIP_CHECK(hipMemsetAsync(g.result + (size_t)x * 3 * Lh * n, 0, 3 * Lh * n * sizeof(u64), st_)); continue; }
+        const size_t job = (size_t)g.in_off[x];
+        tj.push_back(TensorSumJob{ g.ext + job * 2 * Eh * n, c.hext_ptr(1, c.slot(g.ids[x])), dq + job * 3 * Lh * n,
+                                   bsum + (size_t)x * 3 * nBskh * n, g.nin[x], 0 });
+        fj.push_back(FinishSumJob{ dq + job * 3 * Lh * n, bsum + (size_t)x * 3 * nBskh * n, g.result + (size_t)x * 3 * Lh * n, g.nin[x], 0 });
+    }
+    // (the finish applies the inverse transform's twist itself where it is the unrolled kernel: raw output)
+    const int rawf = fast_finish(c.high) ? NTT_MAP_RAW : 0;
+    for (size_t p = 0; p < (size_t)NI * 3; p++) for (size_t j = 0; j < Lh; j++) dmap.push_back((int)j | rawf);
+    for (size_t p = 0; p < (size_t)Bs * 3; p++) for (size_t i = 0; i < nBskh; i++) dmap.push_back(hp_.bsk_id(h.nB, (int)i) | rawf);
+    if (late_cf) for (size_t p = 0; p < (size_t)Bs * 2; p++) for (size_t j = 0; j < Lh; j++) dmap.push_back((int)j);
+    if (plan.fuse_tensor) {
+        // per-term q limbs: product formed by the inverse transform's load; the Bsk sums (and cf) join the launch
+        std::vector<TensorJob> pj;
         for (int x = 0; x < Bs; x++)
-            ij.push_back(I0Job{ ssum + (size_t)x * 2 * Lh * n, vlast + (size_t)x * l * 2 * n, i0 + (size_t)x * 2 * Lh * n, (int)l, 1 });
-        { PROFW(P_MODSWITCH, (size_t)Bs * n * (4 * Lh + 2 * l)); launch_i0_finish(dlevel(low), upload_jobs(ij), n, Bs, st_, raw_i0); }
+            for (int i = 0; i < g.nin[x]; i++) {
+                const size_t job = (size_t)g.in_off[x] + i;
+                pj.push_back(TensorJob{ g.ext + job * 2 * Eh * n, c.hext_ptr(1 + i, c.slot(g.ids[x])), dq + job * 3 * Lh * n });
+            }
+        // (only the Bsk limbs: four operand limbs per term in, three sums per BinBundle out)
+        { PROFW(P_TENSOR, ((size_t)NI * 4 + (size_t)Bs * 3) * (Eh - Lh) * n); launch_tensor_sum(dlevel(c.high), (int)Eh, upload_jobs(tj), n, (int)tj.size(), (int)Lh, st_); }
+        PROF(P_NTT_FUSED, dmap.size());
+        launch_intt_tensor(hp_.logn, upload_jobs(pj), (int)pj.size(), (int)Lh, Eh * n, bsum, dmap.size() - pj.size() * 3 * Lh,
+                           tabs(), upload_jobs(dmap), (int)dmap.size(), st_, ntt_latency_limbs_);
     } else {
-        u64 *termh = term;
-        for (int lv = low; lv > high; lv--) {
-            u64 *nxt = ws((size_t)Bs * l * 2 * lv * n);
-            { PROFW(P_MODSWITCH, (size_t)Bs * l * 2 * n * (2 * lv + 1)); launch_modswitch(dlevel(lv), termh, (size_t)2 * (lv + 1) * n, 2, nxt, n, Bs * (int)l, st_); }
+        { PROFW(P_TENSOR, ((size_t)NI * 4 * Eh + (size_t)NI * 3 * Lh + (size_t)Bs * 3 * (Eh - Lh)) * n); launch_tensor_sum(dlevel(c.high), (int)Eh, upload_jobs(tj), n, (int)tj.size(), 0, st_); }
+        d_ntt(dq, dmap.size(), upload_jobs(dmap), (int)dmap.size(), true, false);
+    }
+    { PROFW(P_BEHZ_FINISH, ((size_t)NI * 3 * Lh + (size_t)Bs * 3 * (Eh - Lh) + (size_t)Bs * 3 * Lh) * n); launch_behz_finish_sum(dlevel(c.high), h.L, h.nB, upload_jobs(fj), n, (int)fj.size(), st_); }
+}
+
+// 5. the same with the per-term finish (the fallback: APSU_HE_EVAL_PER_TERM, more than four limbs, or terms * q_widest >= 2^63): every
+// (BinBundle, block) product is finished (x t, floor, Bsk -> q) by its own threads, then the per-term results are summed per
+// BinBundle (:273,303): the roundings stay per term (note N1)
+void Engine::ps_products_per_term(EvalCall &c, const EvalPlan &plan, PsBatch &g)
+{
+    const size_t n = c.n, Lh = c.Lh, Eh = c.Eh;
+    const int Bs = g.Bs, NI = g.NI;
+    const LevelConstants &h = hlevel(c.high);
+    g.result = ws((size_t)Bs * 3 * Lh * n);                                                     // :238-240
+    if (plan.cf == CF_BEHIND_HIGH_READY) {
+        g.cf = ws((size_t)Bs * 2 * Lh * n);
+        ps_cf_mac(c, g);
+        d_ntt_ct(g.cf, (size_t)Bs * 2, c.high, true);
+    }
+    u64 *dbuf = ws((size_t)NI * 3 * Eh * n);
+    u64 *tbuf = ws((size_t)NI * 3 * Lh * n);
+    std::vector<TensorJob> tj;                               // (one per inner polynomial: NI of them)
+    std::vector<FinishJob> fj;
+    std::vector<SumJob> sj;
+    for (int x = 0; x < Bs; x++) {
+        for (int i = 1; i <= g.nin[x]; i++) {
+            const size_t job = (size_t)g.in_off[x] + i - 1;
+            tj.push_back(TensorJob{ g.ext + job * 2 * Eh * n, c.hext_ptr(i, c.slot(g.ids[x])), dbuf + job * 3 * Eh * n });
+            fj.push_back(FinishJob{ dbuf + job * 3 * Eh * n, tbuf + job * 3 * Lh * n, 1, 0 });
+        }
+        sj.push_back(SumJob{ tbuf + (size_t)g.in_off[x] * 3 * Lh * n, g.result + (size_t)x * 3 * Lh * n, g.nin[x], 0 });
+    }
+    if (plan.fuse_tensor) {
+        PROF(P_NTT_FUSED, tj.size() * 3 * Eh);
+        launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Eh, Eh * n, nullptr, 0, tabs(), map_ext_fin(c.high), (int)Eh, st_, ntt_latency_limbs_);
+    } else {
+        if (!tj.empty()) { PROF(P_TENSOR, 0); launch_tensor(dlevel(c.high), upload_jobs(tj), n, (int)tj.size(), st_); }
+        d_ntt(dbuf, (size_t)NI * 3 * Eh, map_ext_fin(c.high), (int)Eh, true, ext_primes_narrow_);
+    }
+    { PROF(P_BEHZ_FINISH, 0); launch_behz_finish(dlevel(c.high), h.L, h.nB, upload_jobs(fj), false, n, (int)fj.size(), st_); }
+    { PROF(P_BEHZ_FINISH, 0); launch_sum_jobs(dlevel(c.high), (int)Lh, upload_jobs(sj), 3, n, Bs, st_); }
+}
+
+// 7. the i = 0 block, reduced to one exact [2][Lh][n] addend per BinBundle
+u64 *Engine::ps_i0(EvalCall &c, const EvalPlan &plan, PsBatch &g)
+{
+    const size_t n = c.n, Lh = c.Lh;
+    const int Bs = g.Bs;
+    if (plan.i0 == I0_SIDE) return g.i0_side;
+    if (plan.i0 == I0_SSUM) return g.ssum;
+    u64 *i0 = nullptr;
+    if (plan.i0 == I0_FINISH_MAIN) {
+        i0 = ws((size_t)Bs * 2 * Lh * n);
+        ps_i0_finish(c, plan, g, i0);
+    } else {
+        u64 *termh = g.term;
+        for (int lv = c.low; lv > c.high; lv--) {
+            u64 *nxt = ws((size_t)Bs * c.l * 2 * lv * n);
+            { PROFW(P_MODSWITCH, (size_t)Bs * c.l * 2 * n * (2 * lv + 1)); launch_modswitch(dlevel(lv), termh, (size_t)2 * (lv + 1) * n, 2, nxt, n, Bs * (int)c.l, st_); }
             termh = nxt;
         }
         i0 = ws((size_t)Bs * 2 * Lh * n);
         HIP_CHECK(hipMemsetAsync(i0, 0, (size_t)Bs * 2 * Lh * n * sizeof(u64), st_));
-        { PROF(P_OTHER, 0); launch_add_many(dlevel(high), i0, 2 * Lh * n, termh, (int)l, 2, n, Bs, st_); }
+        { PROF(P_OTHER, 0); launch_add_many(dlevel(c.high), i0, 2 * Lh * n, termh, (int)c.l, 2, n, Bs, st_); }
     }
+    return i0;
+}
 
-    // :340-343 the two exact addends, :345 add_plain(a_0), :346 add_plain(mask), :354-356 mod switch to the last
-    // level, :357 clear bits — one pass over the result
+// 8. :340-343 the two exact addends, :345 add_plain(a_0), :346 add_plain(mask), :354-356 mod switch to the last
+// level, :357 clear bits — one pass over the result
+void Engine::ps_epilogue(EvalCall &c, PsBatch &g, const u64 *i0)
+{
+    const size_t n = c.n, Lh = c.Lh;
     std::vector<EpiJob> ej;
-    for (int x = 0; x < Bs; x++)
-        ej.push_back(EpiJob{ result + (size_t)x * 3 * Lh * n, i0 + (size_t)x * 2 * Lh * n, g.cf + (size_t)x * 2 * Lh * n,
-                             bundles[c0 + g.ids[x]]->a0.u(), mask_ptr(g.ids[x]), res_ptr(g.ids[x]),
-                             ks_acc ? ks_acc + (size_t)x * 2 * (Lh + 1) * n : nullptr });
-    { PROFW(P_MODSWITCH, (size_t)Bs * n * (7 * Lh + 4 + (ks_acc ? 2 * (Lh + 1) : 0)));
-      launch_eval_epilogue(dlevel(0), high, upload_jobs(ej), Lh * n, hp_.irrelevant_bit_count, n, Bs, st_, ks_acc ? dkey() : nullptr); }
+    for (int x = 0; x < g.Bs; x++)
+        ej.push_back(EpiJob{ g.result + (size_t)x * 3 * Lh * n, i0 + (size_t)x * 2 * Lh * n, g.cf + (size_t)x * 2 * Lh * n,
+                             c.bundle(g.ids[x]).a0.u(), c.mask_ptr(g.ids[x]), c.res_ptr(g.ids[x]),
+                             g.ks_acc ? g.ks_acc + (size_t)x * 2 * (Lh + 1) * n : nullptr });
+    PROFW(P_MODSWITCH, (size_t)g.Bs * n * (7 * Lh + 4 + (g.ks_acc ? 2 * (Lh + 1) : 0)));
+    launch_eval_epilogue(dlevel(0), c.high, upload_jobs(ej), Lh * n, hp_.irrelevant_bit_count, n, g.Bs, st_, g.ks_acc ? dkey() : nullptr);
+}
 
+// the sequence, and which stream waits for which event (the side lane's own waits: ps_side)
+void Engine::ps_run(EvalCall &c, const EvalPlan &plan, PsBatch &g)
+{
+    ps_mac(c, plan, g);
+    if (plan.side) ps_side(c, plan, g);
+    ps_drop_ext(c, plan, g);
+    if (plan.wait_high_ready) HIP_CHECK(hipStreamWaitEvent(st_, c.pw.high_ready, 0));   // the products read the high powers (second stream)
+    if (plan.summed) ps_products_summed(c, plan, g);
+    else ps_products_per_term(c, plan, g);
+    // 6. the last relinearisation (:308-310).  (round 6: its mod-down is performed by the epilogue kernel, on the way in: one launch fewer at
+    // the end of every query, the updated (c0, c1) never go to memory; APSU_HE_FUSE_TAIL=0 keeps the launch)
+    d_relinearize(g.result, 3 * c.Lh * c.n, g.Bs, *c.rk, c.high, nullptr, 0, plan.fuse_tail ? &g.ks_acc : nullptr);
+    if (plan.side) HIP_CHECK(hipStreamWaitEvent(st_, ev_side_, 0));                     // cf sums (and the i = 0 addend) of the side lane
+    ps_epilogue(c, g, ps_i0(c, plan, g));
 }
 
 void Engine::eval_bundles(const Bundle *const *bundles, int count, const Powers &pw, const RelinKeys *rk,

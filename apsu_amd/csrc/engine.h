@@ -256,7 +256,7 @@ private:
     // the same map for the inverse transform in front of a finish kernel: NTT_MAP_RAW set where that level's finish takes
     // the twist into its own constants (fast_finish), identical to map_ext otherwise
     const int *map_ext_fin(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ext_fin_.p()) + chain_idx * DMAXE; }
-    bool fast_finish(int chain_idx) const { const LevelConstants &h = hp_.level[chain_idx]; return h.L == h.nB && h.L <= 3; }
+    bool fast_finish(int chain_idx) const { return behz_unrolled(hp_.level[chain_idx].L, hp_.level[chain_idx].nB); }
     const int *map_ks(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ks_.p()) + chain_idx * (DMAXL + 1) * DMAXL; }
     const int *map_ksacc(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ksacc_.p()) + chain_idx * (DMAXL + 1); }
     const int *map_ksacc_raw(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ksacc_raw_.p()) + chain_idx * (DMAXL + 1); }
@@ -389,16 +389,27 @@ private:
     void build_schedule();
     void build_schedule_for(Sched &s, const std::vector<char> &member);
     struct DagRun;                    // per-call state of one walk over a schedule
-    void run_dag(const Sched &s, DagRun &run, int stage, int nb, const u64 *const *src, bool on_device, const RelinKeys *rk, Powers &pw,
-                 bool do_low, bool do_high);
-    // eval_bundles in pieces (engine.cpp): per-call context, Paterson-Stockmeyer plan and batch
+    void dag_sources(DagRun &run, const u64 *const *src, bool on_device);
+    void dag_level(DagRun &run, size_t d, const RelinKeys *rk);
+    void dag_outputs(DagRun &run, Powers &pw, bool do_low, bool do_high);
+    void dag_walk(const Sched &s, int nb, const u64 *const *src, bool on_device, const RelinKeys *rk, Powers &pw);
+    // eval_bundles in pieces (engine.cpp): per-call context and Paterson-Stockmeyer batch; the plan: eval_plan.h
     struct EvalCall;
-    struct PsPlan;
     void eval_plain(EvalCall &c, const std::vector<int> &pl_ids);
     void eval_patstock(EvalCall &c, const std::vector<int> &ps_ids);
     void ps_cf_streams(const EvalCall &c, const PsBatch &g, std::vector<MacStream> &out);
-    void ps_tables(EvalCall &c, const PsPlan &plan, PsBatch &g);
-    void ps_run(EvalCall &c, const PsPlan &plan, PsBatch &g);
+    void ps_cf_mac(const EvalCall &c, const PsBatch &g);
+    void ps_term_product(const EvalCall &c, const PsBatch &g);
+    void ps_i0_finish(const EvalCall &c, const EvalPlan &plan, const PsBatch &g, u64 *i0);
+    void ps_tables(EvalCall &c, const EvalPlan &plan, PsBatch &g);
+    void ps_run(EvalCall &c, const EvalPlan &plan, PsBatch &g);        // the steps below, in this order
+    void ps_mac(EvalCall &c, const EvalPlan &plan, PsBatch &g);
+    void ps_side(EvalCall &c, const EvalPlan &plan, PsBatch &g);
+    void ps_drop_ext(EvalCall &c, const EvalPlan &plan, PsBatch &g);
+    void ps_products_summed(EvalCall &c, const EvalPlan &plan, PsBatch &g);
+    void ps_products_per_term(EvalCall &c, const EvalPlan &plan, PsBatch &g);
+    u64 *ps_i0(EvalCall &c, const EvalPlan &plan, PsBatch &g);
+    void ps_epilogue(EvalCall &c, PsBatch &g, const u64 *i0);
     void finish_bundle(Bundle &b, const u64 *raw);     // raw: [degree+1][n] coefficient-form plaintexts mod t (device)
     DevBuf d_slot_map_;
     // seed expansion queued on the stream without a host wait (query_create, relin_keygen): false = the objects need the host's

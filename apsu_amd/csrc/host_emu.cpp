@@ -16,6 +16,7 @@
 #include "params.h"
 #include "powers_dag.h"
 #include "sched_policy.h"
+#include "eval_plan.h"
 
 using namespace apsu_he;
 
@@ -264,6 +265,22 @@ int emu_pick_pooled_buffer(const unsigned char *entries, int count, int inputs_r
     for (int i = 0; i < count; i++) st[i] = PoolEntryState{ (entries[i] & 1) != 0, (entries[i] & 2) != 0, (entries[i] & 4) != 0 };
     return pick_pooled_buffer(st.data(), st.size(), inputs_ready != 0);
 }
+
+// The form decisions of the Paterson-Stockmeyer evaluation (eval_plan.h), for enumeration by tests/test_host_logic.py.
+// bits: 0 high_in_flight, 1 eval_side, 2 prof_on, 3 force_per_term, 4 fuse_tensor, 5 fuse_tail, 6 lane2, 7 on_lane0.  Returns i0_fast |
+// need_vlast << 1 | raw_drop << 2 | raw_i0 << 3 | fused_drop << 4 | summed << 5 | side << 6 | side_i0 << 7 | wait_high_ready << 8 |
+// fuse_tensor << 9 | fuse_tail << 10 | cf << 11 | i0 << 13.
+int emu_plan_eval(unsigned bits, int low, int high, int L, int nB, uint32_t l, uint64_t q_last, uint64_t q_widest, int Bs, int max_terms)
+{
+    EvalState s{};
+    s.low = low; s.high = high; s.L = L; s.nB = nB; s.l = l; s.q_last = q_last; s.q_widest = q_widest; s.Bs = Bs; s.max_terms = max_terms;
+    s.high_in_flight = bits & 1; s.eval_side = bits & 2; s.prof_on = bits & 4; s.force_per_term = bits & 8; s.fuse_tensor = bits & 16;
+    s.fuse_tail = bits & 32; s.lane2 = bits & 64; s.on_lane0 = bits & 128;
+    const EvalPlan p = plan_eval(s);
+    return (int)p.i0_fast | p.need_vlast << 1 | p.raw_drop << 2 | p.raw_i0 << 3 | p.fused_drop << 4 | p.summed << 5 | p.side << 6 | p.side_i0 << 7 |
+           p.wait_high_ready << 8 | p.fuse_tensor << 9 | p.fuse_tail << 10 | p.cf << 11 | p.i0 << 13;
+}
+int emu_behz_unrolled(int L, int nB) { return behz_unrolled(L, nB); }
 
 // The launch form of the transform (ntt_form.h), for tabulation by tests/test_host_logic.py: out = threads, coeffs_per_lane, min_waves, split
 void emu_ntt_form(int logn, int kind, size_t limbs, size_t latency_limbs, int narrow, int *out)

@@ -1210,7 +1210,7 @@ bool launch_drop_behz_ext(const DevLevel *lv, int L, int nB, const u64 *in, size
 {
     if (!cts) return true;
     const dim3 g = ew_grid(n, cts * polys), t(EW_T);
-#define EXT2_CASE(TL) if (L == TL && nB == TL) { \
+#define EXT2_CASE(TL) if (behz_unrolled(L, nB) && L == TL) { \
         if (raw) hipLaunchKernelGGL((k_behz_ext2<TL, true, true>), g, t, 0, st, lv, in, in_stride, polys, out, n); \
         else hipLaunchKernelGGL((k_behz_ext2<TL, true>), g, t, 0, st, lv, in, in_stride, polys, out, n); \
         KERNEL_CHECK(); return true; }
@@ -1224,13 +1224,11 @@ void launch_behz_ext(const DevLevel *lv, int L, int nB, const u64 *in, size_t in
 {
     if (!cts) return;
     const dim3 g = ew_grid(n, cts * polys), t(EW_T);
-#define EXT2_CASE(TL) if (L == TL && nB == TL) { hipLaunchKernelGGL((k_behz_ext2<TL, false>), g, t, 0, st, lv, in, in_stride, polys, out, n); KERNEL_CHECK(); return; }
+#define EXT2_CASE(TL) if (behz_unrolled(L, nB) && L == TL) { hipLaunchKernelGGL((k_behz_ext2<TL, false>), g, t, 0, st, lv, in, in_stride, polys, out, n); KERNEL_CHECK(); return; }
     EXT2_CASE(1) EXT2_CASE(2) EXT2_CASE(3)
 #undef EXT2_CASE
-#define EXT_CASE(TL) if (L == TL && nB == TL) { hipLaunchKernelGGL((k_behz_ext<TL, TL>), g, t, 0, st, lv, in, in_stride, polys, out, n); } else
-    EXT_CASE(4)
-    { hipLaunchKernelGGL((k_behz_ext<0, 0>), g, t, 0, st, lv, in, in_stride, polys, out, n); }
-#undef EXT_CASE
+    if (L == 4 && nB == 4) hipLaunchKernelGGL((k_behz_ext<4, 4>), g, t, 0, st, lv, in, in_stride, polys, out, n);
+    else hipLaunchKernelGGL((k_behz_ext<0, 0>), g, t, 0, st, lv, in, in_stride, polys, out, n);
     KERNEL_CHECK();
 }
 
@@ -1525,13 +1523,11 @@ void launch_behz_finish(const DevLevel *lv, int L, int nB, const FinishJob *jobs
     if (!njobs) return;
     const dim3 g = ew_grid(n, njobs * 3), t(EW_T);
     const int acc = accumulate ? 1 : 0;
-#define FIN2_CASE(TL) if (L == TL && nB == TL) { hipLaunchKernelGGL((k_behz_finish2<TL>), g, t, 0, st, lv, jobs, acc, n); KERNEL_CHECK(); return; }
+#define FIN2_CASE(TL) if (behz_unrolled(L, nB) && L == TL) { hipLaunchKernelGGL((k_behz_finish2<TL>), g, t, 0, st, lv, jobs, acc, n); KERNEL_CHECK(); return; }
     FIN2_CASE(1) FIN2_CASE(2) FIN2_CASE(3)
 #undef FIN2_CASE
-#define FIN_CASE(TL) if (L == TL && nB == TL) { hipLaunchKernelGGL((k_behz_finish<TL, TL>), g, t, 0, st, lv, jobs, acc, n); } else
-    FIN_CASE(4)
-    { hipLaunchKernelGGL((k_behz_finish<0, 0>), g, t, 0, st, lv, jobs, acc, n); }
-#undef FIN_CASE
+    if (L == 4 && nB == 4) hipLaunchKernelGGL((k_behz_finish<4, 4>), g, t, 0, st, lv, jobs, acc, n);
+    else hipLaunchKernelGGL((k_behz_finish<0, 0>), g, t, 0, st, lv, jobs, acc, n);
     KERNEL_CHECK();
 }
 
@@ -1560,7 +1556,7 @@ void launch_behz_finish_sum(const DevLevel *lv, int L, int nB, const FinishSumJo
 {
     if (!njobs) return;
     const dim3 g = ew_grid(n, njobs * 3), t(EW_T);
-#define FS_CASE(TL) if (L == TL && nB == TL) { hipLaunchKernelGGL((k_behz_finish_sum<TL, true>), g, t, 0, st, lv, jobs, n); KERNEL_CHECK(); return; }
+#define FS_CASE(TL) if (behz_unrolled(L, nB) && L == TL) { hipLaunchKernelGGL((k_behz_finish_sum<TL, true>), g, t, 0, st, lv, jobs, n); KERNEL_CHECK(); return; }
     FS_CASE(1) FS_CASE(2) FS_CASE(3)
 #undef FS_CASE
     if (L == 4 && nB == 4) hipLaunchKernelGGL((k_behz_finish_sum<4, false>), g, t, 0, st, lv, jobs, n);

@@ -380,6 +380,105 @@ def test_scheduler_pool_pick_rule(emu):
                 assert got == want, (pool, ready, got, want)
 
 
+CF_WITH_MAC, CF_SIDE_LANE, CF_BEHIND_HIGH_READY = range(3)
+I0_SIDE, I0_SSUM, I0_FINISH_MAIN, I0_GENERAL = range(4)
+EVAL_STATE_BOOLS = ("high_in_flight", "eval_side", "prof_on", "force_per_term", "fuse_tensor", "fuse_tail", "lane2", "on_lane0")
+EVAL_PLAN_BOOLS = ("i0_fast", "need_vlast", "raw_drop", "raw_i0", "fused_drop", "summed", "side", "side_i0", "wait_high_ready", "fuse_tensor",
+                   "fuse_tail")
+
+
+def eval_plan_of(emu, s):
+    """plan_eval (apsu_amd/csrc/eval_plan.h) of the state dict s, as a dict"""
+    emu.emu_plan_eval.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_int]
+    bits = sum(1 << i for i, k in enumerate(EVAL_STATE_BOOLS) if s[k])
+    r = emu.emu_plan_eval(bits, s["low"], s["high"], s["L"], s["nB"], s["l"], s["q_last"], s["q_widest"], s["Bs"], s["max_terms"])
+    p = {k: bool(r >> i & 1) for i, k in enumerate(EVAL_PLAN_BOOLS)}
+    p["cf"], p["i0"] = r >> 11 & 3, r >> 13 & 3
+    return p
+
+
+def check_eval_plan(s, p):
+    """the invariants of a Paterson-Stockmeyer plan p in the state s, stated here and not read off plan_eval"""
+    ctx = (s, p)
+    unrolled = s["L"] == s["nB"] and s["L"] in (1, 2, 3)          # k_behz_ext2 / k_behz_finish2 are instantiated for exactly these
+    # 1: the cf sums run in exactly one place (one enum value); whoever reads the high powers is ordered behind them
+    assert p["cf"] in (CF_WITH_MAC, CF_SIDE_LANE, CF_BEHIND_HIGH_READY), ctx
+    assert p["cf"] != CF_SIDE_LANE or p["side"], ctx
+    assert p["cf"] != CF_WITH_MAC or not s["high_in_flight"], ctx
+    assert not p["side"] or p["cf"] == CF_SIDE_LANE, ctx             # a side lane that runs always computes the sums
+    assert p["wait_high_ready"] == s["high_in_flight"], ctx
+    # 2: the i = 0 block takes exactly one form, and one whose inputs the plan provides
+    assert p["i0"] in (I0_SIDE, I0_SSUM, I0_FINISH_MAIN, I0_GENERAL), ctx
+    assert (p["i0"] == I0_SIDE) == p["side_i0"], ctx
+    assert p["i0"] != I0_SIDE or (p["side"] and s["Bs"] * s["l"] <= 4096), ctx
+    assert p["i0"] != I0_SSUM or (p["i0_fast"] and s["low"] == s["high"]), ctx
+    assert p["i0"] != I0_GENERAL or not p["i0_fast"], ctx
+    assert p["i0"] not in (I0_SIDE, I0_FINISH_MAIN) or (p["i0_fast"] and p["need_vlast"]), ctx      # launch_i0_finish reads ssum and vlast
+    assert not p["i0_fast"] or (s["low"] - s["high"] <= 1 and (s["l"] + 1) * s["q_last"] < 2 ** 64), ctx   # l rounded terms + half in one word
+    assert p["need_vlast"] == (p["i0_fast"] and s["low"] > s["high"]), ctx
+    # 3: the side lane
+    if p["side"]:
+        assert (s["eval_side"] and not s["prof_on"] and p["i0_fast"] and s["low"] != s["high"] and s["high_in_flight"] and s["lane2"]
+                and s["on_lane0"]), ctx
+    assert not p["side_i0"] or p["side"], ctx
+    # 4: a RAW inverse transform is planned exactly where the consumer that absorbs the twist is planned
+    assert p["raw_drop"] == p["fused_drop"], ctx
+    assert not p["raw_drop"] or (s["low"] == s["high"] + 1 and unrolled), ctx
+    assert not p["raw_i0"] or p["i0"] in (I0_SIDE, I0_FINISH_MAIN), ctx
+    # 5: the summed finish adds max_terms canonical residues of the widest limb as plain integers
+    assert not p["summed"] or (not s["force_per_term"] and s["high"] + 1 <= 4 and s["max_terms"] * s["q_widest"] < 2 ** 63), ctx
+    # the switches the steps read from the plan are the engine's
+    assert p["fuse_tensor"] == s["fuse_tensor"] and p["fuse_tail"] == s["fuse_tail"], ctx
+
+
+def test_eval_plan_invariants_hold_in_every_state(emu):
+    """the form decisions of Engine::eval_patstock are one pure function (apsu_amd/csrc/eval_plan.h, plan_eval).  Every combination of its
+    inputs around each threshold is held to the invariants of check_eval_plan; a disagreement between a RAW inverse transform and its
+    consumer (invariant 4) would be silently wrong limbs on the device."""
+    import itertools
+    for L, nB in itertools.product(range(1, 6), repeat=2):
+        assert bool(emu.emu_behz_unrolled(L, nB)) == (L == nB and L <= 3)
+    seen = {k: set() for k in EVAL_PLAN_BOOLS + ("cf", "i0")}
+    Q_WIDEST = 1 << 60
+    for flags in itertools.product((False, True), repeat=len(EVAL_STATE_BOOLS)):
+        # (no state is skipped: profiling can be switched on and a side lane can be missing whatever walk produced the powers.  The engine
+        #  itself only reaches low - high in {0, 1} -- Engine::compute_powers takes chain indices min(first, 2) and min(first, 1) -- the
+        #  plan is also held for a drop of two limbs)
+        for drop, (L, nB), (Bs, l), max_terms, wide_last in itertools.product(
+                (0, 1, 2), ((1, 1), (2, 2), (3, 3), (4, 4), (3, 2)), ((1, 2), (64, 64), (65, 64)), (0, 7, 8), (False, True)):
+            s = dict(zip(EVAL_STATE_BOOLS, flags))
+            q_last = (2 ** 64 - 1) // (l + 1) + (1 if wide_last else 0)      # (l + 1) * q_last on either side of 2^64
+            s.update(high=L - 1, low=L - 1 + drop, L=L, nB=nB, l=l, q_last=q_last, q_widest=Q_WIDEST, Bs=Bs, max_terms=max_terms)
+            assert ((l + 1) * q_last >= 2 ** 64) == wide_last and (8 * Q_WIDEST >= 2 ** 63 > 7 * Q_WIDEST)
+            p = eval_plan_of(emu, s)
+            check_eval_plan(s, p)
+            for k in seen:
+                seen[k].add(p[k])
+    # 6: every form is reached
+    for k in EVAL_PLAN_BOOLS:
+        assert seen[k] == {False, True}, (k, seen[k])
+    assert seen["cf"] == {0, 1, 2} and seen["i0"] == {0, 1, 2, 3}, seen
+    # the check has teeth: plausible wrong plans, through the same checker
+    base = dict(high_in_flight=False, eval_side=True, prof_on=False, force_per_term=False, fuse_tensor=True, fuse_tail=True, lane2=True,
+                on_lane0=True, high=2, low=3, L=3, nB=2, l=2, q_last=(1 << 60) - 1, q_widest=Q_WIDEST, Bs=4, max_terms=7)
+    check_eval_plan(base, eval_plan_of(emu, base))
+    # invariant 4: "at most three limbs" without nB -- L = 3, nB = 2 has no unrolled kernel: launch_drop_behz_ext declines, and the generic
+    # extension would read RAW inner polynomials
+    wrong = dict(eval_plan_of(emu, base), raw_drop=True, fused_drop=True)
+    with pytest.raises(AssertionError):
+        check_eval_plan(base, wrong)
+    # ... and a RAW transform whose consumer is not planned with it
+    unrolled = dict(base, nB=3)
+    assert eval_plan_of(emu, unrolled)["raw_drop"] and eval_plan_of(emu, unrolled)["fused_drop"]
+    with pytest.raises(AssertionError):
+        check_eval_plan(unrolled, dict(eval_plan_of(emu, unrolled), fused_drop=False))
+    # invariant 5: the bound taken as 2^64 (the word) and not 2^63 -- eight terms of a limb of 2^60
+    eight = dict(base, max_terms=8)
+    assert not eval_plan_of(emu, eight)["summed"] and eval_plan_of(emu, base)["summed"]
+    with pytest.raises(AssertionError):
+        check_eval_plan(eight, dict(eval_plan_of(emu, eight), summed=True))
+
+
 NTT_FORM_AUTO = 2 ** 64 - 1
 FWD, INV, GATHER, TENSOR = range(4)
 FORM_LIMBS = (1, 256, 257, 1024, 1025, 6840)
