@@ -245,6 +245,17 @@ int apsu_he_db_build_bundle(apsu_he_ctx *c, uint32_t bundle_idx, uint32_t cache_
         *out = b;
     });
 }
+
+int apsu_he_bundle_update(apsu_he_ctx *c, const apsu_he_bundle *old, const uint64_t *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride,
+                          const uint64_t *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins, apsu_he_bundle **out)
+{
+    return guarded([&] {
+        REQUIRE(c && old && old->b && out, "null argument");
+        auto b = new apsu_he_bundle;
+        try { b->b = c->eng->update_bundle(*old->b, ins_roots, ins_counts, ins_stride, rem_roots, rem_counts, rem_stride, bins); } catch (...) { delete b; throw; }
+        *out = b;
+    });
+}
 int apsu_he_algebraize_items(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t *felts, int felts_on_device)
 {
     return guarded([&] {
@@ -534,6 +545,14 @@ int apsu_he_multi_db_random_bundle(apsu_he_multi *m, int device_slot, uint32_t b
         REQUIRE(m && bundle_id, "null argument");
         REQUIRE(device_slot >= 0 && device_slot < m->m->device_count(), "device slot out of range");
         *bundle_id = m->m->random_bundle(device_slot, bundle_idx, cache_idx, degree, seed);
+    });
+}
+int apsu_he_multi_db_update_bundle(apsu_he_multi *m, int bundle_id, const uint64_t *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride,
+                                   const uint64_t *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins)
+{
+    return guarded([&] {
+        REQUIRE(m, "null argument");
+        m->m->update_bundle(bundle_id, ins_roots, ins_counts, ins_stride, rem_roots, rem_counts, rem_stride, bins);
     });
 }
 int apsu_he_multi_db_load_file(apsu_he_multi *m, const apsu_he_db_file *f, int *n_loaded)

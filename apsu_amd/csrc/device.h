@@ -161,6 +161,13 @@ void launch_seed_expand(const SeedJob *jobs, int njobs, const DevLevel *lv, int 
 // N1: BinBundle build (polyn_with_roots per bin, BatchEncoder scatter, monomial detection)
 void launch_polyn_with_roots(const u64 *roots, const u32 *counts, u32 bins, u32 stride, u32 max_deg, Mod t, u64 *poly, size_t n,
                              hipStream_t st);
+// BinBundle update (Engine::update_bundle): limb 0 of stored plaintext slots, the un-lift, the per-bin polynomial update on the
+// columns of poly[rows][n] (status: two words, both ~0 beforehand), the degree of the batched polynomial (out: one word, 0 beforehand)
+void launch_limb0_rows(const DevLevel *lv, int L, const void *src, size_t slot_bytes, bool packed, u64 *out, size_t n, size_t count, hipStream_t st);
+void launch_unlift(u64 *x, size_t words, u64 t, u64 q0, hipStream_t st);
+void launch_bins_update(const u32 *touched, u32 n_touched, const u64 *ins, const u32 *ins_counts, u32 ins_stride, const u64 *rem,
+                        const u32 *rem_counts, u32 rem_stride, Mod t, u64 *poly, size_t n, u32 rows, u32 *counts_out, u64 *status, hipStream_t st);
+void launch_poly_degree(const u64 *poly, size_t n, u32 rows, u64 *out, hipStream_t st);
 void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 void launch_gather_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 // N1: algebraize_item for `count` 16-byte items -> out[count][felts]; bpf = bits per field element, item_bits = felts * bpf

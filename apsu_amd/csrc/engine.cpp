@@ -379,6 +379,7 @@ Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), 
         HIP_CHECK(hipMemcpy(d_key_.p(), &k, sizeof(DevKey), hipMemcpyHostToDevice));
     }
     if (hp_.batching) {
+        unlift_exact_ = hp_.key_q[0] / 2 >= hp_.t && hp_.key_q[0] > 2 * hp_.t;   // update_bundle's decode (bin_update.h: bin_unlift) refuses otherwise
         d_slot_map_.alloc(hp_.slot_map.size() * sizeof(uint32_t));
         HIP_CHECK(hipMemcpy(d_slot_map_.p(), hp_.slot_map.data(), hp_.slot_map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
@@ -1827,7 +1828,6 @@ std::unique_ptr<Bundle> Engine::build_bundle(uint32_t bundle_idx, uint32_t cache
     b->bundle_idx = bundle_idx;
     b->cache_idx = cache_idx;
     bundle_shape(psu_, hp_, degree, *b);
-    const int tid = hp_.plain_id();
     WITH_ARENA({
         u64 *droots = ws((size_t)bins * stride + 1);
         uint32_t *dcounts = reinterpret_cast<uint32_t *>(ws((bins + 1) / 2 + 1));
@@ -1837,11 +1837,132 @@ std::unique_ptr<Bundle> Engine::build_bundle(uint32_t bundle_idx, uint32_t cache
         }
         u64 *poly = ws((size_t)(degree + 1) * n);                  // [d][slot] slot values of the batched polynomial
         launch_polyn_with_roots(droots, dcounts, bins, stride, degree, make_mod(hp_.t), poly, n, st_);
-        // BatchEncoder::encode (bin_bundle.cpp:409): slot permutation, then inverse negacyclic NTT mod t
-        u64 *raw = ws((size_t)(degree + 1) * n);
-        launch_scatter_slots(poly, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), raw, n, (int)degree + 1, st_);
-        d_ntt(raw, degree + 1, map_ct() + tid, 1, true, false);
-        finish_bundle(*b, raw);
+        encode_bundle(*b, poly);
+        sync();
+    });
+    pack_bundle(*b);
+    return b;
+}
+
+// the tail of build_bundle and update_bundle: slot values [degree+1][n] of the batched polynomial -> the stored BinBundle
+void Engine::encode_bundle(Bundle &b, const u64 *poly)
+{
+    const size_t n = hp_.n;
+    // BatchEncoder::encode (bin_bundle.cpp:409): slot permutation, then inverse negacyclic NTT mod t
+    u64 *raw = ws((size_t)(b.degree + 1) * n);
+    launch_scatter_slots(poly, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), raw, n, (int)b.degree + 1, st_);
+    d_ntt(raw, b.degree + 1, map_ct() + hp_.plain_id(), 1, true, false);
+    finish_bundle(b, raw);
+}
+
+// The inverse of encode_bundle, whoever made the BinBundle: coefficient d -> its stored form as in finish_bundle (a_0 raw; NTT-form
+// rows and the pre-lifted a_{i h}: limb 0, the residues mod q_0), inverse NTT over q_0, un-lift (bin_update.h; SEAL's un-lifted
+// monomials included), forward NTT mod t, slot gather -- BatchEncoder::decode.
+void Engine::decode_bundle(const Bundle &b, u64 *poly)
+{
+    const uint32_t ps = psu_.query_params.ps_low_degree, h = ps + 1, degree = b.degree;
+    const size_t n = hp_.n, Lpt = b.pt_level + 1;
+    const int high = hp_.clamp_chain_idx(1);
+    const size_t Lh = high + 1;
+    u64 *raw = ws((size_t)(degree + 1) * n);
+    D2D(raw, b.a0.u(), n);
+    size_t slot = 0, hi = 0;
+    uint32_t d = 1;
+    while (d <= degree) {                                            // the runs of finish_bundle
+        const bool is_ntt = (!ps && d != 0) || (ps && (d % h) != 0);
+        uint32_t e = d;
+        while (e + 1 <= degree && (((!ps) || ((e + 1) % h) != 0) == is_ntt)) e++;
+        const size_t run = e - d + 1;
+        if (is_ntt) {
+            const size_t sb = b.packed ? b.ntt_slot_bytes : Lpt * n * sizeof(u64);
+            launch_limb0_rows(dlevel(b.pt_level), (int)Lpt, static_cast<const char *>(b.ntt.p()) + slot * sb, sb, b.packed, raw + (size_t)d * n, n, run, st_);
+            slot += run;
+        } else {
+            if (!b.use_ps) throw std::logic_error("BinBundle holds a coefficient-form plaintext it cannot evaluate");
+            const size_t sb = b.packed ? b.lifted_slot_bytes : Lh * n * sizeof(u64);
+            launch_limb0_rows(dlevel(high), (int)Lh, static_cast<const char *>(b.lifted.p()) + hi * sb, sb, b.packed, raw + (size_t)d * n, n, run, st_);
+            hi += run;
+        }
+        d = e + 1;
+    }
+    if (degree) {
+        d_ntt(raw + n, degree, map_ct(), 1, true, data_primes_narrow_);
+        launch_unlift(raw + n, (size_t)degree * n, hp_.t, hp_.key_q[0], st_);
+    }
+    d_ntt(raw, degree + 1, map_ct() + hp_.plain_id(), 1, false, false);
+    launch_gather_slots(raw, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), poly, n, (int)degree + 1, st_);
+}
+
+std::unique_ptr<Bundle> Engine::update_bundle(const Bundle &old, const u64 *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride,
+                                              const u64 *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!hp_.batching) throw std::logic_error("plain_modulus does not support batching");
+    if (!unlift_exact_) throw std::logic_error("q_0 <= 2 * plain_modulus: stored plaintexts cannot be decoded");
+    const size_t n = hp_.n;
+    if (bins > n) throw std::invalid_argument("more bins than batching slots");
+    if ((ins_roots == nullptr) != (ins_counts == nullptr) || (rem_roots == nullptr) != (rem_counts == nullptr))
+        throw std::invalid_argument("a root list and its counts are given together or not at all");
+    const uint32_t max_items = psu_.table_params.max_items_per_bin;
+    std::vector<uint32_t> touched;
+    uint32_t max_ins = 0;
+    for (uint32_t s = 0; s < bins; s++) {
+        const uint32_t ni = ins_counts ? ins_counts[s] : 0, nr = rem_counts ? rem_counts[s] : 0;
+        if (ni > ins_stride || nr > rem_stride) throw std::invalid_argument("bin count exceeds stride");
+        if (ni > max_items) throw std::invalid_argument("bin size exceeds max_items_per_bin");
+        for (uint32_t r = 0; r < ni; r++)
+            if (ins_roots[(size_t)s * ins_stride + r] >= hp_.t) throw std::invalid_argument("field element is not reduced modulo plain_modulus");
+        for (uint32_t r = 0; r < nr; r++)
+            if (rem_roots[(size_t)s * rem_stride + r] >= hp_.t) throw std::invalid_argument("field element is not reduced modulo plain_modulus");
+        max_ins = std::max(max_ins, ni);
+        if (ni || nr) touched.push_back(s);
+    }
+    const uint32_t rows = old.degree + max_ins + 1;                    // no bin can outgrow this
+    const size_t ins_words = ins_counts ? (size_t)bins * ins_stride : 0, rem_words = rem_counts ? (size_t)bins * rem_stride : 0;
+    std::unique_ptr<Bundle> b;
+    WITH_ARENA({
+        u64 *poly = ws((size_t)rows * n);                              // [d][slot] slot values of the batched polynomial
+        decode_bundle(old, poly);
+        if (rows > old.degree + 1) HIP_CHECK(hipMemsetAsync(poly + (size_t)(old.degree + 1) * n, 0, (size_t)(rows - old.degree - 1) * n * sizeof(u64), st_));
+        u64 *status = ws(3);                                           // failed removal, unused slot named (both atomicMin), degree (atomicMax)
+        HIP_CHECK(hipMemsetAsync(status, 0xff, 2 * sizeof(u64), st_));
+        HIP_CHECK(hipMemsetAsync(status + 2, 0, sizeof(u64), st_));
+        std::vector<uint32_t> new_counts(touched.size());
+        if (!touched.empty()) {
+            u64 *dins = ws(ins_words + 1), *drem = ws(rem_words + 1);
+            uint32_t *dic = reinterpret_cast<uint32_t *>(ws((bins + 1) / 2 + 1)), *drc = reinterpret_cast<uint32_t *>(ws((bins + 1) / 2 + 1));
+            uint32_t *dtouched = reinterpret_cast<uint32_t *>(ws((touched.size() + 1) / 2 + 1));
+            uint32_t *dnew = reinterpret_cast<uint32_t *>(ws((touched.size() + 1) / 2 + 1));
+            if (ins_words) H2D(dins, ins_roots, ins_words);
+            if (rem_words) H2D(drem, rem_roots, rem_words);
+            if (ins_counts) HIP_CHECK(hipMemcpyAsync(dic, ins_counts, bins * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+            if (rem_counts) HIP_CHECK(hipMemcpyAsync(drc, rem_counts, bins * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemcpyAsync(dtouched, touched.data(), touched.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+            launch_bins_update(dtouched, (u32)touched.size(), dins, ins_counts ? dic : nullptr, ins_stride, drem, rem_counts ? drc : nullptr, rem_stride,
+                               make_mod(hp_.t), poly, n, rows, dnew, status, st_);
+            HIP_CHECK(hipMemcpyAsync(new_counts.data(), dnew, touched.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        }
+        launch_poly_degree(poly, n, rows, status + 2, st_);
+        u64 st[3];
+        HIP_CHECK(hipMemcpyAsync(st, status, sizeof(st), hipMemcpyDeviceToHost, st_));
+        sync();                                                        // the new shape is decided on the host
+        if (st[1] != ~(u64)0)
+            throw std::invalid_argument("bin " + std::to_string(st[1]) + " is an unused slot (it holds the zero polynomial): nothing can be inserted or removed there");
+        if (st[0] != ~(u64)0) {
+            const uint32_t s = (uint32_t)(st[0] >> 32), r = (uint32_t)st[0];
+            throw std::invalid_argument("bin " + std::to_string(s) + ": " + std::to_string(rem_roots[(size_t)s * rem_stride + r]) + " (removal " +
+                                        std::to_string(r) + ") is not a root of the bin's polynomial");
+        }
+        uint32_t degree = (uint32_t)st[2];                             // untouched bins included (k_poly_degree)
+        for (uint32_t c : new_counts) degree = std::max(degree, c);
+        if (degree > max_items) throw std::invalid_argument("bin size exceeds max_items_per_bin");
+        b = std::make_unique<Bundle>();
+        b->bundle_idx = old.bundle_idx;
+        b->cache_idx = old.cache_idx;
+        bundle_shape(psu_, hp_, degree, *b);
+        encode_bundle(*b, poly);
         sync();
     });
     pack_bundle(*b);

@@ -139,6 +139,12 @@ public:
     // (bin_bundle.cpp:366-430,934-1026): roots[bin * stride + r], r < counts[bin], are the field elements of a bin.
     std::unique_ptr<Bundle> build_bundle(uint32_t bundle_idx, uint32_t cache_idx, const u64 *roots, const uint32_t *counts,
                                          uint32_t bins, uint32_t stride);
+    // N1, the update (ReceiverDB::insert_or_assign / remove -> BinBundle::multi_insert / try_multi_remove -> regen_cache,
+    // receiver_db.cpp:330-433): a new BinBundle = `old` with bin s divided by (x - r) for its rem_counts[s] removal roots, then
+    // multiplied by (x - r) for its ins_counts[s] insertion roots.  Needs no roots of `old`: its stored coefficients are decoded back
+    // to the bins' polynomials mod t.  `old` is only read.  Semantics: include/apsu_he.h (apsu_he_bundle_update).
+    std::unique_ptr<Bundle> update_bundle(const Bundle &old, const u64 *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride,
+                                          const u64 *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins);
     // N1, one step earlier: algebraize_item (common/apsu/util/db_encoding.cpp:209-256,360-366) for `count` hashed items of 16 bytes:
     // out[count][felts_per_item], felt j = bits [j*b, (j+1)*b) of the item's first item_bit_count bits, b = bit_count(t) - 1
     void algebraize_items(const unsigned char *items, size_t count, bool items_on_device, u64 *out, bool out_on_device);
@@ -411,6 +417,9 @@ private:
     u64 *ps_i0(EvalCall &c, const EvalPlan &plan, PsBatch &g);
     void ps_epilogue(EvalCall &c, PsBatch &g, const u64 *i0);
     void finish_bundle(Bundle &b, const u64 *raw);     // raw: [degree+1][n] coefficient-form plaintexts mod t (device)
+    void encode_bundle(Bundle &b, const u64 *poly);    // poly: [degree+1][n] slot values -> BatchEncoder::encode, then finish_bundle
+    void decode_bundle(const Bundle &b, u64 *poly);    // the inverse: the stored coefficients back to slot values [degree+1][n] mod t
+    bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
     // seed expansion queued on the stream without a host wait (query_create, relin_keygen): false = the objects need the host's
     // sampler (seed_expand's rule) and nothing was queued; seeds_overflowed() after the final sync tells whether the device lists sufficed

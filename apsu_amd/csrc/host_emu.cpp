@@ -12,6 +12,7 @@
 #include "ntt_core.h"
 #include "ntt_form.h"
 #include "blake2x.h"
+#include "bin_update.h"
 #include "query_side.h"
 #include "params.h"
 #include "powers_dag.h"
@@ -374,5 +375,66 @@ int emu_level_constants(uint64_t n, const uint64_t *q, int k, uint64_t t, int ch
         return (int)v.size();
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
+
+// k_bins_update on one bin, as the wave runs it (bin_update.h): coefficient i in lane i % 64, register slot i / 64, every shuffle an
+// explicit loop over the 64 lanes.  in / out: `rows` coefficients mod t (out may alias nothing; it is written on success only).
+// Removals first, then insertions.  Returns the new count (index of the highest non-zero coefficient) or -1 with
+// status[0] = 1: rem[status[1]] left a remainder; 2: the zero polynomial (not a bin); 3: the result needs more than `rows` coefficients.
+int64_t emu_bin_update(uint64_t t_, const uint64_t *in, uint32_t rows, const uint64_t *rem, uint32_t n_rem, const uint64_t *ins, uint32_t n_ins,
+                       uint64_t *out, int64_t *status)
+{
+    const ModulusInfo mi(t_);
+    const Mod t{ t_, mi.ratio[0], mi.ratio[1] };
+    constexpr int W = BIN_LANES;
+    const int slots = (int)((rows + W - 1) / W);
+    std::vector<std::vector<u64>> P(slots, std::vector<u64>(W, 0));
+    int top = -1;
+    for (int j = 0; j < slots; j++)
+        for (int lane = 0; lane < W; lane++) {
+            const u32 d = (u32)(j * W + lane);
+            P[j][lane] = d < rows ? in[d] : 0;
+            if (P[j][lane]) top = std::max(top, (int)d);          // the wave's max-reduction
+        }
+    status[0] = status[1] = 0;
+    if (top < 0) { status[0] = 2; return -1; }
+    u32 cnt = (u32)top;
+    for (u32 r = 0; r < n_rem; r++) {
+        const u64 a = rem[r];
+        const int jmax = (int)(cnt >> 6);
+        u64 carry = 0;
+        for (int j = slots - 1; j >= 0; j--) {
+            if (j > jmax) continue;
+            std::vector<ScanPair> p(W);
+            for (int lane = 0; lane < W; lane++) p[lane] = ScanPair{ a, P[j][lane] };
+            for (int o = 1; o < W; o <<= 1) {
+                std::vector<ScanPair> up(W);
+                for (int lane = 0; lane < W; lane++) up[lane] = p[lane + o < W ? lane + o : lane];      // __shfl_down
+                for (int lane = 0; lane < W; lane++) if (lane + o < W) p[lane] = bin_scan_compose(p[lane], up[lane], t);
+            }
+            std::vector<u64> sv(W);
+            for (int lane = 0; lane < W; lane++) sv[lane] = bin_scan_carry(p[lane], carry, t);
+            for (int lane = 0; lane < W; lane++) P[j][lane] = lane == W - 1 ? carry : sv[lane + 1];
+            carry = sv[0];
+        }
+        if (carry != 0) { status[0] = 1; status[1] = r; return -1; }
+        cnt--;
+    }
+    for (u32 r = 0; r < n_ins; r++) {
+        if (cnt + 2 > rows) { status[0] = 3; return -1; }
+        const u64 a = ins[r], neg_a = a ? t.q - a : 0;
+        const int jmax = (int)((cnt + 1) >> 6);
+        for (int j = slots - 1; j >= 0; j--) {
+            if (j > jmax) continue;
+            std::vector<u64> prev(W);
+            for (int lane = 0; lane < W; lane++) prev[lane] = lane ? P[j][lane - 1] : (j > 0 ? P[j - 1][W - 1] : 0);
+            for (int lane = 0; lane < W; lane++) P[j][lane] = bin_insert_step(P[j][lane], prev[lane], neg_a, t);
+        }
+        cnt++;
+    }
+    for (u32 d = 0; d < rows; d++) out[d] = P[d / W][d % W];
+    return (int64_t)cnt;
+}
+
+uint64_t emu_bin_unlift(uint64_t x, uint64_t t, uint64_t q0) { return bin_unlift(x, t, q0); }
 
 } // extern "C"

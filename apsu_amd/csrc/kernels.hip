@@ -6,6 +6,7 @@
 // butterflies and dyadic products (BASELINE.json north_star).
 #include "device.h"
 #include "ntt_wg.h"
+#include "bin_update.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -742,6 +743,214 @@ void launch_polyn_with_roots(const u64 *roots, const u32 *counts, u32 bins, u32 
     PW_CASE(1) PW_CASE(2) PW_CASE(4) PW_CASE(8) PW_CASE(16) PW_CASE(24) PW_CASE(32) PW_CASE(48) PW_CASE(64) PW_CASE(96) PW_CASE(128)
 #undef PW_CASE
     hipLaunchKernelGGL(k_polyn_with_roots_serial, dim3((bins + EW_T - 1) / EW_T), dim3(EW_T), 0, st, roots, counts, bins, stride, t, poly, n);
+    KERNEL_CHECK();
+}
+
+// ---- BinBundle update (Engine::update_bundle): insert / remove items of single bins of a resident BinBundle
+// Decode, first step: limb 0 (the residues mod q_0) of `count` stored plaintext slots -> out[slot][n].  Dense slots are [L][n]
+// words, bit-packed ones (k_pack_rows) hold mac_bits[0] bits per coefficient at the start of the slot.
+__global__ __launch_bounds__(EW_T) void k_limb0_rows(const DevLevel *__restrict__ lv, int L, const char *__restrict__ src, size_t slot_bytes, int packed,
+                                                     u64 *__restrict__ out, size_t n)
+{
+    const size_t c = (size_t)blockIdx.x * EW_T + threadIdx.x, slot = blockIdx.y;
+    if (c >= n) return;
+    u64 v;
+    if (packed) {
+        const u32 w = lv->mac_bits[0];
+        const u32 *row = reinterpret_cast<const u32 *>(src + slot * slot_bytes + lv->mac_row_off[0]);
+        const size_t bit0 = c * w, d0 = bit0 >> 5;
+        const u32 sh = (u32)(bit0 & 31);
+        v = ((u64)row[d0] | ((u64)row[d0 + 1] << 32)) >> sh;      // (a packed buffer ends in 16 readable bytes, as for k_unpack_rows)
+        if (sh && w + sh > 64) v |= (u64)row[d0 + 2] << (64 - sh);
+        if (w != 64) v &= ((u64)1 << w) - 1;
+    } else v = reinterpret_cast<const u64 *>(src)[slot * (size_t)L * n + c];
+    out[slot * n + c] = v;
+}
+
+void launch_limb0_rows(const DevLevel *lv, int L, const void *src, size_t slot_bytes, bool packed, u64 *out, size_t n, size_t count, hipStream_t st)
+{
+    if (!count) return;
+    hipLaunchKernelGGL(k_limb0_rows, ew_grid(n, (int)count), dim3(EW_T), 0, st, lv, L, static_cast<const char *>(src), slot_bytes, packed ? 1 : 0, out, n);
+    KERNEL_CHECK();
+}
+
+// Decode, after the inverse NTT over q_0: residues mod q_0 back to values mod t (bin_update.h)
+__global__ __launch_bounds__(EW_T) void k_unlift(u64 *__restrict__ x, size_t words, u64 t, u64 q0)
+{
+    const size_t i = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (i < words) x[i] = bin_unlift(x[i], t, q0);
+}
+
+void launch_unlift(u64 *x, size_t words, u64 t, u64 q0, hipStream_t st)
+{
+    if (!words) return;
+    hipLaunchKernelGGL(k_unlift, dim3((unsigned)((words + EW_T - 1) / EW_T)), dim3(EW_T), 0, st, x, words, t, q0);
+    KERNEL_CHECK();
+}
+
+// one removal, register slots J .. 0 (top down).  Written as a recursion over the slot index so that every P[J] is a register whatever
+// the unroller's size limits make of a loop this long (as a loop, the instances of 24 slots and more kept P in scratch memory).
+template <int J, int SLOTS>
+__device__ __forceinline__ void bins_remove_slots(u64 (&P)[SLOTS], u64 a, int jmax, u32 lane, u64 &carry, const Mod &t)
+{
+    if constexpr (J >= 0) {
+        if (J <= jmax) {                                          // wave-uniform
+            ScanPair p{ a, P[J] };
+#pragma unroll 1
+            for (int o = 1; o < 64; o <<= 1) {
+                ScanPair up;
+                up.m = __shfl_down((unsigned long long)p.m, o, 64);
+                up.v = __shfl_down((unsigned long long)p.v, o, 64);
+                if (lane + o < 64) p = bin_scan_compose(p, up, t);
+            }
+            const u64 sv = bin_scan_carry(p, carry, t);           // s_{64 J + lane}
+            u64 q = __shfl_down((unsigned long long)sv, 1, 64);   // q_{k-1} = s_k: one lane down
+            if (lane == 63) q = carry;
+            P[J] = q;
+            carry = __shfl((unsigned long long)sv, 0, 64);
+        }
+        bins_remove_slots<J - 1, SLOTS>(P, a, jmax, lane, carry, t);
+    }
+}
+
+// P <- P / prod (x - rem_r) * prod (x - ins_r) for the bins named in `touched`, one WAVE per bin, on the columns of poly[rows][n]
+// (slot values of the batched polynomial; other columns are not visited).  Register layout and insertion step of
+// k_polyn_with_roots; the removal is synthetic division as a wave-level suffix scan (bin_update.h).  A bin's count is the index of its
+// highest non-zero coefficient.  status[0]: atomicMin of (bin << 32 | position in the removal list) over the roots that left a
+// remainder; status[1]: atomicMin of the bins named whose column is the zero polynomial (an unused slot).  Such a wave stops there.
+// counts_out[w] = the new count of touched[w].  rows <= 64 * SLOTS; a bin never outgrows `rows` - 1 (the host sizes it).
+template <int SLOTS>
+__global__ __launch_bounds__(256) void k_bins_update(const u32 *__restrict__ touched, u32 n_touched,
+                                                     const u64 *__restrict__ ins, const u32 *__restrict__ ins_counts, u32 ins_stride,
+                                                     const u64 *__restrict__ rem, const u32 *__restrict__ rem_counts, u32 rem_stride,
+                                                     Mod t, u64 *__restrict__ poly, size_t n, u32 rows, u32 *__restrict__ counts_out,
+                                                     unsigned long long *__restrict__ status)
+{
+    const u32 lane = threadIdx.x & 63;
+    const u32 w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= n_touched) return;
+    const u32 s = touched[w];
+    u64 P[SLOTS];
+    int top = -1;                                                 // highest index of a non-zero coefficient in this lane
+#pragma unroll
+    for (int j = 0; j < SLOTS; j++) {
+        const u32 d = (u32)j * 64 + lane;
+        P[j] = d < rows ? poly[(size_t)d * n + s] : 0;
+        if (P[j]) top = (int)d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o, 64));
+    if (top < 0) {
+        if (lane == 0) atomicMin(status + 1, (unsigned long long)s);
+        return;
+    }
+    u32 cnt = (u32)top;
+    const u32 n_rem = rem_counts ? rem_counts[s] : 0, n_ins = ins_counts ? ins_counts[s] : 0;
+    for (u32 r = 0; r < n_rem; r++) {
+        const u64 a = rem[(size_t)s * rem_stride + r];
+        const int jmax = (int)(cnt >> 6);
+        u64 carry = 0;                                            // s at lane 0 of the slot above
+        if constexpr (SLOTS <= 32) bins_remove_slots<SLOTS - 1>(P, a, jmax, lane, carry, t);
+        else {                                                    // (P lives in scratch memory in these instances anyway, as in the build)
+#pragma unroll
+            for (int j = SLOTS - 1; j >= 0; j--) {
+                if (j > jmax) continue;                           // wave-uniform
+                bins_remove_slots<0, 1>(reinterpret_cast<u64 (&)[1]>(P[j]), a, 0, lane, carry, t);
+            }
+        }
+        if (carry != 0) {                                         // the remainder s_0
+            if (lane == 0) atomicMin(status, (unsigned long long)bin_fail_word(s, r));
+            return;
+        }
+        cnt--;
+    }
+    for (u32 r = 0; r < n_ins; r++) {
+        const u64 a = ins[(size_t)s * ins_stride + r];
+        const u64 neg_a = a ? t.q - a : 0;
+        const int jmax = (int)((cnt + 1) >> 6);
+#pragma unroll
+        for (int j = SLOTS - 1; j >= 0; j--) {
+            if (j > jmax) continue;
+            u64 prev = __shfl_up((unsigned long long)P[j], 1, 64);
+            const u64 wrap = j > 0 ? (u64)__shfl((unsigned long long)P[j > 0 ? j - 1 : 0], 63, 64) : 0;
+            if (lane == 0) prev = wrap;
+            P[j] = bin_insert_step(P[j], prev, neg_a, t);
+        }
+        cnt++;
+    }
+#pragma unroll
+    for (int j = 0; j < SLOTS; j++) {
+        const u32 d = (u32)j * 64 + lane;
+        if (d < rows) poly[(size_t)d * n + s] = P[j];             // zero above the new count
+    }
+    if (lane == 0) counts_out[w] = cnt;
+}
+
+// the same beyond the largest wave-per-bin instance: one thread per bin, coefficients stay in global memory
+__global__ __launch_bounds__(EW_T) void k_bins_update_serial(const u32 *__restrict__ touched, u32 n_touched,
+                                                             const u64 *__restrict__ ins, const u32 *__restrict__ ins_counts, u32 ins_stride,
+                                                             const u64 *__restrict__ rem, const u32 *__restrict__ rem_counts, u32 rem_stride,
+                                                             Mod t, u64 *__restrict__ poly, size_t n, u32 rows, u32 *__restrict__ counts_out,
+                                                             unsigned long long *__restrict__ status)
+{
+    const u32 w = blockIdx.x * EW_T + threadIdx.x;
+    if (w >= n_touched) return;
+    const u32 s = touched[w];
+    u64 *P = poly + s;                                            // P[d * n]
+    int top = (int)rows - 1;
+    while (top >= 0 && P[(size_t)top * n] == 0) top--;
+    if (top < 0) { atomicMin(status + 1, (unsigned long long)s); return; }
+    u32 cnt = (u32)top;
+    const u32 n_rem = rem_counts ? rem_counts[s] : 0, n_ins = ins_counts ? ins_counts[s] : 0;
+    for (u32 r = 0; r < n_rem; r++) {
+        const u64 a = rem[(size_t)s * rem_stride + r];
+        u64 sv = 0;                                               // s_{k+1}
+        for (int k = (int)cnt; k >= 0; k--) {
+            const u64 pk = P[(size_t)k * n];
+            P[(size_t)k * n] = sv;                                // q_k = s_{k+1}
+            sv = addmod(pk, mulmod(a, sv, t), t.q);
+        }
+        if (sv != 0) { atomicMin(status, (unsigned long long)bin_fail_word(s, r)); return; }
+        cnt--;
+    }
+    for (u32 r = 0; r < n_ins; r++) {
+        const u64 a = ins[(size_t)s * ins_stride + r];
+        const u64 neg_a = a ? t.q - a : 0;
+        for (u32 i = cnt + 1; i > 0; i--) P[(size_t)i * n] = bin_insert_step(P[(size_t)i * n], P[(size_t)(i - 1) * n], neg_a, t);
+        P[0] = mulmod(P[0], neg_a, t);
+        cnt++;
+    }
+    counts_out[w] = cnt;
+}
+
+void launch_bins_update(const u32 *touched, u32 n_touched, const u64 *ins, const u32 *ins_counts, u32 ins_stride, const u64 *rem,
+                        const u32 *rem_counts, u32 rem_stride, Mod t, u64 *poly, size_t n, u32 rows, u32 *counts_out, u64 *status, hipStream_t st)
+{
+    if (!n_touched) return;
+    unsigned long long *stw = reinterpret_cast<unsigned long long *>(status);
+    const u32 slots = (rows + 63) / 64;
+    const dim3 g((n_touched + 3) / 4), b(256);
+#define BU_CASE(S) if (slots <= S) { hipLaunchKernelGGL((k_bins_update<S>), g, b, 0, st, touched, n_touched, ins, ins_counts, ins_stride, rem, rem_counts, rem_stride, t, poly, n, rows, counts_out, stw); KERNEL_CHECK(); return; }
+    BU_CASE(1) BU_CASE(2) BU_CASE(4) BU_CASE(8) BU_CASE(16) BU_CASE(24) BU_CASE(32) BU_CASE(48) BU_CASE(64) BU_CASE(96) BU_CASE(128)
+#undef BU_CASE
+    hipLaunchKernelGGL(k_bins_update_serial, dim3((n_touched + EW_T - 1) / EW_T), dim3(EW_T), 0, st, touched, n_touched, ins, ins_counts, ins_stride,
+                       rem, rem_counts, rem_stride, t, poly, n, rows, counts_out, stw);
+    KERNEL_CHECK();
+}
+
+// the degree of the batched polynomial: atomicMax over the slots of the index of the highest non-zero row of poly[rows][n]
+__global__ __launch_bounds__(EW_T) void k_poly_degree(const u64 *__restrict__ poly, size_t n, u32 rows, unsigned long long *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (i >= n) return;
+    int top = (int)rows - 1;
+    while (top > 0 && poly[(size_t)top * n + i] == 0) top--;
+    if (top > 0) atomicMax(out, (unsigned long long)top);
+}
+
+void launch_poly_degree(const u64 *poly, size_t n, u32 rows, u64 *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_poly_degree, dim3((unsigned)((n + EW_T - 1) / EW_T)), dim3(EW_T), 0, st, poly, n, rows, reinterpret_cast<unsigned long long *>(out));
     KERNEL_CHECK();
 }
 

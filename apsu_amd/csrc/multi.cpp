@@ -190,6 +190,18 @@ void MultiEngine::save_file(const std::string &path)
     db_file_save(path, engs.data(), bs.data(), bs.size());
 }
 
+void MultiEngine::update_bundle(int id, const u64 *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride, const u64 *rem_roots,
+                                const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    if (id < 0 || (size_t)id >= where_.size()) throw std::invalid_argument("no BinBundle with this id");
+    Dev &d = *devs_[where_[id].first];
+    std::unique_ptr<Bundle> &cur = d.bundles[where_[id].second];
+    std::unique_ptr<Bundle> next = d.eng->update_bundle(*cur, ins_roots, ins_counts, ins_stride, rem_roots, rem_counts, rem_stride, bins);
+    d.eng->wait();                                                // an evaluation with device-side results may still read the old rows
+    cur = std::move(next);
+}
+
 void MultiEngine::clear_bundles()
 {
     std::lock_guard<std::mutex> g(mu_);

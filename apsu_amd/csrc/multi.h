@@ -45,6 +45,10 @@ public:
     int bundle_device(int id) const { return where_.at(id).first; }
     const Bundle &bundle(int id) const { const auto &w = where_.at(id); return *devs_[w.first]->bundles[w.second]; }
     void clear_bundles();
+    // Engine::update_bundle on BinBundle `id`, on its device; the new BinBundle takes its place (same id, same output row) once
+    // that device has finished what was queued on the old one
+    void update_bundle(int id, const u64 *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride, const u64 *rem_roots,
+                       const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins);
 
     // One query.  src_cts[b * source_count + s]: ciphertexts of every bundle index (each device reads its own);
     // masks[id]: n words mod t; out: bundle_count * 2n words, row = bundle id — host memory when out_slot < 0, else device

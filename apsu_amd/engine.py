@@ -102,6 +102,25 @@ def _ptr_array(items):
     return arr
 
 
+def _update_lists(inserts, removes):
+    """per-bin lists -> the six list arguments of apsu_he_bundle_update (+ the arrays that back them, + bins)"""
+    nb = max(len(inserts or []), len(removes or []))
+    args, keep = [], []
+    for lists in (inserts, removes):
+        if lists is None:
+            args += [None, None, 0]
+            continue
+        stride = max([len(b) for b in lists] + [1])
+        roots = np.zeros((max(nb, 1), stride), dtype=np.uint64)
+        counts = np.zeros(max(nb, 1), dtype=np.uint32)
+        for i, b in enumerate(lists):
+            counts[i] = len(b)
+            roots[i, :len(b)] = b
+        keep += [roots, counts]
+        args += [_p(roots), C.c_void_p(counts.ctypes.data), stride]
+    return args, keep, nb
+
+
 class RelinKeys:
     def __init__(self, ctx, handle):
         self._ctx, self.h = ctx, handle
@@ -363,6 +382,17 @@ class HeContext:
         deg = C.c_uint32()
         _check(load_library().apsu_he_bundle_degree(h, C.byref(deg)))
         return Bundle(self, h, bundle_idx, cache_idx, deg.value)
+
+    def update_bundle(self, bundle, inserts=None, removes=None):
+        """ReceiverDB::insert_or_assign / remove on the GPU: -> a new Bundle = `bundle` with, per bin, the values of removes[bin]
+        taken out and then those of inserts[bin] put in (per-bin lists as in build_bundle; None = nothing of that kind).  `bundle`
+        needs no roots behind it and stays valid."""
+        args, keep, nb = _update_lists(inserts, removes)
+        h = C.c_void_p()
+        _check(load_library().apsu_he_bundle_update(self.h, bundle.h, *args, nb, C.byref(h)))
+        deg = C.c_uint32()
+        _check(load_library().apsu_he_bundle_degree(h, C.byref(deg)))
+        return Bundle(self, h, bundle.bundle_idx, bundle.cache_idx, deg.value)
 
     def algebraize_items(self, items):
         """util::algebraize_item for items [count][16] uint8 -> felts [count][felts_per_item] (db_encoding.cpp:209-256,360-366)"""
@@ -677,6 +707,11 @@ class MultiContext:
                                                              C.byref(bid)))
         self.n_bundles = max(self.n_bundles, bid.value + 1)
         return bid.value
+
+    def update_bundle(self, bundle_id, inserts=None, removes=None):
+        """HeContext.update_bundle on BinBundle `bundle_id`, on its device; it keeps its id (its row of eval_all)"""
+        args, keep, nb = _update_lists(inserts, removes)
+        _check(load_library().apsu_he_multi_db_update_bundle(self.h, int(bundle_id), *args, nb))
 
     def clear_bundles(self):
         _check(load_library().apsu_he_multi_db_clear(self.h))

@@ -152,6 +152,30 @@ int apsu_he_db_random_bundle(apsu_he_ctx *ctx, uint32_t bundle_idx, uint32_t cac
  * polynomial 1.  The result is identical to uploading the reference-built cache with apsu_he_db_upload_bundle. */
 int apsu_he_db_build_bundle(apsu_he_ctx *ctx, uint32_t bundle_idx, uint32_t cache_idx, const uint64_t *roots,
                             const uint32_t *counts, uint32_t bins, uint32_t stride, apsu_he_bundle **out);
+/* N1, the update: insert items into and remove items from single bins of a resident BinBundle, the GPU side of
+ * ReceiverDB::insert_or_assign / remove (receiver_db.cpp:330-433 -> BinBundle::multi_insert / try_multi_remove -> regen_cache).
+ * ins_roots[bin*ins_stride + r], r < ins_counts[bin], and rem_roots / rem_counts / rem_stride likewise, follow the conventions of
+ * apsu_he_db_build_bundle; either list may be NULL together with its counts (nothing of that kind).  `old` needs no roots behind
+ * it: a built, uploaded, loaded (image, DB file, reference-saved) or already updated BinBundle will do.
+ *  - The polynomial of bin (slot) s is whatever `old` holds there; its count is the index of its highest non-zero coefficient.
+ *  - Remove: P <- P / (x - r), once per listed root.  The remainder must be 0: otherwise APSU_HE_INVALID_ARGUMENT, apsu_he_last_error
+ *    names the first bin (lowest slot) and the root for which it was not, and no bundle is produced.  Removals come before insertions,
+ *    so removing and inserting the same value is the identity.
+ *  - Insert: P <- P (x - r) mod plain_modulus, once per listed root; the list is a multiset.
+ *  - A slot holding the zero polynomial is not a bin (the build writes 0 beyond `bins`): a non-empty list for it is an error.  An
+ *    empty bin holds the polynomial 1 and may be inserted into.
+ *  - Refused as by the build: a root >= plain_modulus, bins > poly_modulus_degree, a resulting count above max_items_per_bin, a
+ *    context without PSUParams or without batching (and one whose first coefficient prime is not above 2 * plain_modulus).
+ *  - *out is a NEW bundle with old's bundle_idx and cache_idx; its degree is the largest resulting count (it may grow or shrink), and
+ *    level, Paterson-Stockmeyer layout, monomial flags and row packing follow from it as in the build.  `old` is only read and stays
+ *    valid until the caller frees it (queued evaluations may still read it).
+ *  - If old = build_bundle(B), the image of the result (apsu_he_bundle_save) is byte-identical to that of build_bundle(B') for the
+ *    updated bins B', in whatever order the roots are listed.
+ * Synchronous.  apsu_he_multi_db_update_bundle replaces BinBundle `id` of a multi-device handle on its device, under the handle's
+ * placement lock; the BinBundle keeps its id and therefore its row in apsu_he_eval_all. */
+int apsu_he_bundle_update(apsu_he_ctx *ctx, const apsu_he_bundle *old, const uint64_t *ins_roots, const uint32_t *ins_counts,
+                          uint32_t ins_stride, const uint64_t *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride,
+                          uint32_t bins, apsu_he_bundle **out);
 /* "next" row N2: engine-native image of one BinBundle cache (256-byte header with a parameter
  * fingerprint and checksum + the raw limb arrays), the GPU-resident counterpart of ReceiverDB::save / Load
  * (receiver/apsu/receiver_db.cpp:1182-1429, bin_bundle.fbs).  The buffer may be an mmap of a file. */
@@ -322,6 +346,10 @@ int apsu_he_multi_db_random_bundle(apsu_he_multi *m, int device_slot, uint32_t b
 int apsu_he_multi_db_load_file(apsu_he_multi *m, const apsu_he_db_file *f, int *n_loaded);
 int apsu_he_multi_db_save_file(apsu_he_multi *m, const char *path);
 int apsu_he_multi_db_clear(apsu_he_multi *m);
+/* apsu_he_bundle_update on BinBundle `bundle_id` of the handle (see there) */
+int apsu_he_multi_db_update_bundle(apsu_he_multi *m, int bundle_id, const uint64_t *ins_roots, const uint32_t *ins_counts,
+                                   uint32_t ins_stride, const uint64_t *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride,
+                                   uint32_t bins);
 /* One query on all devices (receiver_osn.cpp:304-364): src_cts[b * source_power_count + s] = host ciphertext of source
  * power s (ascending) of bundle index b, for EVERY bundle index (each device uploads the ones it needs); masks[id] = n
  * words mod t (host).  out_cts: bundle count * 2n words, row = bundle id; host memory when out_device_slot < 0, else
