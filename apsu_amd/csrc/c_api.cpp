@@ -256,6 +256,59 @@ int apsu_he_bundle_update(apsu_he_ctx *c, const apsu_he_bundle *old, const uint6
         *out = b;
     });
 }
+int apsu_he_bundle_bin_counts(apsu_he_ctx *c, const apsu_he_bundle *b, uint32_t *counts)
+{ return guarded([&] { REQUIRE(c && b && b->b && counts, "null argument"); c->eng->bin_counts(*b->b, counts); }); }
+
+static std::vector<const Bundle *> bundle_ptrs(const apsu_he_bundle *const *bundles, uint32_t n_bundles)
+{
+    REQUIRE(bundles || !n_bundles, "null argument");
+    std::vector<const Bundle *> v(n_bundles);
+    for (uint32_t i = 0; i < n_bundles; i++) {
+        REQUIRE(bundles[i] && bundles[i]->b, "null bundle");
+        v[i] = bundles[i]->b.get();
+    }
+    return v;
+}
+
+int apsu_he_bundles_lookup(apsu_he_ctx *c, const apsu_he_bundle *const *bundles, uint32_t n_bundles, const uint64_t *felts, const uint32_t *start_bins,
+                           size_t count, uint8_t *present, uint32_t *room)
+{
+    return guarded([&] {
+        REQUIRE(c && ((felts && start_bins) || !count), "null argument");
+        const auto v = bundle_ptrs(bundles, n_bundles);
+        c->eng->lookup_bundles(v.data(), n_bundles, felts, start_bins, count, present, room);
+    });
+}
+
+int apsu_he_db_apply_entries(apsu_he_ctx *c, uint32_t bundle_idx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, const uint64_t *ins_felts,
+                             const uint32_t *ins_start, size_t n_ins, const uint64_t *rem_felts, const uint32_t *rem_start, size_t n_rem,
+                             uint32_t *bundle_state, apsu_he_bundle **replaced, apsu_he_bundle **appended, uint32_t *n_appended, uint32_t *ins_status,
+                             uint32_t *ins_target, uint32_t *rem_status, uint32_t *rem_target)
+{
+    return guarded([&] {
+        REQUIRE(c && ((ins_felts && ins_start) || !n_ins) && ((rem_felts && rem_start) || !n_rem), "null argument");
+        REQUIRE((bundle_state && replaced) || !n_bundles, "null argument");
+        REQUIRE((appended && n_appended) || !n_ins, "null argument");
+        const auto v = bundle_ptrs(bundles, n_bundles);
+        Engine::ApplyResult r = c->eng->apply_entries(bundle_idx, v.data(), n_bundles, ins_felts, ins_start, n_ins, rem_felts, rem_start, n_rem);
+        // nothing below throws except the allocation of the handles, which come first
+        std::vector<std::unique_ptr<apsu_he_bundle>> hr(n_bundles), ha(r.appended.size());
+        for (uint32_t i = 0; i < n_bundles; i++)
+            if (r.replaced[i]) { hr[i] = std::make_unique<apsu_he_bundle>(); hr[i]->b = std::move(r.replaced[i]); }
+        for (size_t i = 0; i < ha.size(); i++) { ha[i] = std::make_unique<apsu_he_bundle>(); ha[i]->b = std::move(r.appended[i]); }
+        for (uint32_t i = 0; i < n_bundles; i++) { bundle_state[i] = r.place.state[i]; replaced[i] = hr[i].release(); }
+        for (size_t i = 0; i < ha.size(); i++) appended[i] = ha[i].release();
+        if (n_appended) *n_appended = (uint32_t)ha.size();
+        const PlaceResult &p = r.place;
+        if (ins_status) std::copy(p.ins_status.begin(), p.ins_status.end(), ins_status);
+        if (ins_target) std::copy(p.ins_target.begin(), p.ins_target.end(), ins_target);
+        if (rem_status) std::copy(p.rem_status.begin(), p.rem_status.end(), rem_status);
+        if (rem_target) std::copy(p.rem_target.begin(), p.rem_target.end(), rem_target);
+    });
+}
+
+int apsu_he_debug_lookup_times(apsu_he_ctx *c, double *decode_ms, double *kernels_ms)
+{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->lookup_times(decode_ms, kernels_ms); }); }
 int apsu_he_algebraize_items(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t *felts, int felts_on_device)
 {
     return guarded([&] {

@@ -10,6 +10,7 @@
 #include "eval_plan.h"
 #include "blake2x.h"
 #include "query_side.h"
+#include "bin_lookup.h"
 
 namespace apsu_he {
 
@@ -168,6 +169,12 @@ void launch_unlift(u64 *x, size_t words, u64 t, u64 q0, hipStream_t st);
 void launch_bins_update(const u32 *touched, u32 n_touched, const u64 *ins, const u32 *ins_counts, u32 ins_stride, const u64 *rem,
                         const u32 *rem_counts, u32 rem_stride, Mod t, u64 *poly, size_t n, u32 rows, u32 *counts_out, u64 *status, hipStream_t st);
 void launch_poly_degree(const u64 *poly, size_t n, u32 rows, u64 *out, hipStream_t st);
+// find and place (Engine::lookup_bundles; bin_lookup.h): per-slot counts of poly[rows][n] (LOOKUP_NONE: the zero polynomial), and the
+// root test of the planned points (lookup_plan with LOOKUP_R rows per work item) -> flags[part], one byte each
+constexpr int LOOKUP_R = 8;                          // points per lane of k_bins_lookup (resource report: profiles/r10_bundle_lookup.txt)
+void launch_bin_counts(const u64 *poly, size_t n, u32 rows, u32 *counts, hipStream_t st);
+void launch_bins_lookup(const LookupWork *work, u32 n_work, const u64 *pts, const u32 *idx, Mod t, const u64 *poly, size_t n, u32 degree,
+                        unsigned char *flags, hipStream_t st);
 void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 void launch_gather_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 // N1: algebraize_item for `count` 16-byte items -> out[count][felts]; bpf = bits per field element, item_bits = felts * bpf

@@ -437,6 +437,7 @@ Engine::~Engine()
     for (hipEvent_t e : phase_pool_) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : { query_start_, query_end_ }) if (e) (void)hipEventDestroy(e);
     if (ev_main_) (void)hipEventDestroy(ev_main_);
+    for (hipEvent_t e : lookup_evs_) (void)hipEventDestroy(e);
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_side_) (void)hipEventDestroy(ev_side_);
     if (ev_intt_) (void)hipEventDestroy(ev_intt_);
@@ -1967,6 +1968,191 @@ std::unique_ptr<Bundle> Engine::update_bundle(const Bundle &old, const u64 *ins_
     });
     pack_bundle(*b);
     return b;
+}
+
+// ---- N1, find and place: occupancy, membership and the database-level step on resident BinBundles
+void Engine::lookup_check(const char *what) const
+{
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!hp_.batching) throw std::logic_error("plain_modulus does not support batching");
+    if (!unlift_exact_) throw std::logic_error("q_0 <= 2 * plain_modulus: stored plaintexts cannot be decoded");
+    if (psu_.bins_per_bundle > hp_.n) throw std::logic_error(std::string(what) + ": more bins than batching slots");
+}
+
+void Engine::lookup_impl(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count, uint32_t *counts,
+                         unsigned char *flags)
+{
+    const size_t n = hp_.n;
+    const uint32_t F = psu_.item_params.felts_per_item;
+    if (count && count >= (size_t)LOOKUP_NONE / F) throw std::invalid_argument("too many entries for one call");
+    for (size_t e = 0; e < count; e++) {
+        if ((u64)start[e] + F > psu_.bins_per_bundle) throw std::invalid_argument("entry " + std::to_string(e) + ": start bin + felts_per_item exceeds bins_per_bundle");
+        for (uint32_t j = 0; j < F; j++)
+            if (felts[e * F + j] >= hp_.t) throw std::invalid_argument("entry " + std::to_string(e) + ": field element is not reduced modulo plain_modulus");
+    }
+    const size_t parts = count * F;
+    const LookupPlan plan = count ? lookup_plan(felts, start, count, F, n, LOOKUP_R) : LookupPlan();
+    while (lookup_evs_.size() < (size_t)3 * n_bundles) {
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreate(&e));
+        lookup_evs_.push_back(e);
+    }
+    WITH_ARENA({
+        LookupWork *dwork = nullptr;
+        u64 *dpts = nullptr;
+        uint32_t *didx = nullptr;
+        if (count) {
+            dwork = reinterpret_cast<LookupWork *>(ws(plan.work.size() * sizeof(LookupWork) / sizeof(u64)));
+            dpts = ws(plan.pts.size());
+            didx = reinterpret_cast<uint32_t *>(ws((plan.idx.size() + 1) / 2));
+            HIP_CHECK(hipMemcpyAsync(dwork, plan.work.data(), plan.work.size() * sizeof(LookupWork), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemcpyAsync(dpts, plan.pts.data(), plan.pts.size() * sizeof(u64), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemcpyAsync(didx, plan.idx.data(), plan.idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+        }
+        unsigned char *dflags = count ? reinterpret_cast<unsigned char *>(ws((parts + 7) / 8)) : nullptr;
+        uint32_t *dcounts = counts ? reinterpret_cast<uint32_t *>(ws((n + 1) / 2)) : nullptr;
+        const size_t mark = arena_off_;
+        for (uint32_t i = 0; i < n_bundles; i++) {
+            const Bundle &b = *bundles[i];
+            arena_off_ = mark;                                         // one BinBundle after the other through the same workspace (stream order)
+            HIP_CHECK(hipEventRecord(lookup_evs_[3 * i], st_));
+            u64 *poly = ws((size_t)(b.degree + 1) * n);                // [d][slot] slot values of the batched polynomial
+            decode_bundle(b, poly);
+            HIP_CHECK(hipEventRecord(lookup_evs_[3 * i + 1], st_));
+            if (counts) {
+                launch_bin_counts(poly, n, b.degree + 1, dcounts, st_);
+                HIP_CHECK(hipMemcpyAsync(counts + (size_t)i * n, dcounts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+            }
+            if (count) {
+                launch_bins_lookup(dwork, (u32)plan.work.size(), dpts, didx, make_mod(hp_.t), poly, n, b.degree, dflags, st_);
+                HIP_CHECK(hipMemcpyAsync(flags + (size_t)i * parts, dflags, parts, hipMemcpyDeviceToHost, st_));
+            }
+            HIP_CHECK(hipEventRecord(lookup_evs_[3 * i + 2], st_));
+        }
+        sync();
+    });
+    lookup_decode_ms_ = lookup_kernels_ms_ = 0;
+    for (uint32_t i = 0; i < n_bundles; i++) {
+        float a = 0, k = 0;
+        HIP_CHECK(hipEventElapsedTime(&a, lookup_evs_[3 * i], lookup_evs_[3 * i + 1]));
+        HIP_CHECK(hipEventElapsedTime(&k, lookup_evs_[3 * i + 1], lookup_evs_[3 * i + 2]));
+        lookup_decode_ms_ += a;
+        lookup_kernels_ms_ += k;
+    }
+}
+
+void Engine::lookup_times(double *decode_ms, double *kernels_ms)
+{
+    Enter g(this);
+    if (decode_ms) *decode_ms = lookup_decode_ms_;
+    if (kernels_ms) *kernels_ms = lookup_kernels_ms_;
+}
+
+void Engine::bin_counts(const Bundle &b, uint32_t *counts)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("bin_counts");
+    const Bundle *one = &b;
+    lookup_impl(&one, 1, nullptr, nullptr, 0, counts, nullptr);
+}
+
+// present[b][e] = AND over the entry's parts; room[b][e] = max_j(count[s + j] + 1), multi_insert_dry_run's return value, or LOOKUP_NONE
+static void lookup_reduce(const unsigned char *flags, const uint32_t *counts, uint32_t n_bundles, size_t n, const uint32_t *start, size_t count, uint32_t F,
+                          unsigned char *present, uint32_t *room)
+{
+    for (uint32_t b = 0; b < n_bundles; b++)
+        for (size_t e = 0; e < count; e++) {
+            unsigned char all = 1;
+            uint32_t most = 0;
+            for (uint32_t j = 0; j < F; j++) {
+                all &= flags[((size_t)b * count + e) * F + j];
+                const uint32_t c = counts[(size_t)b * n + start[e] + j];
+                most = most == LOOKUP_NONE || c == LOOKUP_NONE ? LOOKUP_NONE : std::max(most, c + 1);
+            }
+            if (present) present[(size_t)b * count + e] = all;
+            if (room) room[(size_t)b * count + e] = most;
+        }
+}
+
+void Engine::lookup_bundles(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count,
+                            unsigned char *present, uint32_t *room)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("lookup");
+    if (!n_bundles || !count) return;
+    const size_t n = hp_.n;
+    const uint32_t F = psu_.item_params.felts_per_item;
+    std::vector<unsigned char> flags((size_t)n_bundles * count * F);
+    std::vector<uint32_t> counts((size_t)n_bundles * n);
+    lookup_impl(bundles, n_bundles, felts, start, count, counts.data(), flags.data());
+    lookup_reduce(flags.data(), counts.data(), n_bundles, n, start, count, F, present, room);
+}
+
+Engine::ApplyResult Engine::apply_entries(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles, const u64 *ins_felts,
+                                          const uint32_t *ins_start, size_t n_ins, const u64 *rem_felts, const uint32_t *rem_start, size_t n_rem)
+{
+    ApplyResult res;
+    const size_t n = hp_.n;
+    uint32_t F = 0, bins = 0;
+    std::vector<uint32_t> counts;
+    {
+        Enter g(this);
+        TIER1_SLOTS();
+        lookup_check("apply_entries");
+        F = psu_.item_params.felts_per_item;
+        bins = psu_.bins_per_bundle;
+        if (bundle_idx >= psu_.bundle_idx_count) throw std::invalid_argument("bundle_idx out of range");
+        for (uint32_t b = 0; b < n_bundles; b++) {
+            if (bundles[b]->bundle_idx != bundle_idx) throw std::invalid_argument("the BinBundles of one call belong to one bundle index");
+            if (b && bundles[b]->cache_idx <= bundles[b - 1]->cache_idx) throw std::invalid_argument("BinBundles are not in cache order");
+        }
+        // the refusals come before any GPU work
+        place_validate(ins_felts, ins_start, n_ins, rem_felts, rem_start, n_rem, F, bins, hp_.t);
+        // one lookup for both lists: removals first, insertions behind them
+        std::vector<u64> felts((n_rem + n_ins) * F);
+        std::vector<uint32_t> start(n_rem + n_ins);
+        std::copy(rem_felts, rem_felts + n_rem * F, felts.begin());
+        std::copy(ins_felts, ins_felts + n_ins * F, felts.begin() + n_rem * F);
+        std::copy(rem_start, rem_start + n_rem, start.begin());
+        std::copy(ins_start, ins_start + n_ins, start.begin() + n_rem);
+        const size_t count = n_rem + n_ins;
+        std::vector<unsigned char> flags((size_t)n_bundles * count * F), present((size_t)n_bundles * count);
+        counts.assign((size_t)n_bundles * n, 0);
+        if (n_bundles) {
+            lookup_impl(bundles, n_bundles, felts.data(), start.data(), count, counts.data(), count ? flags.data() : nullptr);
+            lookup_reduce(flags.data(), counts.data(), n_bundles, n, start.data(), count, F, present.data(), nullptr);
+        }
+        std::vector<uint32_t> bin_counts((size_t)n_bundles * bins);
+        std::vector<unsigned char> ins_present((size_t)n_bundles * n_ins), rem_present((size_t)n_bundles * n_rem);
+        for (uint32_t b = 0; b < n_bundles; b++) {
+            std::copy(counts.begin() + (size_t)b * n, counts.begin() + (size_t)b * n + bins, bin_counts.begin() + (size_t)b * bins);
+            std::copy(present.begin() + (size_t)b * count, present.begin() + (size_t)b * count + n_rem, rem_present.begin() + (size_t)b * n_rem);
+            std::copy(present.begin() + (size_t)b * count + n_rem, present.begin() + (size_t)(b + 1) * count, ins_present.begin() + (size_t)b * n_ins);
+        }
+        PlaceInput in;
+        in.n_bundles = n_bundles; in.bins = bins; in.F = F; in.max_items = psu_.table_params.max_items_per_bin; in.t = hp_.t;
+        in.counts = bin_counts.data(); in.ins_present = ins_present.data(); in.rem_present = rem_present.data();
+        in.ins_felts = ins_felts; in.ins_start = ins_start; in.n_ins = n_ins;
+        in.rem_felts = rem_felts; in.rem_start = rem_start; in.n_rem = n_rem;
+        res.place = place_entries(in);
+    }
+    // the context's lock is taken per step from here on, as by a caller who made these calls one by one; the given BinBundles are only read
+    const PlaceResult &pl = res.place;
+    res.replaced.resize(n_bundles);
+    for (uint32_t b = 0; b < n_bundles; b++) {
+        if (pl.state[b] != PLACE_REPLACED) continue;
+        const PlaceLists &li = pl.ins[b], &lr = pl.rem[b];
+        res.replaced[b] = update_bundle(*bundles[b], li.any() ? li.roots.data() : nullptr, li.any() ? li.counts.data() : nullptr, li.stride,
+                                        lr.any() ? lr.roots.data() : nullptr, lr.any() ? lr.counts.data() : nullptr, lr.stride, bins);
+    }
+    const uint32_t next_cache = n_bundles ? bundles[n_bundles - 1]->cache_idx + 1 : 0;
+    for (uint32_t k = 0; k < pl.n_new; k++) {
+        const PlaceLists &li = pl.ins[n_bundles + k];
+        res.appended.push_back(build_bundle(bundle_idx, next_cache + k, li.roots.data(), li.counts.data(), bins, li.stride));
+    }
+    return res;
 }
 
 // ---- N2: BinBundle image ------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 
 #include "device.h"
 #include "params.h"
+#include "db_place.h"
 #include "powers_dag.h"
 
 namespace apsu_he {
@@ -145,6 +146,24 @@ public:
     // to the bins' polynomials mod t.  `old` is only read.  Semantics: include/apsu_he.h (apsu_he_bundle_update).
     std::unique_ptr<Bundle> update_bundle(const Bundle &old, const u64 *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride,
                                           const u64 *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins);
+    // N1, find and place (include/apsu_he.h: apsu_he_bundle_bin_counts, apsu_he_bundles_lookup, apsu_he_db_apply_entries): what the
+    // reference keeps on the host next to a BinBundle (item_bins_, the cuckoo filters, hashed_items_) is asked of the resident
+    // polynomials instead.  counts: n words (host), LOOKUP_NONE where the slot is not a bin.
+    void bin_counts(const Bundle &b, uint32_t *counts);
+    // felts[count][felts_per_item], start[count]; present / room: [n_bundles][count] (host), either may be null
+    void lookup_bundles(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count,
+                        unsigned char *present, uint32_t *room);
+    // device time of the last bin_counts / lookup_bundles / apply_entries call, summed over its BinBundles: decode_bundle, the kernels behind it
+    void lookup_times(double *decode_ms, double *kernels_ms);
+    struct ApplyResult {
+        PlaceResult place;                                 // per-entry status and target, per-BinBundle state (db_place.h)
+        std::vector<std::unique_ptr<Bundle>> replaced;     // [n_bundles]: the new BinBundle where state == PLACE_REPLACED, else null
+        std::vector<std::unique_ptr<Bundle>> appended;     // [place.n_new]
+    };
+    // lookup -> place_entries -> update_bundle per changed BinBundle -> build_bundle per appended one, for the BinBundles of one bundle
+    // index given in cache order.  The given BinBundles are only read.
+    ApplyResult apply_entries(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles, const u64 *ins_felts, const uint32_t *ins_start,
+                              size_t n_ins, const u64 *rem_felts, const uint32_t *rem_start, size_t n_rem);
     // N1, one step earlier: algebraize_item (common/apsu/util/db_encoding.cpp:209-256,360-366) for `count` hashed items of 16 bytes:
     // out[count][felts_per_item], felt j = bits [j*b, (j+1)*b) of the item's first item_bit_count bits, b = bit_count(t) - 1
     void algebraize_items(const unsigned char *items, size_t count, bool items_on_device, u64 *out, bool out_on_device);
@@ -419,6 +438,12 @@ private:
     void finish_bundle(Bundle &b, const u64 *raw);     // raw: [degree+1][n] coefficient-form plaintexts mod t (device)
     void encode_bundle(Bundle &b, const u64 *poly);    // poly: [degree+1][n] slot values -> BatchEncoder::encode, then finish_bundle
     void decode_bundle(const Bundle &b, u64 *poly);    // the inverse: the stored coefficients back to slot values [degree+1][n] mod t
+    // decode each BinBundle in turn through the arena; counts (may be null): [n_bundles][n]; flags (null when count == 0): [n_bundles][count * F]
+    void lookup_impl(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count, uint32_t *counts,
+                     unsigned char *flags);
+    void lookup_check(const char *what) const;
+    std::vector<hipEvent_t> lookup_evs_;               // three per BinBundle of a call: before decode, behind it, behind the kernels
+    double lookup_decode_ms_ = 0, lookup_kernels_ms_ = 0;
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
     // seed expansion queued on the stream without a host wait (query_create, relin_keygen): false = the objects need the host's

@@ -13,6 +13,8 @@
 #include "ntt_form.h"
 #include "blake2x.h"
 #include "bin_update.h"
+#include "bin_lookup.h"
+#include "db_place.h"
 #include "query_side.h"
 #include "params.h"
 #include "powers_dag.h"
@@ -436,5 +438,106 @@ int64_t emu_bin_update(uint64_t t_, const uint64_t *in, uint32_t rows, const uin
 }
 
 uint64_t emu_bin_unlift(uint64_t x, uint64_t t, uint64_t q0) { return bin_unlift(x, t, q0); }
+
+// k_bin_counts over poly[rows][n]: one lane per slot, rows walked from the top
+void emu_bin_counts(const uint64_t *poly, uint64_t n, uint32_t rows, uint32_t *counts)
+{
+    for (size_t i = 0; i < n; i++) {
+        int top = (int)rows - 1;
+        while (top >= 0 && poly[(size_t)top * n + i] == 0) top--;
+        counts[i] = bin_count_of(top);
+    }
+}
+
+// k_bins_lookup<R> over poly[degree + 1][n] as the waves run it (bin_lookup.h): the points laid out by lookup_plan, one wave per work
+// item, an explicit loop over its 64 lanes, R accumulators per lane, rows from the top four at a time.  flags[count * F] must come in
+// as 0xEE: a part that no lane writes keeps it.  stats (may be null): work items, rows of point storage, largest nrows of a work item.
+// Returns 0, or -1 (emu_last_error) for an entry that does not lie inside the n slots or an R outside 1 .. 16.
+int emu_bins_lookup(uint64_t t_, const uint64_t *poly, uint64_t n, uint32_t degree, const uint64_t *felts, const uint32_t *start, uint64_t count,
+                    uint32_t F, int R, unsigned char *flags, uint64_t *stats)
+{
+    try {
+        if (R < 1 || R > 16) throw std::invalid_argument("R out of range");
+        for (size_t e = 0; e < count; e++)
+            if ((u64)start[e] + F > n) throw std::invalid_argument("entry beyond the last slot");
+        const ModulusInfo mi(t_);
+        const Mod t{ t_, mi.ratio[0], mi.ratio[1] };
+        const LookupPlan plan = lookup_plan(felts, start, count, F, n, R);
+        u32 widest = 0;
+        for (const LookupWork &wk : plan.work) {
+            widest = std::max(widest, wk.nrows);
+            for (u32 lane = 0; lane < LOOKUP_LANES; lane++) {
+                const size_t slot = (size_t)wk.tile * LOOKUP_LANES + lane;
+                const bool live = slot < n;
+                const u64 *col = poly + (live ? slot : 0);
+                u64 x[16], acc[16];
+                for (int r = 0; r < R; r++) {
+                    x[r] = (u32)r < wk.nrows ? plan.pts[((size_t)wk.row0 + r) * LOOKUP_LANES + lane] : 0;
+                    acc[r] = 0;
+                }
+                u64 nz = 0;
+                int d = (int)degree;
+                for (; d >= 3; d -= 4) {
+                    u64 p[4];
+                    for (int k = 0; k < 4; k++) p[k] = col[(size_t)(d - k) * n];
+                    for (int k = 0; k < 4; k++) {
+                        nz |= p[k];
+                        for (int r = 0; r < R; r++) acc[r] = lookup_horner_step(acc[r], x[r], p[k], t);
+                    }
+                }
+                for (; d >= 0; d--) {
+                    const u64 p = col[(size_t)d * n];
+                    nz |= p;
+                    for (int r = 0; r < R; r++) acc[r] = lookup_horner_step(acc[r], x[r], p, t);
+                }
+                for (int r = 0; r < R && (u32)r < wk.nrows; r++) {
+                    const u32 part = plan.idx[((size_t)wk.row0 + r) * LOOKUP_LANES + lane];
+                    if (part != LOOKUP_NONE) flags[part] = live && lookup_found(acc[r], nz) ? 1 : 0;
+                }
+            }
+        }
+        if (stats) { stats[0] = plan.work.size(); stats[1] = plan.rows(); stats[2] = widest; }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// place_entries (db_place.h).  counts [n_bundles][bins]; *_present [n_bundles][count]; felts [count][F].  Outputs: per entry status and
+// target; state [n_bundles]; *n_new; the per-bin lists of every BinBundle, given and appended, in apsu_he_bundle_update's layout with the
+// caller's stride: *_counts_out [n_bundles + n_ins][bins], *_roots_out [n_bundles + n_ins][bins][stride] (rows beyond n_bundles + *n_new
+// are not written).  Returns 0; -1: a refusal (std::invalid_argument); -2: a list longer than `stride`.  Text: emu_last_error.
+int emu_place_entries(uint32_t n_bundles, uint32_t bins, uint32_t F, uint64_t t, uint32_t max_items, const uint32_t *counts,
+                      const unsigned char *ins_present, const unsigned char *rem_present, const uint64_t *ins_felts, const uint32_t *ins_start,
+                      uint64_t n_ins, const uint64_t *rem_felts, const uint32_t *rem_start, uint64_t n_rem, uint32_t *ins_status, uint32_t *ins_target,
+                      uint32_t *rem_status, uint32_t *rem_target, uint32_t *state, uint32_t *n_new, uint32_t stride, uint32_t *ins_counts_out,
+                      uint64_t *ins_roots_out, uint32_t *rem_counts_out, uint64_t *rem_roots_out)
+{
+    try {
+        PlaceInput in;
+        in.n_bundles = n_bundles; in.bins = bins; in.F = F; in.max_items = max_items; in.t = t;
+        in.counts = counts; in.ins_present = ins_present; in.rem_present = rem_present;
+        in.ins_felts = ins_felts; in.ins_start = ins_start; in.n_ins = n_ins;
+        in.rem_felts = rem_felts; in.rem_start = rem_start; in.n_rem = n_rem;
+        const PlaceResult out = place_entries(in);
+        std::copy(out.ins_status.begin(), out.ins_status.end(), ins_status);
+        std::copy(out.ins_target.begin(), out.ins_target.end(), ins_target);
+        std::copy(out.rem_status.begin(), out.rem_status.end(), rem_status);
+        std::copy(out.rem_target.begin(), out.rem_target.end(), rem_target);
+        std::copy(out.state.begin(), out.state.end(), state);
+        *n_new = out.n_new;
+        for (int kind = 0; kind < 2; kind++)
+            for (size_t b = 0; b < out.ins.size(); b++) {
+                const PlaceLists &l = kind ? out.rem[b] : out.ins[b];
+                uint32_t *co = (kind ? rem_counts_out : ins_counts_out) + b * bins;
+                uint64_t *ro = (kind ? rem_roots_out : ins_roots_out) + b * bins * (size_t)stride;
+                if (l.stride > stride) { g_err = "list longer than stride"; return -2; }
+                for (u32 s = 0; s < bins; s++) {
+                    co[s] = l.any() ? l.counts[s] : 0;
+                    for (u32 r = 0; r < co[s]; r++) ro[(size_t)s * stride + r] = l.roots[(size_t)s * l.stride + r];
+                }
+            }
+        return 0;
+    } catch (const std::invalid_argument &e) { g_err = e.what(); return -1;
+    } catch (const std::exception &e) { g_err = e.what(); return -3; }
+}
 
 } // extern "C"

@@ -7,6 +7,7 @@
 #include "device.h"
 #include "ntt_wg.h"
 #include "bin_update.h"
+#include "bin_lookup.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -951,6 +952,82 @@ __global__ __launch_bounds__(EW_T) void k_poly_degree(const u64 *__restrict__ po
 void launch_poly_degree(const u64 *poly, size_t n, u32 rows, u64 *out, hipStream_t st)
 {
     hipLaunchKernelGGL(k_poly_degree, dim3((unsigned)((n + EW_T - 1) / EW_T)), dim3(EW_T), 0, st, poly, n, rows, reinterpret_cast<unsigned long long *>(out));
+    KERNEL_CHECK();
+}
+
+// ---- find and place (Engine::lookup_bundles): questions to the decoded poly[rows][n] of a resident BinBundle (bin_lookup.h)
+// counts[slot] = index of the highest non-zero coefficient of the slot's polynomial, LOOKUP_NONE for the zero polynomial (not a bin).
+// One lane per slot, rows walked from the top: a wave reads a contiguous row segment, and stops at the first row in a full bin.
+__global__ __launch_bounds__(EW_T) void k_bin_counts(const u64 *__restrict__ poly, size_t n, u32 rows, u32 *__restrict__ counts)
+{
+    const size_t i = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (i >= n) return;
+    int top = (int)rows - 1;
+    while (top >= 0 && poly[(size_t)top * n + i] == 0) top--;
+    counts[i] = bin_count_of(top);
+}
+
+void launch_bin_counts(const u64 *poly, size_t n, u32 rows, u32 *counts, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_bin_counts, dim3((unsigned)((n + EW_T - 1) / EW_T)), dim3(EW_T), 0, st, poly, n, rows, counts);
+    KERNEL_CHECK();
+}
+
+// Horner evaluation of the bins' polynomials at the entries' parts.  Lane = slot: one WAVE per work item (tile of 64 consecutive slots,
+// up to R rows of points: lookup_plan), rows d = degree .. 0 with one contiguous 512-byte segment per d and R independent
+// acc = acc x + p steps per lane, so every stored coefficient is read once per R points of its tile and no lane walks down a column.
+// The rows are taken four at a time, loads first, so that four segments are in flight per wave.  flags[part] = 1 iff the point is a
+// root and the slot is a bin (lookup_found); every part is written by exactly one lane.  No LDS.
+template <int R>
+__global__ __launch_bounds__(256) void k_bins_lookup(const LookupWork *__restrict__ work, u32 n_work, const u64 *__restrict__ pts,
+                                                     const u32 *__restrict__ idx, Mod t, const u64 *__restrict__ poly, size_t n, u32 degree,
+                                                     unsigned char *__restrict__ flags)
+{
+    const u32 lane = threadIdx.x & 63;
+    const u32 w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= n_work) return;
+    const LookupWork wk = work[w];
+    const size_t slot = (size_t)wk.tile * LOOKUP_LANES + lane;
+    const bool live = slot < n;                                   // (n < 64 only)
+    const u64 *col = poly + (live ? slot : 0);
+    u64 x[R], acc[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        x[r] = (u32)r < wk.nrows ? pts[((size_t)wk.row0 + r) * LOOKUP_LANES + lane] : 0;
+        acc[r] = 0;
+    }
+    u64 nz = 0;
+    int d = (int)degree;
+    for (; d >= 3; d -= 4) {
+        u64 p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = col[(size_t)(d - k) * n];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            nz |= p[k];
+#pragma unroll
+            for (int r = 0; r < R; r++) acc[r] = lookup_horner_step(acc[r], x[r], p[k], t);
+        }
+    }
+    for (; d >= 0; d--) {
+        const u64 p = col[(size_t)d * n];
+        nz |= p;
+#pragma unroll
+        for (int r = 0; r < R; r++) acc[r] = lookup_horner_step(acc[r], x[r], p, t);
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if ((u32)r >= wk.nrows) break;
+        const u32 part = idx[((size_t)wk.row0 + r) * LOOKUP_LANES + lane];
+        if (part != LOOKUP_NONE) flags[part] = live && lookup_found(acc[r], nz) ? 1 : 0;
+    }
+}
+
+void launch_bins_lookup(const LookupWork *work, u32 n_work, const u64 *pts, const u32 *idx, Mod t, const u64 *poly, size_t n, u32 degree,
+                        unsigned char *flags, hipStream_t st)
+{
+    if (!n_work) return;
+    hipLaunchKernelGGL((k_bins_lookup<LOOKUP_R>), dim3((n_work + 3) / 4), dim3(256), 0, st, work, n_work, pts, idx, t, poly, n, degree, flags);
     KERNEL_CHECK();
 }
 

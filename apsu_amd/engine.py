@@ -9,6 +9,7 @@ Names follow the reference interface this path replaces:
 Errors: APSU_HE_INVALID_ARGUMENT -> ValueError (std::invalid_argument in the reference),
 everything else -> ApsuHeError (std::runtime_error / std::logic_error).
 """
+import collections
 import ctypes as C
 import json
 import os
@@ -119,6 +120,27 @@ def _update_lists(inserts, removes):
         keep += [roots, counts]
         args += [_p(roots), C.c_void_p(counts.ctypes.data), stride]
     return args, keep, nb
+
+
+def _entries(entries, felts_per_item):
+    """entries: (felts [count][F], start_bins [count]) arrays, or a sequence of (start_bin, felts) pairs -> contiguous (uint64, uint32) arrays"""
+    if isinstance(entries, tuple) and len(entries) == 2 and isinstance(entries[0], np.ndarray) and entries[0].ndim == 2:
+        felts, start = entries
+    else:
+        entries = list(entries if entries is not None else [])
+        felts = [[int(v) for v in f] for _, f in entries]
+        start = [int(s) for s, _ in entries]
+    felts = np.ascontiguousarray(felts, dtype=np.uint64).reshape(-1, felts_per_item)
+    start = np.ascontiguousarray(start, dtype=np.uint32).reshape(-1)
+    if len(felts) != len(start):
+        raise ValueError("entries: felts and start bins differ in length")
+    return felts, start
+
+
+NOT_A_BIN = 0xFFFFFFFF
+ENTRY_INSERTED, ENTRY_DUPLICATE, ENTRY_REMOVED, ENTRY_NOT_FOUND = 0, 1, 2, 3
+BUNDLE_UNCHANGED, BUNDLE_REPLACED, BUNDLE_EMPTY = 0, 1, 2
+ApplyResult = collections.namedtuple("ApplyResult", "state bundles appended ins_status ins_target rem_status rem_target")
 
 
 class RelinKeys:
@@ -393,6 +415,63 @@ class HeContext:
         deg = C.c_uint32()
         _check(load_library().apsu_he_bundle_degree(h, C.byref(deg)))
         return Bundle(self, h, bundle.bundle_idx, bundle.cache_idx, deg.value)
+
+    def bin_counts(self, bundle):
+        """-> counts [n] uint32: per slot the index of the highest non-zero coefficient of the bin's polynomial, NOT_A_BIN for the zero
+        polynomial (apsu_he_bundle_bin_counts)"""
+        counts = np.empty(self.n, dtype=np.uint32)
+        _check(load_library().apsu_he_bundle_bin_counts(self.h, bundle.h, C.c_void_p(counts.ctypes.data)))
+        return counts
+
+    def lookup(self, bundles, entries):
+        """entries ((felts [count][F], start_bins [count]) or (start_bin, felts) pairs) against resident BinBundles -> (present
+        [len(bundles)][count] bool, room [len(bundles)][count] uint32 = multi_insert_dry_run's value or NOT_A_BIN); apsu_he_bundles_lookup"""
+        felts, start = _entries(entries, self.felts_per_item)
+        present = np.zeros((len(bundles), len(start)), dtype=np.uint8)
+        room = np.zeros((len(bundles), len(start)), dtype=np.uint32)
+        hs = (C.c_void_p * max(len(bundles), 1))(*[b.h for b in bundles])
+        _check(load_library().apsu_he_bundles_lookup(self.h, hs, len(bundles), _p(felts), C.c_void_p(start.ctypes.data), C.c_size_t(len(start)),
+                                                     C.c_void_p(present.ctypes.data), C.c_void_p(room.ctypes.data)))
+        return present.astype(bool), room
+
+    def lookup_times(self):
+        """-> (decode ms, kernels ms): device time of the last bin_counts / lookup / apply_entries call, summed over its BinBundles"""
+        a, k = C.c_double(), C.c_double()
+        _check(load_library().apsu_he_debug_lookup_times(self.h, C.byref(a), C.byref(k)))
+        return a.value, k.value
+
+    def apply_entries(self, bundles, inserts=None, removes=None, bundle_idx=None):
+        """ReceiverDB::insert_or_assign / remove for a batch of entries on the BinBundles of one bundle index, given in cache order
+        (apsu_he_db_apply_entries) -> ApplyResult: state [len(bundles)] (BUNDLE_*), bundles (the new Bundle where REPLACED, else None),
+        appended (new Bundles), and per entry status (ENTRY_*) and target position.  `bundles` stay valid.  bundle_idx is needed only
+        when no BinBundle is given."""
+        if bundle_idx is None:
+            if not bundles:
+                raise ValueError("apply_entries: bundle_idx is needed when no BinBundle is given")
+            bundle_idx = bundles[0].bundle_idx
+        fi, si = _entries(inserts, self.felts_per_item)
+        fr, sr = _entries(removes, self.felts_per_item)
+        nb = len(bundles)
+        hs = (C.c_void_p * max(nb, 1))(*[b.h for b in bundles])
+        state = np.zeros(nb, dtype=np.uint32)
+        replaced = (C.c_void_p * max(nb, 1))()
+        appended = (C.c_void_p * max(len(si), 1))()
+        n_app = C.c_uint32()
+        out = [np.zeros(len(si), dtype=np.uint32), np.zeros(len(si), dtype=np.uint32), np.zeros(len(sr), dtype=np.uint32), np.zeros(len(sr), dtype=np.uint32)]
+        u32 = lambda a: C.c_void_p(a.ctypes.data)
+        L = load_library()
+        _check(L.apsu_he_db_apply_entries(self.h, C.c_uint32(bundle_idx), hs, nb, _p(fi), u32(si), C.c_size_t(len(si)), _p(fr), u32(sr), C.c_size_t(len(sr)),
+                                          u32(state), replaced, appended, C.byref(n_app), *[u32(a) for a in out]))
+
+        def wrap(h, bundle_idx, cache_idx):
+            h = C.c_void_p(h)
+            deg = C.c_uint32()
+            _check(L.apsu_he_bundle_degree(h, C.byref(deg)))
+            return Bundle(self, h, bundle_idx, cache_idx, deg.value)
+        news = [wrap(replaced[i], b.bundle_idx, b.cache_idx) if replaced[i] else None for i, b in enumerate(bundles)]
+        first = bundles[-1].cache_idx + 1 if bundles else 0
+        apps = [wrap(appended[k], bundle_idx, first + k) for k in range(n_app.value)]
+        return ApplyResult(state, news, apps, *out)
 
     def algebraize_items(self, items):
         """util::algebraize_item for items [count][16] uint8 -> felts [count][felts_per_item] (db_encoding.cpp:209-256,360-366)"""

@@ -176,6 +176,58 @@ int apsu_he_db_build_bundle(apsu_he_ctx *ctx, uint32_t bundle_idx, uint32_t cach
 int apsu_he_bundle_update(apsu_he_ctx *ctx, const apsu_he_bundle *old, const uint64_t *ins_roots, const uint32_t *ins_counts,
                           uint32_t ins_stride, const uint64_t *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride,
                           uint32_t bins, apsu_he_bundle **out);
+/* N1, find and place: the database-level step above apsu_he_bundle_update.  What the reference keeps on the host next to a BinBundle
+ * -- item_bins_, the cuckoo filters, hashed_items_ -- is asked of the resident polynomials instead, so a database that came from an
+ * image, a DB file or a reference-saved cache can have items inserted and removed without anybody knowing its bins.
+ * An ENTRY is what preprocess_unlabeled_data emits per cuckoo location (receiver_db.cpp:292-299): felts_per_item field elements
+ * f_0 .. f_{F-1} (each < plain_modulus) and a start bin s, s + F <= bins_per_bundle; part j belongs to bin s + j.  Cuckoo locations,
+ * OPRF and apsu_he_algebraize_items stay with the caller.
+ *  - A bin's COUNT is the index of the highest non-zero coefficient of its polynomial (the update's definition).  A slot that holds
+ *    the zero polynomial is not a bin: APSU_HE_NOT_A_BIN.
+ *  - An entry is PRESENT in a BinBundle iff P_{s+j}(f_j) = 0 mod plain_modulus for every j and every s + j is a bin.  That is
+ *    try_multi_remove's test part by part, and what the protocol itself detects.  It includes the reference's false positive: every
+ *    part present in its bin, each from a different item.
+ * apsu_he_bundle_bin_counts: counts[poly_modulus_degree] (host) of one BinBundle.
+ * apsu_he_bundles_lookup: felts[count][F], start_bins[count] against n_bundles BinBundles; present[n_bundles][count] (0 / 1) and
+ * room[n_bundles][count] = max_j(count of bin s + j, + 1), the value of BinBundle::multi_insert_dry_run, or APSU_HE_NOT_A_BIN where
+ * some slot is not a bin.  Either output may be NULL.  The BinBundles are decoded and looked up one after the other through the
+ * context's workspace (k_bins_lookup: Horner evaluation with lane = slot, every stored coefficient read once per 8 points of its 64
+ * slots); the work is bounded by the number of parts however they are spread over the bins.
+ * apsu_he_db_apply_entries applies a batch to the BinBundles of ONE bundle index, given in cache order (ascending cache_idx; a
+ * BinBundle of another bundle index, or out of order: APSU_HE_INVALID_ARGUMENT): lookup, the reference's placement rule, then
+ * apsu_he_bundle_update per changed BinBundle and apsu_he_db_build_bundle per appended one.
+ *  - Removals come first, as in the update.  An entry leaves the first BinBundle in cache order that holds it (receiver_db.cpp:543-549):
+ *    APSU_HE_ENTRY_REMOVED, target = its position in `bundles`.  Held by none: APSU_HE_ENTRY_NOT_FOUND, nothing happens for it.
+ *  - Insertions follow in list order, as ReceiverDB::insert_or_assign runs them (receiver_db.cpp:349-434).  An entry that is present in
+ *    any of the BinBundles (before this call's changes), or equal to one placed earlier in the same call, is APSU_HE_ENTRY_DUPLICATE
+ *    (target: where it is) -- the role of hashed_items_.  Otherwise the BinBundles are tried newest first; the entry fits iff every
+ *    s + j is a bin and max_j(count + 1) < max_items_per_bin, strictly, so bins never exceed max_items_per_bin - 1.  Counts follow the
+ *    entries placed before it and this call's removals.  An entry that fits nowhere opens a new BinBundle, which is the newest for the
+ *    entries behind it.  APSU_HE_ENTRY_INSERTED, target = position in `bundles`, or n_bundles + k for the k-th appended BinBundle.
+ *  - Refused as a whole (APSU_HE_INVALID_ARGUMENT, no handle is produced): an entry in both lists, an entry twice in the removal list,
+ *    a part >= plain_modulus, s + F > bins_per_bundle.  Two removals that name the same value of the same bin are both scheduled; if
+ *    the bin holds it only once, the update's division refuses the call ("is not a root").
+ *  - bundle_state[i]: APSU_HE_BUNDLE_UNCHANGED (replaced[i] = NULL), _REPLACED (replaced[i] = a NEW bundle with the old one's bundle_idx
+ *    and cache_idx) or _EMPTY: every bin count is 0 after the removals -- no handle is produced (replaced[i] = NULL), the caller drops
+ *    the BinBundle as receiver_db.cpp:551-555 does, and it takes no insertion of this call.  The given handles are only read and stay
+ *    valid, as with the update.  Surviving BinBundles keep their cache_idx (the reference renumbers by position).
+ *  - appended[k], k < *n_appended <= n_ins: the new BinBundles, cache_idx continuing above the largest given (from 0 when none is given).
+ *  - ins_status / ins_target [n_ins], rem_status / rem_target [n_rem] may each be NULL.  Target of NOT_FOUND: APSU_HE_NOT_A_BIN.
+ * Preconditions and locking are the update's (PSUParams, batching, first coefficient prime above 2 * plain_modulus; synchronous; the
+ * context's lock is taken per step).  Not available on the multi-device handle: appending a BinBundle changes the partition. */
+#define APSU_HE_NOT_A_BIN 0xFFFFFFFFu
+enum { APSU_HE_ENTRY_INSERTED = 0, APSU_HE_ENTRY_DUPLICATE = 1, APSU_HE_ENTRY_REMOVED = 2, APSU_HE_ENTRY_NOT_FOUND = 3 };
+enum { APSU_HE_BUNDLE_UNCHANGED = 0, APSU_HE_BUNDLE_REPLACED = 1, APSU_HE_BUNDLE_EMPTY = 2 };
+int apsu_he_bundle_bin_counts(apsu_he_ctx *ctx, const apsu_he_bundle *bundle, uint32_t *counts);
+int apsu_he_bundles_lookup(apsu_he_ctx *ctx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, const uint64_t *felts,
+                           const uint32_t *start_bins, size_t count, uint8_t *present, uint32_t *room);
+int apsu_he_db_apply_entries(apsu_he_ctx *ctx, uint32_t bundle_idx, const apsu_he_bundle *const *bundles, uint32_t n_bundles,
+                             const uint64_t *ins_felts, const uint32_t *ins_start, size_t n_ins, const uint64_t *rem_felts,
+                             const uint32_t *rem_start, size_t n_rem, uint32_t *bundle_state, apsu_he_bundle **replaced,
+                             apsu_he_bundle **appended, uint32_t *n_appended, uint32_t *ins_status, uint32_t *ins_target,
+                             uint32_t *rem_status, uint32_t *rem_target);
+/* device time of the context's last call of the three above, summed over its BinBundles: the decode, and the kernels behind it */
+int apsu_he_debug_lookup_times(apsu_he_ctx *ctx, double *decode_ms, double *kernels_ms);
 /* "next" row N2: engine-native image of one BinBundle cache (256-byte header with a parameter
  * fingerprint and checksum + the raw limb arrays), the GPU-resident counterpart of ReceiverDB::save / Load
  * (receiver/apsu/receiver_db.cpp:1182-1429, bin_bundle.fbs).  The buffer may be an mmap of a file. */
