@@ -1,101 +1,15 @@
-// Device-side constant blocks and kernel launch entry points of the query-evaluation engine.
-// Everything here is plain-old-data uploaded once per context; kernels read it through
-// wave-uniform (scalar) loads.  Layout of all polynomial data is SEAL's in-memory order
-// [poly][limb][coeff] of uint64.
+// Job structs and kernel launch entry points of the query-evaluation engine.  The constant blocks the kernels read
+// (DevLevel, DevKey, the transform tables and limb maps) are in dev_consts.h.  Layout of all polynomial data is SEAL's
+// in-memory order [poly][limb][coeff] of uint64.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "modmath.h"
-#include "ntt_core.h"
-#include "ntt_form.h"
+#include "dev_consts.h"
 #include "eval_plan.h"
 #include "blake2x.h"
 #include "query_side.h"
 #include "bin_lookup.h"
 
 namespace apsu_he {
-
-constexpr int DMAXL = 8;            // limbs of q at a data level
-constexpr int DMAXB = DMAXL + 2;    // |Bsk|
-constexpr int DMAXE = DMAXL + DMAXB; // limbs of an extended (q u Bsk) polynomial
-
-struct ShoupConst { u64 w, wq; };
-
-// One level of the modulus chain (chain_idx = L-1).
-struct DevLevel {
-    int L, nB, nBsk, E;                         // E = L + nBsk limbs of an extended polynomial
-    Mod q[DMAXL];
-    Mod bsk[DMAXB];                             // B_0..B_{nB-1}, m_sk
-    Mod ext[DMAXE];                             // q_0..q_{L-1}, Bsk..   (modulus of each ext limb)
-    u64 t;
-    u32 mac_shift[DMAXL], mac_chunk[DMAXL];     // k_mac: operand split width s = ceil(bits(q_j)/2) and terms per carry-free chunk
-    u32 mac_chunk_k[DMAXL];                     // ... of the three-product form (middle products have 2 s + 2 bits)
-    // Bit-packed database rows (round 4; k_mac<.., PACKED>): limb j of a stored NTT-form plaintext takes mac_bits[j] bits per
-    // coefficient -- the smallest width >= bits(q_j) for which a lane's 16-byte window covers its two coefficients at every
-    // position (48, 49, 50, 52, 56; else 64 = not packed) -- in rows of n * mac_bits[j] / 8 bytes at byte offset mac_row_off[j]
-    // inside a plaintext slot.  Rows depend on the limb only, so every level's prefix of them is the same.
-    u32 mac_bits[DMAXL], mac_row_off[DMAXL], mac_mask_hi[DMAXL];
-    // add_plain (App. B7) and plaintext lift (B5)
-    u64 coeff_div_plain[DMAXL];
-    u64 q_mod_t, threshold;
-    u64 incr[DMAXL];
-    // drop-last-limb with rounding (B8)
-    u64 half;
-    u64 half_mod[DMAXL];
-    ShoupConst inv_q_last[DMAXL];
-    // BEHZ extension: fastbconv_m_tilde + sm_mrq (B9 steps 1-2)
-    ShoupConst ext_scale[DMAXL];                // m_tilde * (Q/q_j)^-1 mod q_j
-    u64 q_to_bsk[DMAXB][DMAXL];                 // (Q/q_j) mod Bsk_i
-    u32 q_to_mt[DMAXL];                         // (Q/q_j) mod 2^32
-    u32 neg_inv_q_mt;
-    u64 prod_q_bsk[DMAXB];
-    ShoupConst inv_mt_bsk[DMAXB];
-    // BEHZ finish: multiply by t, fast_floor, fastbconv_sk (B9 steps 6-8)
-    ShoupConst t_inv_punct_q[DMAXL];            // t * (Q/q_j)^-1 mod q_j
-    ShoupConst t_bsk[DMAXB];                    // t mod Bsk_i
-    ShoupConst inv_prod_q_bsk[DMAXB];
-    ShoupConst inv_punct_B[DMAXB];
-    u64 B_to_q[DMAXL][DMAXB];                   // (B/b_i) mod q_j
-    u64 B_to_msk[DMAXB];
-    ShoupConst inv_prod_B_msk;
-    u64 prod_B_q[DMAXL], neg_prod_B_q[DMAXL];
-    u64 msk_half;
-    // the same matrices as Shoup constants for the fully unrolled kernels (L = nB <= 3): every product is a
-    // lazy Shoup product (< 2m), sums stay below 8m < 2^64 and are reduced once
-    ShoupConst s_q_to_bsk[DMAXB][DMAXL];
-    ShoupConst s_prod_q_bsk[DMAXB];
-    // the same two with m_tilde^-1 folded in (sm_mrq's closing product becomes a plain reduction: behz_ext2_body)
-    ShoupConst s_q_to_bsk_mt[DMAXB][DMAXL];
-    ShoupConst s_prod_q_bsk_mt[DMAXB];
-    ShoupConst s_fl[DMAXB];                     // i < nB: (Q^-1 * (B/b_i)^-1) mod b_i ; i = nB: Q^-1 mod m_sk
-    ShoupConst s_B_to_q[DMAXL][DMAXB];
-    ShoupConst s_B_to_msk[DMAXB];
-    ShoupConst s_prod_B_q[DMAXL], s_neg_prod_B_q[DMAXL];
-    // The unrolled finish kernels (L = nB <= 3) consume the output of an inverse NTT and start by multiplying it with a
-    // constant (t (Q/q_j)^-1 for the q limbs, t for the Bsk limbs).  For them the inverse transform leaves out its own final
-    // twist (n^-1 psi^-k, one exact Shoup product per coefficient) and writes the raw lazy value; the twist rides on the
-    // finish's constant instead: fin_q[j][k] = t (Q/q_j)^-1 n^-1 psi_j^-k mod q_j, fin_b[i][k] = t n^-1 psi_i^-k mod Bsk_i.
-    // Same residues, one modular product per coefficient less.  Null for levels that use the generic finish.
-    const ShoupConst *fin_q[DMAXL];
-    const ShoupConst *fin_b[DMAXB];
-    // The same idea for the consumers of an inverse NTT that drop this level's last limb (mod_switch_to_next: the fused
-    // drop + extension of eval_patstock's inner polynomials, the i = 0 block's finish): the transform writes raw values and
-    // the twist rides on the drop's own constant, drop_tw[j][k] = n^-1 psi_j^-k q_last^-1 mod q_j (j < L - 1);
-    // last_tw[k] = n^-1 psi_{L-1}^-k (the dropped limb needs its canonical residue).  Null where unused.
-    const ShoupConst *drop_tw[DMAXL];
-    const ShoupConst *last_tw;
-};
-
-// Key-switching constants (App. B10); moduli indexed by key limb.
-struct DevKey {
-    int K;
-    Mod q[DMAXL + 1];
-    u64 p_half;
-    u64 p_half_mod[DMAXL];
-    ShoupConst inv_p[DMAXL];
-    // mod-down behind a RAW inverse transform: md_tw[j][k] = n^-1 psi_j^-k p^-1 mod q_j, p_tw[k] = n^-1 psi_p^-k mod p
-    const ShoupConst *md_tw[DMAXL];
-    const ShoupConst *p_tw;
-};
 
 // Multiply-accumulate job: for g < ng:  out[g][2][L][n] = sum_{j<cnt} PW_j (.) PT_{g,j}   (NTT domain).
 // All streams of a job share the ciphertext powers PW (same bundle index) and the term count.
@@ -116,9 +30,8 @@ struct MacJob {
 
 // ---- launch wrappers (all asynchronous on `st`) --------------------------------------------
 // NTT over `count` consecutive limb polynomials of n coefficients; limb g uses
-// tabs[modmap[g % period] & NTT_MAP_MASK].  An inverse transform of a limb whose map entry carries NTT_MAP_RAW writes its
-// result WITHOUT the final twist n^-1 psi^-k and without the final reduction (consumers: the unrolled BEHZ finish kernels).
-constexpr int NTT_MAP_RAW = 1 << 30, NTT_MAP_MASK = NTT_MAP_RAW - 1;
+// tabs[modmap[g % period] & NTT_MAP_MASK].  An inverse transform of a limb whose map entry carries NTT_MAP_RAW (dev_consts.h) writes
+// its result WITHOUT the final twist n^-1 psi^-k and without the final reduction (consumers: the unrolled BEHZ finish kernels).
 // latency_limbs (NTT_FORM_AUTO, 0 or a limb count) and narrow (every modulus of the launch is a narrow data prime) choose the form of
 // the transform through ntt_form (ntt_form.h).  Same bits in every form.
 void launch_ntt(int logn, bool inverse, u64 *data, size_t count, const NttTable *tabs, const int *modmap,

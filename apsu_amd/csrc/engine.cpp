@@ -16,7 +16,6 @@
 #include <stdexcept>
 
 namespace apsu_he {
-static uint32_t packed_row_bits(u64 q);   // width of a bit-packed database row (see Engine::mac_units)
 
 void throw_hip(hipError_t e, const char *file, int line)
 {
@@ -60,9 +59,6 @@ int Powers::slot_of(uint32_t bundle_idx) const
     return -1;
 }
 
-static ShoupConst shoup_const(u64 w, u64 q) { return ShoupConst{ w, (u64)(((u128)w << 64) / q) }; }
-static Mod make_mod(u64 q) { ModulusInfo m(q); return Mod{ q, m.ratio[0], m.ratio[1] }; }
-
 // ============================================================================ construction
 Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), device_(device)
 {
@@ -72,12 +68,14 @@ Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), 
     if (e != hipSuccess || ndev == 0)
         throw HipError("no HIP device available: the query-evaluation engine has no CPU fallback");
     if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
-    // the NTT keeps one limb in a workgroup's LDS: n = 2^logn coefficients with a compiled pass plan (ntt_core.h)
-    // (32768: the limb is split into two LDS-resident halves around one radix-2 stage over global memory, kernels.hip)
-    const bool split_ntt = hp_.logn == 15;
-    if (plan_passes(hp_.logn) == 0 && !split_ntt)
-        throw std::invalid_argument("poly_modulus_degree " + std::to_string(hp_.n) +
-                                    " is not supported by the GPU engine (supported: 64, 256, 1024, 2048, 4096, 8192, 16384, 32768)");
+    DeviceConstants dc = build_device_constants(hp_);            // (refuses ring sizes and limb counts the kernels do not have)
+    data_primes_narrow_ = dc.data_primes_narrow;
+    ext_primes_narrow_ = dc.ext_primes_narrow;
+    unlift_exact_ = dc.unlift_exact;
+    key_level_ = dc.key_level;
+    max_multiple_ = dc.max_multiple;
+    if (hp_.logn == 15) fuse_tensor_ = false;                    // the fused load belongs to a whole-limb workgroup
+    packed_rows_ = sw_.packed_rows && hp_.using_keyswitching;    // (the single-prime paths keep dense rows)
     struct Restore { int prev = -1; ~Restore() { if (prev >= 0) (void)hipSetDevice(prev); } } restore;
     { int cur = -1; if (hipGetDevice(&cur) == hipSuccess && cur != device) restore.prev = cur; }
     HIP_CHECK(hipSetDevice(device));
@@ -94,292 +92,21 @@ Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), 
     HIP_CHECK(hipEventCreateWithFlags(&ev_side_, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&ev_intt_, hipEventDisableTiming));
 
-    const size_t n = hp_.n;
-    const int nmod = (int)hp_.ntt.size();
-    // twiddles: per modulus [fwd n][dit n][scale n] TwPair
-    {
-        std::vector<TwPair> tw((size_t)nmod * 3 * n + (split_ntt ? (size_t)nmod * n : 0));
-        for (int m = 0; m < nmod; m++) {
-            const NttTablesHost &t = hp_.ntt[m];
-            for (size_t k = 0; k < n; k++) {
-                tw[((size_t)m * 3 + 0) * n + k] = TwPair{ t.fwd[k], t.fwd_q[k] };
-                tw[((size_t)m * 3 + 1) * n + k] = TwPair{ t.dit[k], t.dit_q[k] };
-                tw[((size_t)m * 3 + 2) * n + k] = TwPair{ t.scale[k], t.scale_q[k] };
-            }
-            if (split_ntt) {
-                // forward twiddles of the two half transforms: stage s of half h is stage s + 1 of the big transform,
-                // blocks h 2^s ..: W_h[2^s + b] = W[2^(s+1) + h 2^s + b]
-                for (size_t h = 0; h < 2; h++) {
-                    TwPair *dst = tw.data() + (size_t)nmod * 3 * n + ((size_t)m * 2 + h) * (n / 2);
-                    dst[0] = TwPair{ 0, 0 };
-                    for (size_t m2 = 1; m2 < n / 2; m2 <<= 1)
-                        for (size_t b = 0; b < m2; b++) {
-                            const size_t from = 2 * m2 + h * m2 + b;
-                            dst[m2 + b] = TwPair{ t.fwd[from], t.fwd_q[from] };
-                        }
-                }
-            }
-        }
-        d_tw_.alloc(tw.size() * sizeof(TwPair));
-        HIP_CHECK(hipMemcpy(d_tw_.p(), tw.data(), tw.size() * sizeof(TwPair), hipMemcpyHostToDevice));
-        std::vector<NttTable> tabs(split_ntt ? (size_t)nmod * 2 : (size_t)nmod);
-        const TwPair *base = reinterpret_cast<const TwPair *>(d_tw_.p());
-        for (int m = 0; m < nmod; m++) {
-            NttTable tb{};
-            tb.q = hp_.ntt[m].mod.value;
-            tb.ninv = hp_.ntt[m].ninv;
-            tb.ninv_q = hp_.ntt[m].ninv_q;
-            tb.r1 = hp_.ntt[m].mod.ratio[1];
-            tb.r0 = hp_.ntt[m].mod.ratio[0];
-            tb.narrow = ntt_is_narrow(hp_.ntt[m].mod.value, split_ntt ? hp_.logn - 1 : hp_.logn) ? 1 : 0;   // stages inside one workgroup
-            ntt_fold_params(tb.q, tb.fold_k, tb.fold_c);
-            tb.wide_d4 = ntt_wide_d4(tb.q, tb.narrow != 0);
-            tb.fwd = base + ((size_t)m * 3 + 0) * n;
-            tb.dit = base + ((size_t)m * 3 + 1) * n;
-            tb.scale = base + ((size_t)m * 3 + 2) * n;
-            if (!split_ntt) { tabs[m] = tb; continue; }
-            // split transform: table 2 m + h for half h; ninv / ninv_q carry the first stage's twiddle psi^brv(1)
-            tb.ninv = hp_.ntt[m].fwd[1];
-            tb.ninv_q = hp_.ntt[m].fwd_q[1];
-            for (size_t h = 0; h < 2; h++) {
-                tb.fwd = base + (size_t)nmod * 3 * n + ((size_t)m * 2 + h) * (n / 2);
-                tabs[(size_t)m * 2 + h] = tb;
-            }
-        }
-        d_tabs_.alloc(tabs.size() * sizeof(NttTable));
-        HIP_CHECK(hipMemcpy(d_tabs_.p(), tabs.data(), tabs.size() * sizeof(NttTable), hipMemcpyHostToDevice));
-        // Environment switches (read once per context).  Round 5 retired the switches of A/B experiments that were decided in earlier
-        // rounds together with their losing code paths (separate tensor / extension kernels where the fused forms apply, inverse
-        // transforms with their own twist in front of drop / mod-down kernels, the tensor transform in launch order, canonical products
-        // in the tensor-on-load transform, k_mac's other grid orders, the i = 0 block's per-term products as k_mac chains, the gathered
-        // transforms' unconditional reduce-on-load; the records are in profiles/r03_ab_*.txt and profiles/r04_ab_*.txt).  What is left
-        // either selects a data format, sizes a buffer, or forces a correctness fallback that the engine otherwise takes by itself:
-        //   APSU_HE_SPLIT=0/1          default of apsu_he_set_two_stream (profiling scripts: one-stream kernel traces)
-        //   APSU_HE_EVAL_SIDE=0        the evaluation's side work (coefficient-form sums, i = 0 finish) stays on the main stream
-        //   APSU_HE_PACKED_ROWS=0      BinBundle rows as dense 64-bit words instead of bit-packed (images of either format load anywhere)
-        //   APSU_HE_EVAL_WS_BYTES=n    evaluation workspace -> BinBundles per chunk (default 6 GiB)
-        //   APSU_HE_ARENA_BYTES=n      initial workspace arena (grows on demand)
-        //   APSU_HE_EVAL_PER_TERM=1    eval_patstock's products finished one by one (the fallback of the summed finish)
-        //   APSU_HE_MAC_KARA=0/1       three-product k_mac forced off / on (default: by chain length)
-        //   APSU_HE_SEED_EXPAND_HOST=1 seeded objects expanded by the host codec (the fallback of the device sampler)
-        //   APSU_HE_AUX_BASE=seal      SEAL's 61-bit auxiliary BEHZ base instead of the narrow one (read by c_api.cpp before HeParams; round 7)
-        //   APSU_HE_FUSE_TAIL=0        eval_patstock's last mod-down as its own launch instead of inside the epilogue kernel (round 6)
-        //   APSU_HE_NTT_LATENCY_LIMBS=n transform launches of at most n limbs take the latency form (8 coefficients per lane; round 6);
-        //                              0 = always the throughput form.  Default: the measured crossover per ring size and kind of launch.
-        if (const char *v = std::getenv("APSU_HE_SPLIT")) two_stream_default_ = std::atoi(v) != 0 ? 1 : 0;
-        if (split_ntt) fuse_tensor_ = false;                     // the fused load belongs to a whole-limb workgroup
-        if (const char *v = std::getenv("APSU_HE_MAC_KARA")) mac_kara_ = std::atoi(v) != 0 ? 1 : 0;
-        if (const char *v = std::getenv("APSU_HE_EVAL_SIDE")) eval_side_ = std::atoi(v) != 0;
-        // BinBundle plaintexts bit-packed in HBM (12.5 % fewer bytes for 56-bit primes, 22 % for 50-bit ones; k_mac<.., PACKED>): in-process
-        // A/B on 16M-4096 -0.146 +- 0.017 ms (-4.2 %) on the whole query, -2.4 % on the N = 8 shard, same bits
-        // (profiles/r04_ab_packed_rows.txt).  Only with key switching (the single-prime paths keep dense rows).
-        if (const char *v = std::getenv("APSU_HE_PACKED_ROWS")) packed_rows_ = std::atoi(v) != 0;
-        if (!hp_.using_keyswitching) packed_rows_ = false;
-        if (const char *v = std::getenv("APSU_HE_EVAL_WS_BYTES")) eval_ws_budget_ = std::strtoull(v, nullptr, 10);
-        if (const char *v = std::getenv("APSU_HE_EVAL_PER_TERM")) force_per_term_ = std::atoi(v) != 0;
-        if (const char *v = std::getenv("APSU_HE_SEED_EXPAND_HOST")) seed_expand_host_ = std::atoi(v) != 0;
-        // The latency form of the LDS-resident transform (ntt_core.h plan_k, c = 8): a limb's workgroup has twice the waves, so a launch
-        // that gives a CU at most one limb hides that limb's LDS turnarounds and table loads behind three other waves per SIMD.
-        // Crossovers: ntt_form.h, ntt_form (tools/microbench/ntt_forms.hip, profiles/r06_ntt_forms_n8192.txt / _n4096.txt).
-        ntt_latency_limbs_ = NTT_FORM_AUTO;
-        data_primes_narrow_ = true;
-        for (int j = 0; j < hp_.K; j++) data_primes_narrow_ = data_primes_narrow_ && ntt_is_narrow(hp_.key_q[j], hp_.logn);
-        // launches over the extended base (map_ext / map_ext_fin) state narrowness with this flag: with the engine's own auxiliary base
-        // (params.cpp, narrow_aux_base) the largest forward launch of a query, the extension transform, takes the 8-wave form
-        ext_primes_narrow_ = data_primes_narrow_;
-        for (u64 m : hp_.aux_primes) ext_primes_narrow_ = ext_primes_narrow_ && ntt_is_narrow(m, hp_.logn);
-        if (const char *v = std::getenv("APSU_HE_FUSE_TAIL")) fuse_tail_ = std::atoi(v) != 0;
-        if (const char *v = std::getenv("APSU_HE_NTT_LATENCY_LIMBS")) ntt_latency_limbs_ = std::strtoull(v, nullptr, 10);
-    }
-    // level constants
-    {
-        const int nl = hp_.first_chain_idx + 1;
-        std::vector<DevLevel> lv(nl);
-        std::vector<int> map_ext((size_t)nl * DMAXE, 0), map_ks((size_t)nl * (DMAXL + 1) * DMAXL, 0),
-            map_ksacc((size_t)nl * (DMAXL + 1), 0);
-        const u64 mt = (u64)1 << 32;
-        for (int c = 0; c < nl; c++) {
-            const LevelConstants &h = hp_.level[c];
-            DevLevel &d = lv[c];
-            std::memset(&d, 0, sizeof(d));
-            const int L = h.L, nB = h.nB, nBsk = nB + 1;
-            if (L > DMAXL || nBsk > DMAXB) throw std::invalid_argument("too many RNS limbs");
-            d.L = L; d.nB = nB; d.nBsk = nBsk; d.E = L + nBsk;
-            std::vector<u64> bsk = h.B;
-            bsk.push_back(h.m_sk);
-            d.t = hp_.t;
-            d.q_mod_t = h.q_mod_t;
-            d.threshold = h.upper_half_threshold;
-            d.half = h.q[L - 1] >> 1;
-            for (int j = 0; j < L; j++) {
-                const u64 qj = h.q[j];
-                ModulusInfo mj(qj);
-                d.q[j] = make_mod(qj);
-                d.ext[j] = d.q[j];
-                {
-                    const int bits = 64 - __builtin_clzll(qj);
-                    const int sh = (bits + 1) / 2;                         // both operand halves < 2^sh (sh <= 30)
-                    d.mac_shift[j] = (u32)sh;
-                    // cross sum takes two products (< 2^(2 sh)) per term, plus one slot for the carried residue
-                    const u64 cap = ((u64)1 << (63 - 2 * sh));
-                    d.mac_chunk[j] = (u32)std::min<u64>(cap > 2 ? cap - 1 : 2, 1u << 20);
-                    // three-product form: one middle product (a0 + a1)(c0 + c1) < 2^(2 sh + 2) per term, the carried residue enters as
-                    // (r0, r0 + r1) < 2^(sh + 1): one slot as well
-                    const u64 capk = 2 * sh + 2 < 64 ? ((u64)1 << (62 - 2 * sh)) : 0;
-                    d.mac_chunk_k[j] = (u32)std::min<u64>(capk > 2 ? capk - 1 : 0, 1u << 20);   // 0: not usable for this modulus
-                    // packed row width: the smallest w >= max(bits, 32) whose 2-coefficient group fits a lane's 16-byte window at every
-                    // position: the group starts at bit 2 w m, i.e. (2 w m) mod 32 <= 32 - gcd(2 w, 32) into its first dword
-                    // (the geometry is there in every context: images of either format load anywhere)
-                    const u32 w = hp_.using_keyswitching ? packed_row_bits(qj) : 64;
-                    d.mac_bits[j] = w;
-                    d.mac_row_off[j] = j ? d.mac_row_off[j - 1] + (u32)(hp_.n * d.mac_bits[j - 1] / 8) : 0;
-                    d.mac_mask_hi[j] = w == 64 ? 0xffffffffu : (u32)(((u64)1 << (w - sh)) - 1);
-                }
-                d.coeff_div_plain[j] = h.coeff_div_plain[j];
-                d.incr[j] = h.upper_half_incr[j];
-                d.half_mod[j] = d.half % qj;
-                if (j + 1 < L) d.inv_q_last[j] = shoup_const(h.inv_q_last[j], qj);
-                d.ext_scale[j] = shoup_const(mj.mul(mt % qj, h.inv_punct_q[j]), qj);
-                d.q_to_mt[j] = (u32)h.q_to_mtilde[j];
-                d.t_inv_punct_q[j] = shoup_const(mj.mul(hp_.t % qj, h.inv_punct_q[j]), qj);
-                d.prod_B_q[j] = h.prod_B_mod_q[j];
-                d.neg_prod_B_q[j] = (qj - h.prod_B_mod_q[j]) % qj;
-                d.s_prod_B_q[j] = shoup_const(d.prod_B_q[j], qj);
-                d.s_neg_prod_B_q[j] = shoup_const(d.neg_prod_B_q[j], qj);
-                for (int i = 0; i < nB; i++) { d.B_to_q[j][i] = h.B_to_q[j][i]; d.s_B_to_q[j][i] = shoup_const(h.B_to_q[j][i], qj); }
-                map_ext[(size_t)c * DMAXE + j] = j;
-            }
-            d.neg_inv_q_mt = (u32)h.neg_inv_q_mod_mtilde;
-            for (int i = 0; i < nBsk; i++) {
-                const u64 m = bsk[i];
-                d.bsk[i] = make_mod(m);
-                d.ext[L + i] = d.bsk[i];
-                for (int j = 0; j < L; j++) { d.q_to_bsk[i][j] = h.q_to_bsk[i][j]; d.s_q_to_bsk[i][j] = shoup_const(h.q_to_bsk[i][j], m); }
-                d.prod_q_bsk[i] = h.prod_q_mod_bsk[i];
-                d.s_prod_q_bsk[i] = shoup_const(h.prod_q_mod_bsk[i], m);
-                d.s_fl[i] = shoup_const(i < nB ? ModulusInfo(m).mul(h.inv_prod_q_mod_bsk[i], h.inv_punct_B[i]) : h.inv_prod_q_mod_bsk[i], m);
-                d.inv_mt_bsk[i] = shoup_const(h.inv_mtilde_mod_bsk[i], m);
-                {
-                    const ModulusInfo mi(m);
-                    for (int j = 0; j < L; j++) d.s_q_to_bsk_mt[i][j] = shoup_const(mi.mul(h.q_to_bsk[i][j] % m, h.inv_mtilde_mod_bsk[i]), m);
-                    d.s_prod_q_bsk_mt[i] = shoup_const(mi.mul(h.prod_q_mod_bsk[i], h.inv_mtilde_mod_bsk[i]), m);
-                }
-                d.t_bsk[i] = shoup_const(hp_.t % m, m);
-                d.inv_prod_q_bsk[i] = shoup_const(h.inv_prod_q_mod_bsk[i], m);
-                if (i < nB) {
-                    d.inv_punct_B[i] = shoup_const(h.inv_punct_B[i], m);
-                    d.B_to_msk[i] = h.B_to_msk[i];
-                    d.s_B_to_msk[i] = shoup_const(h.B_to_msk[i], h.m_sk);
-                }
-                map_ext[(size_t)c * DMAXE + L + i] = hp_.bsk_id(nB, i);
-            }
-            d.inv_prod_B_msk = shoup_const(h.inv_prod_B_mod_msk, h.m_sk);
-            d.msk_half = h.m_sk >> 1;
-            // key-switch maps
-            for (int I = 0; I <= L; I++) {
-                const int id = I == L ? hp_.K - 1 : I;
-                for (int J = 0; J < L; J++) map_ks[(size_t)c * (DMAXL + 1) * DMAXL + (size_t)I * L + J] = id;
-                map_ksacc[(size_t)c * (DMAXL + 1) + I] = id;
-            }
-        }
-        // per-position constants of the unrolled finish kernels: their own constant times the inverse transform's twist
-        // (device.h: fin_q / fin_b), and the matching inverse-NTT maps
-        std::vector<int> map_ext_fin = map_ext;
-        {
-            std::vector<ShoupConst> fin;
-            std::vector<std::pair<int, int>> where;                   // (level, ext limb) of each table, in order
-            for (int c = 0; c < nl; c++) {
-                if (!fast_finish(c)) continue;
-                const LevelConstants &h = hp_.level[c];
-                const int L = h.L, nB = h.nB;
-                for (int e = 0; e < L + nB + 1; e++) {
-                    const int id = e < L ? e : hp_.bsk_id(nB, e - L);
-                    const NttTablesHost &tb = hp_.ntt[id];
-                    const u64 m = tb.mod.value;
-                    const u64 cst = e < L ? lv[c].t_inv_punct_q[e].w : lv[c].t_bsk[e - L].w;
-                    for (size_t k = 0; k < n; k++) fin.push_back(shoup_const(tb.mod.mul(cst, tb.scale[k]), m));
-                    where.push_back({ c, e });
-                    map_ext_fin[(size_t)c * DMAXE + e] |= NTT_MAP_RAW;
-                }
-            }
-            if (!fin.empty()) {
-                d_fin_.alloc(fin.size() * sizeof(ShoupConst));
-                HIP_CHECK(hipMemcpy(d_fin_.p(), fin.data(), fin.size() * sizeof(ShoupConst), hipMemcpyHostToDevice));
-                const ShoupConst *base = reinterpret_cast<const ShoupConst *>(d_fin_.p());
-                for (size_t i = 0; i < where.size(); i++) {
-                    DevLevel &d = lv[where[i].first];
-                    const int e = where[i].second;
-                    if (e < d.L) d.fin_q[e] = base + i * n;
-                    else d.fin_b[e - d.L] = base + i * n;
-                }
-            }
-        }
-        // per-position constants of the drop-last-limb consumers of a RAW inverse transform (device.h: drop_tw / last_tw)
-        {
-            std::vector<ShoupConst> dt;
-            std::vector<std::pair<int, int>> where;                   // (level, limb) ; limb = -1: last_tw
-            const TwPair *twbase = reinterpret_cast<const TwPair *>(d_tw_.p());
-            for (int c = 1; c < nl; c++) {
-                const LevelConstants &h = hp_.level[c];
-                const int L = h.L;
-                for (int j = 0; j + 1 < L; j++) {
-                    const NttTablesHost &tb = hp_.ntt[j];
-                    for (size_t k = 0; k < n; k++) dt.push_back(shoup_const(tb.mod.mul(h.inv_q_last[j], tb.scale[k]), tb.mod.value));
-                    where.push_back({ c, j });
-                }
-                // the dropped limb's plain twist is the transform's own scale table (same {w, wq} layout)
-                lv[c].last_tw = reinterpret_cast<const ShoupConst *>(twbase + ((size_t)(L - 1) * 3 + 2) * n);
-            }
-            if (!dt.empty()) {
-                d_drop_.alloc(dt.size() * sizeof(ShoupConst));
-                HIP_CHECK(hipMemcpy(d_drop_.p(), dt.data(), dt.size() * sizeof(ShoupConst), hipMemcpyHostToDevice));
-                const ShoupConst *base = reinterpret_cast<const ShoupConst *>(d_drop_.p());
-                for (size_t i = 0; i < where.size(); i++) lv[where[i].first].drop_tw[where[i].second] = base + i * n;
-            }
-        }
-        d_levels_.alloc(lv.size() * sizeof(DevLevel));
-        HIP_CHECK(hipMemcpy(d_levels_.p(), lv.data(), lv.size() * sizeof(DevLevel), hipMemcpyHostToDevice));
-        auto up = [](DevBuf &b, const std::vector<int> &v) {
-            b.alloc(v.size() * sizeof(int));
-            HIP_CHECK(hipMemcpy(b.p(), v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-        };
-        up(d_map_ext_, map_ext); up(d_map_ext_fin_, map_ext_fin); up(d_map_ks_, map_ks); up(d_map_ksacc_, map_ksacc);
-        std::vector<int> map_ksacc_raw = map_ksacc;
-        for (int &v : map_ksacc_raw) v |= NTT_MAP_RAW;
-        up(d_map_ksacc_raw_, map_ksacc_raw);
-        std::vector<int> ident(DMAXL + DMAXB + 4);                     // identity over every modulus id (incl. plain modulus)
-        for (size_t i = 0; i < ident.size(); i++) ident[i] = (int)i;
-        up(d_map_ct_, ident);
-    }
-    // key-switching constants
-    {
-        DevKey k;
-        std::memset(&k, 0, sizeof(k));
-        k.K = hp_.K;
-        for (int j = 0; j < hp_.K; j++) k.q[j] = make_mod(hp_.key_q[j]);
-        if (hp_.K > 1) {
-            const u64 p = hp_.key_q[hp_.K - 1];
-            k.p_half = p >> 1;
-            for (int j = 0; j < hp_.K - 1; j++) {
-                k.p_half_mod[j] = k.p_half % hp_.key_q[j];
-                k.inv_p[j] = shoup_const(hp_.inv_p_mod_q[j], hp_.key_q[j]);
-            }
-            // per-position constants of the mod-down behind a RAW inverse transform (device.h: md_tw / p_tw)
-            std::vector<ShoupConst> mt;
-            for (int j = 0; j < hp_.K - 1; j++) {
-                const NttTablesHost &tb = hp_.ntt[j];
-                for (size_t kk = 0; kk < n; kk++) mt.push_back(shoup_const(tb.mod.mul(hp_.inv_p_mod_q[j], tb.scale[kk]), tb.mod.value));
-            }
-            d_mdtw_.alloc(mt.size() * sizeof(ShoupConst));
-            HIP_CHECK(hipMemcpy(d_mdtw_.p(), mt.data(), mt.size() * sizeof(ShoupConst), hipMemcpyHostToDevice));
-            for (int j = 0; j < hp_.K - 1; j++) k.md_tw[j] = reinterpret_cast<const ShoupConst *>(d_mdtw_.p()) + (size_t)j * n;
-            k.p_tw = reinterpret_cast<const ShoupConst *>(reinterpret_cast<const TwPair *>(d_tw_.p()) + ((size_t)(hp_.K - 1) * 3 + 2) * n);
-        }
-        d_key_.alloc(sizeof(DevKey));
-        HIP_CHECK(hipMemcpy(d_key_.p(), &k, sizeof(DevKey), hipMemcpyHostToDevice));
-    }
+    // Every constant the kernels read comes from build_device_constants (dev_consts.cpp).  One allocation per table, in this order:
+    // order and sizes are part of the allocator state the database upload meets (k_mac's rate depends on where the
+    // later buffers land).  Then the tables' addresses go into the structs that name them, then everything is uploaded.
+    auto each = [&](auto f) {
+        f(d_tw_, dc.tw); f(d_tabs_, dc.tabs); f(d_fin_, dc.fin); f(d_drop_, dc.drop); f(d_levels_, dc.levels);
+        f(d_map_ext_, dc.map_ext); f(d_map_ext_fin_, dc.map_ext_fin); f(d_map_ks_, dc.map_ks); f(d_map_ksacc_, dc.map_ksacc);
+        f(d_map_ksacc_raw_, dc.map_ksacc_raw); f(d_map_ct_, dc.map_ct); f(d_mdtw_, dc.mdtw);
+    };
+    each([](DevBuf &b, const auto &v) { b.alloc(v.size() * sizeof(v[0])); });
+    d_key_.alloc(sizeof(DevKey));
+    dc.relocate(reinterpret_cast<const TwPair *>(d_tw_.p()), reinterpret_cast<const ShoupConst *>(d_fin_.p()),
+                reinterpret_cast<const ShoupConst *>(d_drop_.p()), reinterpret_cast<const ShoupConst *>(d_mdtw_.p()));
+    each([](DevBuf &b, const auto &v) { if (b.p()) HIP_CHECK(hipMemcpy(b.p(), v.data(), b.bytes(), hipMemcpyHostToDevice)); });
+    HIP_CHECK(hipMemcpy(d_key_.p(), &dc.key, sizeof(DevKey), hipMemcpyHostToDevice));
     if (hp_.batching) {
-        unlift_exact_ = hp_.key_q[0] / 2 >= hp_.t && hp_.key_q[0] > 2 * hp_.t;   // update_bundle's decode (bin_update.h: bin_unlift) refuses otherwise
         d_slot_map_.alloc(hp_.slot_map.size() * sizeof(uint32_t));
         HIP_CHECK(hipMemcpy(d_slot_map_.p(), hp_.slot_map.data(), hp_.slot_map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
@@ -410,8 +137,7 @@ Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), 
                 if (r <= CT_SIZE_MAX) result_polys_ = std::max(result_polys_, r);
             }
     }
-    size_t init = 4096 * n * sizeof(u64);          // 256 MiB at n = 8192; grows on demand
-    if (const char *env = std::getenv("APSU_HE_ARENA_BYTES")) init = std::strtoull(env, nullptr, 10);
+    const size_t init = sw_.arena_bytes != EngineSwitches::ARENA_AUTO ? sw_.arena_bytes : 4096 * hp_.n * sizeof(u64);   // 256 MiB at n = 8192; grows on demand
     arena_.alloc(init);
     lanes_[1].arena.alloc(std::max<size_t>(init / 4, (size_t)1 << 20));
     lanes_[2].arena.alloc((size_t)1 << 20);
@@ -665,16 +391,6 @@ struct ProfScope {
 #define PROFW(kind, words) ProfScope prof_scope_(this, kind, (uint64_t)(words) * 8)
 // P_MAC's profile unit: BITS of database rows streamed per coefficient index, summed over terms, streams and limbs (64 per limb of
 // a dense row, mac_bits of a bit-packed one) -- bytes streamed = units * n / 8
-static uint32_t packed_row_bits(u64 q)
-{
-    const int bits = 64 - __builtin_clzll(q);
-    for (u32 c = (u32)std::max(bits, 32); c < 64; c++) {
-        u32 g = 2 * c, r = 32;
-        while (r) { const u32 t2 = g % r; g = r; r = t2; }
-        if ((32 - g) + 2 * c <= 128) return c;
-    }
-    return 64;
-}
 uint64_t Engine::mac_units(const std::vector<MacJob> &mj) const
 {
     uint64_t u = 0;
@@ -897,7 +613,7 @@ struct EngineAccess {
 // (16M-4096) and 2 % faster at 150 (256M-4096 has 310).  APSU_HE_MAC_KARA=0/1 forces it off / on wherever it is usable.
 bool Engine::mac_kara(int lvl, uint32_t mean_cnt) const
 {
-    if (mac_kara_ == 0 || (mac_kara_ < 0 && mean_cnt < 96)) return false;
+    if (sw_.mac_kara == 0 || (sw_.mac_kara < 0 && mean_cnt < 96)) return false;
     for (int j = 0; j <= lvl; j++) {
         const int bits = 64 - __builtin_clzll(hp_.key_q[j]), sh = (bits + 1) / 2;
         if (62 - 2 * sh < 3) return false;
@@ -908,7 +624,7 @@ bool Engine::mac_kara(int lvl, uint32_t mean_cnt) const
 void Engine::d_ntt(u64 *data, size_t count, const int *modmap, int period, bool inverse, bool narrow)
 {
     PROF(inverse ? P_NTT_INV : P_NTT_FWD, count);
-    launch_ntt(hp_.logn, inverse, data, count, tabs(), modmap, period, st_, ntt_latency_limbs_, narrow);
+    launch_ntt(hp_.logn, inverse, data, count, tabs(), modmap, period, st_, sw_.ntt_latency_limbs, narrow);
 }
 
 bool Engine::d_relinearize(u64 *ct3, size_t ct_stride, int batch, const RelinKeys &rk, int chain_idx, u64 *ext_out, int n_ext, u64 **defer_moddown)
@@ -928,7 +644,7 @@ bool Engine::d_relinearize(u64 *ct3, size_t ct_stride, int batch, const RelinKey
         bool nored = hp_.logn <= 14;
         for (int I = 0; I <= L && nored; I++) nored = ntt_gather_nored_ok(hp_.key_q[I < L ? I : hp_.K - 1], max_src, hp_.logn);
         PROF(P_NTT_FWD, src.size());
-        launch_ntt_gather(hp_.logn, upload_jobs(src), tdec, src.size(), tabs(), map_ks(chain_idx), (L + 1) * L, st_, nored, ntt_latency_limbs_, data_primes_narrow_);
+        launch_ntt_gather(hp_.logn, upload_jobs(src), tdec, src.size(), tabs(), map_ks(chain_idx), (L + 1) * L, st_, nored, sw_.ntt_latency_limbs, data_primes_narrow_);
     }
     u64 *acc = ws((size_t)batch * 2 * (L + 1) * n);
     // the inverse transform leaves its twist to the mod-down kernel, whose own constants absorb it (unrolled sizes)
@@ -1473,7 +1189,7 @@ void Engine::dag_level(DagRun &run, size_t d, const RelinKeys *rk)
     }
     if (fuse_tensor_) {                                                                                              // :422/:424
         PROF(P_NTT_FUSED, tj.size() * 3 * Ef);
-        launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Ef, Ef * n, nullptr, 0, tabs(), map_ext_fin(first), (int)Ef, st_, ntt_latency_limbs_);
+        launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Ef, Ef * n, nullptr, 0, tabs(), map_ext_fin(first), (int)Ef, st_, sw_.ntt_latency_limbs);
     } else {
         { PROF(P_TENSOR, 0); launch_tensor(dlevel(first), upload_jobs(tj), n, (int)tj.size(), st_); }
         d_ntt(run.dbuf, (size_t)nn * nb * 3 * Ef, map_ext_fin(first), (int)Ef, true, ext_primes_narrow_);
@@ -1535,7 +1251,7 @@ void Engine::dag_outputs(DagRun &run, Powers &pw, bool do_low, bool do_high)
         bool nored = hp_.logn <= 14;
         for (size_t j = 0; j < Lf && nored; j++) nored = ntt_gather_nored_ok(hp_.key_q[j], hp_.key_q[j], hp_.logn);
         PROF(P_NTT_FWD, srcp.size());
-        launch_ntt_gather(hp_.logn, upload_jobs(srcp), pw.low.u(), srcp.size(), tabs(), map_ct(), (int)Lf, st_, nored, ntt_latency_limbs_, data_primes_narrow_);
+        launch_ntt_gather(hp_.logn, upload_jobs(srcp), pw.low.u(), srcp.size(), tabs(), map_ct(), (int)Lf, st_, nored, sw_.ntt_latency_limbs, data_primes_narrow_);
     } else if (do_low) {
         convert(s.low_powers, pw.low_level, pw.low.u());
         d_ntt_ct(pw.low.u(), (size_t)pw.n_low * nb * 2, pw.low_level, false);                         // :467,475
@@ -1607,7 +1323,7 @@ std::unique_ptr<Powers> Engine::compute_powers(const uint32_t *bundle_indices, i
     wst.high_async = recycled && pw->high_async && pw->high_ready;
     wst.split_ok = split_ok_;
     wst.prof_on = prof_on_;
-    wst.split_mode = two_stream_mode_ >= 0 ? two_stream_mode_ : two_stream_default_;       // API override, then environment
+    wst.split_mode = two_stream_mode_ >= 0 ? two_stream_mode_ : sw_.two_stream_default;       // API override, then environment
     wst.pipe_cp = pipe_cp_;
     wst.force_pipe = force_pipe_;
     wst.inputs_ready = inputs_ready_;
@@ -2327,61 +2043,19 @@ void Engine::seed_expand(int chain_idx, int count, const u64 *seeds, u64 *const 
     if (!seeds || !dst) throw std::invalid_argument("null argument");
     const bool key_level = chain_idx < 0 || chain_idx == hp_.K - 1;
     if (!key_level) check_level(chain_idx);
+    for (int i = 0; i < count; i++) if (!dst[i]) throw std::invalid_argument("null destination");
     const int L = key_level ? hp_.K : chain_idx + 1;
+    TIER1_SLOTS();
+    job_seq_ = job_seq_base_;
     // The device list holds 8192 rejected words per object.  The rejection rate is ~q / 2^64 per word, so ~60-bit primes with a large
     // L * n may legitimately exceed it (and L may exceed the device tables): those objects are expanded by the host's
     // sample_poly_uniform (seal_codec.cpp) and uploaded -- slower, same words.  APSU_HE_SEED_EXPAND_HOST=1 forces that path (tests).
-    auto host_expand = [&] {
-        std::vector<u64> q(hp_.key_q.begin(), hp_.key_q.begin() + L), buf((size_t)L * hp_.n);
-        for (int i = 0; i < count; i++) {
-            if (!dst[i]) throw std::invalid_argument("null destination");
-            sealio::sample_poly_uniform(seeds + (size_t)i * 8, q.data(), (size_t)L, hp_.n, buf.data());
-            HIP_CHECK(hipMemcpyAsync(dst[i], buf.data(), buf.size() * sizeof(u64), hipMemcpyHostToDevice, st_));
-            sync();                                              // buf is reused
-        }
-    };
-    if (L > DMAXL || seed_expand_host_) { host_expand(); return; }
-    const DevLevel *lv = nullptr;
-    if (key_level && hp_.K - 1 > hp_.first_chain_idx) {
-        // the key level is not a data level: a DevLevel-shaped view that carries its moduli only
-        if (!d_key_level_.p()) {
-            std::vector<unsigned char> raw(sizeof(DevLevel), 0);
-            DevLevel *d = reinterpret_cast<DevLevel *>(raw.data());
-            d->L = hp_.K;
-            for (int j = 0; j < hp_.K; j++) d->q[j] = make_mod(hp_.key_q[j]);
-            d_key_level_.alloc(sizeof(DevLevel));
-            HIP_CHECK(hipMemcpy(d_key_level_.p(), raw.data(), sizeof(DevLevel), hipMemcpyHostToDevice));
-        }
-        lv = reinterpret_cast<const DevLevel *>(d_key_level_.p());
-    } else lv = dlevel(key_level ? hp_.K - 1 : chain_idx);
-    TIER1_SLOTS();
-    job_seq_ = job_seq_base_;
-    std::vector<u64> mm(L);
-    for (int j = 0; j < L; j++) mm[j] = ~(u64)0 - (~(u64)0 % hp_.key_q[j]) - 1;          // util/rlwe.cpp: max_multiple
-    std::vector<SeedJob> jobs(count);
-    for (int i = 0; i < count; i++) {
-        for (int k = 0; k < 8; k++) jobs[i].seed.w[k] = seeds[(size_t)i * 8 + k];
-        jobs[i].dst = dst[i];
-        if (!dst[i]) throw std::invalid_argument("null destination");
-    }
-    const size_t need = ((size_t)count * (1 + 8192) + 1) * sizeof(u32);
-    if (d_seed_rej_.bytes() < need) {
+    bool on_device = queue_seed_expand(L, count, seeds, dst);
+    if (on_device) {
         sync();
-        d_seed_rej_.alloc(need * 2);
-        HIP_CHECK(hipMemsetAsync(d_seed_rej_.p(), 0, d_seed_rej_.bytes(), st_));
+        on_device = !seeds_overflowed(count);                    // more rejected words than the device list holds: the host redoes these objects
     }
-    u32 *rej = reinterpret_cast<u32 *>(d_seed_rej_.p());
-    int *overflow = reinterpret_cast<int *>(rej + (size_t)count * (1 + 8192));
-    HIP_CHECK(hipMemsetAsync(overflow, 0, sizeof(int), st_));
-    { PROF(P_OTHER, 0); launch_seed_expand(upload_jobs(jobs), count, lv, L, upload_jobs(mm), hp_.n, rej, overflow, st_); }
-    int h_overflow = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_overflow, overflow, sizeof(int), hipMemcpyDeviceToHost, st_));
-    sync();
-    if (h_overflow) {
-        HIP_CHECK(hipMemsetAsync(d_seed_rej_.p(), 0, d_seed_rej_.bytes(), st_));
-        sync();
-        host_expand();                                           // more rejected words than the device list holds: the host redoes these objects
-    }
+    if (!on_device) host_seed_expand(L, count, seeds, dst);
 }
 
 // ============================================================================ N4: masks, packing, loopback decrypt
@@ -2508,9 +2182,8 @@ static Blake2xbSeed master_seed(const u64 seed[8])
     return sd;
 }
 
-void Engine::host_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst)
+void Engine::host_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst)
 {
-    const int L = key_level ? hp_.K : hp_.first_chain_idx + 1;
     std::vector<u64> q(hp_.key_q.begin(), hp_.key_q.begin() + L), buf((size_t)L * hp_.n);
     for (int i = 0; i < count; i++) {
         sealio::sample_poly_uniform(seeds + (size_t)i * 8, q.data(), (size_t)L, hp_.n, buf.data());
@@ -2519,24 +2192,16 @@ void Engine::host_seed_expand(bool key_level, int count, const u64 *seeds, u64 *
     }
 }
 
-bool Engine::queue_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst)
+bool Engine::queue_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst)
 {
-    const int L = key_level ? hp_.K : hp_.first_chain_idx + 1;
-    if (L > DMAXL || seed_expand_host_) return false;
-    const DevLevel *lv = nullptr;
-    if (key_level && hp_.K - 1 > hp_.first_chain_idx) {
-        if (!d_key_level_.p()) {                                 // the DevLevel-shaped view of the key level (as in seed_expand)
-            std::vector<unsigned char> raw(sizeof(DevLevel), 0);
-            DevLevel *d = reinterpret_cast<DevLevel *>(raw.data());
-            d->L = hp_.K;
-            for (int j = 0; j < hp_.K; j++) d->q[j] = make_mod(hp_.key_q[j]);
-            d_key_level_.alloc(sizeof(DevLevel));
-            HIP_CHECK(hipMemcpy(d_key_level_.p(), raw.data(), sizeof(DevLevel), hipMemcpyHostToDevice));
-        }
-        lv = reinterpret_cast<const DevLevel *>(d_key_level_.p());
-    } else lv = dlevel(key_level ? hp_.K - 1 : hp_.first_chain_idx);
-    std::vector<u64> mm(L);
-    for (int j = 0; j < L; j++) mm[j] = ~(u64)0 - (~(u64)0 % hp_.key_q[j]) - 1;          // util/rlwe.cpp: max_multiple
+    if (L > DMAXL || sw_.seed_expand_host) return false;
+    const bool key_view = L == hp_.K && !key_level_.empty();     // the key level is not a data level: its moduli-only view (engine.h)
+    if (key_view && !d_key_level_.p()) {
+        d_key_level_.alloc(sizeof(DevLevel));
+        HIP_CHECK(hipMemcpy(d_key_level_.p(), key_level_.data(), sizeof(DevLevel), hipMemcpyHostToDevice));
+    }
+    const DevLevel *lv = key_view ? reinterpret_cast<const DevLevel *>(d_key_level_.p()) : dlevel(L - 1);
+    const std::vector<u64> mm(max_multiple_.begin(), max_multiple_.begin() + L);
     std::vector<SeedJob> jobs(count);
     for (int i = 0; i < count; i++) {
         for (int k = 0; k < 8; k++) jobs[i].seed.w[k] = seeds[(size_t)i * 8 + k];
@@ -2605,8 +2270,8 @@ void Engine::relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_ho
         HIP_CHECK(hipMemcpyAsync(sk, sk_ntt_host, (size_t)K * n * sizeof(u64), hipMemcpyHostToDevice, st_));
         signed char *small = reinterpret_cast<signed char *>(ws((size_t)nk * n / 8));
         u64 *e = ws((size_t)nk * K * n);
-        bool on_device = queue_seed_expand(true, nk, seeds.data(), a.data());
-        if (!on_device) host_seed_expand(true, nk, seeds.data(), a.data());
+        bool on_device = queue_seed_expand(K, nk, seeds.data(), a.data());
+        if (!on_device) host_seed_expand(K, nk, seeds.data(), a.data());
         auto rest = [&] {
             { PROF(P_OTHER, 0); launch_sample_cbd(master, 0, small, n, nk, st_); }
             { PROF(P_OTHER, 0); launch_small_lift(dkey(), small, e, K, n, nk, st_); }
@@ -2616,7 +2281,7 @@ void Engine::relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_ho
         };
         rest();
         if (on_device && seeds_overflowed(nk)) {                 // (seed_expand's fallback: the host redoes the public halves)
-            host_seed_expand(true, nk, seeds.data(), a.data());
+            host_seed_expand(K, nk, seeds.data(), a.data());
             rest();
         }
     });
@@ -2669,8 +2334,8 @@ void Engine::query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint3
         d_ntt(pt, count, map_ct() + tid, 1, true, false);
         { PROF(P_OTHER, 0); launch_sample_cbd(master, QS_KEY_OBJECTS, small, n, count, st_); }
         // Encryptor::encrypt_symmetric: c1 from its public seed, v = c1 s, c0 = Delta(m) - e - v
-        bool on_device = queue_seed_expand(false, count, seeds.data(), c1.data());
-        if (!on_device) host_seed_expand(false, count, seeds.data(), c1.data());
+        bool on_device = queue_seed_expand(L, count, seeds.data(), c1.data());
+        if (!on_device) host_seed_expand(L, count, seeds.data(), c1.data());
         auto rest = [&] {
             std::vector<const u64 *> src((size_t)count * L);
             for (int c = 0; c < count; c++)
@@ -2678,7 +2343,7 @@ void Engine::query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint3
             bool nored = hp_.logn <= 14;                         // (limb j of c1 is a canonical residue of q_j: nothing to reduce)
             for (int j = 0; j < L && nored; j++) nored = ntt_gather_nored_ok(hp_.key_q[j], hp_.key_q[j], hp_.logn);
             { PROF(P_NTT_FWD, src.size());
-              launch_ntt_gather(hp_.logn, upload_jobs(src), v, src.size(), tabs(), map_ct(), L, st_, nored, ntt_latency_limbs_, data_primes_narrow_); }
+              launch_ntt_gather(hp_.logn, upload_jobs(src), v, src.size(), tabs(), map_ct(), L, st_, nored, sw_.ntt_latency_limbs, data_primes_narrow_); }
             { PROF(P_OTHER, 0); launch_dyadic_plain(dlevel(first), v, sk, v, 1, n, count, 0, st_); }
             d_ntt(v, (size_t)count * L, map_ct(), L, true, data_primes_narrow_);
             { PROF(P_OTHER, 0); launch_enc_finish(dlevel(first), pt, v, small, cts_dev, n, count, st_); }
@@ -2687,7 +2352,7 @@ void Engine::query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint3
         };
         rest();
         if (on_device && seeds_overflowed(count)) {
-            host_seed_expand(false, count, seeds.data(), c1.data());
+            host_seed_expand(L, count, seeds.data(), c1.data());
             rest();
         }
     });
@@ -2805,7 +2470,7 @@ void Engine::eval_patstock(EvalCall &c, const std::vector<int> &ps_ids)
     for (size_t j = 0; j < c.Lh; j++) s.q_widest = std::max(s.q_widest, hlevel(c.high).q[j]);
     s.Bs = g.Bs;
     s.high_in_flight = c.pw.high_async && c.pw.high_ready;
-    s.eval_side = eval_side_; s.prof_on = prof_on_; s.force_per_term = force_per_term_; s.fuse_tensor = fuse_tensor_; s.fuse_tail = fuse_tail_;
+    s.eval_side = sw_.eval_side; s.prof_on = prof_on_; s.force_per_term = sw_.force_per_term; s.fuse_tensor = fuse_tensor_; s.fuse_tail = sw_.fuse_tail;
     s.lane2 = lanes_[2].st != nullptr; s.on_lane0 = cur_lane_ == 0;
     const EvalPlan plan = plan_eval(s);
     ps_tables(c, plan, g);
@@ -3015,7 +2680,7 @@ void Engine::ps_products_summed(EvalCall &c, const EvalPlan &plan, PsBatch &g)
         { PROFW(P_TENSOR, ((size_t)NI * 4 + (size_t)Bs * 3) * (Eh - Lh) * n); launch_tensor_sum(dlevel(c.high), (int)Eh, upload_jobs(tj), n, (int)tj.size(), (int)Lh, st_); }
         PROF(P_NTT_FUSED, dmap.size());
         launch_intt_tensor(hp_.logn, upload_jobs(pj), (int)pj.size(), (int)Lh, Eh * n, bsum, dmap.size() - pj.size() * 3 * Lh,
-                           tabs(), upload_jobs(dmap), (int)dmap.size(), st_, ntt_latency_limbs_);
+                           tabs(), upload_jobs(dmap), (int)dmap.size(), st_, sw_.ntt_latency_limbs);
     } else {
         { PROFW(P_TENSOR, ((size_t)NI * 4 * Eh + (size_t)NI * 3 * Lh + (size_t)Bs * 3 * (Eh - Lh)) * n); launch_tensor_sum(dlevel(c.high), (int)Eh, upload_jobs(tj), n, (int)tj.size(), 0, st_); }
         d_ntt(dq, dmap.size(), upload_jobs(dmap), (int)dmap.size(), true, false);
@@ -3052,7 +2717,7 @@ void Engine::ps_products_per_term(EvalCall &c, const EvalPlan &plan, PsBatch &g)
     }
     if (plan.fuse_tensor) {
         PROF(P_NTT_FUSED, tj.size() * 3 * Eh);
-        launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Eh, Eh * n, nullptr, 0, tabs(), map_ext_fin(c.high), (int)Eh, st_, ntt_latency_limbs_);
+        launch_intt_tensor(hp_.logn, upload_jobs(tj), (int)tj.size(), (int)Eh, Eh * n, nullptr, 0, tabs(), map_ext_fin(c.high), (int)Eh, st_, sw_.ntt_latency_limbs);
     } else {
         if (!tj.empty()) { PROF(P_TENSOR, 0); launch_tensor(dlevel(c.high), upload_jobs(tj), n, (int)tj.size(), st_); }
         d_ntt(dbuf, (size_t)NI * 3 * Eh, map_ext_fin(c.high), (int)Eh, true, ext_primes_narrow_);
@@ -3185,7 +2850,7 @@ void Engine::eval_bundles(const Bundle *const *bundles, int count, const Powers 
         else w += (size_t)(6 * Ll + 8) * n;
         per_bundle_words = std::max(per_bundle_words, w);
     }
-    const size_t budget = eval_ws_budget_;
+    const size_t budget = sw_.eval_ws_bytes;
     int chunk = (int)std::max<size_t>(1, budget / (per_bundle_words * sizeof(u64)));
     chunk = std::min(chunk, count);
 

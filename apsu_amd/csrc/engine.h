@@ -298,7 +298,6 @@ private:
     // level has no RAW mod-down constants (L > 4).
     bool d_relinearize(u64 *ct3, size_t ct_stride, int batch, const RelinKeys &rk, int chain_idx, u64 *ext_out = nullptr, int n_ext = 0,
                        u64 **defer_moddown = nullptr);
-    bool fuse_tail_ = true;           // eval_patstock: the last key switch's mod-down inside the epilogue kernel (APSU_HE_FUSE_TAIL=0: its own launch)
     void check_level(int chain_idx) const;
     // tier-1 caller data (host operands): every word of limb j of each of `polys` polynomials at chain_idx below q_j, else invalid_argument
     void check_tier1_residues(const u64 *ct, size_t polys, int chain_idx, const char *what) const;
@@ -316,6 +315,7 @@ private:
     uint32_t result_polys_ = 2;
 
     HeParams hp_;
+    const EngineSwitches sw_ = read_switches();   // the environment, read once per context (dev_consts.h)
     PSUParams psu_;
     bool has_psu_ = false;
     PowersDag dag_;
@@ -341,8 +341,6 @@ private:
     bool force_pipe_ = false;         // ... whether or not an evaluation is still running (set_query_overlap 3)
     bool data_primes_narrow_ = false; // every key prime runs the transform without range control (ntt_is_narrow)
     bool ext_primes_narrow_ = false;  // ... and so does every modulus of the extended base q u Bsk (HeParams::aux_narrow)
-    size_t ntt_latency_limbs_ = 0;    // transform launches of at most this many limbs take the 8-coefficient-per-lane form (APSU_HE_NTT_LATENCY_LIMBS)
-    bool eval_side_ = true;           // cf sums + i = 0 finish of eval_patstock on a side stream (APSU_HE_EVAL_SIDE=0: on the main stream)
     bool async_results_ = false;      // eval_bundles with device masks + device output returns once the work is queued
     // Asynchronous evaluations in flight: the host may run at most max_inflight_ queries ahead of the device.  Unbounded
     // run-ahead (20 queued queries = 1300 launches + 200 stream events) makes the HIP runtime block the host inside a
@@ -397,20 +395,16 @@ private:
     } sched_, sched_low_, sched_high_;
     void mask_generate_impl(uint32_t count, u64 *masks_dev, u64 *values_host, u64 *blocks_host, const std::function<void(u64 *, size_t)> &fill);
     bool fuse_tensor_ = true;         // BEHZ step 4 is formed by the inverse transform's load (k_intt_tensor); off only for n = 32768, whose limb does not fit one workgroup
-    bool force_per_term_ = false;     // APSU_HE_EVAL_PER_TERM: eval_patstock's products finished one by one (the fallback of the summed finish)
-    bool seed_expand_host_ = false;   // APSU_HE_SEED_EXPAND_HOST: seeded objects expanded by the host codec (the fallback of the device sampler)
     bool tier1_device_ = false;       // tier-1 operands are device memory and calls do not synchronise
     void tier1_done() { if (!tier1_device_ || prof_on_) sync(); }
-    bool packed_rows_ = true;         // BinBundle plaintexts are kept bit-packed in HBM (APSU_HE_PACKED_ROWS=0: dense 64-bit words; Bundle::packed)
+    bool packed_rows_ = true;         // BinBundle plaintexts are kept bit-packed in HBM (EngineSwitches::packed_rows, with key switching only; Bundle::packed)
     size_t slot_bytes(int chain_idx, bool packed) const;          // bytes of one NTT-form plaintext at a level, either format
     void pack_bundle(Bundle &b);      // dense -> packed when this context keeps packed rows (no-op otherwise)
     void unpack_bundle(Bundle &b);    // packed -> dense (images of the other format)
-    int mac_kara_ = -1;               // k_mac with three products per term instead of four: -1 by chain length, 0 / 1 forced (APSU_HE_MAC_KARA)
     bool mac_kara(int lvl, uint32_t mean_cnt) const;
     uint64_t mac_units(const std::vector<MacJob> &mj) const;      // bits of database rows per coefficient index (profile unit of P_MAC)
-    size_t eval_ws_budget_ = (size_t)6 << 30;
     bool split_ok_ = false;           // the low-power and high-power halves of the PowersDag share no node
-    int two_stream_mode_ = -1, two_stream_default_ = -1;   // apsu_he_set_two_stream ; APSU_HE_SPLIT
+    int two_stream_mode_ = -1;        // apsu_he_set_two_stream (-1: EngineSwitches::two_stream_default)
     void build_schedule();
     void build_schedule_for(Sched &s, const std::vector<char> &member);
     struct DagRun;                    // per-call state of one walk over a schedule
@@ -446,13 +440,18 @@ private:
     double lookup_decode_ms_ = 0, lookup_kernels_ms_ = 0;
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
-    // seed expansion queued on the stream without a host wait (query_create, relin_keygen): false = the objects need the host's
+    // seed expansion of `count` objects of L limbs queued on the stream without a host wait (seed_expand, query_create, relin_keygen): false = the objects need the host's
     // sampler (seed_expand's rule) and nothing was queued; seeds_overflowed() after the final sync tells whether the device lists sufficed
-    bool queue_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst);
+    bool queue_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst);
     bool seeds_overflowed(int count);
-    void host_seed_expand(bool key_level, int count, const u64 *seeds, u64 *const *dst);
+    void host_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst);
     void check_key_residues(const u64 *sk_ntt_host, int limbs) const;
-    DevBuf d_seed_rej_, d_seed_mm_, d_key_level_;   // seed expansion: rejection lists, max_multiple per (level, limb), DevLevel-shaped view of the key level
+    // seed expansion: rejection lists; the DevLevel-shaped view of the key level and max_multiple per key prime as build_device_constants
+    // made them.  The view is uploaded by the first expansion at the key level, not at creation: one more allocation in front of the
+    // database upload would move every buffer behind it (k_mac's rate depends on where they land).
+    DevBuf d_seed_rej_, d_key_level_;
+    std::vector<DevLevel> key_level_;
+    std::vector<u64> max_multiple_;
 
     // profiling state
     struct ProfRec { hipEvent_t a, b; int kind; uint64_t units; };

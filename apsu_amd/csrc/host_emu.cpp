@@ -9,8 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "ntt_core.h"
-#include "ntt_form.h"
+#include "dev_consts.h"
 #include "blake2x.h"
 #include "bin_update.h"
 #include "bin_lookup.h"
@@ -102,10 +101,7 @@ int emu_ntt_limb_c(int logn, int inverse, uint64_t q, uint64_t *data, int thread
             fwd[k] = { t.fwd[k], t.fwd_q[k] };
             dit[k] = { t.dit[k], t.dit_q[k] }; sc[k] = { t.scale[k], t.scale_q[k] };
         }
-        NttTable tab{ q, t.ninv, t.ninv_q, t.mod.ratio[1], fwd.data(), dit.data(), sc.data(),
-                      ntt_is_narrow(q, logn) ? 1 : 0, 0, 0, 0 };
-        ntt_fold_params(q, tab.fold_k, tab.fold_c);
-        tab.wide_d4 = ntt_wide_d4(q, tab.narrow != 0);
+        const NttTable tab = make_ntt_table(t, logn, fwd.data(), dit.data(), sc.data());
         if (coeffs == 8) {
             if (logn == 13) { if (inverse) emu_ntt<13, true, 8>(data, tab, threads); else emu_ntt<13, false, 8>(data, tab, threads); }
             else { if (inverse) emu_ntt<12, true, 8>(data, tab, threads); else emu_ntt<12, false, 8>(data, tab, threads); }
@@ -140,9 +136,7 @@ int emu_intt_tensor_limb_c(int logn, uint64_t q, const uint64_t *x0, const uint6
             fwd[k] = { t.fwd[k], t.fwd_q[k] };
             dit[k] = { t.dit[k], t.dit_q[k] }; sc[k] = { t.scale[k], t.scale_q[k] };
         }
-        NttTable tab{ q, t.ninv, t.ninv_q, t.mod.ratio[1], fwd.data(), dit.data(), sc.data(), ntt_is_narrow(q, logn) ? 1 : 0, 0, 0, 0 };
-        ntt_fold_params(q, tab.fold_k, tab.fold_c);
-        tab.wide_d4 = ntt_wide_d4(q, tab.narrow != 0);
+        const NttTable tab = make_ntt_table(t, logn, fwd.data(), dit.data(), sc.data());
         if (!ntt_fold128_ok(tab.fold_k, tab.fold_c)) return -2;
         // coeffs | 0x100: the products enter as the fold's last word (< 4q) where the engine would take them so (k_intt_tensor: ntt_lazy_input_ok)
         const bool lazy = (coeffs & 0x100) != 0;
@@ -230,9 +224,7 @@ int emu_qs_pow_mod(uint64_t t, const uint64_t *x, const uint32_t *e, uint64_t *o
 // ntt_reduce128_fold on explicit (hi, lo) pairs; returns 0 when the modulus does not admit it
 int emu_reduce128(uint64_t q, const uint64_t *hi, const uint64_t *lo, uint64_t *out, int count)
 {
-    NttTable tab{};
-    tab.q = q;
-    ntt_fold_params(q, tab.fold_k, tab.fold_c);
+    const NttTable tab = make_ntt_table(q, 0);                  // (the reductions do not look at the transform's depth)
     if (!ntt_fold128_ok(tab.fold_k, tab.fold_c)) return 0;
     for (int i = 0; i < count; i++) out[i] = ntt_reduce128_fold(hi[i], lo[i], tab);
     return (int)tab.fold_k;
@@ -241,10 +233,7 @@ int emu_reduce128(uint64_t q, const uint64_t *hi, const uint64_t *lo, uint64_t *
 // ntt_reduce_any (the fold / Barrett final reduction of the NTT kernels) on explicit values; returns fold_k
 int emu_reduce_any(uint64_t q, const uint64_t *x, uint64_t *out, int count)
 {
-    ModulusInfo m(q);
-    NttTable tab{};
-    tab.q = q; tab.r1 = m.ratio[1];
-    ntt_fold_params(q, tab.fold_k, tab.fold_c);
+    const NttTable tab = make_ntt_table(q, 0);
     for (int i = 0; i < count; i++) out[i] = ntt_reduce_any(x[i], tab);
     return (int)tab.fold_k;
 }
@@ -331,6 +320,62 @@ int emu_aux_base(const char *json, int narrow, uint64_t *out, int cap)
         for (size_t i = 0; i < v.size() && (int)i < cap; i++) out[i] = v[i];
         return (int)v.size();
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// The constant blocks a context uploads (dev_consts.h: build_device_constants), for tests/test_dev_consts_cpu.py.  The context comes
+// from a parameter file (json) or, with json = NULL, from HeParams::Create(n, primes[k], t); narrow = 1: AuxBase::Narrow, the engine's
+// default, 0: SEAL's base.  block: tw, tabs, fin, drop, levels, map_ext, map_ext_fin, map_ks, map_ksacc, map_ksacc_raw, map_ct, mdtw, key,
+// key_level, max_multiple (u64 per key prime), scalars (u64: data_primes_narrow, ext_primes_narrow, unlift_exact, then
+// packed_row_bits per key prime).  A block is the bytes the engine uploads (arrays of TwPair / NttTable / ShoupConst / DevLevel / int,
+// one DevKey; padding is zero), except that every pointer member holds its table reference: 1 + the element offset into the table it
+// points into (16-byte elements), 0 for null.  Returns the block's size in bytes (copied to out when cap is large enough), or -1.
+int64_t emu_device_constants(const char *json, uint64_t n, const uint64_t *primes, int k, uint64_t t, int narrow, const char *block, void *out,
+                             uint64_t cap)
+{
+    try {
+        const AuxBase aux = narrow ? AuxBase::Narrow : AuxBase::Seal;
+        const HeParams hp = json ? HeParams::FromPSUParams(PSUParams::Load(json), aux) : HeParams::Create((size_t)n, std::vector<u64>(primes, primes + k), t, aux);
+        const DeviceConstants dc = build_device_constants(hp);
+        std::vector<u64> scalars{ dc.data_primes_narrow, dc.ext_primes_narrow, dc.unlift_exact };
+        scalars.insert(scalars.end(), dc.row_bits.begin(), dc.row_bits.end());
+        const std::string b = block;
+        const void *p = nullptr;
+        size_t bytes = 0;
+        auto take = [&](const char *name, const auto &v) { if (b == name) { p = v.data(); bytes = v.size() * sizeof(v[0]); } return b == name; };
+        if (b == "key") { p = &dc.key; bytes = sizeof(DevKey); }
+        else if (!(take("tw", dc.tw) || take("tabs", dc.tabs) || take("fin", dc.fin) || take("drop", dc.drop) || take("levels", dc.levels) ||
+                   take("map_ext", dc.map_ext) || take("map_ext_fin", dc.map_ext_fin) || take("map_ks", dc.map_ks) || take("map_ksacc", dc.map_ksacc) ||
+                   take("map_ksacc_raw", dc.map_ksacc_raw) || take("map_ct", dc.map_ct) || take("mdtw", dc.mdtw) || take("key_level", dc.key_level) ||
+                   take("max_multiple", dc.max_multiple) || take("scalars", scalars)))
+            throw std::invalid_argument("unknown block");
+        if (bytes && bytes <= cap) std::memcpy(out, p, bytes);
+        return (int64_t)bytes;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// sizeof NttTable, DevLevel, DevKey, then DMAXL, DMAXB (the test's mirror of the layouts checks itself against these)
+void emu_dev_layout(uint64_t *out) { out[0] = sizeof(NttTable); out[1] = sizeof(DevLevel); out[2] = sizeof(DevKey); out[3] = DMAXL; out[4] = DMAXB; }
+
+// make_ntt_table for modulus q and `logn` stages: out = q, ninv, ninv_q, r1, r0, narrow, fold_k, fold_c, wide_d4.  with_tables = 1: the
+// form that takes the modulus' tables (q = 1 mod 2^(logn+1)); 0: the modulus-only form (ninv = ninv_q = 0)
+int emu_ntt_table(uint64_t q, int logn, int with_tables, uint64_t *out)
+{
+    try {
+        const NttTable tab = with_tables ? make_ntt_table(HeParams::Create((size_t)1 << logn, { q }, 65537 < q ? 65537 : 3).ntt[0], logn, nullptr, nullptr, nullptr)
+                                         : make_ntt_table(q, logn);
+        const u64 v[9] = { tab.q, tab.ninv, tab.ninv_q, tab.r1, tab.r0, (u64)tab.narrow, tab.fold_k, tab.fold_c, tab.wide_d4 };
+        for (int i = 0; i < 9; i++) out[i] = v[i];
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// read_switches() under the caller's environment: two_stream_default, eval_side, packed_rows, eval_ws_bytes, arena_bytes, force_per_term,
+// mac_kara, seed_expand_host, fuse_tail, ntt_latency_limbs (signed values as int64)
+void emu_switches(int64_t *out)
+{
+    const EngineSwitches s = read_switches();
+    const int64_t v[10] = { s.two_stream_default, s.eval_side, s.packed_rows, (int64_t)s.eval_ws_bytes, (int64_t)s.arena_bytes, s.force_per_term,
+                            s.mac_kara, s.seed_expand_host, s.fuse_tail, (int64_t)s.ntt_latency_limbs };
+    for (int i = 0; i < 10; i++) out[i] = v[i];
 }
 
 // PowersDag::configure on explicit sets; nodes: [power, depth, p1, p2] ascending by power

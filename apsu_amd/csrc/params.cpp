@@ -2,7 +2,7 @@
 // :290-374 (Load from JSON), common/apsu/util/utils.cpp:146-177 (create_powers_set).
 // SEAL-defined constants follow SURVEY.md App. B ([SEAL-recall]: SEAL is not in the image).
 #include "params.h"
-#include "ntt_core.h"
+#include "dev_consts.h"
 
 #include <algorithm>
 #include <cctype>
@@ -460,10 +460,7 @@ bool narrow_aux_base(HeParams &hp)
     const int maxL = hp.first_chain_idx + 1;
     const size_t count = (size_t)maxL + 3;
     auto usable = [&](u64 q) {
-        NttTable tab{};
-        tab.q = q;
-        tab.narrow = ntt_is_narrow(q, hp.logn) ? 1 : 0;
-        ntt_fold_params(q, tab.fold_k, tab.fold_c);
+        const NttTable tab = make_ntt_table(q, hp.logn);
         return tab.narrow && ntt_lazy_input_ok(tab, hp.logn);
     };
     std::vector<u64> primes;

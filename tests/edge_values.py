@@ -4,7 +4,7 @@ The kernels keep values above q for several steps or sum products without carrie
 random residues sit far below those bounds.  These helpers build the operands that reach them:
 
   * extremes(q, s): the range edges of one residue, plus the residue whose two s-bit halves (k_mac's operand split,
-    engine.cpp: s = ceil(bits(q) / 2)) are both as large as a residue below q allows;
+    dev_consts.cpp, build_level: s = ceil(bits(q) / 2)) are both as large as a residue below q allows;
   * fill(...): whole polynomials of one extreme, of alternating extremes, or random with extremes sprinkled in;
   * source_with_ntt_image(C, lvl, V): a coefficient-form ciphertext whose forward transform is exactly V (the oracle's
     inverse transform), so a test picks the NTT-form operands a multiply-accumulate reads.
@@ -20,7 +20,7 @@ def mac_shift(q):
 
 
 def mac_chunk(q):
-    """terms per carry-free chunk of the two-cross-product form (engine.cpp, DevLevel::mac_chunk)"""
+    """terms per carry-free chunk of the two-cross-product form (dev_consts.cpp build_level, DevLevel::mac_chunk; held to it by test_dev_consts_cpu.py)"""
     s = mac_shift(q)
     cap = 1 << (63 - 2 * s)
     return min(cap - 1 if cap > 2 else 2, 1 << 20)

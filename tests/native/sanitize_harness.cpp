@@ -1,6 +1,6 @@
 // CPU tier, sanitizer build (AddressSanitizer + UndefinedBehaviorSanitizer) of the product's HOST code that parses untrusted or
 // structured input: the N3 framing reader (wire.cpp), the PSUParams JSON reader + constant derivation (params.cpp), the
-// PowersDag (powers_dag.cpp) and the partition rule (sharding.cpp).  Built and run by tests/test_host_sanitizers.py; any
+// constant blocks built from them (dev_consts.cpp), the PowersDag (powers_dag.cpp) and the partition rule (sharding.cpp).  Built and run by tests/test_host_sanitizers.py; any
 // out-of-bounds read in the verifier, signed overflow or misaligned access aborts the run.
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../apsu_amd/csrc/params.h"
+#include "../../apsu_amd/csrc/dev_consts.h"
 #include "../../apsu_amd/csrc/powers_dag.h"
 #include "../../apsu_amd/csrc/sharding.h"
 #include "../../apsu_amd/csrc/wire.h"
@@ -195,6 +196,25 @@ int main(int argc, char **argv)
         std::stringstream ss; ss << f.rdbuf();
         PSUParams p = PSUParams::Load(ss.str());
         HeParams hp = HeParams::FromPSUParams(p);
+        // the constant blocks of both auxiliary bases; after relocate() every table pointer must lie inside the table it names
+        for (AuxBase aux : { AuxBase::Seal, AuxBase::Narrow }) {
+            DeviceConstants dc = build_device_constants(HeParams::FromPSUParams(p, aux));
+            dc.relocate(dc.tw.data(), dc.fin.data(), dc.drop.data(), dc.mdtw.data());
+            const size_t n = hp.n;
+            auto inside = [&](const void *ptr, const auto &table, size_t len) {      // null, or `len` elements inside the table
+                const size_t at = (size_t)(static_cast<const char *>(ptr) - reinterpret_cast<const char *>(table.data())) / 16;
+                return !ptr || (at < table.size() && len <= table.size() - at);
+            };
+            for (const NttTable &tb : dc.tabs)
+                if (!inside(tb.fwd, dc.tw, hp.logn == 15 ? n / 2 : n) || !inside(tb.dit, dc.tw, n) || !inside(tb.scale, dc.tw, n)) return 21;
+            for (const DevLevel &d : dc.levels) {
+                for (int j = 0; j < DMAXL; j++) if (!inside(d.fin_q[j], dc.fin, n) || !inside(d.drop_tw[j], dc.drop, n)) return 22;
+                for (int j = 0; j < DMAXB; j++) if (!inside(d.fin_b[j], dc.fin, n)) return 22;
+                if (!inside(d.last_tw, dc.tw, n)) return 22;
+            }
+            for (int j = 0; j < DMAXL; j++) if (!inside(dc.key.md_tw[j], dc.mdtw, n)) return 23;
+            if (!inside(dc.key.p_tw, dc.tw, n)) return 23;
+        }
         PowersDag dag;
         if (!dag.configure(p.query_params.query_powers, create_powers_set(p.query_params.ps_low_degree, p.table_params.max_items_per_bin))) return 20;
         std::printf("%s: n=%zu K=%d t=%llu depth=%u\n", argv[i], hp.n, hp.K, (unsigned long long)hp.t, dag.depth());

@@ -234,6 +234,29 @@ def test_relin_keys(name):
     sd.close()
 
 
+def test_seed_expansion_waiting_and_queued_agree_at_the_key_level(monkeypatch):
+    """One set-up, two entries: relin_keygen queues the expansion of its public halves, apsu_he_seed_expand waits for its own.  At a
+    key level above the first data level (K = 3 on the smallest ring) both read the engine's moduli-only view of that level; the same
+    seeds must give the same words either way, and again in a fresh context that expands on the host (APSU_HE_SEED_EXPAND_HOST=1)."""
+    js = common.toy_json(coeff_bits=(40, 40, 36))
+    words = []
+    for host in (False, True):
+        if host:
+            monkeypatch.setenv("APSU_HE_SEED_EXPAND_HOST", "1")
+        G = apsu_amd.HeContext(js)
+        K, n = G.K, 64
+        assert K == 3 and K - 1 > G.first_chain_idx
+        ksk, kseeds = G.relin_keygen(G.keygen(SEED), SEED, want_resident=False)[:2]
+        out = torch.zeros((K - 1, K, n), dtype=torch.int64, device="cuda")
+        for _ in range(2):                                      # (the second call finds the view uploaded)
+            G.seed_expand(-1, kseeds, [out.data_ptr() + i * K * n * 8 for i in range(K - 1)])
+            waited = out.cpu().numpy().view(np.uint64)
+            assert (waited == ksk[:, 1]).all()
+        words.append(waited)
+        G.close()
+    assert (words[0] == words[1]).all()
+
+
 # ---- 5 + 6: the loop closes without the oracle as producer, and over the wire
 def make_bins(sd, x, rng, max_count):
     bins = []

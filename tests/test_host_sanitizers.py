@@ -1,6 +1,6 @@
 """CPU tier: the product's host code that parses untrusted or structured input, built with AddressSanitizer +
 UndefinedBehaviorSanitizer and driven through a fuzzing harness (tests/native/sanitize_harness.cpp): the N3 framing reader and the SEAL object codec (seeded / zlib ciphertexts, RelinKeys),
-the PSUParams JSON reader with the derived constants, the PowersDag and the partition rule.  (GPU AddressSanitizer is not
+the PSUParams JSON reader with the derived constants and the constant blocks built from them, the PowersDag and the partition rule.  (GPU AddressSanitizer is not
 available on this pool; the device side is covered by the bit-exact parity tests.)"""
 import os
 import subprocess
@@ -15,7 +15,7 @@ def test_host_parsers_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "sanitize_harness")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
            os.path.join(ROOT, "tests", "native", "sanitize_harness.cpp")] + \
-          [os.path.join(SRC, f) for f in ("wire.cpp", "seal_codec.cpp", "params.cpp", "powers_dag.cpp", "sharding.cpp")] + ["-lz", "-ldl", "-o", exe]
+          [os.path.join(SRC, f) for f in ("wire.cpp", "seal_codec.cpp", "params.cpp", "dev_consts.cpp", "powers_dag.cpp", "sharding.cpp")] + ["-lz", "-ldl", "-o", exe]
     subprocess.check_call(cmd)
     params = [os.path.join(ROOT, "tests", "params", f + ".json") for f in ("100K-1", "1M-1024-com", "1M-4096-32", "256M-4096")]
     # seeds for the saved-BinBundle reader come from the FlatBuffers model of tests/test_wire_framing.py (with and without a cache)
