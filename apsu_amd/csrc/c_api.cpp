@@ -307,6 +307,36 @@ int apsu_he_db_apply_entries(apsu_he_ctx *c, uint32_t bundle_idx, const apsu_he_
     });
 }
 
+int apsu_he_bundles_merge(apsu_he_ctx *c, const apsu_he_bundle *const *bundles, uint32_t n_bundles, uint32_t cache_idx, apsu_he_bundle **out)
+{
+    return guarded([&] {
+        REQUIRE(c && out, "null argument");
+        const auto v = bundle_ptrs(bundles, n_bundles);
+        auto b = new apsu_he_bundle;
+        try { b->b = c->eng->merge_bundles(v.data(), n_bundles, cache_idx); } catch (...) { delete b; throw; }
+        *out = b;
+    });
+}
+
+int apsu_he_db_compact(apsu_he_ctx *c, uint32_t bundle_idx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, uint32_t *group,
+                       apsu_he_bundle **merged, uint32_t *n_merged)
+{
+    return guarded([&] {
+        REQUIRE(c && ((group && merged) || !n_bundles), "null argument");
+        const auto v = bundle_ptrs(bundles, n_bundles);
+        Engine::CompactResult r = c->eng->compact(bundle_idx, v.data(), n_bundles);
+        // nothing below throws except the allocation of the handles, which come first
+        std::vector<std::unique_ptr<apsu_he_bundle>> hm(r.merged.size());
+        uint32_t made = 0;
+        for (size_t g = 0; g < hm.size(); g++)
+            if (r.merged[g]) { hm[g] = std::make_unique<apsu_he_bundle>(); hm[g]->b = std::move(r.merged[g]); made++; }
+        for (uint32_t i = 0; i < n_bundles; i++) { group[i] = r.plan.group[i]; merged[i] = i < hm.size() ? hm[i].release() : nullptr; }
+        if (n_merged) *n_merged = made;
+    });
+}
+
+int apsu_he_debug_merge_times(apsu_he_ctx *c, double *decode_ms, double *kernel_ms, double *encode_ms)
+{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->merge_times(decode_ms, kernel_ms, encode_ms); }); }
 int apsu_he_debug_lookup_times(apsu_he_ctx *c, double *decode_ms, double *kernels_ms)
 { return guarded([&] { REQUIRE(c, "null argument"); c->eng->lookup_times(decode_ms, kernels_ms); }); }
 int apsu_he_algebraize_items(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t *felts, int felts_on_device)

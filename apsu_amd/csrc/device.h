@@ -8,6 +8,7 @@
 #include "blake2x.h"
 #include "query_side.h"
 #include "bin_lookup.h"
+#include "bin_merge.h"
 
 namespace apsu_he {
 
@@ -88,6 +89,10 @@ constexpr int LOOKUP_R = 8;                          // points per lane of k_bin
 void launch_bin_counts(const u64 *poly, size_t n, u32 rows, u32 *counts, hipStream_t st);
 void launch_bins_lookup(const LookupWork *work, u32 n_work, const u64 *pts, const u32 *idx, Mod t, const u64 *poly, size_t n, u32 degree,
                         unsigned char *flags, hipStream_t st);
+// merge (Engine::merge_bundles; bin_merge.h): C[rows][n] = the per-slot products of A's and B's polynomials mod t, rows = the largest
+// count of A + that of B + 1.  topsA / topsB: per tile of 64 slots the largest count, -1 for none (merge_tile_tops); A and B hold at
+// least top + 1 rows for every tile.
+void launch_bins_merge(const u64 *A, const int *topsA, const u64 *B, const int *topsB, Mod t, u64 *C, size_t n, u32 rows, hipStream_t st);
 void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 void launch_gather_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 // N1: algebraize_item for `count` 16-byte items -> out[count][felts]; bpf = bits per field element, item_bits = felts * bpf

@@ -164,6 +164,7 @@ Engine::~Engine()
     for (hipEvent_t e : { query_start_, query_end_ }) if (e) (void)hipEventDestroy(e);
     if (ev_main_) (void)hipEventDestroy(ev_main_);
     for (hipEvent_t e : lookup_evs_) (void)hipEventDestroy(e);
+    for (hipEvent_t e : merge_evs_) (void)hipEventDestroy(e);
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_side_) (void)hipEventDestroy(ev_side_);
     if (ev_intt_) (void)hipEventDestroy(ev_intt_);
@@ -1867,6 +1868,127 @@ Engine::ApplyResult Engine::apply_entries(uint32_t bundle_idx, const Bundle *con
     for (uint32_t k = 0; k < pl.n_new; k++) {
         const PlaceLists &li = pl.ins[n_bundles + k];
         res.appended.push_back(build_bundle(bundle_idx, next_cache + k, li.roots.data(), li.counts.data(), bins, li.stride));
+    }
+    return res;
+}
+
+// ---- N1, compaction: several BinBundles of one bundle index into one (bin_merge.h, db_compact.h)
+std::unique_ptr<Bundle> Engine::merge_bundles(const Bundle *const *bundles, uint32_t n_bundles, uint32_t cache_idx)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("merge");
+    if (n_bundles < 2) throw std::invalid_argument("a merge takes at least two BinBundles");
+    for (uint32_t i = 1; i < n_bundles; i++)
+        if (bundles[i]->bundle_idx != bundles[0]->bundle_idx)
+            throw std::invalid_argument("BinBundle " + std::to_string(i) + " belongs to bundle index " + std::to_string(bundles[i]->bundle_idx) +
+                                        ", the first to " + std::to_string(bundles[0]->bundle_idx));
+    const size_t n = hp_.n, tiles = (n + MERGE_LANES - 1) / MERGE_LANES;
+    const uint32_t max_items = psu_.table_params.max_items_per_bin;
+    while (merge_evs_.size() < 5) {
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreate(&e));
+        merge_evs_.push_back(e);
+    }
+    std::unique_ptr<Bundle> b;
+    WITH_ARENA({
+        HIP_CHECK(hipEventRecord(merge_evs_[0], st_));
+        std::vector<u64 *> poly(n_bundles);
+        for (uint32_t i = 0; i < n_bundles; i++) poly[i] = ws((size_t)(bundles[i]->degree + 1) * n);       // [d][slot] slot values
+        uint32_t *dcounts = reinterpret_cast<uint32_t *>(ws(((size_t)n_bundles * n + 1) / 2));
+        const size_t mark = arena_off_;
+        for (uint32_t i = 0; i < n_bundles; i++) {
+            arena_off_ = mark;                                         // the decodes share their workspace (stream order)
+            decode_bundle(*bundles[i], poly[i]);
+            launch_bin_counts(poly[i], n, bundles[i]->degree + 1, dcounts + (size_t)i * n, st_);
+        }
+        arena_off_ = mark;
+        std::vector<uint32_t> counts((size_t)n_bundles * n);
+        HIP_CHECK(hipMemcpyAsync(counts.data(), dcounts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipEventRecord(merge_evs_[1], st_));
+        sync();                                                        // what may be merged, and every step's shape, is decided on the host
+        // step k multiplies the product of BinBundles 0 .. k by BinBundle k + 1; every refusal comes before the first product
+        const uint32_t steps = n_bundles - 1;
+        std::vector<uint32_t> run(counts.begin(), counts.begin() + n), next(n);
+        std::vector<int> tops((size_t)2 * steps * tiles);
+        std::vector<uint32_t> rows(steps);
+        auto top_of = [](const int *t, size_t count) { int m = 0; for (size_t i = 0; i < count; i++) m = std::max(m, t[i]); return (uint32_t)m; };
+        for (uint32_t k = 0; k < steps; k++) {
+            const uint32_t *cb = counts.data() + (size_t)(k + 1) * n;
+            merge_counts(run.data(), cb, n, max_items, next.data());
+            const std::vector<int> ta = merge_tile_tops(run.data(), n), tb = merge_tile_tops(cb, n);
+            std::copy(ta.begin(), ta.end(), tops.begin() + (size_t)2 * k * tiles);
+            std::copy(tb.begin(), tb.end(), tops.begin() + (size_t)(2 * k + 1) * tiles);
+            rows[k] = top_of(ta.data(), tiles) + top_of(tb.data(), tiles) + 1;
+            if (top_of(tb.data(), tiles) > bundles[k + 1]->degree || (!k && top_of(ta.data(), tiles) > bundles[0]->degree))
+                throw std::logic_error("merge: a bin count exceeds its BinBundle's degree");
+            run.swap(next);
+        }
+        const std::vector<int> tfinal = merge_tile_tops(run.data(), n);
+        const uint32_t degree = top_of(tfinal.data(), tiles);
+        int *dtops = reinterpret_cast<int *>(ws((tops.size() + 1) / 2));
+        HIP_CHECK(hipMemcpyAsync(dtops, tops.data(), tops.size() * sizeof(int), hipMemcpyHostToDevice, st_));
+        // (rows[] adds the largest counts of two inputs, which need not be in the same slot: an early step can be the tallest)
+        const uint32_t most_rows = *std::max_element(rows.begin(), rows.end());
+        u64 *buf[2] = { ws((size_t)most_rows * n), steps > 1 ? ws((size_t)most_rows * n) : nullptr };
+        HIP_CHECK(hipEventRecord(merge_evs_[2], st_));
+        const u64 *cur = poly[0];
+        for (uint32_t k = 0; k < steps; k++) {
+            u64 *out = buf[(steps - 1 - k) & 1];                       // the last step writes buf[0]
+            launch_bins_merge(cur, dtops + (size_t)2 * k * tiles, poly[k + 1], dtops + (size_t)(2 * k + 1) * tiles, make_mod(hp_.t), out, n, rows[k], st_);
+            cur = out;
+        }
+        HIP_CHECK(hipEventRecord(merge_evs_[3], st_));
+        b = std::make_unique<Bundle>();
+        b->bundle_idx = bundles[0]->bundle_idx;
+        b->cache_idx = cache_idx;
+        bundle_shape(psu_, hp_, degree, *b);
+        encode_bundle(*b, cur);                                        // rows above `degree` are 0: rows[] is a bound over tiles, degree over slots
+        HIP_CHECK(hipEventRecord(merge_evs_[4], st_));
+        sync();
+    });
+    pack_bundle(*b);
+    const int span[3][2] = { { 0, 1 }, { 2, 3 }, { 3, 4 } };
+    for (int i = 0; i < 3; i++) {
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, merge_evs_[span[i][0]], merge_evs_[span[i][1]]));
+        merge_ms_[i] = ms;
+    }
+    return b;
+}
+
+void Engine::merge_times(double *decode_ms, double *kernel_ms, double *encode_ms)
+{
+    Enter g(this);
+    if (decode_ms) *decode_ms = merge_ms_[0];
+    if (kernel_ms) *kernel_ms = merge_ms_[1];
+    if (encode_ms) *encode_ms = merge_ms_[2];
+}
+
+Engine::CompactResult Engine::compact(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles)
+{
+    CompactResult res;
+    const size_t n = hp_.n;
+    {
+        Enter g(this);
+        TIER1_SLOTS();
+        lookup_check("compact");
+        if (bundle_idx >= psu_.bundle_idx_count) throw std::invalid_argument("bundle_idx out of range");
+        for (uint32_t b = 0; b < n_bundles; b++) {
+            if (bundles[b]->bundle_idx != bundle_idx) throw std::invalid_argument("the BinBundles of one call belong to one bundle index");
+            if (b && bundles[b]->cache_idx <= bundles[b - 1]->cache_idx) throw std::invalid_argument("BinBundles are not in cache order");
+        }
+        std::vector<uint32_t> counts((size_t)n_bundles * n);
+        if (n_bundles) lookup_impl(bundles, n_bundles, nullptr, nullptr, 0, counts.data(), nullptr);
+        res.plan = plan_compaction(counts.data(), n_bundles, n, psu_.table_params.max_items_per_bin);
+    }
+    // the context's lock is taken per merge from here on, as by a caller who made these calls one by one; the given BinBundles are only read
+    res.merged.resize(res.plan.degree.size());
+    for (size_t g = 0; g < res.merged.size(); g++) {
+        std::vector<const Bundle *> members;
+        for (uint32_t b = 0; b < n_bundles; b++)
+            if (res.plan.group[b] == g) members.push_back(bundles[b]);
+        if (members.size() >= 2) res.merged[g] = merge_bundles(members.data(), (uint32_t)members.size(), members[0]->cache_idx);
     }
     return res;
 }

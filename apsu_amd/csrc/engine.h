@@ -19,6 +19,7 @@
 #include "device.h"
 #include "params.h"
 #include "db_place.h"
+#include "db_compact.h"
 #include "powers_dag.h"
 
 namespace apsu_he {
@@ -164,6 +165,19 @@ public:
     // index given in cache order.  The given BinBundles are only read.
     ApplyResult apply_entries(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles, const u64 *ins_felts, const uint32_t *ins_start,
                               size_t n_ins, const u64 *rem_felts, const uint32_t *rem_start, size_t n_rem);
+    // N1, compaction (include/apsu_he.h: apsu_he_bundles_merge, apsu_he_db_compact): the union of two bins is the product of their
+    // polynomials, so n >= 2 BinBundles of one bundle index become ONE new BinBundle without anybody's roots: decode each, per-slot
+    // products pairwise (k_bins_merge, bin_merge.h), the tail of the build.  The given BinBundles are only read.
+    std::unique_ptr<Bundle> merge_bundles(const Bundle *const *bundles, uint32_t n_bundles, uint32_t cache_idx);
+    // device time of the last merge_bundles call: the decodes and counts, the product kernels, the re-encode
+    void merge_times(double *decode_ms, double *kernel_ms, double *encode_ms);
+    struct CompactResult {
+        CompactPlan plan;                                  // group per BinBundle, degree per group (db_compact.h)
+        std::vector<std::unique_ptr<Bundle>> merged;       // [groups]: the new BinBundle of a group of two or more, else null
+    };
+    // bin_counts per BinBundle -> plan_compaction -> merge_bundles per group of two or more, for the BinBundles of one bundle index
+    // given in cache order
+    CompactResult compact(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles);
     // N1, one step earlier: algebraize_item (common/apsu/util/db_encoding.cpp:209-256,360-366) for `count` hashed items of 16 bytes:
     // out[count][felts_per_item], felt j = bits [j*b, (j+1)*b) of the item's first item_bit_count bits, b = bit_count(t) - 1
     void algebraize_items(const unsigned char *items, size_t count, bool items_on_device, u64 *out, bool out_on_device);
@@ -438,6 +452,8 @@ private:
     void lookup_check(const char *what) const;
     std::vector<hipEvent_t> lookup_evs_;               // three per BinBundle of a call: before decode, behind it, behind the kernels
     double lookup_decode_ms_ = 0, lookup_kernels_ms_ = 0;
+    std::vector<hipEvent_t> merge_evs_;                // merge_bundles' five time stamps (created on first use)
+    double merge_ms_[3] = { 0, 0, 0 };
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
     // seed expansion of `count` objects of L limbs queued on the stream without a host wait (seed_expand, query_create, relin_keygen): false = the objects need the host's

@@ -13,6 +13,8 @@
 #include "blake2x.h"
 #include "bin_update.h"
 #include "bin_lookup.h"
+#include "bin_merge.h"
+#include "db_compact.h"
 #include "db_place.h"
 #include "query_side.h"
 #include "params.h"
@@ -583,6 +585,108 @@ int emu_place_entries(uint32_t n_bundles, uint32_t bins, uint32_t F, uint64_t t,
         return 0;
     } catch (const std::invalid_argument &e) { g_err = e.what(); return -1;
     } catch (const std::exception &e) { g_err = e.what(); return -3; }
+}
+
+// k_bins_merge over A[dA + 1][n] and B[dB + 1][n] as the waves run it (bin_merge.h): one wave per (tile, block of K output rows), an explicit
+// loop over its 64 lanes, the K-row window of B in slots r mod K, the walk in chunks of K steps from a multiple of K, a fold every
+// `fold` steps (0: merge_fold_interval(bits(t)), the device's; the sums are 64-bit for t < 2^32 and 128-bit otherwise, as there).
+// The tops come from emu_bin_counts of each input, the refusals from merge_counts without a bound on the sum.  C: [dA + dB + 1][n].
+// stats (may be null): work items, folds inside the walks, longest walk in steps.  Returns 0, or -1 (emu_last_error).
+int emu_bins_merge(uint64_t t_, const uint64_t *A, uint32_t dA, const uint64_t *B, uint32_t dB, uint64_t n, int K, uint32_t fold, uint64_t *C,
+                   uint64_t *stats)
+{
+    try {
+        if (K < 1 || K > 16) throw std::invalid_argument("K out of range");
+        const ModulusInfo mi(t_);
+        const Mod t{ t_, mi.ratio[0], mi.ratio[1] };
+        const int bits = merge_bits(t_);
+        const bool narrow = merge_narrow(bits);
+        if (!fold) fold = merge_fold_interval(bits);
+        std::vector<u32> ca(n), cb(n), sum(n);
+        emu_bin_counts(A, n, dA + 1, ca.data());
+        emu_bin_counts(B, n, dB + 1, cb.data());
+        merge_counts(ca.data(), cb.data(), n, 0, sum.data());
+        const std::vector<int> topsA = merge_tile_tops(ca.data(), n), topsB = merge_tile_tops(cb.data(), n);
+        const u32 rows = dA + dB + 1, blocks = (rows + K - 1) / K;
+        u64 folds = 0, longest = 0;
+        for (size_t tile = 0; tile < topsA.size(); tile++)
+            for (u32 blk = 0; blk < blocks; blk++) {
+                const int k0 = (int)blk * K, topA = topsA[tile], topB = topsB[tile];
+                const MergeWalk wk = merge_walk(k0, K, topA, topB);
+                if (wk.i1 >= wk.i0) longest = std::max(longest, (u64)((wk.i1 - wk.i0) / K + 1) * K);
+                for (int lane = 0; lane < MERGE_LANES; lane++) {
+                    const size_t slot = tile * MERGE_LANES + lane;
+                    if (slot >= n) continue;                       // (the kernel's idle lanes work on slot 0 and store nothing)
+                    const u64 *colA = A + slot, *colB = B + slot;
+                    u64 acc64[16] = { 0 };
+                    u128p acc128[16] = {};
+                    if (wk.i1 >= wk.i0) {
+                        auto rowB = [&](int r) -> u64 {
+                            const int rc = r < 0 ? 0 : (r > topB ? topB : r);
+                            const u64 v = colB[(size_t)rc * n];
+                            return r == rc ? v : 0;
+                        };
+                        auto rowA = [&](int i) -> u64 {
+                            const u64 v = colA[(size_t)(i > wk.i1 ? wk.i1 : i) * n];
+                            return i <= wk.i1 ? v : 0;
+                        };
+                        u64 win[16];
+                        win[0] = 0;
+                        for (int j = 1; j < K; j++) win[j] = rowB(k0 - wk.i0 + j);
+                        u32 pending = 0;
+                        for (int ib = wk.i0; ib <= wk.i1; ib += K) {
+                            u64 a[16], nb[16];
+                            for (int u = 0; u < K; u++) {
+                                a[u] = rowA(ib + u);
+                                nb[u] = rowB(k0 - ib - u);
+                            }
+                            for (int u = 0; u < K; u++) {
+                                if (pending == fold) {
+                                    for (int j = 0; j < K; j++) {
+                                        if (narrow) acc64[j] = merge_fold_narrow(acc64[j], t);
+                                        else acc128[j] = u128p{ merge_fold_wide(acc128[j], t), 0 };
+                                    }
+                                    pending = 0;
+                                    if (!lane) folds++;
+                                }
+                                pending++;
+                                win[(K - u) % K] = nb[u];
+                                for (int j = 0; j < K; j++) {
+                                    if (narrow) merge_mac_narrow(acc64[j], a[u], win[(j - u + K) % K]);
+                                    else merge_mac_wide(acc128[j], a[u], win[(j - u + K) % K]);
+                                }
+                            }
+                        }
+                    }
+                    for (int j = 0; j < K && (u32)(k0 + j) < rows; j++)
+                        C[(size_t)(k0 + j) * n + slot] = narrow ? merge_fold_narrow(acc64[j], t) : merge_fold_wide(acc128[j], t);
+                }
+            }
+        if (stats) { stats[0] = topsA.size() * (u64)blocks; stats[1] = folds; stats[2] = longest; }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+uint32_t emu_merge_fold_interval(int bits) { return merge_fold_interval(bits); }
+int emu_merge_fold_exact(int bits) { return merge_fold_exact(bits) ? 1 : 0; }
+int emu_merge_k() { return MERGE_K; }
+
+// merge_counts (bin_merge.h): sum[n], or -1 with the first offending slot named in emu_last_error.  max_items 0: no bound on the sum.
+int emu_merge_counts(const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t max_items, uint32_t *sum)
+{
+    try { merge_counts(a, b, n, max_items, sum); return 0; } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// plan_compaction (db_compact.h).  counts [n_bundles][n]; group [n_bundles]; degree [n_bundles] (the first `return value` are written).
+// Returns the number of groups.
+int emu_plan_compaction(const uint32_t *counts, uint32_t n_bundles, uint64_t n, uint32_t max_items, uint32_t *group, uint32_t *degree)
+{
+    try {
+        const CompactPlan plan = plan_compaction(counts, n_bundles, n, max_items);
+        std::copy(plan.group.begin(), plan.group.end(), group);
+        std::copy(plan.degree.begin(), plan.degree.end(), degree);
+        return (int)plan.degree.size();
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
 } // extern "C"

@@ -8,6 +8,7 @@
 #include "ntt_wg.h"
 #include "bin_update.h"
 #include "bin_lookup.h"
+#include "bin_merge.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1028,6 +1029,102 @@ void launch_bins_lookup(const LookupWork *work, u32 n_work, const u64 *pts, cons
 {
     if (!n_work) return;
     hipLaunchKernelGGL((k_bins_lookup<LOOKUP_R>), dim3((n_work + 3) / 4), dim3(256), 0, st, work, n_work, pts, idx, t, poly, n, degree, flags);
+    KERNEL_CHECK();
+}
+
+// ---- merge (Engine::merge_bundles): the per-slot product of two decoded BinBundles, C[k] = sum_{i+j=k} A[i] B[j] mod t (bin_merge.h)
+// Lane = slot: one WAVE per (tile of 64 consecutive slots, block of K = MERGE_K consecutive output rows), the K sums in registers.
+// The wave walks A's rows i; a step takes the contiguous row segment A[i] and ONE new row B[k0 - i] of the K-row window of B that
+// slides with it, and does K multiply-adds, so no lane walks down a column and every row segment is read once per K output rows.
+// The walk is unrolled K times from a multiple of K, which turns the window's shift into compile-time slot numbers, and the 2 K row
+// loads of a chunk are issued before its K K multiply-adds.  Rows outside 0 .. top read the nearest row inside (no branch, no
+// out-of-range address) and count as 0.  tops: the tile's largest counts (-1: no bin), which bound the walk.  NARROW (t < 2^32):
+// operands are the low words, the sums 64-bit (v_mad_u64_u32); otherwise 128-bit sums.  `fold` steps between two reductions
+// (merge_fold_interval).  Every row k < rows of C is written for every slot.  No LDS.
+template <bool NARROW>
+__global__ __launch_bounds__(256) void k_bins_merge(const u64 *__restrict__ A, const int *__restrict__ topsA, const u64 *__restrict__ B,
+                                                    const int *__restrict__ topsB, Mod t, u32 fold, u64 *__restrict__ C, size_t n, u32 rows,
+                                                    u32 blocks, u32 n_work)
+{
+    constexpr int K = MERGE_K;
+    using Acc = typename std::conditional<NARROW, u64, u128p>::type;
+    using Val = typename std::conditional<NARROW, u32, u64>::type;
+    const u32 lane = threadIdx.x & 63;
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (w >= n_work) return;
+    const u32 tile = w / blocks;
+    const int k0 = (int)(w % blocks) * K;
+    const size_t slot = (size_t)tile * MERGE_LANES + lane;
+    const bool live = slot < n;                                   // (n < 64 only)
+    const u64 *colA = A + (live ? slot : 0), *colB = B + (live ? slot : 0);
+    const int topA = __builtin_amdgcn_readfirstlane(topsA[tile]), topB = __builtin_amdgcn_readfirstlane(topsB[tile]);
+    const MergeWalk wk = merge_walk(k0, K, topA, topB);
+    Acc acc[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = Acc{};
+    if (wk.i1 >= wk.i0) {                                         // (then topA >= 0 and topB >= 0)
+        // a row of B, 0 outside 0 .. topB; of A, 0 beyond the walk's last step
+        auto rowB = [&](int r) -> Val {
+            const int rc = r < 0 ? 0 : (r > topB ? topB : r);
+            const Val v = (Val)colB[(size_t)rc * n];
+            return r == rc ? v : (Val)0;
+        };
+        auto rowA = [&](int i) -> Val {
+            const Val v = (Val)colA[(size_t)(i > wk.i1 ? wk.i1 : i) * n];
+            return i <= wk.i1 ? v : (Val)0;
+        };
+        Val win[K];
+        win[0] = 0;
+#pragma unroll
+        for (int j = 1; j < K; j++) win[j] = rowB(k0 - wk.i0 + j);
+        u32 pending = 0;
+        for (int ib = wk.i0; ib <= wk.i1; ib += K) {
+            Val a[K], nb[K];
+#pragma unroll
+            for (int u = 0; u < K; u++) {
+                a[u] = rowA(ib + u);
+                nb[u] = rowB(k0 - ib - u);
+            }
+#pragma unroll
+            for (int u = 0; u < K; u++) {
+                if (pending == fold) {                            // wave-uniform
+#pragma unroll
+                    for (int j = 0; j < K; j++) {
+                        if constexpr (NARROW) acc[j] = merge_fold_narrow(acc[j], t);
+                        else acc[j] = u128p{ merge_fold_wide(acc[j], t), 0 };
+                    }
+                    pending = 0;
+                }
+                pending++;
+                win[(K - u) % K] = nb[u];
+#pragma unroll
+                for (int j = 0; j < K; j++) {
+                    if constexpr (NARROW) merge_mac_narrow(acc[j], a[u], win[(j - u + K) % K]);
+                    else merge_mac_wide(acc[j], a[u], win[(j - u + K) % K]);
+                }
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        if ((u32)(k0 + j) >= rows) break;
+        if constexpr (NARROW) C[(size_t)(k0 + j) * n + slot] = merge_fold_narrow(acc[j], t);
+        else C[(size_t)(k0 + j) * n + slot] = merge_fold_wide(acc[j], t);
+    }
+}
+
+void launch_bins_merge(const u64 *A, const int *topsA, const u64 *B, const int *topsB, Mod t, u64 *C, size_t n, u32 rows, hipStream_t st)
+{
+    const int bits = merge_bits(t.q);
+    const u64 tiles = (n + MERGE_LANES - 1) / MERGE_LANES, blocks = ((u64)rows + MERGE_K - 1) / MERGE_K, n_work = tiles * blocks;
+    if (!n_work) return;
+    if (n_work > 0x7fffffffu) throw std::invalid_argument("merge: too many rows for one launch");
+    const dim3 g((unsigned)((n_work + 3) / 4)), b(256);
+    if (merge_narrow(bits))
+        hipLaunchKernelGGL((k_bins_merge<true>), g, b, 0, st, A, topsA, B, topsB, t, merge_fold_interval(bits), C, n, rows, (u32)blocks, (u32)n_work);
+    else
+        hipLaunchKernelGGL((k_bins_merge<false>), g, b, 0, st, A, topsA, B, topsB, t, merge_fold_interval(bits), C, n, rows, (u32)blocks, (u32)n_work);
     KERNEL_CHECK();
 }
 

@@ -141,6 +141,7 @@ NOT_A_BIN = 0xFFFFFFFF
 ENTRY_INSERTED, ENTRY_DUPLICATE, ENTRY_REMOVED, ENTRY_NOT_FOUND = 0, 1, 2, 3
 BUNDLE_UNCHANGED, BUNDLE_REPLACED, BUNDLE_EMPTY = 0, 1, 2
 ApplyResult = collections.namedtuple("ApplyResult", "state bundles appended ins_status ins_target rem_status rem_target")
+CompactResult = collections.namedtuple("CompactResult", "group merged")
 
 
 class RelinKeys:
@@ -472,6 +473,51 @@ class HeContext:
         first = bundles[-1].cache_idx + 1 if bundles else 0
         apps = [wrap(appended[k], bundle_idx, first + k) for k in range(n_app.value)]
         return ApplyResult(state, news, apps, *out)
+
+    def merge_bundles(self, bundles, cache_idx=None):
+        """two or more BinBundles of one bundle index -> a new Bundle holding, per bin, the union (a multiset) of their bins: the
+        product of the bins' polynomials (apsu_he_bundles_merge).  cache_idx: the new BinBundle's, default the first input's.  The
+        inputs need no roots behind them and stay valid."""
+        if cache_idx is None:
+            if not bundles:
+                raise ValueError("a merge takes at least two BinBundles")
+            cache_idx = bundles[0].cache_idx
+        hs = (C.c_void_p * max(len(bundles), 1))(*[b.h for b in bundles])
+        h = C.c_void_p()
+        _check(load_library().apsu_he_bundles_merge(self.h, hs, len(bundles), C.c_uint32(cache_idx), C.byref(h)))
+        deg = C.c_uint32()
+        _check(load_library().apsu_he_bundle_degree(h, C.byref(deg)))
+        return Bundle(self, h, bundles[0].bundle_idx, cache_idx, deg.value)
+
+    def merge_times(self):
+        """-> (decode ms, kernel ms, encode ms): device time of the last merge_bundles call"""
+        a, k, e = C.c_double(), C.c_double(), C.c_double()
+        _check(load_library().apsu_he_debug_merge_times(self.h, C.byref(a), C.byref(k), C.byref(e)))
+        return a.value, k.value, e.value
+
+    def compact(self, bundle_idx, bundles):
+        """the sparse BinBundles of one bundle index, given in cache order, into as few as the placement rule's bound allows
+        (apsu_he_db_compact) -> CompactResult: group [len(bundles)] and merged [groups] (the new Bundle of a group of two or more, with
+        its first member's cache_idx; None for a group of one, whose BinBundle stays as it is).  `bundles` stay valid."""
+        nb = len(bundles)
+        hs = (C.c_void_p * max(nb, 1))(*[b.h for b in bundles])
+        group = np.zeros(nb, dtype=np.uint32)
+        merged = (C.c_void_p * max(nb, 1))()
+        made = C.c_uint32()
+        L = load_library()
+        _check(L.apsu_he_db_compact(self.h, C.c_uint32(bundle_idx), hs, nb, C.c_void_p(group.ctypes.data), merged, C.byref(made)))
+        out = []
+        for g in range(int(group.max()) + 1 if nb else 0):
+            if not merged[g]:
+                out.append(None)
+                continue
+            h = C.c_void_p(merged[g])
+            deg = C.c_uint32()
+            _check(L.apsu_he_bundle_degree(h, C.byref(deg)))
+            first = next(b for i, b in enumerate(bundles) if group[i] == g)
+            out.append(Bundle(self, h, bundle_idx, first.cache_idx, deg.value))
+        assert sum(m is not None for m in out) == made.value
+        return CompactResult(group, out)
 
     def algebraize_items(self, items):
         """util::algebraize_item for items [count][16] uint8 -> felts [count][felts_per_item] (db_encoding.cpp:209-256,360-366)"""

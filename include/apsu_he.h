@@ -228,6 +228,45 @@ int apsu_he_db_apply_entries(apsu_he_ctx *ctx, uint32_t bundle_idx, const apsu_h
                              uint32_t *rem_status, uint32_t *rem_target);
 /* device time of the context's last call of the three above, summed over its BinBundles: the decode, and the kernels behind it */
 int apsu_he_debug_lookup_times(apsu_he_ctx *ctx, double *decode_ms, double *kernels_ms);
+/* N1, compaction: the way back from many sparse BinBundles to few full ones.  The placement rule tries BinBundles newest first and
+ * drops one only when it is empty, so after insertions and removals a bundle index keeps several half-empty BinBundles, and each costs
+ * every query its fixed share: the high-power ciphertext products, a key switch, one result ciphertext, one block of PEQT / OT work.
+ * The union of two bins is the PRODUCT of their polynomials, so BinBundles are merged without anybody's roots: each input is decoded to
+ * its bins' polynomials mod plain_modulus (as by the update), the polynomials of equal slots are multiplied (k_bins_merge: lane = slot,
+ * a wave holds 8 output coefficients of 64 slots in registers; products are summed unreduced, in one 64-bit word for a plain modulus
+ * below 2^32 and in 128 bits above, and reduced once per fold interval), and the tail of the build re-encodes.
+ * apsu_he_bundles_merge: n_bundles >= 2 BinBundles of ONE bundle index -> *out, a NEW BinBundle with that bundle index and the given
+ * cache_idx, holding per bin the union of the inputs' bins.
+ *  - The list of a bin is a multiset: a value that two inputs hold in the same bin is a double root of the merged bin, and one
+ *    removal (apsu_he_bundle_update) takes out one occurrence.
+ *  - If the inputs are build_bundle(B_1) .. build_bundle(B_k), the image of the result (apsu_he_bundle_save) is byte-identical to that
+ *    of build_bundle of the bin-wise union, in whatever order the inputs are given.  Degree, level, Paterson-Stockmeyer layout,
+ *    monomial flags and row packing follow from the merged counts as in the build.
+ *  - A merged BinBundle answers apsu_he_bundles_lookup, apsu_he_bundle_update and queries like any other.  The false-positive note of
+ *    apsu_he_bundles_lookup applies to fuller bins as it does to the reference's: every part present in its bin, each from another item.
+ *  - A slot that holds the zero polynomial in every input keeps it.  Refused (APSU_HE_INVALID_ARGUMENT, apsu_he_last_error names the
+ *    first slot, no bundle is produced): a bin whose summed count reaches max_items_per_bin -- the placement rule's strict bound, so no
+ *    merged bin exceeds max_items_per_bin - 1; inputs whose sets of bins differ (a slot that is a bin in one and holds the zero
+ *    polynomial in another); inputs of different bundle indices; fewer than two inputs.
+ *  - The inputs are only read and stay valid until the caller frees them (queued evaluations may still read them).
+ * apsu_he_db_compact: for the BinBundles of ONE bundle index, given in cache order as for apsu_he_db_apply_entries:
+ * apsu_he_bundle_bin_counts of each, then the rule -- walk them in cache order; a BinBundle joins the FIRST earlier group that has the
+ * same set of bins and, for every bin, count_group + count_bundle < max_items_per_bin (strictly), else it opens a new group; a group's
+ * counts grow as BinBundles join -- then one apsu_he_bundles_merge per group of two or more.
+ *  - group[i], i < n_bundles: the group of BinBundle i; groups are numbered 0, 1, .. in the order of their first members.
+ *  - merged[g]: the NEW BinBundle of group g, with the cache_idx of the group's first member; NULL for a group of one, whose BinBundle
+ *    stays as it is, and for g at or above the number of groups (merged has n_bundles entries, all written).  *n_merged (may be NULL):
+ *    the number of handles produced.  The caller replaces the members of a merged group by merged[g] and frees them when no queued
+ *    evaluation reads them any more.  A second call on the result merges nothing.
+ * Preconditions and locking are the update's (PSUParams, batching, first coefficient prime above 2 * plain_modulus; synchronous;
+ * apsu_he_db_compact takes the context's lock per step).  Single-device contexts only: merging changes the partition of a
+ * multi-device handle, as appending does. */
+int apsu_he_bundles_merge(apsu_he_ctx *ctx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, uint32_t cache_idx,
+                          apsu_he_bundle **out);
+int apsu_he_db_compact(apsu_he_ctx *ctx, uint32_t bundle_idx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, uint32_t *group,
+                       apsu_he_bundle **merged, uint32_t *n_merged);
+/* device time of the context's last apsu_he_bundles_merge: the decodes and counts, the product kernels, the re-encode */
+int apsu_he_debug_merge_times(apsu_he_ctx *ctx, double *decode_ms, double *kernel_ms, double *encode_ms);
 /* "next" row N2: engine-native image of one BinBundle cache (256-byte header with a parameter
  * fingerprint and checksum + the raw limb arrays), the GPU-resident counterpart of ReceiverDB::save / Load
  * (receiver/apsu/receiver_db.cpp:1182-1429, bin_bundle.fbs).  The buffer may be an mmap of a file. */
