@@ -21,6 +21,7 @@
 #include "db_place.h"
 #include "db_compact.h"
 #include "powers_dag.h"
+#include "bundle_layout.h"
 
 namespace apsu_he {
 
@@ -50,7 +51,8 @@ struct RelinKeys {                   // [decomp K-1][2][K][n], NTT form (SEAL KS
 };
 
 // One uploaded BinBundle cache = the batched matching polynomial of BatchedPlaintextPolyn
-// (bin_bundle.h:52-134): coefficient d for all bins, stored per the ctor's rule (bin_bundle.cpp:385-420).
+// (bin_bundle.h:52-134): coefficient d for all bins, stored per the ctor's rule (bin_bundle.cpp:385-420), which bundle_layout.h
+// decides: degree .. ntt_count below are copied from its BundleLayout (Engine::new_bundle), the evaluation reads them.
 struct Bundle {
     uint32_t bundle_idx = 0, cache_idx = 0;
     uint32_t degree = 0;             // batched_coeffs.size() - 1
@@ -103,6 +105,16 @@ struct Powers {
 
 struct MacStream;
 struct PsBatch;
+
+// time stamps of a resident-database call on the engine's stream: events created before the call's first stamp (outside the timed
+// spans), elapsed times read after the call's sync
+struct EventStamps {
+    std::vector<hipEvent_t> ev;
+    void reserve(size_t count);
+    void record(size_t i, hipStream_t st);
+    double ms(size_t from, size_t to) const;
+    void release();
+};
 
 class Engine {
 public:
@@ -283,6 +295,7 @@ public:
 private:
     // arena (bump allocator reset per top-level operation)
     u64 *ws(size_t words);
+    template <class T> T *ws_as(size_t count, size_t extra_words = 0);   // engine_impl.h
     void ws_reset(size_t need_bytes_hint = 0);
     template <class T> const T *upload_jobs(const std::vector<T> &v);
 
@@ -412,6 +425,9 @@ private:
     bool tier1_device_ = false;       // tier-1 operands are device memory and calls do not synchronise
     void tier1_done() { if (!tier1_device_ || prof_on_) sync(); }
     bool packed_rows_ = true;         // BinBundle plaintexts are kept bit-packed in HBM (EngineSwitches::packed_rows, with key switching only; Bundle::packed)
+    // ---- the resident database (engine_bundles.cpp); where a coefficient is stored: bundle_layout.h
+    BundleLayout layout_of(uint32_t degree) const { return bundle_layout(psu_.query_params.ps_low_degree, degree, hp_.first_chain_idx); }
+    std::unique_ptr<Bundle> new_bundle(uint32_t bundle_idx, uint32_t cache_idx, uint32_t degree, BundleLayout *layout = nullptr) const;   // the shape, no buffers yet
     size_t slot_bytes(int chain_idx, bool packed) const;          // bytes of one NTT-form plaintext at a level, either format
     void pack_bundle(Bundle &b);      // dense -> packed when this context keeps packed rows (no-op otherwise)
     void unpack_bundle(Bundle &b);    // packed -> dense (images of the other format)
@@ -443,6 +459,7 @@ private:
     void ps_products_per_term(EvalCall &c, const EvalPlan &plan, PsBatch &g);
     u64 *ps_i0(EvalCall &c, const EvalPlan &plan, PsBatch &g);
     void ps_epilogue(EvalCall &c, PsBatch &g, const u64 *i0);
+    // (engine_bundles.cpp, like everything from here to unlift_exact_)
     void finish_bundle(Bundle &b, const u64 *raw);     // raw: [degree+1][n] coefficient-form plaintexts mod t (device)
     void encode_bundle(Bundle &b, const u64 *poly);    // poly: [degree+1][n] slot values -> BatchEncoder::encode, then finish_bundle
     void decode_bundle(const Bundle &b, u64 *poly);    // the inverse: the stored coefficients back to slot values [degree+1][n] mod t
@@ -450,9 +467,9 @@ private:
     void lookup_impl(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count, uint32_t *counts,
                      unsigned char *flags);
     void lookup_check(const char *what) const;
-    std::vector<hipEvent_t> lookup_evs_;               // three per BinBundle of a call: before decode, behind it, behind the kernels
+    EventStamps lookup_evs_;                           // three per BinBundle of a call: before decode, behind it, behind the kernels
     double lookup_decode_ms_ = 0, lookup_kernels_ms_ = 0;
-    std::vector<hipEvent_t> merge_evs_;                // merge_bundles' five time stamps (created on first use)
+    EventStamps merge_evs_;                            // merge_bundles' five time stamps
     double merge_ms_[3] = { 0, 0, 0 };
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
@@ -489,7 +506,7 @@ private:
     hipEvent_t phase_event(hipStream_t st);
     void phase_close_query();
     void phase_collect();
-    struct Enter;                     // lock + current-device guard taken by every public entry point
+    struct Enter;                     // lock + current-device guard taken by every public entry point (engine_impl.h)
     friend struct EngineAccess;
     friend struct ProfScope;
 };

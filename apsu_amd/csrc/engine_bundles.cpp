@@ -1,0 +1,792 @@
+// See engine.h.  The resident database: BinBundles uploaded, generated, built from bins, updated, searched, merged, saved and loaded.
+// Where each coefficient of a BinBundle is stored is decided in bundle_layout.h alone; this file shares with the query path
+// (engine.cpp) the arena, the streams and the transform launcher (engine_impl.h).
+#include "engine_impl.h"
+
+namespace apsu_he {
+
+static void bundle_shape(const BundleLayout &y, Bundle &b)
+{
+    b.degree = y.degree; b.use_ps = y.use_ps; b.H = y.H; b.r = y.r;
+    b.pt_level = y.pt_level; b.ntt_count = y.ntt_count;
+}
+
+std::unique_ptr<Bundle> Engine::new_bundle(uint32_t bundle_idx, uint32_t cache_idx, uint32_t degree, BundleLayout *layout) const
+{
+    auto b = std::make_unique<Bundle>();
+    b->bundle_idx = bundle_idx;
+    b->cache_idx = cache_idx;
+    BundleLayout y = layout_of(degree);                          // (refuses ps_low_degree == 1 above degree 1)
+    bundle_shape(y, *b);
+    if (layout) *layout = std::move(y);
+    return b;
+}
+
+// bytes of one NTT-form plaintext slot at a level: dense 64-bit words, or bit-packed rows (the same widths as DevLevel::mac_bits)
+size_t Engine::slot_bytes(int chain_idx, bool packed) const
+{
+    const size_t n = hp_.n;
+    if (!packed) return (size_t)(chain_idx + 1) * n * sizeof(u64);
+    size_t b = 0;
+    for (int j = 0; j <= chain_idx; j++) {
+        const u32 w = packed_row_bits(hp_.key_q[j]);
+        b += n * w / 8;
+    }
+    return b;
+}
+
+void Engine::pack_bundle(Bundle &b)
+{
+    if (!packed_rows_ || b.packed) return;
+    const size_t n = hp_.n;
+    const int high = hp_.clamp_chain_idx(1);
+    b.ntt_slot_bytes = slot_bytes(b.pt_level, true);
+    b.lifted_slot_bytes = slot_bytes(high, true);
+    const size_t H = b.lifted.bytes() / ((size_t)(high + 1) * n * sizeof(u64));
+    if (b.ntt_count) {
+        DevBuf pk;
+        pk.alloc(b.ntt_count * b.ntt_slot_bytes + 16);
+        HIP_CHECK(hipMemsetAsync(static_cast<char *>(pk.p()) + b.ntt_count * b.ntt_slot_bytes, 0, 16, st_));
+        launch_pack_rows(dlevel(b.pt_level), b.pt_level + 1, b.ntt.u(), pk.p(), b.ntt_slot_bytes, n, b.ntt_count, st_);
+        sync();
+        b.ntt = std::move(pk);
+    }
+    if (H) {
+        DevBuf pk;
+        pk.alloc(H * b.lifted_slot_bytes + 16);
+        HIP_CHECK(hipMemsetAsync(static_cast<char *>(pk.p()) + H * b.lifted_slot_bytes, 0, 16, st_));
+        launch_pack_rows(dlevel(high), high + 1, b.lifted.u(), pk.p(), b.lifted_slot_bytes, n, H, st_);
+        sync();
+        b.lifted = std::move(pk);
+    }
+    b.packed = true;
+}
+
+void Engine::unpack_bundle(Bundle &b)
+{
+    if (!b.packed) return;
+    const size_t n = hp_.n;
+    const int high = hp_.clamp_chain_idx(1);
+    if (b.ntt_count) {
+        DevBuf dn;
+        dn.alloc(b.ntt_count * (size_t)(b.pt_level + 1) * n * sizeof(u64));
+        launch_unpack_rows(dlevel(b.pt_level), b.pt_level + 1, b.ntt.p(), b.ntt_slot_bytes, dn.u(), n, b.ntt_count, st_);
+        sync();
+        b.ntt = std::move(dn);
+    }
+    const size_t H = b.use_ps ? b.H : 0;
+    if (H && b.lifted.bytes()) {
+        DevBuf dn;
+        dn.alloc(H * (size_t)(high + 1) * n * sizeof(u64));
+        launch_unpack_rows(dlevel(high), high + 1, b.lifted.p(), b.lifted_slot_bytes, dn.u(), n, H, st_);
+        sync();
+        b.lifted = std::move(dn);
+    }
+    b.packed = false;
+    b.ntt_slot_bytes = b.lifted_slot_bytes = 0;
+}
+
+std::unique_ptr<Bundle> Engine::upload_bundle(uint32_t bundle_idx, uint32_t cache_idx, uint32_t n_coeffs,
+                                              const u64 *const *coeff_ptrs, const unsigned char *is_ntt)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!n_coeffs) throw std::invalid_argument("batched_coeffs is empty");
+    if (n_coeffs - 1 > psu_.table_params.max_items_per_bin) throw std::invalid_argument("degree exceeds max_items_per_bin");
+    if (bundle_idx >= psu_.bundle_idx_count) throw std::invalid_argument("bundle_idx out of range");
+    BundleLayout y;
+    auto b = new_bundle(bundle_idx, cache_idx, n_coeffs - 1, &y);
+    const size_t n = hp_.n, Lpt = b->pt_level + 1;
+    const int high = hp_.clamp_chain_idx(1);
+    const size_t Lh = high + 1;
+    for (uint32_t i = 0; i < n_coeffs; i++)
+        if ((is_ntt[i] != 0) != (y.where(i).kind == COEFF_NTT)) throw std::invalid_argument("plaintext NTT form does not match the BinBundle layout rule");
+    b->ntt.alloc(b->ntt_count * Lpt * n * sizeof(u64));
+    b->a0.alloc(n * sizeof(u64));
+    HIP_CHECK(hipMemcpy(b->a0.p(), coeff_ptrs[0], n * sizeof(u64), hipMemcpyHostToDevice));
+    std::vector<unsigned char> mono;
+    std::vector<const u64 *> cf;
+    for (uint32_t i = 1; i < n_coeffs; i++) {
+        if (is_ntt[i]) {
+            HIP_CHECK(hipMemcpy(b->ntt.u() + y.where(i).slot * Lpt * n, coeff_ptrs[i], Lpt * n * sizeof(u64), hipMemcpyHostToDevice));
+        } else {
+            cf.push_back(coeff_ptrs[i]);
+            mono.push_back(is_monomial(coeff_ptrs[i], n) ? 1 : 0);
+        }
+    }
+    if (b->use_ps) {
+        // K4: pre-lift and pre-NTT the coefficient-form plaintexts a_{i*h} at the high level; this
+        // is what multiply_plain (bin_bundle.cpp:334) recomputes on every call in the reference.
+        const size_t H = cf.size();
+        b->lifted.alloc(H * Lh * n * sizeof(u64));
+        WITH_ARENA({
+            u64 *raw = ws(H * n);
+            unsigned char *flags = ws_as<unsigned char>(H, 1);
+            for (size_t i = 0; i < H; i++) H2D(raw + i * n, cf[i], n);
+            HIP_CHECK(hipMemcpyAsync(flags, mono.data(), H, hipMemcpyHostToDevice, st_));
+            launch_lift(dlevel(high), raw, b->lifted.u(), n, (int)H, flags, st_);
+            d_ntt_ct(b->lifted.u(), H, high, false);
+            sync();
+        });
+    }
+    pack_bundle(*b);
+    return b;
+}
+
+// ============================================================================ tier 2: BinBundle construction
+// raw = the batched polynomial's coefficient-form plaintexts [degree+1][n] mod t on the device.  Applies the
+// layout rule of the BatchedPlaintextPolyn ctor (bin_bundle.cpp:385-420): NTT-form coefficients are lifted
+// and transformed at pt_level; coefficient-form a_{i*h} are pre-lifted (honouring SEAL's monomial
+// shortcut of multiply_plain) and pre-NTT'd at the high level; a_0 stays raw.
+void Engine::finish_bundle(Bundle &b, const u64 *raw)
+{
+    const uint32_t degree = b.degree;
+    const size_t n = hp_.n, Lpt = b.pt_level + 1;
+    const int high = hp_.clamp_chain_idx(1);
+    const size_t Lh = high + 1;
+    b.ntt.alloc(b.ntt_count * Lpt * n * sizeof(u64));
+    b.a0.alloc(n * sizeof(u64));
+    const size_t H = b.use_ps ? b.H : 0;
+    if (H) b.lifted.alloc(H * Lh * n * sizeof(u64));
+    D2D(b.a0.u(), raw, n);
+    unsigned char *flags = ws_as<unsigned char>(degree + 1, 1);
+    launch_flag_monomial(raw, n, (int)degree + 1, flags, st_);
+    for (const BundleRun &r : layout_of(degree).runs) {
+        if (r.kind == COEFF_NTT) launch_lift(dlevel(b.pt_level), raw + (size_t)r.d0 * n, b.ntt.u() + r.first_slot * Lpt * n, n, (int)r.count, nullptr, st_);
+        else if (H) launch_lift(dlevel(high), raw + (size_t)r.d0 * n, b.lifted.u() + r.first_slot * Lh * n, n, (int)r.count, flags + r.d0, st_);
+    }
+    d_ntt_ct(b.ntt.u(), b.ntt_count, b.pt_level, false);
+    if (H) d_ntt_ct(b.lifted.u(), H, high, false);
+}
+
+std::unique_ptr<Bundle> Engine::random_bundle(uint32_t bundle_idx, uint32_t cache_idx, uint32_t degree, u64 seed)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (degree > psu_.table_params.max_items_per_bin) throw std::invalid_argument("degree exceeds max_items_per_bin");
+    auto b = new_bundle(bundle_idx, cache_idx, degree);
+    const size_t n = hp_.n;
+    // coefficient d, index k of the batched polynomial = splitmix64 stream at offset d*n + k (mod t), coefficient form
+    WITH_ARENA({
+        u64 *raw = ws((size_t)(degree + 1) * n);
+        launch_fill_random(raw, (size_t)(degree + 1) * n, seed, hp_.t, st_);
+        finish_bundle(*b, raw);
+        sync();
+    });
+    pack_bundle(*b);
+    return b;
+}
+
+std::unique_ptr<Bundle> Engine::build_bundle(uint32_t bundle_idx, uint32_t cache_idx, const u64 *roots, const uint32_t *counts,
+                                             uint32_t bins, uint32_t stride)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!hp_.batching) throw std::logic_error("plain_modulus does not support batching");
+    const size_t n = hp_.n;
+    if (bins > n) throw std::invalid_argument("more bins than batching slots");
+    if (bundle_idx >= psu_.bundle_idx_count) throw std::invalid_argument("bundle_idx out of range");
+    uint32_t degree = 0;
+    for (uint32_t s = 0; s < bins; s++) {
+        if (counts[s] > stride) throw std::invalid_argument("bin count exceeds stride");
+        degree = std::max(degree, counts[s]);
+    }
+    // a bin may hold at most max_items_per_bin - 1 items (receiver_db.cpp:388-389: insertion requires size < max)
+    if (degree > psu_.table_params.max_items_per_bin) throw std::invalid_argument("bin size exceeds max_items_per_bin");
+    for (uint32_t s = 0; s < bins; s++)
+        for (uint32_t r = 0; r < counts[s]; r++)
+            if (roots[(size_t)s * stride + r] >= hp_.t) throw std::invalid_argument("field element is not reduced modulo plain_modulus");
+    auto b = new_bundle(bundle_idx, cache_idx, degree);
+    WITH_ARENA({
+        u64 *droots = ws((size_t)bins * stride + 1);
+        uint32_t *dcounts = ws_as<uint32_t>(bins, 1);
+        if (bins) {
+            H2D(droots, roots, (size_t)bins * stride);
+            HIP_CHECK(hipMemcpyAsync(dcounts, counts, bins * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+        }
+        u64 *poly = ws((size_t)(degree + 1) * n);                  // [d][slot] slot values of the batched polynomial
+        launch_polyn_with_roots(droots, dcounts, bins, stride, degree, make_mod(hp_.t), poly, n, st_);
+        encode_bundle(*b, poly);
+        sync();
+    });
+    pack_bundle(*b);
+    return b;
+}
+
+// the tail of build_bundle and update_bundle: slot values [degree+1][n] of the batched polynomial -> the stored BinBundle
+void Engine::encode_bundle(Bundle &b, const u64 *poly)
+{
+    const size_t n = hp_.n;
+    // BatchEncoder::encode (bin_bundle.cpp:409): slot permutation, then inverse negacyclic NTT mod t
+    u64 *raw = ws((size_t)(b.degree + 1) * n);
+    launch_scatter_slots(poly, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), raw, n, (int)b.degree + 1, st_);
+    d_ntt(raw, b.degree + 1, map_ct() + hp_.plain_id(), 1, true, false);
+    finish_bundle(b, raw);
+}
+
+// The inverse of encode_bundle, whoever made the BinBundle: coefficient d -> its stored form as in finish_bundle (a_0 raw; NTT-form
+// rows and the pre-lifted a_{i h}: limb 0, the residues mod q_0), inverse NTT over q_0, un-lift (bin_update.h; SEAL's un-lifted
+// monomials included), forward NTT mod t, slot gather -- BatchEncoder::decode.
+void Engine::decode_bundle(const Bundle &b, u64 *poly)
+{
+    const uint32_t degree = b.degree;
+    const size_t n = hp_.n, Lpt = b.pt_level + 1;
+    const int high = hp_.clamp_chain_idx(1);
+    const size_t Lh = high + 1;
+    u64 *raw = ws((size_t)(degree + 1) * n);
+    D2D(raw, b.a0.u(), n);
+    for (const BundleRun &r : layout_of(degree).runs) {                  // the runs finish_bundle wrote
+        const bool ntt = r.kind == COEFF_NTT;
+        if (!ntt && !b.use_ps) throw std::logic_error("BinBundle holds a coefficient-form plaintext it cannot evaluate");
+        const size_t L = ntt ? Lpt : Lh, sb = !b.packed ? L * n * sizeof(u64) : ntt ? b.ntt_slot_bytes : b.lifted_slot_bytes;
+        launch_limb0_rows(dlevel(ntt ? b.pt_level : high), (int)L, static_cast<const char *>((ntt ? b.ntt : b.lifted).p()) + r.first_slot * sb, sb, b.packed,
+                          raw + (size_t)r.d0 * n, n, r.count, st_);
+    }
+    if (degree) {
+        d_ntt(raw + n, degree, map_ct(), 1, true, data_primes_narrow_);
+        launch_unlift(raw + n, (size_t)degree * n, hp_.t, hp_.key_q[0], st_);
+    }
+    d_ntt(raw, degree + 1, map_ct() + hp_.plain_id(), 1, false, false);
+    launch_gather_slots(raw, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), poly, n, (int)degree + 1, st_);
+}
+
+std::unique_ptr<Bundle> Engine::update_bundle(const Bundle &old, const u64 *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride,
+                                              const u64 *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!hp_.batching) throw std::logic_error("plain_modulus does not support batching");
+    if (!unlift_exact_) throw std::logic_error("q_0 <= 2 * plain_modulus: stored plaintexts cannot be decoded");
+    const size_t n = hp_.n;
+    if (bins > n) throw std::invalid_argument("more bins than batching slots");
+    if ((ins_roots == nullptr) != (ins_counts == nullptr) || (rem_roots == nullptr) != (rem_counts == nullptr))
+        throw std::invalid_argument("a root list and its counts are given together or not at all");
+    const uint32_t max_items = psu_.table_params.max_items_per_bin;
+    std::vector<uint32_t> touched;
+    uint32_t max_ins = 0;
+    for (uint32_t s = 0; s < bins; s++) {
+        const uint32_t ni = ins_counts ? ins_counts[s] : 0, nr = rem_counts ? rem_counts[s] : 0;
+        if (ni > ins_stride || nr > rem_stride) throw std::invalid_argument("bin count exceeds stride");
+        if (ni > max_items) throw std::invalid_argument("bin size exceeds max_items_per_bin");
+        for (uint32_t r = 0; r < ni; r++)
+            if (ins_roots[(size_t)s * ins_stride + r] >= hp_.t) throw std::invalid_argument("field element is not reduced modulo plain_modulus");
+        for (uint32_t r = 0; r < nr; r++)
+            if (rem_roots[(size_t)s * rem_stride + r] >= hp_.t) throw std::invalid_argument("field element is not reduced modulo plain_modulus");
+        max_ins = std::max(max_ins, ni);
+        if (ni || nr) touched.push_back(s);
+    }
+    const uint32_t rows = old.degree + max_ins + 1;                    // no bin can outgrow this
+    const size_t ins_words = ins_counts ? (size_t)bins * ins_stride : 0, rem_words = rem_counts ? (size_t)bins * rem_stride : 0;
+    std::unique_ptr<Bundle> b;
+    WITH_ARENA({
+        u64 *poly = ws((size_t)rows * n);                              // [d][slot] slot values of the batched polynomial
+        decode_bundle(old, poly);
+        if (rows > old.degree + 1) HIP_CHECK(hipMemsetAsync(poly + (size_t)(old.degree + 1) * n, 0, (size_t)(rows - old.degree - 1) * n * sizeof(u64), st_));
+        u64 *status = ws(3);                                           // failed removal, unused slot named (both atomicMin), degree (atomicMax)
+        HIP_CHECK(hipMemsetAsync(status, 0xff, 2 * sizeof(u64), st_));
+        HIP_CHECK(hipMemsetAsync(status + 2, 0, sizeof(u64), st_));
+        std::vector<uint32_t> new_counts(touched.size());
+        if (!touched.empty()) {
+            u64 *dins = ws(ins_words + 1), *drem = ws(rem_words + 1);
+            uint32_t *dic = ws_as<uint32_t>(bins, 1), *drc = ws_as<uint32_t>(bins, 1);
+            uint32_t *dtouched = ws_as<uint32_t>(touched.size(), 1), *dnew = ws_as<uint32_t>(touched.size(), 1);
+            if (ins_words) H2D(dins, ins_roots, ins_words);
+            if (rem_words) H2D(drem, rem_roots, rem_words);
+            if (ins_counts) HIP_CHECK(hipMemcpyAsync(dic, ins_counts, bins * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+            if (rem_counts) HIP_CHECK(hipMemcpyAsync(drc, rem_counts, bins * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemcpyAsync(dtouched, touched.data(), touched.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+            launch_bins_update(dtouched, (u32)touched.size(), dins, ins_counts ? dic : nullptr, ins_stride, drem, rem_counts ? drc : nullptr, rem_stride,
+                               make_mod(hp_.t), poly, n, rows, dnew, status, st_);
+            HIP_CHECK(hipMemcpyAsync(new_counts.data(), dnew, touched.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        }
+        launch_poly_degree(poly, n, rows, status + 2, st_);
+        u64 st[3];
+        HIP_CHECK(hipMemcpyAsync(st, status, sizeof(st), hipMemcpyDeviceToHost, st_));
+        sync();                                                        // the new shape is decided on the host
+        if (st[1] != ~(u64)0)
+            throw std::invalid_argument("bin " + std::to_string(st[1]) + " is an unused slot (it holds the zero polynomial): nothing can be inserted or removed there");
+        if (st[0] != ~(u64)0) {
+            const uint32_t s = (uint32_t)(st[0] >> 32), r = (uint32_t)st[0];
+            throw std::invalid_argument("bin " + std::to_string(s) + ": " + std::to_string(rem_roots[(size_t)s * rem_stride + r]) + " (removal " +
+                                        std::to_string(r) + ") is not a root of the bin's polynomial");
+        }
+        uint32_t degree = (uint32_t)st[2];                             // untouched bins included (k_poly_degree)
+        for (uint32_t c : new_counts) degree = std::max(degree, c);
+        if (degree > max_items) throw std::invalid_argument("bin size exceeds max_items_per_bin");
+        b = new_bundle(old.bundle_idx, old.cache_idx, degree);
+        encode_bundle(*b, poly);
+        sync();
+    });
+    pack_bundle(*b);
+    return b;
+}
+
+void EventStamps::reserve(size_t count)
+{
+    while (ev.size() < count) {
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreate(&e));
+        ev.push_back(e);
+    }
+}
+void EventStamps::record(size_t i, hipStream_t st) { HIP_CHECK(hipEventRecord(ev.at(i), st)); }
+double EventStamps::ms(size_t from, size_t to) const
+{
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[from], ev[to]));
+    return ms;
+}
+void EventStamps::release()
+{
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    ev.clear();
+}
+
+// ---- N1, find and place: occupancy, membership and the database-level step on resident BinBundles
+void Engine::lookup_check(const char *what) const
+{
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!hp_.batching) throw std::logic_error("plain_modulus does not support batching");
+    if (!unlift_exact_) throw std::logic_error("q_0 <= 2 * plain_modulus: stored plaintexts cannot be decoded");
+    if (psu_.bins_per_bundle > hp_.n) throw std::logic_error(std::string(what) + ": more bins than batching slots");
+}
+
+void Engine::lookup_impl(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count, uint32_t *counts,
+                         unsigned char *flags)
+{
+    const size_t n = hp_.n;
+    const uint32_t F = psu_.item_params.felts_per_item;
+    if (count && count >= (size_t)LOOKUP_NONE / F) throw std::invalid_argument("too many entries for one call");
+    for (size_t e = 0; e < count; e++) {
+        if ((u64)start[e] + F > psu_.bins_per_bundle) throw std::invalid_argument("entry " + std::to_string(e) + ": start bin + felts_per_item exceeds bins_per_bundle");
+        for (uint32_t j = 0; j < F; j++)
+            if (felts[e * F + j] >= hp_.t) throw std::invalid_argument("entry " + std::to_string(e) + ": field element is not reduced modulo plain_modulus");
+    }
+    const size_t parts = count * F;
+    const LookupPlan plan = count ? lookup_plan(felts, start, count, F, n, LOOKUP_R) : LookupPlan();
+    lookup_evs_.reserve((size_t)3 * n_bundles);
+    WITH_ARENA({
+        LookupWork *dwork = nullptr;
+        u64 *dpts = nullptr;
+        uint32_t *didx = nullptr;
+        if (count) {
+            dwork = ws_as<LookupWork>(plan.work.size());
+            dpts = ws(plan.pts.size());
+            didx = ws_as<uint32_t>(plan.idx.size());
+            HIP_CHECK(hipMemcpyAsync(dwork, plan.work.data(), plan.work.size() * sizeof(LookupWork), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemcpyAsync(dpts, plan.pts.data(), plan.pts.size() * sizeof(u64), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemcpyAsync(didx, plan.idx.data(), plan.idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+        }
+        unsigned char *dflags = count ? ws_as<unsigned char>(parts) : nullptr;
+        uint32_t *dcounts = counts ? ws_as<uint32_t>(n) : nullptr;
+        const size_t mark = arena_off_;
+        for (uint32_t i = 0; i < n_bundles; i++) {
+            const Bundle &b = *bundles[i];
+            arena_off_ = mark;                                         // one BinBundle after the other through the same workspace (stream order)
+            lookup_evs_.record(3 * i, st_);
+            u64 *poly = ws((size_t)(b.degree + 1) * n);                // [d][slot] slot values of the batched polynomial
+            decode_bundle(b, poly);
+            lookup_evs_.record(3 * i + 1, st_);
+            if (counts) {
+                launch_bin_counts(poly, n, b.degree + 1, dcounts, st_);
+                HIP_CHECK(hipMemcpyAsync(counts + (size_t)i * n, dcounts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+            }
+            if (count) {
+                launch_bins_lookup(dwork, (u32)plan.work.size(), dpts, didx, make_mod(hp_.t), poly, n, b.degree, dflags, st_);
+                HIP_CHECK(hipMemcpyAsync(flags + (size_t)i * parts, dflags, parts, hipMemcpyDeviceToHost, st_));
+            }
+            lookup_evs_.record(3 * i + 2, st_);
+        }
+        sync();
+    });
+    lookup_decode_ms_ = lookup_kernels_ms_ = 0;
+    for (uint32_t i = 0; i < n_bundles; i++) {
+        lookup_decode_ms_ += lookup_evs_.ms(3 * i, 3 * i + 1);
+        lookup_kernels_ms_ += lookup_evs_.ms(3 * i + 1, 3 * i + 2);
+    }
+}
+
+void Engine::lookup_times(double *decode_ms, double *kernels_ms)
+{
+    Enter g(this);
+    if (decode_ms) *decode_ms = lookup_decode_ms_;
+    if (kernels_ms) *kernels_ms = lookup_kernels_ms_;
+}
+
+void Engine::bin_counts(const Bundle &b, uint32_t *counts)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("bin_counts");
+    const Bundle *one = &b;
+    lookup_impl(&one, 1, nullptr, nullptr, 0, counts, nullptr);
+}
+
+// present[b][e] = AND over the entry's parts; room[b][e] = max_j(count[s + j] + 1), multi_insert_dry_run's return value, or LOOKUP_NONE
+static void lookup_reduce(const unsigned char *flags, const uint32_t *counts, uint32_t n_bundles, size_t n, const uint32_t *start, size_t count, uint32_t F,
+                          unsigned char *present, uint32_t *room)
+{
+    for (uint32_t b = 0; b < n_bundles; b++)
+        for (size_t e = 0; e < count; e++) {
+            unsigned char all = 1;
+            uint32_t most = 0;
+            for (uint32_t j = 0; j < F; j++) {
+                all &= flags[((size_t)b * count + e) * F + j];
+                const uint32_t c = counts[(size_t)b * n + start[e] + j];
+                most = most == LOOKUP_NONE || c == LOOKUP_NONE ? LOOKUP_NONE : std::max(most, c + 1);
+            }
+            if (present) present[(size_t)b * count + e] = all;
+            if (room) room[(size_t)b * count + e] = most;
+        }
+}
+
+void Engine::lookup_bundles(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count,
+                            unsigned char *present, uint32_t *room)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("lookup");
+    if (!n_bundles || !count) return;
+    const size_t n = hp_.n;
+    const uint32_t F = psu_.item_params.felts_per_item;
+    std::vector<unsigned char> flags((size_t)n_bundles * count * F);
+    std::vector<uint32_t> counts((size_t)n_bundles * n);
+    lookup_impl(bundles, n_bundles, felts, start, count, counts.data(), flags.data());
+    lookup_reduce(flags.data(), counts.data(), n_bundles, n, start, count, F, present, room);
+}
+
+// apply_entries and compact take the BinBundles of one bundle index, in cache order
+static void check_one_index_in_cache_order(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles)
+{
+    for (uint32_t b = 0; b < n_bundles; b++) {
+        if (bundles[b]->bundle_idx != bundle_idx) throw std::invalid_argument("the BinBundles of one call belong to one bundle index");
+        if (b && bundles[b]->cache_idx <= bundles[b - 1]->cache_idx) throw std::invalid_argument("BinBundles are not in cache order");
+    }
+}
+
+Engine::ApplyResult Engine::apply_entries(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles, const u64 *ins_felts,
+                                          const uint32_t *ins_start, size_t n_ins, const u64 *rem_felts, const uint32_t *rem_start, size_t n_rem)
+{
+    ApplyResult res;
+    const size_t n = hp_.n;
+    uint32_t F = 0, bins = 0;
+    std::vector<uint32_t> counts;
+    {
+        Enter g(this);
+        TIER1_SLOTS();
+        lookup_check("apply_entries");
+        F = psu_.item_params.felts_per_item;
+        bins = psu_.bins_per_bundle;
+        if (bundle_idx >= psu_.bundle_idx_count) throw std::invalid_argument("bundle_idx out of range");
+        check_one_index_in_cache_order(bundle_idx, bundles, n_bundles);
+        // the refusals come before any GPU work
+        place_validate(ins_felts, ins_start, n_ins, rem_felts, rem_start, n_rem, F, bins, hp_.t);
+        // one lookup for both lists: removals first, insertions behind them
+        std::vector<u64> felts((n_rem + n_ins) * F);
+        std::vector<uint32_t> start(n_rem + n_ins);
+        std::copy(rem_felts, rem_felts + n_rem * F, felts.begin());
+        std::copy(ins_felts, ins_felts + n_ins * F, felts.begin() + n_rem * F);
+        std::copy(rem_start, rem_start + n_rem, start.begin());
+        std::copy(ins_start, ins_start + n_ins, start.begin() + n_rem);
+        const size_t count = n_rem + n_ins;
+        std::vector<unsigned char> flags((size_t)n_bundles * count * F), present((size_t)n_bundles * count);
+        counts.assign((size_t)n_bundles * n, 0);
+        if (n_bundles) {
+            lookup_impl(bundles, n_bundles, felts.data(), start.data(), count, counts.data(), count ? flags.data() : nullptr);
+            lookup_reduce(flags.data(), counts.data(), n_bundles, n, start.data(), count, F, present.data(), nullptr);
+        }
+        std::vector<uint32_t> bin_counts((size_t)n_bundles * bins);
+        std::vector<unsigned char> ins_present((size_t)n_bundles * n_ins), rem_present((size_t)n_bundles * n_rem);
+        for (uint32_t b = 0; b < n_bundles; b++) {
+            std::copy(counts.begin() + (size_t)b * n, counts.begin() + (size_t)b * n + bins, bin_counts.begin() + (size_t)b * bins);
+            std::copy(present.begin() + (size_t)b * count, present.begin() + (size_t)b * count + n_rem, rem_present.begin() + (size_t)b * n_rem);
+            std::copy(present.begin() + (size_t)b * count + n_rem, present.begin() + (size_t)(b + 1) * count, ins_present.begin() + (size_t)b * n_ins);
+        }
+        PlaceInput in;
+        in.n_bundles = n_bundles; in.bins = bins; in.F = F; in.max_items = psu_.table_params.max_items_per_bin; in.t = hp_.t;
+        in.counts = bin_counts.data(); in.ins_present = ins_present.data(); in.rem_present = rem_present.data();
+        in.ins_felts = ins_felts; in.ins_start = ins_start; in.n_ins = n_ins;
+        in.rem_felts = rem_felts; in.rem_start = rem_start; in.n_rem = n_rem;
+        res.place = place_entries(in);
+    }
+    // the context's lock is taken per step from here on, as by a caller who made these calls one by one; the given BinBundles are only read
+    const PlaceResult &pl = res.place;
+    res.replaced.resize(n_bundles);
+    for (uint32_t b = 0; b < n_bundles; b++) {
+        if (pl.state[b] != PLACE_REPLACED) continue;
+        const PlaceLists &li = pl.ins[b], &lr = pl.rem[b];
+        res.replaced[b] = update_bundle(*bundles[b], li.any() ? li.roots.data() : nullptr, li.any() ? li.counts.data() : nullptr, li.stride,
+                                        lr.any() ? lr.roots.data() : nullptr, lr.any() ? lr.counts.data() : nullptr, lr.stride, bins);
+    }
+    const uint32_t next_cache = n_bundles ? bundles[n_bundles - 1]->cache_idx + 1 : 0;
+    for (uint32_t k = 0; k < pl.n_new; k++) {
+        const PlaceLists &li = pl.ins[n_bundles + k];
+        res.appended.push_back(build_bundle(bundle_idx, next_cache + k, li.roots.data(), li.counts.data(), bins, li.stride));
+    }
+    return res;
+}
+
+// ---- N1, compaction: several BinBundles of one bundle index into one (bin_merge.h, db_compact.h)
+std::unique_ptr<Bundle> Engine::merge_bundles(const Bundle *const *bundles, uint32_t n_bundles, uint32_t cache_idx)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("merge");
+    if (n_bundles < 2) throw std::invalid_argument("a merge takes at least two BinBundles");
+    for (uint32_t i = 1; i < n_bundles; i++)
+        if (bundles[i]->bundle_idx != bundles[0]->bundle_idx)
+            throw std::invalid_argument("BinBundle " + std::to_string(i) + " belongs to bundle index " + std::to_string(bundles[i]->bundle_idx) +
+                                        ", the first to " + std::to_string(bundles[0]->bundle_idx));
+    const size_t n = hp_.n, tiles = (n + MERGE_LANES - 1) / MERGE_LANES;
+    const uint32_t max_items = psu_.table_params.max_items_per_bin;
+    std::unique_ptr<Bundle> b;
+    merge_evs_.reserve(5);
+    WITH_ARENA({
+        merge_evs_.record(0, st_);
+        std::vector<u64 *> poly(n_bundles);
+        for (uint32_t i = 0; i < n_bundles; i++) poly[i] = ws((size_t)(bundles[i]->degree + 1) * n);       // [d][slot] slot values
+        uint32_t *dcounts = ws_as<uint32_t>((size_t)n_bundles * n);
+        const size_t mark = arena_off_;
+        for (uint32_t i = 0; i < n_bundles; i++) {
+            arena_off_ = mark;                                         // the decodes share their workspace (stream order)
+            decode_bundle(*bundles[i], poly[i]);
+            launch_bin_counts(poly[i], n, bundles[i]->degree + 1, dcounts + (size_t)i * n, st_);
+        }
+        arena_off_ = mark;
+        std::vector<uint32_t> counts((size_t)n_bundles * n);
+        HIP_CHECK(hipMemcpyAsync(counts.data(), dcounts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        merge_evs_.record(1, st_);
+        sync();                                                        // what may be merged, and every step's shape, is decided on the host
+        // step k multiplies the product of BinBundles 0 .. k by BinBundle k + 1; every refusal comes before the first product
+        const uint32_t steps = n_bundles - 1;
+        std::vector<uint32_t> run(counts.begin(), counts.begin() + n), next(n);
+        std::vector<int> tops((size_t)2 * steps * tiles);
+        std::vector<uint32_t> rows(steps);
+        auto top_of = [](const int *t, size_t count) { int m = 0; for (size_t i = 0; i < count; i++) m = std::max(m, t[i]); return (uint32_t)m; };
+        for (uint32_t k = 0; k < steps; k++) {
+            const uint32_t *cb = counts.data() + (size_t)(k + 1) * n;
+            merge_counts(run.data(), cb, n, max_items, next.data());
+            const std::vector<int> ta = merge_tile_tops(run.data(), n), tb = merge_tile_tops(cb, n);
+            std::copy(ta.begin(), ta.end(), tops.begin() + (size_t)2 * k * tiles);
+            std::copy(tb.begin(), tb.end(), tops.begin() + (size_t)(2 * k + 1) * tiles);
+            rows[k] = top_of(ta.data(), tiles) + top_of(tb.data(), tiles) + 1;
+            if (top_of(tb.data(), tiles) > bundles[k + 1]->degree || (!k && top_of(ta.data(), tiles) > bundles[0]->degree))
+                throw std::logic_error("merge: a bin count exceeds its BinBundle's degree");
+            run.swap(next);
+        }
+        const std::vector<int> tfinal = merge_tile_tops(run.data(), n);
+        const uint32_t degree = top_of(tfinal.data(), tiles);
+        int *dtops = ws_as<int>(tops.size());
+        HIP_CHECK(hipMemcpyAsync(dtops, tops.data(), tops.size() * sizeof(int), hipMemcpyHostToDevice, st_));
+        // (rows[] adds the largest counts of two inputs, which need not be in the same slot: an early step can be the tallest)
+        const uint32_t most_rows = *std::max_element(rows.begin(), rows.end());
+        u64 *buf[2] = { ws((size_t)most_rows * n), steps > 1 ? ws((size_t)most_rows * n) : nullptr };
+        merge_evs_.record(2, st_);
+        const u64 *cur = poly[0];
+        for (uint32_t k = 0; k < steps; k++) {
+            u64 *out = buf[(steps - 1 - k) & 1];                       // the last step writes buf[0]
+            launch_bins_merge(cur, dtops + (size_t)2 * k * tiles, poly[k + 1], dtops + (size_t)(2 * k + 1) * tiles, make_mod(hp_.t), out, n, rows[k], st_);
+            cur = out;
+        }
+        merge_evs_.record(3, st_);
+        b = new_bundle(bundles[0]->bundle_idx, cache_idx, degree);
+        encode_bundle(*b, cur);                                        // rows above `degree` are 0: rows[] is a bound over tiles, degree over slots
+        merge_evs_.record(4, st_);
+        sync();
+    });
+    pack_bundle(*b);
+    const int span[3][2] = { { 0, 1 }, { 2, 3 }, { 3, 4 } };
+    for (int i = 0; i < 3; i++) merge_ms_[i] = merge_evs_.ms(span[i][0], span[i][1]);
+    return b;
+}
+
+void Engine::merge_times(double *decode_ms, double *kernel_ms, double *encode_ms)
+{
+    Enter g(this);
+    if (decode_ms) *decode_ms = merge_ms_[0];
+    if (kernel_ms) *kernel_ms = merge_ms_[1];
+    if (encode_ms) *encode_ms = merge_ms_[2];
+}
+
+Engine::CompactResult Engine::compact(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles)
+{
+    CompactResult res;
+    const size_t n = hp_.n;
+    {
+        Enter g(this);
+        TIER1_SLOTS();
+        lookup_check("compact");
+        if (bundle_idx >= psu_.bundle_idx_count) throw std::invalid_argument("bundle_idx out of range");
+        check_one_index_in_cache_order(bundle_idx, bundles, n_bundles);
+        std::vector<uint32_t> counts((size_t)n_bundles * n);
+        if (n_bundles) lookup_impl(bundles, n_bundles, nullptr, nullptr, 0, counts.data(), nullptr);
+        res.plan = plan_compaction(counts.data(), n_bundles, n, psu_.table_params.max_items_per_bin);
+    }
+    // the context's lock is taken per merge from here on, as by a caller who made these calls one by one; the given BinBundles are only read
+    res.merged.resize(res.plan.degree.size());
+    for (size_t g = 0; g < res.merged.size(); g++) {
+        std::vector<const Bundle *> members;
+        for (uint32_t b = 0; b < n_bundles; b++)
+            if (res.plan.group[b] == g) members.push_back(bundles[b]);
+        if (members.size() >= 2) res.merged[g] = merge_bundles(members.data(), (uint32_t)members.size(), members[0]->cache_idx);
+    }
+    return res;
+}
+
+// ---- N2: BinBundle image ------------------------------------------------------------------------------------
+void Engine::algebraize_items(const unsigned char *items, size_t count, bool items_on_device, u64 *out, bool out_on_device)
+{
+    Enter g(this);
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (!count) return;
+    TIER1_SLOTS();
+    const u32 felts = psu_.item_params.felts_per_item, bpf = psu_.item_bit_count_per_felt, bits = psu_.item_bit_count;
+    WITH_ARENA({
+        const unsigned char *src = items;
+        if (!items_on_device) {
+            unsigned char *d = ws_as<unsigned char>(count * 16);
+            HIP_CHECK(hipMemcpyAsync(d, items, count * 16, hipMemcpyHostToDevice, st_));
+            src = d;
+        }
+        u64 *dst = out_on_device ? out : ws(count * felts);
+        { PROF(P_OTHER, 0); launch_algebraize(src, count, felts, bpf, bits, dst, st_); }
+        if (!out_on_device) D2H(out, dst, count * felts);
+        sync();
+    });
+}
+
+namespace {
+struct ImageHeader {                     // little-endian, 256 bytes
+    char magic[8];                       // "APSUHEB2"
+    uint64_t header_bytes, total_bytes;
+    uint64_t n, t, K, q[8];
+    uint32_t ps_low_degree, max_items_per_bin;
+    uint32_t bundle_idx, cache_idx, degree, use_ps, H, r, pt_level, row_format;   // row_format: 0 dense 64-bit words, 1 bit-packed rows (was `reserved`)
+    uint64_t ntt_count, ntt_bytes, lifted_bytes, a0_bytes;
+    uint64_t checksum;                   // checksum64 over the payload
+    unsigned char pad[256 - 8 - 16 - 88 - 8 - 32 - 32 - 8];
+};
+static_assert(sizeof(ImageHeader) == 256, "image header layout");
+uint64_t fnv1a64(const unsigned char *p, size_t n, uint64_t h = 1469598103934665603ull)
+{
+    for (size_t i = 0; i < n; i++) { h ^= p[i]; h *= 1099511628211ull; }
+    return h;
+}
+// Payload checksum: four interleaved FNV-1a-style lanes over 64-bit little-endian words, folded together with the tail bytes and
+// the length at the end.  (Byte-serial FNV-1a, the "APSUHEB1" images of round 2, is one dependent multiply per byte: under
+// 1 GB/s, minutes for a 75 GiB database on every load; this runs at memory speed.)
+uint64_t checksum64(const unsigned char *p, size_t n)
+{
+    const uint64_t P = 1099511628211ull;
+    uint64_t h[4] = { 1469598103934665603ull, 0x9e3779b97f4a7c15ull, 0xc2b2ae3d27d4eb4full, 0x165667b19e3779f9ull };
+    size_t i = 0;
+    for (; i + 32 <= n; i += 32) {
+        uint64_t w[4];
+        std::memcpy(w, p + i, 32);
+        for (int k = 0; k < 4; k++) h[k] = (h[k] ^ w[k]) * P;
+    }
+    uint64_t r = fnv1a64(p + i, n - i);
+    for (int k = 0; k < 4; k++) { r = (r ^ h[k]) * P; r ^= r >> 31; }
+    return r ^ (uint64_t)n;
+}
+}
+
+size_t Engine::bundle_image_size(const Bundle &b) const { return sizeof(ImageHeader) + b.ntt.bytes() + b.lifted.bytes() + b.a0.bytes(); }
+
+size_t Engine::save_bundle(const Bundle &b, unsigned char *buf, size_t capacity)
+{
+    Enter g(this);
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    const size_t total = bundle_image_size(b);
+    if (capacity < total) throw std::invalid_argument("image buffer too small");
+    sync();
+    ImageHeader hd;
+    std::memset(&hd, 0, sizeof(hd));
+    std::memcpy(hd.magic, "APSUHEB2", 8);
+    hd.header_bytes = sizeof(hd); hd.total_bytes = total;
+    hd.n = hp_.n; hd.t = hp_.t; hd.K = hp_.K;
+    for (int j = 0; j < hp_.K && j < 8; j++) hd.q[j] = hp_.key_q[j];
+    hd.ps_low_degree = psu_.query_params.ps_low_degree; hd.max_items_per_bin = psu_.table_params.max_items_per_bin;
+    hd.bundle_idx = b.bundle_idx; hd.cache_idx = b.cache_idx; hd.degree = b.degree; hd.use_ps = b.use_ps; hd.H = b.H; hd.r = b.r;
+    hd.pt_level = (uint32_t)b.pt_level; hd.ntt_count = b.ntt_count; hd.row_format = b.packed ? 1 : 0;
+    hd.ntt_bytes = b.ntt.bytes(); hd.lifted_bytes = b.lifted.bytes(); hd.a0_bytes = b.a0.bytes();
+    unsigned char *p = buf + sizeof(hd);
+    if (hd.ntt_bytes) HIP_CHECK(hipMemcpy(p, b.ntt.p(), hd.ntt_bytes, hipMemcpyDeviceToHost));
+    p += hd.ntt_bytes;
+    if (hd.lifted_bytes) HIP_CHECK(hipMemcpy(p, b.lifted.p(), hd.lifted_bytes, hipMemcpyDeviceToHost));
+    p += hd.lifted_bytes;
+    HIP_CHECK(hipMemcpy(p, b.a0.p(), hd.a0_bytes, hipMemcpyDeviceToHost));
+    hd.checksum = checksum64(buf + sizeof(hd), total - sizeof(hd));
+    std::memcpy(buf, &hd, sizeof(hd));
+    return total;
+}
+
+std::unique_ptr<Bundle> Engine::load_bundle(const unsigned char *buf, size_t size)
+{
+    Enter g(this);
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    ImageHeader hd;
+    if (size < sizeof(hd)) throw std::invalid_argument("BinBundle image is truncated");
+    std::memcpy(&hd, buf, sizeof(hd));
+    if (std::memcmp(hd.magic, "APSUHEB2", 8) != 0 || hd.header_bytes != sizeof(hd)) throw std::invalid_argument("not a BinBundle image");
+    if (hd.total_bytes != size || hd.total_bytes != sizeof(hd) + hd.ntt_bytes + hd.lifted_bytes + hd.a0_bytes)
+        throw std::invalid_argument("BinBundle image size mismatch");
+    bool same = hd.n == hp_.n && hd.t == hp_.t && hd.K == (uint64_t)hp_.K && hd.ps_low_degree == psu_.query_params.ps_low_degree &&
+                hd.max_items_per_bin == psu_.table_params.max_items_per_bin;
+    for (int j = 0; same && j < hp_.K && j < 8; j++) same = hd.q[j] == hp_.key_q[j];
+    if (!same) throw std::invalid_argument("BinBundle image was built for different parameters");
+    if (checksum64(buf + sizeof(hd), size - sizeof(hd)) != hd.checksum) throw std::invalid_argument("BinBundle image is corrupt (checksum)");
+    BundleLayout y;                                               // the header must say what the layout says
+    auto b = new_bundle(hd.bundle_idx, hd.cache_idx, hd.degree, &y);
+    const size_t n = hp_.n;
+    if (hd.row_format > 1 || (hd.row_format == 1 && !hp_.using_keyswitching)) throw std::invalid_argument("BinBundle image header is inconsistent");
+    const bool img_packed = hd.row_format == 1;
+    const size_t ntt_slot = slot_bytes(b->pt_level, img_packed), lift_slot = slot_bytes(hp_.clamp_chain_idx(1), img_packed);
+    const size_t want_ntt = y.ntt_count ? y.ntt_count * ntt_slot + (img_packed ? 16 : 0) : 0;
+    const size_t want_lift = y.lifted_count ? y.lifted_count * lift_slot + (img_packed ? 16 : 0) : 0;
+    if (y.H != hd.H || y.r != hd.r || (uint32_t)y.use_ps != hd.use_ps || (uint32_t)y.pt_level != hd.pt_level || y.ntt_count != hd.ntt_count ||
+        hd.ntt_bytes != want_ntt || hd.a0_bytes != n * sizeof(u64) || hd.lifted_bytes != want_lift || hd.bundle_idx >= psu_.bundle_idx_count)
+        throw std::invalid_argument("BinBundle image header is inconsistent");
+    const unsigned char *p = buf + sizeof(hd);
+    b->ntt.alloc(hd.ntt_bytes); b->lifted.alloc(hd.lifted_bytes); b->a0.alloc(hd.a0_bytes);
+    if (hd.ntt_bytes) HIP_CHECK(hipMemcpy(b->ntt.p(), p, hd.ntt_bytes, hipMemcpyHostToDevice));
+    p += hd.ntt_bytes;
+    if (hd.lifted_bytes) HIP_CHECK(hipMemcpy(b->lifted.p(), p, hd.lifted_bytes, hipMemcpyHostToDevice));
+    p += hd.lifted_bytes;
+    HIP_CHECK(hipMemcpy(b->a0.p(), p, hd.a0_bytes, hipMemcpyHostToDevice));
+    b->packed = img_packed;
+    if (img_packed) { b->ntt_slot_bytes = ntt_slot; b->lifted_slot_bytes = lift_slot; }
+    // an image of the other row format is converted to this context's (APSU_HE_PACKED_ROWS)
+    if (packed_rows_ && !b->packed) pack_bundle(*b);
+    else if (!packed_rows_ && b->packed) unpack_bundle(*b);
+    return b;
+}
+
+size_t Engine::download_coeff(const Bundle &b, uint32_t d, u64 *out, size_t capacity, int *kind)
+{
+    Enter g(this);
+    sync();
+    const size_t n = hp_.n;
+    if (d > b.degree) throw std::invalid_argument("degree out of range");
+    const BundleWhere w = layout_of(b.degree).where(d);
+    if (w.kind == COEFF_LIFTED && !b.use_ps) throw std::invalid_argument("coefficient is not stored for this bundle");
+    const int k = w.kind, lvl = k == COEFF_NTT ? b.pt_level : hp_.clamp_chain_idx(1);
+    const DevBuf &buf = k == COEFF_RAW ? b.a0 : k == COEFF_NTT ? b.ntt : b.lifted;
+    const size_t words = k == COEFF_RAW ? n : (size_t)(lvl + 1) * n;
+    if (capacity < words) throw std::invalid_argument("output buffer too small");
+    if (b.packed && k != COEFF_RAW) {                            // one bit-packed slot -> dense words
+        const size_t sb = k == COEFF_NTT ? b.ntt_slot_bytes : b.lifted_slot_bytes;
+        DevBuf tmp(words * sizeof(u64));
+        launch_unpack_rows(dlevel(lvl), lvl + 1, static_cast<const char *>(buf.p()) + w.slot * sb, sb, tmp.u(), n, 1, st_);
+        sync();
+        HIP_CHECK(hipMemcpy(out, tmp.p(), words * sizeof(u64), hipMemcpyDeviceToHost));
+    } else HIP_CHECK(hipMemcpy(out, buf.u() + w.slot * words, words * sizeof(u64), hipMemcpyDeviceToHost));
+    if (kind) *kind = k;
+    return words;
+}
+
+} // namespace apsu_he

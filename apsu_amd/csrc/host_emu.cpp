@@ -21,6 +21,7 @@
 #include "powers_dag.h"
 #include "sched_policy.h"
 #include "eval_plan.h"
+#include "bundle_layout.h"
 
 using namespace apsu_he;
 
@@ -275,6 +276,21 @@ int emu_plan_eval(unsigned bits, int low, int high, int L, int nB, uint32_t l, u
            p.wait_high_ready << 8 | p.fuse_tensor << 9 | p.fuse_tail << 10 | p.cf << 11 | p.i0 << 13;
 }
 int emu_behz_unrolled(int L, int nB) { return behz_unrolled(L, nB); }
+
+// The stored layout of a BinBundle (bundle_layout.h), for enumeration by tests/test_bundle_layout_cpu.py.  out = use_ps, H, r, pt_level,
+// ntt_count, lifted_count, the number of runs, then d0, count, kind, first_slot per run; where (may be null): kind, slot of
+// d = 0 .. degree.  Returns the words of `out` (the first `cap` are written), or -1 for a refused shape (emu_last_error).
+int emu_bundle_layout(uint32_t ps_low_degree, uint32_t degree, int first_chain_idx, uint64_t *out, int cap, uint32_t *where)
+{
+    try {
+        const BundleLayout y = bundle_layout(ps_low_degree, degree, first_chain_idx);
+        std::vector<u64> v{ y.use_ps, y.H, y.r, (u64)y.pt_level, y.ntt_count, y.lifted_count, y.runs.size() };
+        for (const BundleRun &r : y.runs) v.insert(v.end(), { r.d0, r.count, (u64)r.kind, r.first_slot });
+        for (size_t i = 0; i < v.size() && (int)i < cap; i++) out[i] = v[i];
+        for (uint32_t d = 0; where && d <= degree; d++) { where[2 * d] = (uint32_t)y.where(d).kind; where[2 * d + 1] = y.where(d).slot; }
+        return (int)v.size();
+    } catch (const std::invalid_argument &e) { g_err = e.what(); return -1; }
+}
 
 // The launch form of the transform (ntt_form.h), for tabulation by tests/test_host_logic.py: out = threads, coeffs_per_lane, min_waves, split
 void emu_ntt_form(int logn, int kind, size_t limbs, size_t latency_limbs, int narrow, int *out)

@@ -14,6 +14,7 @@
 
 #include "../../apsu_amd/csrc/params.h"
 #include "../../apsu_amd/csrc/dev_consts.h"
+#include "../../apsu_amd/csrc/bundle_layout.h"
 #include "../../apsu_amd/csrc/powers_dag.h"
 #include "../../apsu_amd/csrc/sharding.h"
 #include "../../apsu_amd/csrc/wire.h"
@@ -236,6 +237,25 @@ int main(int argc, char **argv)
         const std::vector<int> s = partition_units(u, nb, world);
         for (int v : s) if (v < 0 || v >= world) return 30;
     }
+    // ---- the stored layout of a BinBundle (bundle_layout.h): every run lies inside the slots of its kind, every slot is written once
+    for (uint32_t ps = 0; ps <= 8; ps++)
+        for (uint32_t degree = 0; degree <= 3 * (ps + 1) + 2; degree++)
+            for (int first = 0; first <= 3; first++) {
+                try {
+                    const BundleLayout y = bundle_layout(ps, degree, first);
+                    if (ps == 1 && degree >= 2) return 44;                                   // this shape must be refused
+                    std::vector<char> ntt(y.ntt_count, 0), lifted(y.lifted_count, 0);       // one byte per slot
+                    for (const BundleRun &r : y.runs) {
+                        if (r.kind != COEFF_NTT && r.kind != COEFF_LIFTED) return 40;
+                        std::vector<char> &slots = r.kind == COEFF_NTT ? ntt : lifted;
+                        if ((size_t)r.first_slot + r.count > slots.size()) return 41;
+                        for (uint32_t j = 0; j < r.count; j++) slots[r.first_slot + j]++;
+                    }
+                    for (uint32_t d = 1; d <= degree; d++) (y.where(d).kind == COEFF_NTT ? ntt : lifted).at(y.where(d).slot)++;
+                    for (char c : ntt) if (c != 2) return 42;
+                    for (char c : lifted) if (c != 2) return 42;
+                } catch (const std::invalid_argument &) { if (ps != 1 || degree < 2) return 43; }
+            }
     std::printf("ok\n");
     return 0;
 }
