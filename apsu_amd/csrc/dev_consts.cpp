@@ -1,6 +1,7 @@
 // See dev_consts.h.  Host arithmetic only; part of the engine library and of the CPU emulation library.
 #include "dev_consts.h"
 #include "eval_plan.h"
+#include "mac_core.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -109,21 +110,15 @@ static void build_level(const HeParams &hp, int c, DevLevel &d)
         d.q[j] = make_mod(qj);
         d.ext[j] = d.q[j];
         {
-            const int bits = 64 - __builtin_clzll(qj);
-            const int sh = (bits + 1) / 2;                         // both operand halves < 2^sh (sh <= 30)
+            const int sh = mac_shift_of(qj);                       // both operand halves < 2^sh (sh <= 30); the chunk rules: mac_core.h
             d.mac_shift[j] = (u32)sh;
-            // cross sum takes two products (< 2^(2 sh)) per term, plus one slot for the carried residue
-            const u64 cap = ((u64)1 << (63 - 2 * sh));
-            d.mac_chunk[j] = (u32)std::min<u64>(cap > 2 ? cap - 1 : 2, 1u << 20);
-            // three-product form: one middle product (a0 + a1)(c0 + c1) < 2^(2 sh + 2) per term, the carried residue enters as
-            // (r0, r0 + r1) < 2^(sh + 1): one slot as well
-            const u64 capk = 2 * sh + 2 < 64 ? ((u64)1 << (62 - 2 * sh)) : 0;
-            d.mac_chunk_k[j] = (u32)std::min<u64>(capk > 2 ? capk - 1 : 0, 1u << 20);   // 0: not usable for this modulus
+            d.mac_chunk[j] = mac_chunk_of(qj);
+            d.mac_chunk_k[j] = mac_chunk_k_of(qj);                  // (below 7 terms: not used, mac_kara_usable)
             // packed row width (the geometry is there in every context: images of either format load anywhere)
             const u32 w = hp.using_keyswitching ? packed_row_bits(qj) : 64;
             d.mac_bits[j] = w;
             d.mac_row_off[j] = j ? d.mac_row_off[j - 1] + (u32)(hp.n * d.mac_bits[j - 1] / 8) : 0;
-            d.mac_mask_hi[j] = w == 64 ? 0xffffffffu : (u32)(((u64)1 << (w - sh)) - 1);
+            d.mac_mask_hi[j] = mac_mask_hi_of(w, sh);
         }
         d.coeff_div_plain[j] = h.coeff_div_plain[j];
         d.incr[j] = h.upper_half_incr[j];

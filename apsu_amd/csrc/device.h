@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_consts.h"
+#include "mac_plan.h"
 #include "eval_plan.h"
 #include "blake2x.h"
 #include "query_side.h"
@@ -11,23 +12,6 @@
 #include "bin_merge.h"
 
 namespace apsu_he {
-
-// Multiply-accumulate job: for g < ng:  out[g][2][L][n] = sum_{j<cnt} PW_j (.) PT_{g,j}   (NTT domain).
-// All streams of a job share the ciphertext powers PW (same bundle index) and the term count.
-#ifndef APSU_MAC_GMAX
-#define APSU_MAC_GMAX 4
-#endif
-constexpr int MAC_G = APSU_MAC_GMAX;
-struct MacJob {
-    const u64 *pt[MAC_G]; // first plaintext of stream g; term j at + j*pt_stride ; limb l at + l*n
-    u64 *out[MAC_G];      // [2][L][n]
-    const u64 *pw;        // first ciphertext; term j at pw + j*pw_stride ; poly p at + p*pw_poly_stride
-    u32 cnt, ng;
-    u32 pt_stride, pw_stride, pw_poly_stride;        // in u64 words
-    u32 out_poly_stride;  // words between the two output polynomials (L*n for a full ciphertext)
-    u32 limb0, nl;        // limbs limb0 .. limb0+nl-1 are handled (grid.y >= nl exits); modulus = q[limb]
-    u32 packed, pad;      // packed: pt[] point at bit-packed plaintext slots and pt_stride is in BYTES (DevLevel::mac_bits)
-};
 
 // ---- launch wrappers (all asynchronous on `st`) --------------------------------------------
 // NTT over `count` consecutive limb polynomials of n coefficients; limb g uses
@@ -151,12 +135,10 @@ void launch_ks_inner(const DevKey *key, int L, const u64 *tdec, const u64 *rk, u
 // raw: acc comes from an inverse NTT that left out its twist (L <= 4; needs key->md_tw / p_tw)
 void launch_ks_moddown(const DevKey *key, int L, const u64 *acc, u64 *ct, size_t ct_stride, size_t n, int batch,
                        hipStream_t st, const DevLevel *lv = nullptr, u64 *ext = nullptr, int n_ext = 0, bool raw = false);
-// kara: the three-product accumulation (k_mac<.., true>, lv->mac_chunk_k)
-// packed: every job of the launch reads bit-packed plaintexts (MacJob::packed)
-void launch_mac(const DevLevel *lv, int nlimbs, const MacJob *jobs, size_t n, int njobs, hipStream_t st, bool kara = false, bool packed = false);
+// k_mac over njobs MacJobs (mac_core.h) in the form (kara: three products; packed: bit-packed plaintexts) and on the grid of a MacPlan (mac_plan.h)
+void launch_mac(const DevLevel *lv, int nlimbs, const MacJob *jobs, size_t n, int njobs, hipStream_t st, bool kara, bool packed, MacGrid grid);
 // single products on one limb: out[0][k] = a[k] * pw[limb][k], out[out_poly_stride + k] = a[k] * pw[pw_poly_stride + limb n + k]  (mod q_limb);
 // pt: the plaintext's slot as k_mac takes it (dense: [L][n] words; packed: the bit-packed slot, rows per DevLevel::mac_row_off)
-struct TermJob { const u64 *pt; const u64 *pw; u64 *out; };
 void launch_term_product(const DevLevel *lv, const TermJob *jobs, size_t njobs, size_t n, int limb, u32 pw_poly_stride, u32 out_poly_stride,
                          bool packed, hipStream_t st);
 // dense [slots][L][n] u64 <-> bit-packed [slots][slot_bytes] (rows per DevLevel::mac_bits / mac_row_off of `lv`)

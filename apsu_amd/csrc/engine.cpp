@@ -364,29 +364,6 @@ void Engine::phase_read(PhaseSummary *out, bool reset)
     if (reset) for (int i = 0; i < PH_COUNT; i++) phase_[i] = PhaseSummary{};
 }
 
-// P_MAC's profile unit: BITS of database rows streamed per coefficient index, summed over terms, streams and limbs (64 per limb of
-// a dense row, mac_bits of a bit-packed one) -- bytes streamed = units * n / 8
-uint64_t Engine::mac_units(const std::vector<MacJob> &mj) const
-{
-    uint64_t u = 0;
-    for (auto &j : mj) {
-        uint64_t w = 0;
-        for (u32 l = j.limb0; l < j.limb0 + j.nl; l++) w += j.packed ? packed_row_bits(hp_.key_q[l]) : 64;
-        u += (uint64_t)j.cnt * j.ng * w;
-    }
-    return u;
-}
-// mean number of terms per (stream, limb) chain of a launch: the three-product form pays for long chains only
-static uint32_t mac_mean_cnt(const std::vector<MacJob> &mj)
-{
-    uint64_t u = 0, c = 0;
-    for (auto &j : mj) { u += (uint64_t)j.cnt * j.ng * j.nl; c += (uint64_t)j.ng * j.nl; }
-    return c ? (uint32_t)(u / c) : 0;
-}
-
-// single-stream description of a multiply-accumulate; group_mac() packs streams that share the
-// ciphertext powers and the term count into MacJobs of up to MAC_G streams
-struct MacStream { const u64 *pt; const u64 *pw; u64 *out; u32 cnt, pt_stride, pw_stride, pw_poly_stride, out_poly_stride, limb0, nl; u32 packed = 0; };
 // where slot `slot` of a BinBundle's NTT-form plaintexts (lifted = false) or of its pre-lifted coefficient-form ones starts, and the
 // distance between consecutive slots in the unit k_mac takes it in (words for dense rows, BYTES for bit-packed ones)
 static const u64 *bundle_slot(const Bundle &b, bool lifted, size_t slot, size_t dense_words)
@@ -399,39 +376,6 @@ static u32 bundle_stride(const Bundle &b, bool lifted, size_t dense_words)
 {
     return b.packed ? (u32)(lifted ? b.lifted_slot_bytes : b.ntt_slot_bytes) : (u32)dense_words;
 }
-static bool mac_packed(const std::vector<MacJob> &mj) { return !mj.empty() && mj[0].packed != 0; }
-static std::vector<MacJob> group_mac(const std::vector<MacStream> &ss)
-{
-    std::vector<MacJob> jobs;
-    std::vector<char> used(ss.size(), 0);
-    // streams are generated bundle-major; match each unused stream with later ones of equal key
-    std::vector<size_t> order(ss.size());
-    for (size_t i = 0; i < ss.size(); i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        if (ss[a].pw != ss[b].pw) return ss[a].pw < ss[b].pw;
-        if (ss[a].limb0 != ss[b].limb0) return ss[a].limb0 < ss[b].limb0;
-        if (ss[a].nl != ss[b].nl) return ss[a].nl < ss[b].nl;
-        return ss[a].cnt < ss[b].cnt;
-    });
-    for (size_t x = 0; x < order.size();) {
-        const MacStream &f = ss[order[x]];
-        MacJob j{};
-        j.pw = f.pw; j.cnt = f.cnt; j.pt_stride = f.pt_stride; j.pw_stride = f.pw_stride; j.pw_poly_stride = f.pw_poly_stride;
-        j.out_poly_stride = f.out_poly_stride; j.limb0 = f.limb0; j.nl = f.nl; j.packed = f.packed;
-        u32 g = 0;
-        while (x < order.size() && g < (u32)MAC_G) {
-            const MacStream &s = ss[order[x]];
-            if (s.pw != f.pw || s.cnt != f.cnt || s.packed != f.packed || s.pt_stride != f.pt_stride || s.pw_stride != f.pw_stride ||
-                s.pw_poly_stride != f.pw_poly_stride || s.out_poly_stride != f.out_poly_stride || s.limb0 != f.limb0 || s.nl != f.nl) break;
-            j.pt[g] = s.pt; j.out[g] = s.out; g++; x++;
-        }
-        j.ng = g;
-        for (u32 r = g; r < (u32)MAC_G; r++) { j.pt[r] = j.pt[0]; j.out[r] = j.out[0]; }
-        jobs.push_back(j);
-    }
-    return jobs;
-}
-
 void Engine::check_level(int chain_idx) const
 {
     if (chain_idx < 0 || chain_idx > hp_.first_chain_idx) throw std::invalid_argument("chain_idx is not a data level");
@@ -566,17 +510,13 @@ void Engine::recycle_powers(std::unique_ptr<Powers> p)
 }
 
 // ============================================================================ device building blocks
-// Does the multiply-accumulate launch of a level use its three-product form?  It needs carry-free chunks of at least 7 terms for
-// every limb, and it pays for long chains only: macbench (profiles/r04_mac_kara.txt) has it 1.2 % slower at 44 terms per chain
-// (16M-4096) and 2 % faster at 150 (256M-4096 has 310).  APSU_HE_MAC_KARA=0/1 forces it off / on wherever it is usable.
-bool Engine::mac_kara(int lvl, uint32_t mean_cnt) const
+// the multiply-accumulate launch of `streams` over the first nlimbs primes: planned (mac_plan.h: jobs, form, grid) ...
+MacPlan Engine::plan_mac(const std::vector<MacStream> &streams, size_t nlimbs, size_t n) const { return mac_plan(streams, hp_.key_q.data(), (int)nlimbs, n, sw_.mac_kara); }
+// ... and launched on the current stream (jobs: the plan's jobs where they were uploaded earlier, ps_tables)
+void Engine::d_mac(const MacPlan &p, const MacJob *jobs)
 {
-    if (sw_.mac_kara == 0 || (sw_.mac_kara < 0 && mean_cnt < 96)) return false;
-    for (int j = 0; j <= lvl; j++) {
-        const int bits = 64 - __builtin_clzll(hp_.key_q[j]), sh = (bits + 1) / 2;
-        if (62 - 2 * sh < 3) return false;
-    }
-    return true;
+    PROF(P_MAC, p.units);
+    launch_mac(dlevel(p.nlimbs - 1), p.nlimbs, jobs ? jobs : upload_jobs(p.jobs), p.n, (int)p.jobs.size(), st_, p.kara, p.packed, p.grid);
 }
 
 void Engine::d_ntt(u64 *data, size_t count, const int *modmap, int period, bool inverse, bool narrow)
@@ -1627,9 +1567,8 @@ struct PsBatch {
     std::vector<int> imap;                              // modulus of every limb polynomial of the merged block
     const int *imap_dev = nullptr;
     size_t n_vlast_side = 0;                            // limb polynomials at the end of the block that the side lane transforms back
-    const MacJob *mac_jobs = nullptr;
-    int n_mac = 0;
-    uint64_t units = 0; uint32_t mean_cnt = 0; bool mac_is_packed = false;
+    MacPlan mac;                                        // the multiply-accumulate launch, planned by ps_tables ...
+    const MacJob *mac_jobs = nullptr;                   // ... its jobs on the device
     const TermJob *term_jobs = nullptr;                 // the i = 0 block's per-term products on the dropped limb (k_term_product)
     size_t n_term = 0; bool term_packed = false;
     // what the steps of ps_run hand on: the extended inner polynomials, the summed products, the deferred mod-down of the last
@@ -1655,7 +1594,7 @@ void Engine::eval_plain(EvalCall &c, const std::vector<int> &pl_ids)
         else HIP_CHECK(hipMemsetAsync(o, 0, 2 * Lv * c.n * sizeof(u64), st_));
         ej.push_back(EpiJob{ o, nullptr, nullptr, b.a0.u(), c.mask_ptr(pl_ids[x]), c.res_ptr(pl_ids[x]) });
     }
-    { auto mj = group_mac(ms); PROF(P_MAC, mac_units(mj)); launch_mac(dlevel(lvl), (int)Lv, upload_jobs(mj), c.n, (int)mj.size(), st_, mac_kara(lvl, mac_mean_cnt(mj)), mac_packed(mj)); }
+    d_mac(plan_mac(ms, Lv, c.n));
     d_ntt_ct(acc, (size_t)Bp * 2, lvl, true);                                                 // :154
     // :159 add_plain(a_0), :162 add_plain(mask), :168-170 mod switch to the last level, :171 clear bits
     { PROFW(P_MODSWITCH, (size_t)Bp * c.n * (2 * Lv + 4)); launch_eval_epilogue(dlevel(0), lvl, upload_jobs(ej), Lv * c.n, hp_.irrelevant_bit_count, c.n, Bp, st_); }
@@ -1676,9 +1615,7 @@ void Engine::ps_cf_mac(const EvalCall &c, const PsBatch &g)
 {
     std::vector<MacStream> cs;
     ps_cf_streams(c, g, cs);
-    auto mj = group_mac(cs);
-    PROF(P_MAC, mac_units(mj));
-    launch_mac(dlevel(c.high), (int)c.Lh, upload_jobs(mj), c.n, (int)mj.size(), st_, mac_kara(c.high, mac_mean_cnt(mj)), mac_packed(mj));
+    d_mac(plan_mac(cs, c.Lh, c.n));
 }
 
 // BatchedPlaintextPolyn::eval_patstock (bin_bundle.cpp:192-360) for the BinBundles ps_ids of the chunk: the batch, the plan
@@ -1784,12 +1721,8 @@ void Engine::ps_tables(EvalCall &c, const EvalPlan &plan, PsBatch &g)
     }
     if (plan.side_i0) g.n_vlast_side = (size_t)Bs * l * 2;
     if (cf_here) { ps_cf_streams(c, g, ms); map_push((size_t)Bs * 2, 0, (int)Lh); }
-    auto mj = group_mac(ms);
-    g.mac_jobs = upload_jobs(mj);
-    g.n_mac = (int)mj.size();
-    g.units = mac_units(mj);
-    g.mean_cnt = mac_mean_cnt(mj);
-    g.mac_is_packed = mac_packed(mj);
+    g.mac = plan_mac(ms, Ll, n);
+    g.mac_jobs = upload_jobs(g.mac.jobs);
     if (!tj.empty()) { g.term_jobs = upload_jobs(tj); g.n_term = tj.size(); }
 }
 
@@ -1816,7 +1749,7 @@ void Engine::ps_i0_finish(const EvalCall &c, const EvalPlan &plan, const PsBatch
 // ev_fork_ marks the end of k_mac (the powers and the database are read-only from here on), ev_intt_ the end of the transforms.
 void Engine::ps_mac(EvalCall &c, const EvalPlan &plan, PsBatch &g)
 {
-    { PROF(P_MAC, g.units); launch_mac(dlevel(c.low), (int)c.Ll, g.mac_jobs, c.n, g.n_mac, st_, mac_kara(c.low, g.mean_cnt), g.mac_is_packed); }
+    d_mac(g.mac, g.mac_jobs);
     g.imap_dev = upload_jobs(g.imap);
     if (plan.side_i0) HIP_CHECK(hipEventRecord(ev_fork_, st_));
     else if (g.n_term) ps_term_product(c, g);
@@ -2348,7 +2281,7 @@ void Engine::eval_bundles_nks(const Bundle *const *bundles, int count, const Pow
             if (!b.use_ps) {                                                                        // bin_bundle.cpp:106-174
                 if (b.degree) {
                     low_streams(b.ntt.u(), b.degree, rs[x], result);                                // :140-149
-                    { auto mj = group_mac(ms); PROF(P_MAC, mac_units(mj)); launch_mac(dlevel(0), 1, upload_jobs(mj), n, (int)mj.size(), st_, mac_kara(0, mac_mean_cnt(mj))); }
+                    d_mac(plan_mac(ms, 1, n));
                     d_ntt_ct(result, RS, 0, true);                                                  // :154
                 } else {
                     HIP_CHECK(hipMemsetAsync(result, 0, (size_t)RS * n * sizeof(u64), st_));
@@ -2377,7 +2310,7 @@ void Engine::eval_bundles_nks(const Bundle *const *bundles, int count, const Pow
                 for (uint32_t pp = 0; pp < even(s_high) / 2; pp++)
                     ms.push_back(MacStream{ b.lifted.u(), hext_ptr(1, bs) + (size_t)pp * 2 * E * n, cf + (size_t)pp * 2 * n, H, (u32)n,
                                             (u32)(S * E * n), (u32)(E * n), (u32)n, 0, 1 });
-                { auto mj = group_mac(ms); PROF(P_MAC, mac_units(mj)); launch_mac(dlevel(0), 1, upload_jobs(mj), n, (int)mj.size(), st_, mac_kara(0, mac_mean_cnt(mj))); }
+                d_mac(plan_mac(ms, 1, n));
                 d_ntt_ct(blk, (words / n) + even(s_low) + even(s_high), 0, true);                   // :268,297,321 and the product's transform
                 HIP_CHECK(hipMemsetAsync(result, 0, (size_t)RS * n * sizeof(u64), st_));            // :238-240
                 for (uint32_t i = 1; i <= nin; i++) {                                               // :272-273,301-303

@@ -103,7 +103,6 @@ struct Powers {
     int slot_of(uint32_t bundle_idx) const;
 };
 
-struct MacStream;
 struct PsBatch;
 
 // time stamps of a resident-database call on the engine's stream: events created before the call's first stamp (outside the timed
@@ -431,8 +430,8 @@ private:
     size_t slot_bytes(int chain_idx, bool packed) const;          // bytes of one NTT-form plaintext at a level, either format
     void pack_bundle(Bundle &b);      // dense -> packed when this context keeps packed rows (no-op otherwise)
     void unpack_bundle(Bundle &b);    // packed -> dense (images of the other format)
-    bool mac_kara(int lvl, uint32_t mean_cnt) const;
-    uint64_t mac_units(const std::vector<MacJob> &mj) const;      // bits of database rows per coefficient index (profile unit of P_MAC)
+    MacPlan plan_mac(const std::vector<MacStream> &streams, size_t nlimbs, size_t n) const;   // mac_plan.h with this context's primes and switch
+    void d_mac(const MacPlan &p, const MacJob *jobs = nullptr);
     bool split_ok_ = false;           // the low-power and high-power halves of the PowersDag share no node
     int two_stream_mode_ = -1;        // apsu_he_set_two_stream (-1: EngineSwitches::two_stream_default)
     void build_schedule();

@@ -55,7 +55,6 @@ __global__ __launch_bounds__(T, MINW) void k_ntt(u64 *__restrict__ data, const N
     else ntt_body<LOGN, INV, NTT_WIDE, T, 0, false, SRC, true, false, 0, -1, C>(lds, p, tab, tid, nullptr, SRC());
 }
 
-constexpr int EW_T = 256;                                         // threads per workgroup of the coefficient-parallel kernels
 // ---- poly_modulus_degree 32768: one radix-2 stage over global memory around two half-size LDS-resident transforms.
 // Tables: entry 2 m (+ 1) of `tabs`; its ninv / ninv_q fields carry the first stage's twiddle psi^brv(1) (the twist comes
 // from the scale table), dit and scale are the full-size tables.
@@ -759,12 +758,7 @@ __global__ __launch_bounds__(EW_T) void k_limb0_rows(const DevLevel *__restrict_
     u64 v;
     if (packed) {
         const u32 w = lv->mac_bits[0];
-        const u32 *row = reinterpret_cast<const u32 *>(src + slot * slot_bytes + lv->mac_row_off[0]);
-        const size_t bit0 = c * w, d0 = bit0 >> 5;
-        const u32 sh = (u32)(bit0 & 31);
-        v = ((u64)row[d0] | ((u64)row[d0 + 1] << 32)) >> sh;      // (a packed buffer ends in 16 readable bytes, as for k_unpack_rows)
-        if (sh && w + sh > 64) v |= (u64)row[d0 + 2] << (64 - sh);
-        if (w != 64) v &= ((u64)1 << w) - 1;
+        v = packed_coeff(reinterpret_cast<const u32 *>(src + slot * slot_bytes + lv->mac_row_off[0]), c, w);   // (mac_core.h)
     } else v = reinterpret_cast<const u64 *>(src)[slot * (size_t)L * n + c];
     out[slot * n + c] = v;
 }
@@ -2055,398 +2049,6 @@ void launch_ks_moddown(const DevKey *key, int L, const u64 *acc, u64 *ct, size_t
                              else hipLaunchKernelGGL((k_ks_moddown<TL>), g, t, 0, st, key, L, acc, ct, ct_stride, n, nullptr, nullptr, 0); break;
     switch (L) { KS_CASE(1) KS_CASE(2) KS_CASE(3) KS_CASE(4) default: hipLaunchKernelGGL((k_ks_moddown<0>), g, t, 0, st, key, L, acc, ct, ct_stride, n, nullptr, nullptr, 0); }
 #undef KS_CASE
-    KERNEL_CHECK();
-}
-
-// ============================================================================ K3: dyadic multiply-accumulate
-// The inner loops of BatchedPlaintextPolyn::eval / eval_patstock
-// (bin_bundle.cpp:140-149, 250-265, 279-294, 314-324, 328-337): out_g = sum_j C^j (.) a_{g,j} in the NTT
-// domain for plaintext streams that share the same ciphertext powers (the inner polynomials of the
-// BinBundles of one bundle index).  The HBM-resident plaintexts are streamed exactly once (16-byte
-// non-temporal loads, two adjacent coefficients per lane); every power load is shared by G streams.
-//
-// Carry-free accumulation: both operands are < q < 2^(2s) (s = ceil(bits(q)/2)), so each is split into two
-// s-bit halves and the three partial sums  S00 += lo*lo,  Sx += lo*hi + hi*lo,  S11 += hi*hi  are plain
-// 64-bit v_mad_u64_u32 accumulations (no carries, no compares): 4 multiply-adds per product and nothing
-// else.  `chunk` terms (2*chunk*2^(2s) < 2^64) are accumulated before the sums are recombined
-// (S00 + Sx*2^s + S11*2^(2s)) and reduced; for the 48..56-bit coefficient primes a whole inner polynomial
-// fits in one chunk.
-// KARA: three products per (stream, coefficient, polynomial, term) instead of four -- S00 += a0 c0, S11 += a1 c1,
-// Smid += (a0 + a1)(c0 + c1), the cross sum recovered at fold time as Smid - S00 - S11; the power-side sums c0 + c1 are formed
-// once per term and shared by the G streams.  A middle product has 2s + 2 bits, so a carry-free chunk is half as long
-// (lv->mac_chunk_k) and the carried residue r re-enters as the "term" (a0 c0, mid) = (r mod 2^s, r mod 2^s + (r >> s)).
-#ifdef APSU_MAC_STAMPS
-// diagnostic build of tools/microbench/macbench.hip only: where a k_mac workgroup's lifetime goes (shader-clock stamps of lane 0 of
-// wave 0: entry | descriptor and pointers read | first term consumed | last pair consumed | folded | stored; realtime at entry and exit)
-__device__ unsigned long long *g_mac_stamps = nullptr;
-#define MAC_STAMP(i) do { if (g_mac_stamps && threadIdx.x == 0) { asm volatile("" ::: "memory"); stamp_[i] = __builtin_amdgcn_s_memtime(); asm volatile("" ::: "memory"); } } while (0)
-#else
-#define MAC_STAMP(i) do { } while (0)
-#endif
-// PACKED: the plaintexts are stored bit-packed, limb j at lv->mac_bits[j] bits per coefficient (56-bit primes: 7 bytes instead
-// of 8, 50-bit: 6.25).  A lane still issues ONE 16-byte load per term and stream: its two coefficients occupy 2 * bits
-// consecutive bits from bit 2 * bits * (k / 2) of the row, i.e. inside the 16-byte window that starts at the dword holding that
-// bit (the host picks widths for which shift + 2 * bits <= 128 everywhere); the window is shifted down by the lane's bit offset
-// with funnel shifts and the operand halves are cut out of it.  Fewer HBM bytes per term, the same number of load instructions.
-// Kept sums (round 4): an empty assembly statement on every partial sum of k_mac's inner loop.  Without it the compiler pairs two
-// products first (v_mad_u64_u32 with a zero addend, then one with the first product as addend) and adds the pair to the running sum
-// with a separate 64-bit add; with it every product is ONE v_mad_u64_u32 whose addend is the sum: 283 instead of 315 VALU instructions
-// per two terms, -2.2 % on the 16M-4096 query (the cycles go to the next query's ComputePowers, which runs next to the scan;
-// profiles/r04_ab_mac_kept_sums.txt).  APSU_MAC_NO_KEEP restores the compiler's form.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(APSU_MAC_NO_KEEP)
-#define MAC_KEEP(v) asm("" : "+v"(v))
-#else
-#define MAC_KEEP(v) do { } while (0)
-#endif
-#ifndef APSU_MAC_MINWAVES
-#define APSU_MAC_MINWAVES 1                                        // waves per SIMD the register allocation must allow (experiment switch)
-#endif
-template <int G, int C, bool KARA = false, bool PACKED = false>
-__global__ __launch_bounds__(EW_T, APSU_MAC_MINWAVES) void k_mac(const DevLevel *__restrict__ lv, const MacJob *__restrict__ jobs, size_t n, int limb_slow)
-{
-    static_assert(C == 1 || C == 2, "coefficients per lane");
-    static_assert(!PACKED || C == 2, "packed rows are read two coefficients per lane");
-#ifdef APSU_MAC_STAMPS
-    unsigned long long stamp_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    const unsigned long long rt0_ = __builtin_amdgcn_s_memrealtime();
-#endif
-    MAC_STAMP(0);
-    // grid order (launch_mac).  Workgroups go to the XCDs round-robin in launch order, so what is FAST in the grid decides which
-    // workgroups are resident behind one L2 together, i.e. how much of the shared powers that L2 has to hold:
-    //   limb_slow 0: (block, limb, job)  -- an XCD holds blocks x, x + 8 of every limb of ~10 jobs: 2 * limbs * terms * 8 KiB
-    //   limb_slow 1: (block, job, limb)  -- ... of ONE limb of ~32 jobs: 2 * terms * 8 KiB  (-2.5 ... -2.9 % on the 256M-4096 query,
-    //                level at 16M-4096; one block per XCD measured level with it: profiles/r04_ab_mac_grid_order.txt)
-    unsigned b_x = blockIdx.x, b_limb = blockIdx.y, b_job = blockIdx.z;
-    if (limb_slow) { b_limb = blockIdx.z; b_job = blockIdx.y; }
-    const size_t k = ((size_t)b_x * EW_T + threadIdx.x) * C;
-    if (k >= n) return;
-    constexpr int SPLIT = MAC_G / G;                            // a job's streams are covered by SPLIT blocks
-    const MacJob *__restrict__ jp = jobs + b_job / SPLIT;        // stream pointers are indexed dynamically: read them from memory
-    struct { const u64 *pw; u32 cnt, ng, pt_stride, pw_stride, pw_poly_stride, out_poly_stride, limb0; } job =
-        { jp->pw, jp->cnt, jp->ng, jp->pt_stride, jp->pw_stride, jp->pw_poly_stride, jp->out_poly_stride, jp->limb0 };
-    const int g0 = (b_job % SPLIT) * G;
-    if (g0 >= (int)job.ng || b_limb >= jp->nl) return;
-    const int j = b_limb + job.limb0;                          // limb
-    const Mod m = lv->q[j];
-    const u32 s = lv->mac_shift[j], chunk = KARA ? lv->mac_chunk_k[j] : lv->mac_chunk[j];
-    const u32 lomask = (1u << s) - 1;                          // s <= 30
-    const u64 *p0 = job.pw + (size_t)j * n + k;
-    const u64 *p1 = p0 + job.pw_poly_stride;
-    const u64 *pt[G];
-    const u32 *ptw[G];                                          // PACKED: first dword of this lane's 16-byte window
-    u32 psh = 0, kb = 64, himask = 0xffffffffu;
-    if constexpr (PACKED) {
-        kb = lv->mac_bits[j];
-        himask = lv->mac_mask_hi[j];
-#ifdef APSU_MAC_TILED_EXPERIMENT
-        if (jp->pad == 1) {                                     // tools/microbench/macbench.hip: the G streams' tiles of one (term, limb, block) adjacent in memory
-            const u32 bitoff = threadIdx.x * 2 * kb, tile = EW_T * C * kb / 8, nblk = (u32)(n / (EW_T * C));
-            psh = bitoff & 31;
-#pragma unroll
-            for (int g = 0; g < G; g++)
-                ptw[g] = reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(jp->pt[0]) + ((size_t)(j * nblk + b_x) * G + g) * tile) + (bitoff >> 5);
-        } else if (jp->pad == 2) {                              // macbench: BLOCK-MAJOR rows -- the terms of one (stream, limb, block) contiguous, a tile per term
-            const u32 bitoff = threadIdx.x * 2 * kb, tile = EW_T * C * kb / 8, nblk = (u32)(n / (EW_T * C));
-            psh = bitoff & 31;
-#pragma unroll
-            for (int g = 0; g < G; g++)
-                ptw[g] = reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(jp->pt[g0 + g < (int)job.ng ? g0 + g : g0]) + ((size_t)(j * nblk + b_x) * job.cnt) * tile) + (bitoff >> 5);
-        } else
-#endif
-        {
-        const u32 bitoff = (u32)(k >> 1) * 2 * kb;
-        psh = bitoff & 31;
-#pragma unroll
-        for (int g = 0; g < G; g++)
-            ptw[g] = reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(jp->pt[g0 + g < (int)job.ng ? g0 + g : g0]) + lv->mac_row_off[j]) + (bitoff >> 5);
-        }
-    } else {
-#ifdef APSU_MAC_TILED_EXPERIMENT
-        if (jp->pad == 1) {
-            const u32 nblk = (u32)(n / (EW_T * C));
-#pragma unroll
-            for (int g = 0; g < G; g++) pt[g] = jp->pt[0] + ((size_t)(j * nblk + b_x) * G + g) * (EW_T * C) + threadIdx.x * C;
-        } else
-#endif
-#pragma unroll
-        for (int g = 0; g < G; g++) pt[g] = jp->pt[g0 + g < (int)job.ng ? g0 + g : g0] + (size_t)j * n + k;   // missing streams alias a real one
-    }
-
-    // accumulators [stream][coef][poly]
-    u64 s00[G][C][2], sx[G][C][2], s11[G][C][2];
-#pragma unroll
-    for (int g = 0; g < G; g++)
-#pragma unroll
-        for (int c = 0; c < C; c++)
-#pragma unroll
-            for (int p = 0; p < 2; p++) s00[g][c][p] = sx[g][c][p] = s11[g][c][p] = 0;
-
-    struct Term { u64 c[2][C]; u64 a[G][C]; };                  // powers (poly, coef) and plaintext values (stream, coef)
-#ifdef APSU_MAC_TILED_EXPERIMENT
-    // macbench ROTATE (round 6): every workgroup walks its chain from another starting term (the sum is exact in any order), so that the
-    // workgroups resident together do not all read offset t x row-stride of their streams at the same time: -0.9 % stand-alone, does
-    // not remove the placement effect (profiles/r06_mac_rotate.txt); not in the library
-    const u32 rot_ = jp->pad == 3 ? (u32)((b_job * 7u + b_limb * 13u + b_x * 5u) % job.cnt) : 0u;
-#endif
-    auto load_term = [&](u32 i, Term &t) {
-#ifdef APSU_MAC_TILED_EXPERIMENT
-        i += rot_; if (i >= job.cnt) i -= job.cnt;
-#endif
-        if (C == 2) {
-            const u64x2 v0 = ldg16(p0 + (size_t)i * job.pw_stride), v1 = ldg16(p1 + (size_t)i * job.pw_stride);
-            t.c[0][0] = v0[0]; t.c[0][C - 1] = v0[1]; t.c[1][0] = v1[0]; t.c[1][C - 1] = v1[1];
-#pragma unroll
-            for (int g = 0; g < G; g++) {
-                if constexpr (PACKED) {
-                    const u32x4a4 w = ldg16_a4_nt(ptw[g] + (size_t)i * (job.pt_stride >> 2));      // pt_stride in bytes
-                    t.a[g][0] = (u64)w[0] | ((u64)w[1] << 32); t.a[g][C - 1] = (u64)w[2] | ((u64)w[3] << 32);
-                } else {
-                    const u64x2 a = ldg16_nt(pt[g] + (size_t)i * job.pt_stride);
-                    t.a[g][0] = a[0]; t.a[g][C - 1] = a[1];
-                }
-            }
-        } else {
-            t.c[0][0] = p0[(size_t)i * job.pw_stride]; t.c[1][0] = p1[(size_t)i * job.pw_stride];
-#pragma unroll
-            for (int g = 0; g < G; g++) t.a[g][0] = __builtin_nontemporal_load(pt[g] + (size_t)i * job.pt_stride);
-        }
-    };
-    auto mac_term = [&](const Term &t) {
-        u32 clo[2][C], chi[2][C];
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int c = 0; c < C; c++) { clo[p][c] = (u32)t.c[p][c] & lomask; chi[p][c] = (u32)(t.c[p][c] >> s); }
-        u32 csum[2][C];
-        if (KARA) {
-#pragma unroll
-            for (int p = 0; p < 2; p++)
-#pragma unroll
-                for (int c = 0; c < C; c++) csum[p][c] = clo[p][c] + chi[p][c];
-        }
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            u64 av[C];
-            if constexpr (PACKED) {
-                // window >> psh, then coefficient 0 = bits [0, kb), coefficient 1 = bits [kb, 2 kb)
-                const u32 w0 = (u32)t.a[g][0], w1 = (u32)(t.a[g][0] >> 32), w2 = (u32)t.a[g][C - 1], w3 = (u32)(t.a[g][C - 1] >> 32);
-                const u32 n0 = __builtin_amdgcn_alignbit(w1, w0, psh), n1 = __builtin_amdgcn_alignbit(w2, w1, psh),
-                          n2 = __builtin_amdgcn_alignbit(w3, w2, psh), n3 = w3 >> psh;
-                const u64 lo64 = (u64)n0 | ((u64)n1 << 32), hi64 = (u64)n2 | ((u64)n3 << 32);
-                av[0] = lo64;
-                av[C - 1] = kb == 64 ? hi64 : ((lo64 >> kb) | (hi64 << (64 - kb)));
-            } else {
-#pragma unroll
-                for (int c = 0; c < C; c++) av[c] = t.a[g][c];
-            }
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                const u32 alo = (u32)av[c] & lomask, ahi = PACKED ? ((u32)(av[c] >> s) & himask) : (u32)(av[c] >> s);
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-                    // (MAC_KEEP: an empty statement on every sum keeps the compiler from pairing two products first and adding the pair
-                    //  to the sum with a separate 64-bit add: one v_mad_u64_u32 per product and nothing else)
-                    s00[g][c][p] += (u64)alo * clo[p][c]; MAC_KEEP(s00[g][c][p]);
-                    if (KARA) { sx[g][c][p] += (u64)(alo + ahi) * csum[p][c]; MAC_KEEP(sx[g][c][p]); }
-                    else {
-                        sx[g][c][p] += (u64)alo * chi[p][c]; MAC_KEEP(sx[g][c][p]);
-                        sx[g][c][p] += (u64)ahi * clo[p][c]; MAC_KEEP(sx[g][c][p]);
-                    }
-                    s11[g][c][p] += (u64)ahi * chi[p][c]; MAC_KEEP(s11[g][c][p]);
-                }
-            }
-        }
-    };
-    // recombine S00 + Sx*2^s + S11*2^(2s) (< 2^128) and reduce; the residue re-enters as the next chunk's S00
-    auto fold = [&](bool last) {
-#pragma unroll
-        for (int g = 0; g < G; g++)
-#pragma unroll
-            for (int c = 0; c < C; c++)
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-                    u128p acc{ s00[g][c][p], 0 };
-                    const u64 cross = KARA ? sx[g][c][p] - s00[g][c][p] - s11[g][c][p] : sx[g][c][p];
-                    add128(acc, u128p{ cross << s, cross >> (64 - s) });
-                    add128(acc, u128p{ s11[g][c][p] << (2 * s), s11[g][c][p] >> (64 - 2 * s) });
-                    const u64 r = barrett128(acc, m);
-                    if (KARA && !last) { s00[g][c][p] = r & lomask; sx[g][c][p] = (r & lomask) + (r >> s); }
-                    else { s00[g][c][p] = r; sx[g][c][p] = 0; }
-                    s11[g][c][p] = 0;
-                }
-    };
-
-    const u32 cnt = job.cnt;
-    Term A, B;                                                   // ping-pong register sets: no copies
-    MAC_STAMP(1);
-    load_term(0, A);
-    u32 in_chunk = 0;
-    const u32 npairs = cnt >> 1;
-    for (u32 pr = 0; pr < npairs; pr++) {                        // branch-free body: two terms per trip
-        const u32 i = pr * 2;
-        load_term(i + 1, B);
-        mac_term(A);
-#ifdef APSU_MAC_STAMPS
-        if (pr == 0) MAC_STAMP(2);
-#endif
-        load_term(i + 2 < cnt ? i + 2 : cnt - 1, A);             // clamped prefetch (a re-read hits the cache)
-        mac_term(B);
-        in_chunk += 2;
-        if (in_chunk + 3 > chunk) { fold(false); in_chunk = 1; } // the folded residue counts as one term
-    }
-    if (cnt & 1) mac_term(A);                                    // A holds the last term
-    MAC_STAMP(3);
-    fold(true);
-    MAC_STAMP(4);
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        if (g0 + g < (int)job.ng) {
-            u64 *o = jp->out[g0 + g] + (size_t)b_limb * n + k;
-            if (C == 2) {
-                u64x2 r0, r1;
-                r0[0] = s00[g][0][0]; r0[1] = s00[g][C - 1][0];
-                r1[0] = s00[g][0][1]; r1[1] = s00[g][C - 1][1];
-                *reinterpret_cast<u64x2 *>(o) = r0;
-                *reinterpret_cast<u64x2 *>(o + job.out_poly_stride) = r1;
-            } else {
-                o[0] = s00[g][0][0];
-                o[job.out_poly_stride] = s00[g][0][1];
-            }
-        }
-    }
-#ifdef APSU_MAC_STAMPS
-    if (g_mac_stamps && threadIdx.x == 0) {
-        __builtin_amdgcn_s_waitcnt(0);                           // the stores have left
-        MAC_STAMP(5);
-        const size_t lin = blockIdx.x + gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z);
-        unsigned long long *o = g_mac_stamps + lin * 8;
-        for (int i = 0; i < 6; i++) o[i] = stamp_[i];
-        o[6] = rt0_; o[7] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
-}
-
-#ifndef APSU_MAC_G
-#define APSU_MAC_G 4
-#endif
-#ifndef APSU_MAC_C
-#define APSU_MAC_C 2
-#endif
-void launch_mac(const DevLevel *lv, int nlimbs, const MacJob *jobs, size_t n, int njobs, hipStream_t st, bool kara, bool packed)
-{
-    if (!njobs || !nlimbs) return;
-    constexpr int G = APSU_MAC_G, C = APSU_MAC_C;
-    // (round 4, measured and not adopted -- tools/microbench/mac_persist.hip, profiles/r04_mac_{units,persist,stagger}.txt: a launch
-    //  costs ~0.26 ms more than its chains' length explains, i.e. ~14 us per workgroup; long-lived workgroups that keep the load
-    //  pipeline running across chains were 4-9 % SLOWER, starting the first resident generation in phases changed nothing)
-    const unsigned gx = (unsigned)((n / C + EW_T - 1) / EW_T), gl = (unsigned)nlimbs, gj = (unsigned)(njobs * (MAC_G / G));
-    const int ls = gj <= 65535u ? 1 : 0;                          // limb slowest (k_mac) unless the jobs do not fit grid dimension y
-    const dim3 grid = ls ? dim3(gx, gj, gl) : dim3(gx, gl, gj);
-    if (packed) {
-        if constexpr (C == 2) {
-            if (kara) hipLaunchKernelGGL((k_mac<G, C, true, true>), grid, dim3(EW_T), 0, st, lv, jobs, n, ls);
-            else hipLaunchKernelGGL((k_mac<G, C, false, true>), grid, dim3(EW_T), 0, st, lv, jobs, n, ls);
-        } else throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
-    } else if (kara) hipLaunchKernelGGL((k_mac<G, C, true>), grid, dim3(EW_T), 0, st, lv, jobs, n, ls);
-    else hipLaunchKernelGGL((k_mac<G, C, false>), grid, dim3(EW_T), 0, st, lv, jobs, n, ls);
-    KERNEL_CHECK();
-}
-
-// ---- single dyadic products on ONE limb (round 4): out[p][k] = a[k] * C_p[k] mod q_limb for p = 0, 1.
-// The i = 0 block of eval_patstock (bin_bundle.cpp:314-324) switches every term a_j (.) C^j to the next level on its own, so
-// the dropped limb of every term is needed by itself (k_i0_finish): terms x BinBundles chains of length ONE.  As k_mac jobs each
-// of them paid a whole workgroup's fixed costs (descriptor and pointer reads, the first term's latency, the 128-bit fold, the
-// drain of the stores: ~10 us at two workgroups per CU) for 1.4 us of work -- 9 % of the launch for 2.6 % of its bytes at
-// 16M-4096, more at 256M-4096 (31 620 such chains).  Here: one thread per coefficient pair, ~40 registers, full occupancy,
-// the same canonical residue (k_mac's fold of a single product IS barrett128 of that product).
-template <bool PACKED>
-__global__ __launch_bounds__(EW_T) void k_term_product(const DevLevel *__restrict__ lv, const TermJob *__restrict__ jobs, size_t njobs, size_t n, int limb,
-                                                       u32 pw_poly_stride, u32 out_poly_stride)
-{
-    const size_t k = ((size_t)blockIdx.x * EW_T + threadIdx.x) * 2;
-    const size_t u = blockIdx.y + (size_t)gridDim.y * blockIdx.z;
-    if (k >= n || u >= njobs) return;
-    const TermJob job = jobs[u];
-    const Mod m = lv->q[limb];
-    u64 a0, a1;
-    if constexpr (PACKED) {
-        const u32 kb = lv->mac_bits[limb];
-        const u32 bitoff = (u32)(k >> 1) * 2 * kb, psh = bitoff & 31;
-        const u32x4a4 w = ldg16_a4_nt(reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(job.pt) + lv->mac_row_off[limb]) + (bitoff >> 5));
-        const u32 n0 = __builtin_amdgcn_alignbit(w[1], w[0], psh), n1 = __builtin_amdgcn_alignbit(w[2], w[1], psh),
-                  n2 = __builtin_amdgcn_alignbit(w[3], w[2], psh), n3 = w[3] >> psh;
-        const u64 lo64 = (u64)n0 | ((u64)n1 << 32), hi64 = (u64)n2 | ((u64)n3 << 32);
-        if (kb == 64) { a0 = lo64; a1 = hi64; }
-        else { const u64 mask = ((u64)1 << kb) - 1; a0 = lo64 & mask; a1 = ((lo64 >> kb) | (hi64 << (64 - kb))) & mask; }
-    } else {
-        const u64x2 a = ldg16_nt(job.pt + (size_t)limb * n + k);
-        a0 = a[0]; a1 = a[1];
-    }
-    const u64 *pw = job.pw + (size_t)limb * n + k;
-    const u64x2 c0 = ldg16(pw), c1 = ldg16(pw + pw_poly_stride);
-    u64x2 r0, r1;
-    r0[0] = barrett128(mul128(a0, c0[0]), m); r0[1] = barrett128(mul128(a1, c0[1]), m);
-    r1[0] = barrett128(mul128(a0, c1[0]), m); r1[1] = barrett128(mul128(a1, c1[1]), m);
-    *reinterpret_cast<u64x2 *>(job.out + k) = r0;
-    *reinterpret_cast<u64x2 *>(job.out + out_poly_stride + k) = r1;
-}
-
-void launch_term_product(const DevLevel *lv, const TermJob *jobs, size_t njobs, size_t n, int limb, u32 pw_poly_stride, u32 out_poly_stride,
-                         bool packed, hipStream_t st)
-{
-    if (!njobs) return;
-    const unsigned gy = (unsigned)std::min<size_t>(njobs, 32768), gz = (unsigned)((njobs + gy - 1) / gy);
-    const dim3 grid((unsigned)((n / 2 + EW_T - 1) / EW_T), gy, gz);
-    if (packed) hipLaunchKernelGGL((k_term_product<true>), grid, dim3(EW_T), 0, st, lv, jobs, njobs, n, limb, pw_poly_stride, out_poly_stride);
-    else hipLaunchKernelGGL((k_term_product<false>), grid, dim3(EW_T), 0, st, lv, jobs, njobs, n, limb, pw_poly_stride, out_poly_stride);
-    KERNEL_CHECK();
-}
-
-// ---- bit-packed database rows: dense u64 limbs <-> rows of mac_bits[j] bits per coefficient (DevLevel)
-// one thread per OUTPUT dword: bits [32 d, 32 d + 32) of the row come from at most two coefficients (widths are >= 32)
-__global__ __launch_bounds__(EW_T) void k_pack_rows(const DevLevel *__restrict__ lv, int L, const u64 *__restrict__ dense, char *__restrict__ packed,
-                                                    size_t slot_bytes, size_t n)
-{
-    const size_t slot = blockIdx.y / L;
-    const int j = (int)(blockIdx.y % L);
-    const u32 w = lv->mac_bits[j];
-    const size_t d = (size_t)blockIdx.x * EW_T + threadIdx.x, ndw = n * w / 32;
-    if (d >= ndw) return;
-    const u64 *src = dense + (slot * L + j) * n;
-    const size_t bit0 = d * 32, c0 = bit0 / w;
-    const u32 off = (u32)(bit0 - c0 * w), got = w - off;
-    u64 v = src[c0] >> off;
-    if (got < 32 && c0 + 1 < n) v |= src[c0 + 1] << got;
-    reinterpret_cast<u32 *>(packed + slot * slot_bytes + lv->mac_row_off[j])[d] = (u32)v;
-}
-// one thread per coefficient (a bit-packed slot is followed by at least 16 readable bytes: the engine pads its buffers)
-__global__ __launch_bounds__(EW_T) void k_unpack_rows(const DevLevel *__restrict__ lv, int L, const char *__restrict__ packed, size_t slot_bytes,
-                                                      u64 *__restrict__ dense, size_t n)
-{
-    const size_t slot = blockIdx.y / L;
-    const int j = (int)(blockIdx.y % L);
-    const size_t c = (size_t)blockIdx.x * EW_T + threadIdx.x;
-    if (c >= n) return;
-    const u32 w = lv->mac_bits[j];
-    const u32 *row = reinterpret_cast<const u32 *>(packed + slot * slot_bytes + lv->mac_row_off[j]);
-    const size_t bit0 = c * w, d0 = bit0 >> 5;
-    const u32 sh = (u32)(bit0 & 31);
-    u64 v = ((u64)row[d0] | ((u64)row[d0 + 1] << 32)) >> sh;
-    if (sh && w + sh > 64) v |= (u64)row[d0 + 2] << (64 - sh);
-    dense[(slot * L + j) * n + c] = w == 64 ? v : (v & (((u64)1 << w) - 1));
-}
-void launch_pack_rows(const DevLevel *lv, int L, const u64 *dense, void *packed, size_t slot_bytes, size_t n, size_t slots, hipStream_t st)
-{
-    if (!slots) return;
-    hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((n * 2 + EW_T - 1) / EW_T), (unsigned)(slots * L)), dim3(EW_T), 0, st, lv, L, dense,
-                       static_cast<char *>(packed), slot_bytes, n);
-    KERNEL_CHECK();
-}
-void launch_unpack_rows(const DevLevel *lv, int L, const void *packed, size_t slot_bytes, u64 *dense, size_t n, size_t slots, hipStream_t st)
-{
-    if (!slots) return;
-    hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((n + EW_T - 1) / EW_T), (unsigned)(slots * L)), dim3(EW_T), 0, st, lv, L,
-                       static_cast<const char *>(packed), slot_bytes, dense, n);
     KERNEL_CHECK();
 }
 

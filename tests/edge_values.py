@@ -20,14 +20,14 @@ def mac_shift(q):
 
 
 def mac_chunk(q):
-    """terms per carry-free chunk of the two-cross-product form (dev_consts.cpp build_level, DevLevel::mac_chunk; held to it by test_dev_consts_cpu.py)"""
+    """terms per carry-free chunk of the two-cross-product form (mac_core.h mac_chunk_of, DevLevel::mac_chunk; held to it by test_dev_consts_cpu.py and test_mac_core_cpu.py)"""
     s = mac_shift(q)
     cap = 1 << (63 - 2 * s)
     return min(cap - 1 if cap > 2 else 2, 1 << 20)
 
 
 def mac_chunk_kara(q):
-    """terms per chunk of the three-product form; 0 where the form is not usable for q (Engine::mac_kara: 62 - 2 s >= 3)"""
+    """terms per chunk of the three-product form; 0 where the form is not usable for q (mac_core.h: mac_chunk_k_of where mac_kara_usable)"""
     s = mac_shift(q)
     if 62 - 2 * s < 3:
         return 0

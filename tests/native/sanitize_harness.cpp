@@ -1,7 +1,8 @@
 // CPU tier, sanitizer build (AddressSanitizer + UndefinedBehaviorSanitizer) of the product's HOST code that parses untrusted or
 // structured input: the N3 framing reader (wire.cpp), the PSUParams JSON reader + constant derivation (params.cpp), the
 // constant blocks built from them (dev_consts.cpp), the PowersDag (powers_dag.cpp) and the partition rule (sharding.cpp).  Built and run by tests/test_host_sanitizers.py; any
-// out-of-bounds read in the verifier, signed overflow or misaligned access aborts the run.
+// out-of-bounds read in the verifier, signed overflow or misaligned access aborts the run.  Also the reads of k_mac, k_term_product and
+// packed_coeff (mac_core.h, the functions the kernels run) at the very end of a bit-packed buffer.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +16,7 @@
 #include "../../apsu_amd/csrc/params.h"
 #include "../../apsu_amd/csrc/dev_consts.h"
 #include "../../apsu_amd/csrc/bundle_layout.h"
+#include "../../apsu_amd/csrc/mac_core.h"
 #include "../../apsu_amd/csrc/powers_dag.h"
 #include "../../apsu_amd/csrc/sharding.h"
 #include "../../apsu_amd/csrc/wire.h"
@@ -256,6 +258,40 @@ int main(int argc, char **argv)
                     for (char c : lifted) if (c != 2) return 42;
                 } catch (const std::invalid_argument &) { if (ps != 1 || degree < 2) return 43; }
             }
+    // ---- bit-packed rows (mac_core.h): the LAST lane of the LAST term reads a 16-byte window that may reach past its slot; the engine pads
+    // a packed buffer by 16 bytes.  Heap buffers of EXACTLY slots * slot size + 16 bytes: one byte more is an ASan error.
+    for (uint32_t w : { 48u, 49u, 50u, 52u, 56u, 64u }) {
+        const size_t n = 512, terms = 3, slot_bytes = n * w / 8;
+        const u64 q = ((u64)1 << (w == 64 ? 60 : w)) - 59;
+        DevLevel lv;
+        std::memset(&lv, 0, sizeof(lv));
+        lv.L = 1; lv.q[0] = make_mod(q);
+        lv.mac_shift[0] = (u32)mac_shift_of(q); lv.mac_chunk[0] = mac_chunk_of(q); lv.mac_chunk_k[0] = mac_chunk_k_of(q);
+        lv.mac_bits[0] = w; lv.mac_mask_hi[0] = mac_mask_hi_of(w, mac_shift_of(q));
+        std::vector<u64> dense(terms * n), pw(terms * 2 * n), out(2 * n, 0), one(2 * n, 0);
+        for (auto &v : dense) v = rnd() % q;
+        for (auto &v : pw) v = rnd() % q;
+        char *packed = static_cast<char *>(std::malloc(terms * slot_bytes + 16));
+        std::memset(packed, 0xff, terms * slot_bytes + 16);
+        for (unsigned slot = 0; slot < terms; slot++)
+            for (size_t d = 0; d < n * w / 32; d++) pack_rows_lane(&lv, 1, dense.data(), packed, slot_bytes, n, d, slot, 0);
+        MacJob job{};
+        for (int g = 0; g < MAC_G; g++) { job.pt[g] = reinterpret_cast<const u64 *>(packed); job.out[g] = out.data(); }
+        job.pw = pw.data(); job.cnt = (u32)terms; job.ng = 1; job.pt_stride = (u32)slot_bytes; job.pw_stride = (u32)(2 * n); job.pw_poly_stride = (u32)n;
+        job.out_poly_stride = (u32)n; job.limb0 = 0; job.nl = 1; job.packed = 1;
+        const unsigned last = (unsigned)(n / 2 - 1);                                 // the lane of coefficients n - 2, n - 1
+        k_mac<false, true>(&lv, &job, n, 1, 0, 0, 0, last);
+        const TermJob tj{ reinterpret_cast<const u64 *>(packed + (terms - 1) * slot_bytes), pw.data() + (terms - 1) * 2 * n, one.data() };
+        term_product_lane<true>(&lv, &tj, 1, n, 0, (u32)n, (u32)n, n - 2, 0);
+        for (size_t c = n - 2; c < n; c++) {
+            unsigned __int128 sum = 0;
+            for (size_t t = 0; t < terms; t++) sum += (unsigned __int128)dense[t * n + c] * pw[t * 2 * n + c] % q;
+            if (out[c] != (u64)(sum % q)) return 50;
+            if (one[c] != (u64)((unsigned __int128)dense[(terms - 1) * n + c] * pw[(terms - 1) * 2 * n + c] % q)) return 51;
+            if (packed_coeff(reinterpret_cast<const u32 *>(packed + (terms - 1) * slot_bytes), c, w) != dense[(terms - 1) * n + c]) return 52;
+        }
+        std::free(packed);
+    }
     std::printf("ok\n");
     return 0;
 }

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(EW_T, 2) void k_mac_p(const DevLevel *__restrict__ 
 static int g_mac_persist_r = 0;
 inline void launch_mac_persist(const DevLevel *lv, const MacJob *jobs, size_t n, int njobs, hipStream_t st, bool kara, int r_req)
 {
-    constexpr int G = APSU_MAC_G, C = APSU_MAC_C;
+    constexpr int G = MAC_G, C = MAC_C;
     const unsigned gx = (unsigned)((n / C + EW_T - 1) / EW_T), nz = (unsigned)(njobs * (MAC_G / G));
     unsigned r = r_req > 0 ? (unsigned)r_req : std::max(1u, 2u * 256u / gx);
     r = std::min(r, nz);

@@ -1,5 +1,5 @@
 // LDS-DMA ring variant of the engine's dyadic multiply-accumulate (k_mac), kept OUT of the library: measured neutral to
-// slower (profiles/r03_mac_ring.txt).  Included by macbench.hip behind kernels.hip; `RING=1 ./macbench` runs it against k_mac
+// slower (profiles/r03_mac_ring.txt).  Included by macbench.hip behind kernels_mac.hip; `RING=1 ./macbench` runs it against k_mac
 // on the same jobs and compares the outputs bit for bit.
 #pragma once
 namespace apsu_he {

@@ -1,6 +1,5 @@
-#define APSU_MAC_TILED_EXPERIMENT 1
 // Stand-alone timing of the engine's k_mac on a synthetic DB, to bisect its HBM efficiency (see readbw.hip for the ceilings).
-#include "../../apsu_amd/csrc/kernels.hip"
+#include "../../apsu_amd/csrc/kernels_mac.hip"
 #ifndef MACBENCH_PLAIN      // -DMACBENCH_PLAIN: k_mac only (the ring / persistent variants are written for four streams per job)
 #include "mac_ring.hip"
 #include "mac_persist.hip"
@@ -12,6 +11,8 @@
 #include <algorithm>
 namespace apsu_he { void throw_hip(hipError_t e, const char* f, int l) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), f, l); abort(); } }
 using namespace apsu_he;
+// k_mac as the library launches it for these jobs (the grid of mac_plan.h)
+static void bench_mac(const DevLevel *lv, int nl, const MacJob *jobs, size_t n, int njobs, hipStream_t st, bool kara = false, bool packed = false) { launch_mac(lv, nl, jobs, n, njobs, st, kara, packed, mac_grid(n, (size_t)njobs)); }
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 __global__ void k_fillrand(u64* p, size_t words, u64 mask) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) {
@@ -101,47 +102,16 @@ int main(int argc, char** argv) {
     {
         std::vector<float> t;
         for (int rep = 0; rep < 16; rep++) {
-            CHECK(hipEventRecord(e0)); launch_mac(lv, 3, dj, n, (int)jobs.size(), 0); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
+            CHECK(hipEventRecord(e0)); bench_mac(lv, 3, dj, n, (int)jobs.size(), 0); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
             float ms; CHECK(hipEventElapsedTime(&ms, e0, e1));
             if (rep >= 2) t.push_back(ms);
         }
         std::sort(t.begin(), t.end());
-        printf("k_mac<%d,%d> ring=%d nb=%d pad=%zu: min %.3f ms (%.0f GB/s)  median %.3f ms (%.0f GB/s)  max %.3f\n", APSU_MAC_G, APSU_MAC_C, 2, nb, pad,
+        printf("k_mac<%d,%d> ring=%d nb=%d pad=%zu: min %.3f ms (%.0f GB/s)  median %.3f ms (%.0f GB/s)  max %.3f\n", MAC_G, MAC_C, 2, nb, pad,
                t[0], words * 8 / (t[0] * 1e-3) / 1e9, t[t.size() / 2], words * 8 / (t[t.size() / 2] * 1e-3) / 1e9, t.back());
     }
-#ifdef APSU_MAC_STAMPS
-    if (getenv("STAMPS")) {
-        // build with -DAPSU_MAC_STAMPS: the per-workgroup timeline of k_mac (in-kernel shader-clock stamps of lane 0)
-        const size_t nwg = (size_t)16 * 3 * jobs.size();
-        unsigned long long *dst; CHECK(hipMalloc(&dst, nwg * 8 * sizeof(unsigned long long))); CHECK(hipMemset(dst, 0, nwg * 8 * sizeof(unsigned long long)));
-        CHECK(hipMemcpyToSymbol(HIP_SYMBOL(apsu_he::g_mac_stamps), &dst, sizeof(dst)));
-        for (int rep = 0; rep < 3; rep++) { launch_mac(lv, 3, dj, n, (int)jobs.size(), 0); CHECK(hipDeviceSynchronize()); }
-        std::vector<unsigned long long> h(nwg * 8);
-        CHECK(hipMemcpy(h.data(), dst, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        unsigned long long *nul = nullptr; CHECK(hipMemcpyToSymbol(HIP_SYMBOL(apsu_he::g_mac_stamps), &nul, sizeof(nul)));
-        const char *names[5] = { "setup (descriptor, pointers)", "first term arrives + consumed", "steady loop", "fold", "store + drain" };
-        std::vector<double> ph[5], life, start;
-        unsigned long long t0 = ~0ull;
-        for (size_t w = 0; w < nwg; w++) if (h[w * 8 + 6] && h[w * 8 + 6] < t0) t0 = h[w * 8 + 6];
-        for (size_t w = 0; w < nwg; w++) {
-            const unsigned long long *s2 = &h[w * 8];
-            if (!s2[5]) continue;
-            for (int i = 0; i < 5; i++) ph[i].push_back((double)(s2[i + 1] - s2[i]));
-            life.push_back((double)(s2[7] - s2[6]) / 100.0);     // us (100 MHz)
-            start.push_back((double)(s2[6] - t0) / 100.0);
-        }
-        auto med = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; };
-        auto p90 = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() * 9 / 10]; };
-        double tot = 0; for (int i = 0; i < 5; i++) tot += med(ph[i]);
-        printf("workgroups stamped: %zu of %zu; median lifetime %.1f us (p90 %.1f); last start at %.1f us\n", life.size(), nwg, med(life), p90(life), *std::max_element(start.begin(), start.end()));
-        for (int i = 0; i < 5; i++) printf("  %-32s median %9.0f cycles (%4.1f %%)   p90 %9.0f\n", names[i], med(ph[i]), 100 * med(ph[i]) / tot, p90(ph[i]));
-        std::vector<int> hist(100, 0);
-        for (double st2 : start) { size_t b = (size_t)(st2 / 20.0); if (b < hist.size()) hist[b]++; }
-        printf("  starts per 20 us:"); for (size_t b = 0; b < hist.size() && b < 80; b++) printf(" %d", hist[b]); printf("\n");
-    }
-#endif
     // (the grid-order comparison that lived here -- ORDER=1: orders 0 / 1 / 2 with real powers and with one term's powers -- is recorded in
-    //  profiles/r04_mac_grid_order.txt; the library keeps order 1 and launch_mac no longer takes an order)
+    //  profiles/r04_mac_grid_order.txt; the library keeps order 1 and the plan (mac_plan.h) holds it)
     if (getenv("PLACEMENT")) {
         // Does the scan's speed depend on WHERE the database lies?  (Identical binaries run one after the other alternate between 1.12 and
         // 1.26 ms, profiles/r05_mac_ring3.txt.)  Several copies of the same database in ONE process, the same kernel on each in turn;
@@ -160,23 +130,11 @@ int main(int argc, char** argv) {
                     MacJob *djc; CHECK(hipMalloc(&djc, jc.size() * sizeof(MacJob))); CHECK(hipMemcpy(djc, jc.data(), jc.size() * sizeof(MacJob), hipMemcpyHostToDevice));
                     std::vector<float> t;
                     for (int rep = 0; rep < 8; rep++) {
-                        CHECK(hipEventRecord(e0)); launch_mac(lv, 3, djc, n, (int)jc.size(), 0); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
+                        CHECK(hipEventRecord(e0)); bench_mac(lv, 3, djc, n, (int)jc.size(), 0); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
                         float ms; CHECK(hipEventElapsedTime(&ms, e0, e1)); if (rep >= 2) t.push_back(ms);
                     }
                     std::sort(t.begin(), t.end());
                     printf("pass %d  copy %zu at %p  skew %5zu words: median %.3f ms (%.0f GB/s)\n", pass, c, (void *)dbs[c], sk, t[t.size() / 2], words * 8 / (t[t.size() / 2] * 1e-3) / 1e9);
-                    if (getenv("ROTATE")) {                          // the same copy, every workgroup starting at another term (MacJob::pad = 3)
-                        for (auto &x : jc) x.pad = 3;
-                        CHECK(hipMemcpy(djc, jc.data(), jc.size() * sizeof(MacJob), hipMemcpyHostToDevice));
-                        std::vector<float> tr;
-                        for (int rep = 0; rep < 8; rep++) {
-                            CHECK(hipEventRecord(e0)); launch_mac(lv, 3, djc, n, (int)jc.size(), 0); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
-                            float ms; CHECK(hipEventElapsedTime(&ms, e0, e1)); if (rep >= 2) tr.push_back(ms);
-                        }
-                        std::sort(tr.begin(), tr.end());
-                        printf("        rotated start terms on copy %zu: median %.3f ms (%.0f GB/s)  %+.1f %%\n", c, tr[tr.size() / 2], words * 8 / (tr[tr.size() / 2] * 1e-3) / 1e9,
-                               100.0 * (tr[tr.size() / 2] / t[t.size() / 2] - 1));
-                    }
                     CHECK(hipFree(djc));
                     if (getenv("PROBE") && pass == 2 && sk == 0) {
                         for (size_t stride : { (size_t)4096, (size_t)65536, (size_t)(2u << 20) }) {
@@ -193,41 +151,6 @@ int main(int argc, char** argv) {
                     }
                 }
     }
-    if (getenv("TILED")) {
-        // Is the scan bound by bytes or by the NUMBER of separate pieces it reads?  Row layout (the engine's): a workgroup's G streams
-        // are G pieces of 4 KiB (dense) / 3.5 KiB (56-bit packed) per term, each in another stream's slot.  Tiled layout: the G pieces
-        // of one (term, limb, block) adjacent -- one piece of 16 / 14 KiB per workgroup and term.  Timing only (same bytes, other sums).
-        DevLevel hp = h;
-        const u32 kbits = getenv("KBITS") ? atoi(getenv("KBITS")) : 56;
-        for (int j = 0; j < 3; j++) { hp.mac_bits[j] = kbits; hp.mac_mask_hi[j] = (1u << (kbits - 28)) - 1; hp.mac_row_off[j] = (u32)(j * n * kbits / 8); }
-        DevLevel *lvp; CHECK(hipMalloc(&lvp, sizeof(hp))); CHECK(hipMemcpy(lvp, &hp, sizeof(hp), hipMemcpyHostToDevice));
-        const size_t slot_b = 3 * n * kbits / 8;
-        std::vector<MacJob> jd = jobs, jdt = jobs, jp = jobs, jpt = jobs, jpb = jobs;
-        for (size_t x = 0; x < jobs.size(); x++) {
-            const size_t s0 = x * MAC_G;
-            jdt[x].pad = 1; jdt[x].pt_stride = (u32)(ptw * MAC_G); jdt[x].pt[0] = db + s0 * terms * ptw;
-            for (int g = 0; g < MAC_G; g++) jp[x].pt[g] = reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(db) + (s0 + g) * terms * slot_b);
-            jp[x].packed = 1; jp[x].pt_stride = (u32)slot_b;
-            jpb[x] = jp[x]; jpb[x].pad = 2; jpb[x].pt_stride = (u32)(256 * 2 * kbits / 8);      // block-major: a term = the next 3.5 KiB tile
-            jpt[x] = jp[x]; jpt[x].pad = 1; jpt[x].pt_stride = (u32)(slot_b * MAC_G); jpt[x].pt[0] = reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(db) + s0 * terms * slot_b);
-        }
-        auto upj = [&](const std::vector<MacJob> &v) { MacJob *d; if (hipMalloc(&d, v.size() * sizeof(MacJob)) != hipSuccess) abort(); if (hipMemcpy(d, v.data(), v.size() * sizeof(MacJob), hipMemcpyHostToDevice) != hipSuccess) abort(); return d; };
-        MacJob *d_jd = upj(jd), *d_jdt = upj(jdt), *d_jp = upj(jp), *d_jpt = upj(jpt), *d_jpb = upj(jpb);
-        const double coefs = (double)streams * terms * ptw;
-        for (int pass = 0; pass < 2; pass++)
-            for (int v = 0; v < 5; v++) {
-                const bool packed = v >= 2; MacJob *dv = v == 0 ? d_jd : v == 1 ? d_jdt : v == 2 ? d_jp : v == 3 ? d_jpt : d_jpb;
-                std::vector<float> t;
-                for (int rep = 0; rep < 10; rep++) {
-                    CHECK(hipEventRecord(e0)); launch_mac(packed ? lvp : lv, 3, dv, n, (int)jobs.size(), 0, false, packed); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
-                    float ms; CHECK(hipEventElapsedTime(&ms, e0, e1)); if (rep >= 2) t.push_back(ms);
-                }
-                std::sort(t.begin(), t.end());
-                const double by = coefs * (packed ? kbits / 8.0 : 8.0), med = t[t.size() / 2];
-                printf("terms %d  %-22s %s: median %.3f ms  %.0f GB/s  %.3f Tcoef/s\n", terms, packed ? (kbits == 56 ? "packed 56 bits" : "packed") : "dense", v == 4 ? "block-major" : (v & 1) ? "tiled" : "rows ", med,
-                       by / (med * 1e-3) / 1e9, coefs / (med * 1e-3) / 1e12);
-            }
-    }
 #ifndef MACBENCH_PLAIN
     if (getenv("PERSIST")) {
         // long-lived workgroups (k_mac_p) against one workgroup per unit (k_mac): separate output, bit-compared; A B A B timing
@@ -240,7 +163,7 @@ int main(int argc, char** argv) {
             std::vector<float> ta, tb;
             for (int rep = 0; rep < 14; rep++) {
                 float ms;
-                CHECK(hipEventRecord(e0)); launch_mac(lv, 3, dj, n, (int)jobs.size(), 0, kara); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
+                CHECK(hipEventRecord(e0)); bench_mac(lv, 3, dj, n, (int)jobs.size(), 0, kara); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
                 CHECK(hipEventElapsedTime(&ms, e0, e1)); if (rep >= 2) ta.push_back(ms);
                 CHECK(hipEventRecord(e0)); launch_mac_persist(lv, dj2, n, (int)jobs2.size(), 0, kara, r); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
                 CHECK(hipEventElapsedTime(&ms, e0, e1)); if (rep >= 2) tb.push_back(ms);
@@ -262,7 +185,7 @@ int main(int argc, char** argv) {
             std::vector<float> t;
             for (int rep = 0; rep < 8; rep++) {
                 CHECK(hipEventRecord(e0));
-                for (int k = 0; k < nl; k++) launch_mac(lv, 3, dj, n, (int)jobs.size(), 0);
+                for (int k = 0; k < nl; k++) bench_mac(lv, 3, dj, n, (int)jobs.size(), 0);
                 CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
                 float ms; CHECK(hipEventElapsedTime(&ms, e0, e1));
                 if (rep >= 2) t.push_back(ms);
@@ -280,9 +203,9 @@ int main(int argc, char** argv) {
         std::vector<float> ta, tb;
         for (int rep = 0; rep < 24; rep++) {
             float ms;
-            CHECK(hipEventRecord(e0)); launch_mac(lv, 3, dj, n, (int)jobs.size(), 0, false); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
+            CHECK(hipEventRecord(e0)); bench_mac(lv, 3, dj, n, (int)jobs.size(), 0, false); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
             CHECK(hipEventElapsedTime(&ms, e0, e1)); if (rep >= 4) ta.push_back(ms);
-            CHECK(hipEventRecord(e0)); launch_mac(lv, 3, dj2, n, (int)jobs2.size(), 0, true); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
+            CHECK(hipEventRecord(e0)); bench_mac(lv, 3, dj2, n, (int)jobs2.size(), 0, true); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize());
             CHECK(hipEventElapsedTime(&ms, e0, e1)); if (rep >= 4) tb.push_back(ms);
         }
         std::sort(ta.begin(), ta.end()); std::sort(tb.begin(), tb.end());
@@ -320,7 +243,7 @@ int main(int argc, char** argv) {
         printf("ring vs k_mac: %zu of %zu output words differ\n", bad, ow);
         // once more k_mac, after the ring runs (same clocks / thermal state)
         std::vector<float> t;
-        for (int rep = 0; rep < 12; rep++) { CHECK(hipEventRecord(e0)); launch_mac(lv, 3, dj, n, (int)jobs.size(), 0); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize()); float ms; CHECK(hipEventElapsedTime(&ms, e0, e1)); t.push_back(ms); }
+        for (int rep = 0; rep < 12; rep++) { CHECK(hipEventRecord(e0)); bench_mac(lv, 3, dj, n, (int)jobs.size(), 0); CHECK(hipEventRecord(e1)); CHECK(hipDeviceSynchronize()); float ms; CHECK(hipEventElapsedTime(&ms, e0, e1)); t.push_back(ms); }
         std::sort(t.begin(), t.end());
         printf("k_mac again: min %.3f median %.3f\n", t[0], t[t.size() / 2]);
     }
