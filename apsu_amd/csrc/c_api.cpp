@@ -638,6 +638,82 @@ int apsu_he_multi_db_update_bundle(apsu_he_multi *m, int bundle_id, const uint64
         m->m->update_bundle(bundle_id, ins_roots, ins_counts, ins_stride, rem_roots, rem_counts, rem_stride, bins);
     });
 }
+// ---- the resident database maintained on the handle (MultiEngine, multi_db.cpp)
+int apsu_he_multi_db_bundle_count(apsu_he_multi *m, int *count)
+{ return guarded([&] { REQUIRE(m && count, "null argument"); *count = (int)m->m->registry().size(); }); }
+int apsu_he_multi_db_bundle_info(apsu_he_multi *m, int bundle_id, int *device_slot, uint32_t *bundle_idx, uint32_t *cache_idx, uint32_t *degree)
+{
+    return guarded([&] {
+        REQUIRE(m, "null argument");
+        const std::vector<RegUnit> reg = m->m->registry();
+        REQUIRE(bundle_id >= 0 && (size_t)bundle_id < reg.size(), "no BinBundle with this id");
+        const RegUnit &u = reg[(size_t)bundle_id];
+        if (device_slot) *device_slot = u.slot;
+        if (bundle_idx) *bundle_idx = u.bundle_idx;
+        if (cache_idx) *cache_idx = u.cache_idx;
+        if (degree) *degree = u.degree;
+    });
+}
+int apsu_he_multi_db_index_bundles(apsu_he_multi *m, uint32_t bundle_idx, int *ids, int capacity, int *n)
+{
+    return guarded([&] {
+        REQUIRE(m && n && capacity >= 0 && (ids || !capacity), "null argument");
+        const std::vector<int> v = m->m->index_bundles(bundle_idx);
+        *n = (int)v.size();
+        std::copy(v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)capacity), ids);
+    });
+}
+int apsu_he_multi_db_bin_counts(apsu_he_multi *m, int bundle_id, uint32_t *counts)
+{ return guarded([&] { REQUIRE(m && counts, "null argument"); m->m->bin_counts(bundle_id, counts); }); }
+int apsu_he_multi_db_build_bundle(apsu_he_multi *m, int device_slot, uint32_t bundle_idx, uint32_t cache_idx, const uint64_t *roots,
+                                  const uint32_t *counts, uint32_t bins, uint32_t stride, int *bundle_id)
+{
+    return guarded([&] {
+        REQUIRE(m && counts && bundle_id && (roots || !bins), "null argument");
+        *bundle_id = m->m->build_bundle(device_slot, bundle_idx, cache_idx, roots, counts, bins, stride);
+    });
+}
+int apsu_he_multi_db_remove_bundle(apsu_he_multi *m, int bundle_id, int *new_id)
+{ return guarded([&] { REQUIRE(m, "null argument"); m->m->remove_bundle(bundle_id, new_id); }); }
+int apsu_he_multi_db_move_bundle(apsu_he_multi *m, int bundle_id, int device_slot)
+{ return guarded([&] { REQUIRE(m, "null argument"); m->m->move_bundle(bundle_id, device_slot); }); }
+int apsu_he_multi_db_lookup(apsu_he_multi *m, uint32_t bundle_idx, const uint64_t *felts, const uint32_t *start_bins, size_t count, uint8_t *present,
+                            uint32_t *room)
+{
+    return guarded([&] {
+        REQUIRE(m && ((felts && start_bins) || !count), "null argument");
+        m->m->lookup(bundle_idx, felts, start_bins, count, present, room);
+    });
+}
+int apsu_he_multi_db_apply_entries(apsu_he_multi *m, uint32_t bundle_idx, const uint64_t *ins_felts, const uint32_t *ins_start, size_t n_ins,
+                                   const uint64_t *rem_felts, const uint32_t *rem_start, size_t n_rem, int *new_id, uint32_t *n_appended,
+                                   uint32_t *ins_status, uint32_t *ins_target, uint32_t *rem_status, uint32_t *rem_target)
+{
+    return guarded([&] {
+        REQUIRE(m && ((ins_felts && ins_start) || !n_ins) && ((rem_felts && rem_start) || !n_rem), "null argument");
+        const MultiEngine::ApplyOutcome r = m->m->apply_entries(bundle_idx, ins_felts, ins_start, n_ins, rem_felts, rem_start, n_rem);
+        // targets are old ids: a position among the index's BinBundles -> its id, the k-th appended BinBundle -> old count + k
+        const size_t nb = r.ids.size();
+        auto as_id = [&](uint32_t pos) { return pos == PLACE_NO_TARGET ? pos : pos < nb ? (uint32_t)r.ids[pos] : (uint32_t)r.old_count + (pos - (uint32_t)nb); };
+        const PlaceResult &p = r.place;
+        if (new_id) std::copy(r.new_id.begin(), r.new_id.end(), new_id);
+        if (n_appended) *n_appended = p.n_new;
+        if (ins_status) std::copy(p.ins_status.begin(), p.ins_status.end(), ins_status);
+        if (rem_status) std::copy(p.rem_status.begin(), p.rem_status.end(), rem_status);
+        if (ins_target) for (size_t e = 0; e < p.ins_target.size(); e++) ins_target[e] = as_id(p.ins_target[e]);
+        if (rem_target) for (size_t e = 0; e < p.rem_target.size(); e++) rem_target[e] = as_id(p.rem_target[e]);
+    });
+}
+int apsu_he_multi_db_merge_bundles(apsu_he_multi *m, const int *bundle_ids, uint32_t n_ids, int *new_id)
+{ return guarded([&] { REQUIRE(m && (bundle_ids || !n_ids), "null argument"); m->m->merge_bundles(bundle_ids, n_ids, new_id); }); }
+int apsu_he_multi_db_compact(apsu_he_multi *m, uint32_t bundle_idx, int *new_id, uint32_t *n_merged)
+{
+    return guarded([&] {
+        REQUIRE(m, "null argument");
+        const uint32_t made = m->m->compact(bundle_idx, new_id);
+        if (n_merged) *n_merged = made;
+    });
+}
 int apsu_he_multi_db_load_file(apsu_he_multi *m, const apsu_he_db_file *f, int *n_loaded)
 {
     return guarded([&] {

@@ -115,6 +115,12 @@ struct EventStamps {
     void release();
 };
 
+// apply_entries' host step: what a lookup found (counts [n_bundles][n], present [n_bundles][n_rem + n_ins] with the removals first, both
+// in cache order) -> place_entries (db_place.h).  Engine::apply_entries and MultiEngine::apply_entries share it.
+PlaceResult place_from_lookup(uint32_t n_bundles, size_t n, uint32_t bins, uint32_t F, uint32_t max_items, u64 t, const uint32_t *counts,
+                              const unsigned char *present, const u64 *ins_felts, const uint32_t *ins_start, size_t n_ins, const u64 *rem_felts,
+                              const uint32_t *rem_start, size_t n_rem);
+
 class Engine {
 public:
     Engine(const HeParams &hp, const PSUParams *psu, int device);
@@ -165,6 +171,14 @@ public:
     // felts[count][felts_per_item], start[count]; present / room: [n_bundles][count] (host), either may be null
     void lookup_bundles(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count,
                         unsigned char *present, uint32_t *room);
+    // the same call for a caller that places entries itself (MultiEngine: the BinBundles of one bundle index lie on several contexts):
+    // counts [n_bundles][n] and present [n_bundles][count] (host) of these BinBundles, in the given order.  count == 0: counts alone.
+    // n_bundles == 0: only the context's own refusals (what apply_entries and compact check before any GPU work).
+    void lookup_counts(const char *what, const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count,
+                       uint32_t *counts, unsigned char *present);
+    // a BinBundle of ANOTHER context with the same parameters (on src_device) as a BinBundle of this one: its three arrays go device to
+    // device on this context's stream (hipMemcpyPeerAsync), no host image.  `src` is only read; the copy is complete on return.
+    std::unique_ptr<Bundle> clone_bundle(const Bundle &src, int src_device);
     // device time of the last bin_counts / lookup_bundles / apply_entries call, summed over its BinBundles: decode_bundle, the kernels behind it
     void lookup_times(double *decode_ms, double *kernels_ms);
     struct ApplyResult {

@@ -468,6 +468,62 @@ static void check_one_index_in_cache_order(uint32_t bundle_idx, const Bundle *co
     }
 }
 
+PlaceResult place_from_lookup(uint32_t n_bundles, size_t n, uint32_t bins, uint32_t F, uint32_t max_items, u64 t, const uint32_t *counts,
+                              const unsigned char *present, const u64 *ins_felts, const uint32_t *ins_start, size_t n_ins, const u64 *rem_felts,
+                              const uint32_t *rem_start, size_t n_rem)
+{
+    const size_t count = n_rem + n_ins;
+    std::vector<uint32_t> bin_counts((size_t)n_bundles * bins);
+    std::vector<unsigned char> ins_present((size_t)n_bundles * n_ins), rem_present((size_t)n_bundles * n_rem);
+    for (uint32_t b = 0; b < n_bundles; b++) {
+        std::copy(counts + (size_t)b * n, counts + (size_t)b * n + bins, bin_counts.begin() + (size_t)b * bins);
+        std::copy(present + (size_t)b * count, present + (size_t)b * count + n_rem, rem_present.begin() + (size_t)b * n_rem);
+        std::copy(present + (size_t)b * count + n_rem, present + (size_t)(b + 1) * count, ins_present.begin() + (size_t)b * n_ins);
+    }
+    PlaceInput in;
+    in.n_bundles = n_bundles; in.bins = bins; in.F = F; in.max_items = max_items; in.t = t;
+    in.counts = bin_counts.data(); in.ins_present = ins_present.data(); in.rem_present = rem_present.data();
+    in.ins_felts = ins_felts; in.ins_start = ins_start; in.n_ins = n_ins;
+    in.rem_felts = rem_felts; in.rem_start = rem_start; in.n_rem = n_rem;
+    return place_entries(in);
+}
+
+void Engine::lookup_counts(const char *what, const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count,
+                           uint32_t *counts, unsigned char *present)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check(what);
+    if (!n_bundles) return;
+    const size_t n = hp_.n;
+    const uint32_t F = psu_.item_params.felts_per_item;
+    std::vector<unsigned char> flags((size_t)n_bundles * count * F);
+    lookup_impl(bundles, n_bundles, felts, start, count, counts, count ? flags.data() : nullptr);
+    if (count) lookup_reduce(flags.data(), counts, n_bundles, n, start, count, F, present, nullptr);
+}
+
+std::unique_ptr<Bundle> Engine::clone_bundle(const Bundle &src, int src_device)
+{
+    Enter g(this);
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (src.packed != packed_rows_) throw std::logic_error("the BinBundle's rows are in the other format (APSU_HE_PACKED_ROWS differs between the contexts)");
+    auto b = new_bundle(src.bundle_idx, src.cache_idx, src.degree);
+    if (b->ntt_count != src.ntt_count || b->pt_level != src.pt_level || b->use_ps != src.use_ps || b->H != src.H)
+        throw std::invalid_argument("BinBundle was made for different parameters");
+    b->packed = src.packed; b->ntt_slot_bytes = src.ntt_slot_bytes; b->lifted_slot_bytes = src.lifted_slot_bytes;
+    const DevBuf *from[3] = { &src.ntt, &src.lifted, &src.a0 };
+    DevBuf *to[3] = { &b->ntt, &b->lifted, &b->a0 };
+    for (int i = 0; i < 3; i++) {
+        if (!from[i]->bytes()) continue;
+        to[i]->alloc(from[i]->bytes());
+        // (a handle may list one device twice: two contexts, one device, an ordinary copy)
+        if (src_device == device_) HIP_CHECK(hipMemcpyAsync(to[i]->p(), from[i]->p(), from[i]->bytes(), hipMemcpyDeviceToDevice, st_));
+        else HIP_CHECK(hipMemcpyPeerAsync(to[i]->p(), device_, from[i]->p(), src_device, from[i]->bytes(), st_));
+    }
+    sync();
+    return b;
+}
+
 Engine::ApplyResult Engine::apply_entries(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles, const u64 *ins_felts,
                                           const uint32_t *ins_start, size_t n_ins, const u64 *rem_felts, const uint32_t *rem_start, size_t n_rem)
 {
@@ -499,19 +555,8 @@ Engine::ApplyResult Engine::apply_entries(uint32_t bundle_idx, const Bundle *con
             lookup_impl(bundles, n_bundles, felts.data(), start.data(), count, counts.data(), count ? flags.data() : nullptr);
             lookup_reduce(flags.data(), counts.data(), n_bundles, n, start.data(), count, F, present.data(), nullptr);
         }
-        std::vector<uint32_t> bin_counts((size_t)n_bundles * bins);
-        std::vector<unsigned char> ins_present((size_t)n_bundles * n_ins), rem_present((size_t)n_bundles * n_rem);
-        for (uint32_t b = 0; b < n_bundles; b++) {
-            std::copy(counts.begin() + (size_t)b * n, counts.begin() + (size_t)b * n + bins, bin_counts.begin() + (size_t)b * bins);
-            std::copy(present.begin() + (size_t)b * count, present.begin() + (size_t)b * count + n_rem, rem_present.begin() + (size_t)b * n_rem);
-            std::copy(present.begin() + (size_t)b * count + n_rem, present.begin() + (size_t)(b + 1) * count, ins_present.begin() + (size_t)b * n_ins);
-        }
-        PlaceInput in;
-        in.n_bundles = n_bundles; in.bins = bins; in.F = F; in.max_items = psu_.table_params.max_items_per_bin; in.t = hp_.t;
-        in.counts = bin_counts.data(); in.ins_present = ins_present.data(); in.rem_present = rem_present.data();
-        in.ins_felts = ins_felts; in.ins_start = ins_start; in.n_ins = n_ins;
-        in.rem_felts = rem_felts; in.rem_start = rem_start; in.n_rem = n_rem;
-        res.place = place_entries(in);
+        res.place = place_from_lookup(n_bundles, n, bins, F, psu_.table_params.max_items_per_bin, hp_.t, counts.data(), present.data(), ins_felts,
+                                      ins_start, n_ins, rem_felts, rem_start, n_rem);
     }
     // the context's lock is taken per step from here on, as by a caller who made these calls one by one; the given BinBundles are only read
     const PlaceResult &pl = res.place;

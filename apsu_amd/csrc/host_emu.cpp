@@ -16,6 +16,7 @@
 #include "bin_merge.h"
 #include "db_compact.h"
 #include "db_place.h"
+#include "multi_place.h"
 #include "query_side.h"
 #include "params.h"
 #include "powers_dag.h"
@@ -703,6 +704,76 @@ int emu_plan_compaction(const uint32_t *counts, uint32_t n_bundles, uint64_t n, 
         std::copy(plan.group.begin(), plan.group.end(), group);
         std::copy(plan.degree.begin(), plan.degree.end(), degree);
         return (int)plan.degree.size();
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// ---- the multi-device handle's rules (multi_place.h)
+// place_new_unit: the slot, or -1 (emu_last_error)
+int emu_place_new_unit(uint32_t bundle_idx, uint32_t bundle_idx_count, int world, const uint64_t *load)
+{
+    try { return place_new_unit(bundle_idx, bundle_idx_count, world, load); } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+static std::vector<RegUnit> emu_units(const int32_t *slot, const uint32_t *bundle_idx, const uint32_t *cache_idx, const uint32_t *degree, uint32_t count)
+{
+    std::vector<RegUnit> v(count);
+    for (uint32_t i = 0; i < count; i++) { v[i].slot = slot[i]; v[i].bundle_idx = bundle_idx[i]; v[i].cache_idx = cache_idx[i]; v[i].degree = degree[i]; }
+    return v;
+}
+
+// device_loads: load[world]; 0, or -1
+int emu_device_loads(const int32_t *slot, const uint32_t *degree, uint32_t count, int world, uint64_t *load)
+{
+    try {
+        std::vector<uint32_t> zero(count, 0);
+        const std::vector<uint64_t> l = device_loads(emu_units(slot, zero.data(), zero.data(), degree, count), world);
+        std::copy(l.begin(), l.end(), load);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// index_in_cache_order: ids[count] (the first `return value` are written), or -1: two BinBundles of the index share a cache_idx
+int emu_index_in_cache_order(const uint32_t *bundle_idx, const uint32_t *cache_idx, uint32_t count, uint32_t which, int32_t *ids)
+{
+    try {
+        std::vector<int32_t> slot(count, 0);
+        std::vector<uint32_t> zero(count, 0);
+        const std::vector<int> v = index_in_cache_order(emu_units(slot.data(), bundle_idx, cache_idx, zero.data(), count), which);
+        std::copy(v.begin(), v.end(), ids);
+        return (int)v.size();
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// merge_home of the members given by slot and cache_idx: the slot; *first = the position of the first member in cache order.  -1: no members
+int emu_merge_home(const int32_t *slot, const uint32_t *cache_idx, uint32_t count, uint32_t *first)
+{
+    try {
+        std::vector<uint32_t> zero(count, 0);
+        const std::vector<RegUnit> m = emu_units(slot, zero.data(), cache_idx, zero.data(), count);
+        if (first) *first = (uint32_t)merge_first(m);
+        return merge_home(m);
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// registry_after.  The old registry and the appended BinBundles as four arrays each; dropped[old_count]; replaced_degree[old_count]
+// (< 0: unchanged).  Outputs: new_id[old_count + n_appended] and the new registry's four arrays (capacity old_count + n_appended).
+// Returns the new count, or -1 (emu_last_error).
+int emu_registry_after(const int32_t *slot, const uint32_t *bundle_idx, const uint32_t *cache_idx, const uint32_t *degree, uint32_t old_count,
+                       const unsigned char *dropped, const int64_t *replaced_degree, const int32_t *app_slot, const uint32_t *app_bundle_idx,
+                       const uint32_t *app_cache_idx, const uint32_t *app_degree, uint32_t n_appended, int32_t *new_id, int32_t *out_slot,
+                       uint32_t *out_bundle_idx, uint32_t *out_cache_idx, uint32_t *out_degree)
+{
+    try {
+        const RegistryAfter r = registry_after(emu_units(slot, bundle_idx, cache_idx, degree, old_count),
+                                               std::vector<unsigned char>(dropped, dropped + old_count),
+                                               std::vector<int64_t>(replaced_degree, replaced_degree + old_count),
+                                               emu_units(app_slot, app_bundle_idx, app_cache_idx, app_degree, n_appended));
+        std::copy(r.new_id.begin(), r.new_id.end(), new_id);
+        for (size_t i = 0; i < r.registry.size(); i++) {
+            out_slot[i] = r.registry[i].slot; out_bundle_idx[i] = r.registry[i].bundle_idx;
+            out_cache_idx[i] = r.registry[i].cache_idx; out_degree[i] = r.registry[i].degree;
+        }
+        return (int)r.registry.size();
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 

@@ -42,6 +42,7 @@ MultiEngine::MultiEngine(const HeParams &hp, const PSUParams &psu, const std::ve
     for (int dev : devices) {
         auto d = std::make_unique<Dev>();
         d->device = dev;
+        d->slot = (int)devs_.size();
         d->eng = std::make_unique<Engine>(hp_, &psu_, dev);       // validates the device index
         devs_.push_back(std::move(d));
     }

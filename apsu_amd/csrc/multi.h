@@ -13,6 +13,7 @@
 
 #include "db_file.h"
 #include "engine.h"
+#include "multi_place.h"
 #include "sharding.h"
 
 namespace apsu_he {
@@ -32,7 +33,7 @@ public:
     void upload_relin_keys(const u64 *ksk);                      // replicated on every device
     // the same with seeded keys: c1 of entry i (at word c1_at[i] of ksk) is sampled from seeds[i * 8 ..] on every device, in place
     void upload_relin_keys_seeded(const u64 *ksk, const u64 *seeds, const size_t *c1_at, int n_seeded);
-    // DB placement: the bundle's id is its registration order (= its row in eval_all's output)
+    // DB placement: the bundle's id is its registration order (= its row in eval_all's output) until a maintenance call below renumbers
     int upload_bundle(int slot, uint32_t bundle_idx, uint32_t cache_idx, uint32_t n_coeffs, const u64 *const *coeff_ptrs,
                       const unsigned char *is_ntt);
     int random_bundle(int slot, uint32_t bundle_idx, uint32_t cache_idx, uint32_t degree, u64 seed);
@@ -49,6 +50,39 @@ public:
     // that device has finished what was queued on the old one
     void update_bundle(int id, const u64 *ins_roots, const uint32_t *ins_counts, uint32_t ins_stride, const u64 *rem_roots,
                        const uint32_t *rem_counts, uint32_t rem_stride, uint32_t bins);
+
+    // ---- the resident database maintained on the handle (multi_db.cpp).  The rules -- where a new BinBundle goes, every id after a
+    // change, where a merge is made -- are multi_place.h's.  Every call takes the handle's lock, is synchronous and is all-or-nothing:
+    // new BinBundles are built first, every owning engine is waited for (evaluations with device-side results may still read the old
+    // rows), and only then are ids and rows committed; a call that throws leaves ids, count and results as they were.  Work of different
+    // devices is queued on their workers at once.  After a call that drops BinBundles the ids are dense again: new_id[old id] is the
+    // id a BinBundle has from now on, -1 for a dropped one.
+    std::vector<RegUnit> registry();                              // per id: slot, bundle_idx, cache_idx, degree
+    std::vector<int> index_bundles(uint32_t bundle_idx);          // the ids of one bundle index in cache order (index_in_cache_order)
+    void bin_counts(int id, uint32_t *counts);                    // Engine::bin_counts on the owning device
+    // Engine::build_bundle on `slot`, or with slot == -1 on the slot place_new_unit chooses; registered last.  Returns the id.
+    int build_bundle(int slot, uint32_t bundle_idx, uint32_t cache_idx, const u64 *roots, const uint32_t *counts, uint32_t bins, uint32_t stride);
+    void remove_bundle(int id, int *new_id);                      // new_id[bundle_count()] (may be null)
+    // the BinBundle's arrays go device to device (Engine::clone_bundle); the id stays.  A move to its own slot does nothing.
+    void move_bundle(int id, int slot);
+    // Engine::lookup_bundles against index_bundles(bundle_idx), rows in that order; every device looks up its own BinBundles
+    void lookup(uint32_t bundle_idx, const u64 *felts, const uint32_t *start, size_t count, unsigned char *present, uint32_t *room);
+    struct ApplyOutcome {
+        PlaceResult place;                                        // targets: positions among index_bundles(bundle_idx), then the appended ones
+        std::vector<int> ids;                                     // index_bundles(bundle_idx) before the call
+        int old_count = 0;                                        // bundle_count() before the call: the k-th appended BinBundle is old id old_count + k
+        std::vector<int> new_id;                                  // [old_count + place.n_new]
+    };
+    // Engine::apply_entries' contract on index_bundles(bundle_idx): per-device lookup, place_entries on the host, update_bundle per
+    // changed BinBundle on its device, build_bundle per appended one on the slot place_new_unit gives it (loads taken after the updates,
+    // the EMPTY BinBundles still counted; appended ones placed in order), EMPTY BinBundles dropped, ids renumbered
+    ApplyOutcome apply_entries(uint32_t bundle_idx, const u64 *ins_felts, const uint32_t *ins_start, size_t n_ins, const u64 *rem_felts,
+                               const uint32_t *rem_start, size_t n_rem);
+    // Engine::merge_bundles on the given BinBundles of one bundle index, wherever they lie: members that are not on merge_home travel
+    // there as temporaries; the merged BinBundle takes the first member's (cache order) id slot and cache_idx, the others are dropped
+    void merge_bundles(const int *ids, uint32_t n_ids, int *new_id);
+    // counts per BinBundle on its device, plan_compaction on the host, one merge per group of two or more.  Returns the BinBundles made.
+    uint32_t compact(uint32_t bundle_idx, int *new_id);
 
     // One query.  src_cts[b * source_count + s]: ciphertexts of every bundle index (each device reads its own);
     // masks[id]: n words mod t; out: bundle_count * 2n words, row = bundle id — host memory when out_slot < 0, else device
@@ -68,7 +102,7 @@ public:
 
 private:
     struct Dev {
-        int device = 0;
+        int device = 0, slot = 0;
         std::unique_ptr<Engine> eng;
         std::unique_ptr<RelinKeys> rk;
         std::vector<std::unique_ptr<Bundle>> bundles;
@@ -89,6 +123,13 @@ private:
         std::exception_ptr error;
     };
     void run_all(const std::function<void(Dev &)> &fn);
+    // (multi_db.cpp; all of them with mu_ held)
+    std::vector<RegUnit> registry_locked() const;
+    const Bundle &bundle_locked(int id) const { const auto &w = where_.at((size_t)id); return *devs_[w.first]->bundles[w.second]; }
+    void check_id(int id) const;
+    struct Change;                                                // what a call replaces, drops and appends
+    void commit(Change &c, int *new_id, std::vector<int> *new_id_out);
+    std::vector<std::unique_ptr<Bundle>> merge_groups(const std::vector<std::vector<int>> &groups);
     static void worker(Dev *d);
 
     HeParams hp_;

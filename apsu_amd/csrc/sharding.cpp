@@ -1,5 +1,7 @@
 #include "sharding.h"
 
+#include "multi_place.h"
+
 #include <algorithm>
 #include <stdexcept>
 
@@ -9,8 +11,7 @@ std::vector<int> partition_units(const std::vector<ShardUnit> &units, uint32_t b
 {
     if (world <= 0) throw std::invalid_argument("no devices");
     if (!bundle_idx_count) throw std::invalid_argument("bundle_idx_count is zero");
-    constexpr uint64_t UNIT_OVERHEAD = 64;                       // relinearisation, epilogue
-    auto cost = [&](size_t i) { return (uint64_t)units[i].degree + UNIT_OVERHEAD; };
+    auto cost = [&](size_t i) { return unit_cost(units[i].degree); };   // degree + 64 (multi_place.h: place_new_unit counts in the same unit)
     std::vector<std::vector<int>> devs_of(bundle_idx_count);
     if ((uint32_t)world >= bundle_idx_count)
         for (int r = 0; r < world; r++) devs_of[(uint32_t)r % bundle_idx_count].push_back(r);

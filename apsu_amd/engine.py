@@ -142,6 +142,8 @@ ENTRY_INSERTED, ENTRY_DUPLICATE, ENTRY_REMOVED, ENTRY_NOT_FOUND = 0, 1, 2, 3
 BUNDLE_UNCHANGED, BUNDLE_REPLACED, BUNDLE_EMPTY = 0, 1, 2
 ApplyResult = collections.namedtuple("ApplyResult", "state bundles appended ins_status ins_target rem_status rem_target")
 CompactResult = collections.namedtuple("CompactResult", "group merged")
+BundleInfo = collections.namedtuple("BundleInfo", "slot bundle_idx cache_idx degree")
+MultiApplyResult = collections.namedtuple("MultiApplyResult", "new_id n_appended ins_status ins_target rem_status rem_target")
 
 
 class RelinKeys:
@@ -799,6 +801,9 @@ class MultiContext:
         self.h = h
         self.devices = list(devices)
         self.n_bundles = 0
+        js = json.loads(psu_params_json)
+        self.felts_per_item = int(js["item_params"]["felts_per_item"])
+        self.n = int(js["seal_params"]["poly_modulus_degree"])
         rp = C.c_uint32()
         _check(L.apsu_he_multi_result_polys(self.h, C.byref(rp)))
         self.result_polys = rp.value
@@ -841,6 +846,101 @@ class MultiContext:
     def clear_bundles(self):
         _check(load_library().apsu_he_multi_db_clear(self.h))
         self.n_bundles = 0
+
+    # ---- the resident database maintained on the handle (include/apsu_he.h: apsu_he_multi_db_*).  Ids stay dense: a call that drops
+    # BinBundles returns new_id (old id -> id from now on, -1 for a dropped one), and n_bundles follows.
+    def bundle_count(self):
+        k = C.c_int()
+        _check(load_library().apsu_he_multi_db_bundle_count(self.h, C.byref(k)))
+        self.n_bundles = k.value
+        return k.value
+
+    def bundle_info(self, bundle_id):
+        """-> BundleInfo(slot, bundle_idx, cache_idx, degree)"""
+        slot, b, c, d = C.c_int(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(load_library().apsu_he_multi_db_bundle_info(self.h, int(bundle_id), C.byref(slot), C.byref(b), C.byref(c), C.byref(d)))
+        return BundleInfo(slot.value, b.value, c.value, d.value)
+
+    def index_bundles(self, bundle_idx):
+        """-> the ids of one bundle index in cache order (ascending cache_idx)"""
+        cap = max(self.bundle_count(), 1)
+        ids = (C.c_int * cap)()
+        k = C.c_int()
+        _check(load_library().apsu_he_multi_db_index_bundles(self.h, C.c_uint32(bundle_idx), ids, cap, C.byref(k)))
+        return [int(v) for v in ids[:k.value]]
+
+    def bin_counts(self, bundle_id):
+        """HeContext.bin_counts of BinBundle `bundle_id`, on its device"""
+        counts = np.empty(self.n, dtype=np.uint32)
+        _check(load_library().apsu_he_multi_db_bin_counts(self.h, int(bundle_id), C.c_void_p(counts.ctypes.data)))
+        return counts
+
+    def build_bundle(self, bundle_idx, cache_idx, bins, slot=-1):
+        """HeContext.build_bundle on `slot`, or (slot -1) on the slot the placement rule chooses -> the new id (registered last)"""
+        nb = len(bins)
+        stride = max([len(b) for b in bins] + [1])
+        roots = np.zeros((max(nb, 1), stride), dtype=np.uint64)
+        counts = np.zeros(max(nb, 1), dtype=np.uint32)
+        for i, b in enumerate(bins):
+            counts[i] = len(b)
+            roots[i, :len(b)] = b
+        bid = C.c_int()
+        _check(load_library().apsu_he_multi_db_build_bundle(self.h, int(slot), C.c_uint32(bundle_idx), C.c_uint32(cache_idx), _p(roots),
+                                                            C.c_void_p(counts.ctypes.data), nb, stride, C.byref(bid)))
+        self.n_bundles = bid.value + 1
+        return bid.value
+
+    def _renumbered(self, call, extra=0):
+        """runs call(new_id pointer) with room for the ids before the call (+ extra) -> new_id as a list; n_bundles follows"""
+        before = self.bundle_count()
+        new_id = np.full(before + extra, -2, dtype=np.int32)
+        keep = call(C.c_void_p(new_id.ctypes.data) if len(new_id) else None)
+        self.bundle_count()
+        return [int(v) for v in new_id], keep
+
+    def remove_bundle(self, bundle_id):
+        """drops one BinBundle -> new_id"""
+        return self._renumbered(lambda p: _check(load_library().apsu_he_multi_db_remove_bundle(self.h, int(bundle_id), p)))[0]
+
+    def move_bundle(self, bundle_id, slot):
+        """the BinBundle's arrays go to `slot`, device to device; it keeps its id"""
+        _check(load_library().apsu_he_multi_db_move_bundle(self.h, int(bundle_id), int(slot)))
+
+    def lookup(self, bundle_idx, entries):
+        """HeContext.lookup against the BinBundles of index_bundles(bundle_idx), rows in that order -> (present, room)"""
+        felts, start = _entries(entries, self.felts_per_item)
+        rows = len(self.index_bundles(bundle_idx))
+        present = np.zeros((rows, len(start)), dtype=np.uint8)
+        room = np.zeros((rows, len(start)), dtype=np.uint32)
+        _check(load_library().apsu_he_multi_db_lookup(self.h, C.c_uint32(bundle_idx), _p(felts), C.c_void_p(start.ctypes.data), C.c_size_t(len(start)),
+                                                      C.c_void_p(present.ctypes.data), C.c_void_p(room.ctypes.data)))
+        return present.astype(bool), room
+
+    def apply_entries(self, bundle_idx, inserts=None, removes=None):
+        """HeContext.apply_entries on index_bundles(bundle_idx) -> MultiApplyResult: new_id [ids before the call + n_appended], and per
+        entry status (ENTRY_*) and target = an OLD id (the k-th appended BinBundle: ids before the call + k)"""
+        fi, si = _entries(inserts, self.felts_per_item)
+        fr, sr = _entries(removes, self.felts_per_item)
+        n_app = C.c_uint32()
+        out = [np.zeros(len(si), dtype=np.uint32), np.zeros(len(si), dtype=np.uint32), np.zeros(len(sr), dtype=np.uint32), np.zeros(len(sr), dtype=np.uint32)]
+        u32 = lambda a: C.c_void_p(a.ctypes.data)
+        L = load_library()
+        new_id, _ = self._renumbered(lambda p: _check(L.apsu_he_multi_db_apply_entries(
+            self.h, C.c_uint32(bundle_idx), _p(fi), u32(si), C.c_size_t(len(si)), _p(fr), u32(sr), C.c_size_t(len(sr)), p, C.byref(n_app),
+            *[u32(a) for a in out])), extra=len(si))
+        return MultiApplyResult(new_id[:len(new_id) - len(si) + n_app.value], n_app.value, *out)
+
+    def merge_bundles(self, bundle_ids):
+        """HeContext.merge_bundles on BinBundles of one bundle index, wherever they lie -> new_id (the merged BinBundle takes the place
+        of the first member in cache order)"""
+        ids = (C.c_int * max(len(bundle_ids), 1))(*[int(i) for i in bundle_ids])
+        return self._renumbered(lambda p: _check(load_library().apsu_he_multi_db_merge_bundles(self.h, ids, len(bundle_ids), p)))[0]
+
+    def compact(self, bundle_idx):
+        """HeContext.compact on index_bundles(bundle_idx) -> (new_id, merged BinBundles made)"""
+        made = C.c_uint32()
+        new_id, _ = self._renumbered(lambda p: _check(load_library().apsu_he_multi_db_compact(self.h, C.c_uint32(bundle_idx), p, C.byref(made))))
+        return new_id, made.value
 
     def load_db_file(self, path):
         """every BinBundle of the file onto the handle's devices (partition rule, each device reads its own shard) -> count"""

@@ -214,7 +214,7 @@ int apsu_he_bundle_update(apsu_he_ctx *ctx, const apsu_he_bundle *old, const uin
  *  - appended[k], k < *n_appended <= n_ins: the new BinBundles, cache_idx continuing above the largest given (from 0 when none is given).
  *  - ins_status / ins_target [n_ins], rem_status / rem_target [n_rem] may each be NULL.  Target of NOT_FOUND: APSU_HE_NOT_A_BIN.
  * Preconditions and locking are the update's (PSUParams, batching, first coefficient prime above 2 * plain_modulus; synchronous; the
- * context's lock is taken per step).  Not available on the multi-device handle: appending a BinBundle changes the partition. */
+ * context's lock is taken per step).  The multi-device handle has its own form, apsu_he_multi_db_apply_entries. */
 #define APSU_HE_NOT_A_BIN 0xFFFFFFFFu
 enum { APSU_HE_ENTRY_INSERTED = 0, APSU_HE_ENTRY_DUPLICATE = 1, APSU_HE_ENTRY_REMOVED = 2, APSU_HE_ENTRY_NOT_FOUND = 3 };
 enum { APSU_HE_BUNDLE_UNCHANGED = 0, APSU_HE_BUNDLE_REPLACED = 1, APSU_HE_BUNDLE_EMPTY = 2 };
@@ -259,8 +259,8 @@ int apsu_he_debug_lookup_times(apsu_he_ctx *ctx, double *decode_ms, double *kern
  *    the number of handles produced.  The caller replaces the members of a merged group by merged[g] and frees them when no queued
  *    evaluation reads them any more.  A second call on the result merges nothing.
  * Preconditions and locking are the update's (PSUParams, batching, first coefficient prime above 2 * plain_modulus; synchronous;
- * apsu_he_db_compact takes the context's lock per step).  Single-device contexts only: merging changes the partition of a
- * multi-device handle, as appending does. */
+ * apsu_he_db_compact takes the context's lock per step).  The multi-device handle has its own forms, apsu_he_multi_db_merge_bundles
+ * and apsu_he_multi_db_compact. */
 int apsu_he_bundles_merge(apsu_he_ctx *ctx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, uint32_t cache_idx,
                           apsu_he_bundle **out);
 int apsu_he_db_compact(apsu_he_ctx *ctx, uint32_t bundle_idx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, uint32_t *group,
@@ -441,6 +441,57 @@ int apsu_he_multi_db_clear(apsu_he_multi *m);
 int apsu_he_multi_db_update_bundle(apsu_he_multi *m, int bundle_id, const uint64_t *ins_roots, const uint32_t *ins_counts,
                                    uint32_t ins_stride, const uint64_t *rem_roots, const uint32_t *rem_counts, uint32_t rem_stride,
                                    uint32_t bins);
+/* ---- the resident database maintained on the handle: file -> load -> insert / remove items -> compact -> query, for a database
+ * that lies on several devices.  The kernels and the host steps are the single context's (apsu_he_bundle_bin_counts, apsu_he_bundles_lookup,
+ * apsu_he_db_apply_entries, apsu_he_bundles_merge, apsu_he_db_compact: their contracts hold here); every BinBundle is worked on by the
+ * device that owns it, devices work side by side.  Added without an ABI step (additive; the ABI stays 7).  What a handle adds:
+ *  - IDS STAY DENSE.  A BinBundle's id is its row in apsu_he_eval_all's masks and output.  A handle that never calls the functions
+ *    below numbers by registration order, as before.  A call that drops BinBundles renumbers: survivors keep their relative order and
+ *    take 0, 1, ..; BinBundles appended by the call follow in order of appending; a merged BinBundle takes the place of its group's
+ *    first member in cache order.  new_id[old id] is the id from now on, -1 for a dropped BinBundle; the caller moves its masks and
+ *    reads its result rows accordingly.  new_id may be NULL.
+ *  - PLACEMENT.  A new BinBundle goes to the least loaded device (load = sum of degree + 64, the partition rule's unit) among those
+ *    the partition rule's first pass gives its bundle index: the slots r with r % bundle_idx_count == bundle_idx when the handle has at
+ *    least as many devices as bundle indices, else the slot bundle_idx % devices; ties go to the lowest slot.  The spill pass is not
+ *    re-run; apsu_he_multi_db_move_bundle rebalances by hand.  A merged BinBundle is made on the device of its group's first member in
+ *    cache order; members on other devices travel there device to device (no host image).
+ *  - ALL OR NOTHING.  New BinBundles are built first; ids and rows change only when every step on every device has succeeded, and
+ *    after the owning engines have finished what was queued on the old rows.  After a refusal the handle answers exactly as before.
+ *  - Every call takes the handle's lock (ordered against apsu_he_eval_all and each other) and is synchronous.
+ *  - CACHE ORDER of a bundle index: ascending cache_idx.  Two BinBundles of one bundle index with the same cache_idx make
+ *    apsu_he_multi_db_index_bundles, _lookup, _apply_entries and _compact refuse with APSU_HE_INVALID_ARGUMENT.
+ * apsu_he_multi_db_bundle_info: where BinBundle `bundle_id` lies and what it is (every output may be NULL).
+ * apsu_he_multi_db_index_bundles: the ids of one bundle index in cache order; *n = how many there are, the first min(*n, capacity) are written.
+ * apsu_he_multi_db_bin_counts: apsu_he_bundle_bin_counts on the owning device.
+ * apsu_he_multi_db_build_bundle: apsu_he_db_build_bundle on device_slot, or with device_slot = -1 on the slot the placement rule
+ *   chooses; the new BinBundle is registered last (*bundle_id = the count before the call).
+ * apsu_he_multi_db_remove_bundle: drops one BinBundle; new_id[count before the call].
+ * apsu_he_multi_db_move_bundle: the BinBundle's arrays go to device_slot, device to device; it keeps its id, and its image
+ *   (apsu_he_bundle_save) is the same bytes.  A move to the slot it is on does nothing.
+ * apsu_he_multi_db_lookup: apsu_he_bundles_lookup against the BinBundles of apsu_he_multi_db_index_bundles(bundle_idx), rows in that order.
+ * apsu_he_multi_db_apply_entries: apsu_he_db_apply_entries on the BinBundles of apsu_he_multi_db_index_bundles(bundle_idx).  Targets
+ *   are OLD ids: the id a BinBundle had before the call, and (count before the call) + k for the k-th appended BinBundle; new_id
+ *   [count before the call + *n_appended, at most + n_ins] translates them.  EMPTY BinBundles are dropped by the call itself.  Appended
+ *   BinBundles are placed one after the other, against the loads as the call's updates left them (an EMPTY BinBundle still counts).
+ * apsu_he_multi_db_merge_bundles: apsu_he_bundles_merge on n_ids >= 2 BinBundles of one bundle index, wherever they lie.  The merged
+ *   BinBundle takes the id slot and the cache_idx of the first member in cache order; the others are dropped.  new_id[count before the call].
+ * apsu_he_multi_db_compact: apsu_he_db_compact's rule on apsu_he_multi_db_index_bundles(bundle_idx), one merge per group of two or more;
+ *   *n_merged (may be NULL) = merged BinBundles made.  new_id[count before the call].  A second call merges nothing. */
+int apsu_he_multi_db_bundle_count(apsu_he_multi *m, int *count);
+int apsu_he_multi_db_bundle_info(apsu_he_multi *m, int bundle_id, int *device_slot, uint32_t *bundle_idx, uint32_t *cache_idx, uint32_t *degree);
+int apsu_he_multi_db_index_bundles(apsu_he_multi *m, uint32_t bundle_idx, int *ids, int capacity, int *n);
+int apsu_he_multi_db_bin_counts(apsu_he_multi *m, int bundle_id, uint32_t *counts);
+int apsu_he_multi_db_build_bundle(apsu_he_multi *m, int device_slot, uint32_t bundle_idx, uint32_t cache_idx, const uint64_t *roots,
+                                  const uint32_t *counts, uint32_t bins, uint32_t stride, int *bundle_id);
+int apsu_he_multi_db_remove_bundle(apsu_he_multi *m, int bundle_id, int *new_id);
+int apsu_he_multi_db_move_bundle(apsu_he_multi *m, int bundle_id, int device_slot);
+int apsu_he_multi_db_lookup(apsu_he_multi *m, uint32_t bundle_idx, const uint64_t *felts, const uint32_t *start_bins, size_t count,
+                            uint8_t *present, uint32_t *room);
+int apsu_he_multi_db_apply_entries(apsu_he_multi *m, uint32_t bundle_idx, const uint64_t *ins_felts, const uint32_t *ins_start, size_t n_ins,
+                                   const uint64_t *rem_felts, const uint32_t *rem_start, size_t n_rem, int *new_id, uint32_t *n_appended,
+                                   uint32_t *ins_status, uint32_t *ins_target, uint32_t *rem_status, uint32_t *rem_target);
+int apsu_he_multi_db_merge_bundles(apsu_he_multi *m, const int *bundle_ids, uint32_t n_ids, int *new_id);
+int apsu_he_multi_db_compact(apsu_he_multi *m, uint32_t bundle_idx, int *new_id, uint32_t *n_merged);
 /* One query on all devices (receiver_osn.cpp:304-364): src_cts[b * source_power_count + s] = host ciphertext of source
  * power s (ascending) of bundle index b, for EVERY bundle index (each device uploads the ones it needs); masks[id] = n
  * words mod t (host).  out_cts: bundle count * 2n words, row = bundle id; host memory when out_device_slot < 0, else

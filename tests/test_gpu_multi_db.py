@@ -1,0 +1,595 @@
+"""GPU tier: a resident database maintained on the multi-device handle (apsu_he_multi_db_*: bundle_info, index_bundles, bin_counts,
+build_bundle, remove_bundle, move_bundle, lookup, apply_entries, merge_bundles, compact).  The ground truth is the single-context
+implementation: a HeContext and the handle start from the same BinBundles and take the same call; statuses, targets (positions mapped
+to ids), groups and every BinBundle image -- the handle's through save_db_file -> load_db_file -> save_bundle, paired by (bundle_idx,
+cache_idx) -- must be equal, and ids and slots must be what the CPU tier's rules (tests/test_multi_place_cpu.py) say.  All comparisons
+are exact.  Device lists: one device, the same device twice and three times (with two bundle indices the third list puts index 0 on
+slots 0 and 2: the cross-device case on one GPU), and two distinct GPUs where the machine has them."""
+import itertools
+
+import numpy as np
+import pytest
+
+import apsu_amd
+import common
+import test_gpu_bundle_lookup as L
+import test_gpu_bundle_merge as MG
+import test_gpu_bundle_update as U
+import test_multi_place_cpu as P
+from oracle import ref
+
+pytestmark = pytest.mark.gpu
+
+NONE = 0xFFFFFFFF
+F = 5
+NIDX = 2                                                  # bundle indices of toy_json
+_file_no = itertools.count()
+
+
+def device_sets():
+    import torch
+    sets = [[0], [0, 0], [0, 0, 0]]
+    if torch.cuda.device_count() >= 2:
+        sets += [[0, 1]]
+    return sets
+
+
+DEVS = pytest.mark.parametrize("devs", device_sets(), ids=lambda d: "devs" + "".join(str(x) for x in d))
+
+
+class Twin:
+    """a HeContext and a MultiContext that hold the same BinBundles; `single` maps (bundle_idx, cache_idx) to the HeContext's Bundle"""
+
+    def __init__(self, js, devs, tmp_path):
+        self.G = apsu_amd.HeContext(js)
+        self.M = apsu_amd.MultiContext(js, devs)
+        self.world = len(devs)
+        self.nidx = self.G.bundle_idx_count
+        self.single = {}
+        self.tmp = tmp_path
+
+    def close(self):
+        self.M.close()
+        self.G.close()
+
+    def build(self, bundle_idx, cache_idx, bins, slot=-1):
+        self.single[(bundle_idx, cache_idx)] = self.G.build_bundle(bundle_idx, cache_idx, bins)
+        return self.M.build_bundle(bundle_idx, cache_idx, bins, slot=slot)
+
+    def index(self, bundle_idx):
+        return [self.single[k] for k in sorted(self.single) if k[0] == bundle_idx]
+
+    def registry(self):
+        return [tuple(self.M.bundle_info(i)) for i in range(self.M.bundle_count())]
+
+    def slots_of(self, bundle_idx):
+        return P.candidates(bundle_idx, self.nidx, self.world)
+
+    def handle_images(self):
+        """[((bundle_idx, cache_idx), image bytes)] in id order"""
+        path = str(self.tmp / ("db%d.bin" % next(_file_no)))
+        self.M.save_db_file(path)
+        return [((b.bundle_idx, b.cache_idx), self.G.save_bundle(b).tobytes()) for b in self.G.load_db_file(path)]
+
+    def check_images(self):
+        imgs = self.handle_images()
+        assert [k for k, _ in imgs] == [(u[1], u[2]) for u in self.registry()]           # the file is in id order
+        assert len(set(k for k, _ in imgs)) == len(imgs)
+        want = {k: self.G.save_bundle(b).tobytes() for k, b in self.single.items()}
+        assert sorted(want) == sorted(k for k, _ in imgs)
+        for k, img in imgs:
+            assert img == want[k], k
+        return imgs
+
+    def snapshot(self):
+        return self.M.bundle_count(), self.registry(), self.handle_images()
+
+    def loads(self, reg):
+        load = [0] * self.world
+        for slot, _, _, degree in reg:
+            load[slot] += degree + 64
+        return load
+
+    def apply(self, bundle_idx, inserts, removes):
+        """the same call on both sides; every output of the handle is held against the single context's and the CPU tier's rules"""
+        G, M = self.G, self.M
+        old = self.index(bundle_idx)
+        res = G.apply_entries(old, inserts=inserts, removes=removes, bundle_idx=bundle_idx)
+        reg, ids = self.registry(), M.index_bundles(bundle_idx)
+        assert [(reg[i][1], reg[i][2]) for i in ids] == [(b.bundle_idx, b.cache_idx) for b in old]
+        r = M.apply_entries(bundle_idx, inserts=inserts, removes=removes)
+        nb, old_count = len(ids), len(reg)
+        as_id = lambda p: NONE if p == NONE else ids[p] if p < nb else old_count + (p - nb)
+        assert [int(v) for v in r.ins_status] == [int(v) for v in res.ins_status]
+        assert [int(v) for v in r.rem_status] == [int(v) for v in res.rem_status]
+        assert [int(v) for v in r.ins_target] == [as_id(int(p)) for p in res.ins_target]
+        assert [int(v) for v in r.rem_target] == [as_id(int(p)) for p in res.rem_target]
+        assert r.n_appended == len(res.appended)
+        # ids and slots by the CPU tier's rules
+        dropped, replaced = [0] * old_count, [-1] * old_count
+        for p, i in enumerate(ids):
+            if int(res.state[p]) == apsu_amd.engine.BUNDLE_EMPTY:
+                dropped[i] = 1
+                del self.single[(bundle_idx, old[p].cache_idx)]
+            elif int(res.state[p]) == apsu_amd.engine.BUNDLE_REPLACED:
+                replaced[i] = res.bundles[p].degree
+                self.single[(bundle_idx, old[p].cache_idx)] = res.bundles[p]
+        load = self.loads([u if replaced[i] < 0 else (u[0], u[1], u[2], replaced[i]) for i, u in enumerate(reg)])   # EMPTY ones still count
+        appended = []
+        for b in res.appended:
+            slot = P.model_place_new_unit(bundle_idx, self.nidx, self.world, load)
+            load[slot] += b.degree + 64
+            appended.append((slot, bundle_idx, b.cache_idx, b.degree))
+            self.single[(bundle_idx, b.cache_idx)] = b
+        self.check_renumbering(reg, dropped, replaced, appended, r.new_id)
+        return res, r
+
+    def check_renumbering(self, reg, dropped, replaced, appended, new_id):
+        want_new_id, want_reg = P.emu_registry_after(P.load_emu(), reg, dropped, replaced, appended)
+        assert (want_new_id, want_reg) == P.model_registry_after(reg, dropped, replaced, appended)
+        assert new_id == want_new_id
+        assert self.registry() == want_reg and self.M.n_bundles == len(want_reg)
+
+    def compact(self, bundle_idx):
+        G, M = self.G, self.M
+        old = self.index(bundle_idx)
+        res = G.compact(bundle_idx, old)
+        reg, ids = self.registry(), M.index_bundles(bundle_idx)
+        new_id, made = M.compact(bundle_idx)
+        group = [int(g) for g in res.group]
+        assert made == sum(m is not None for m in res.merged)
+        dropped, replaced = [0] * len(reg), [-1] * len(reg)
+        for g, m in enumerate(res.merged):
+            if m is None:
+                continue
+            members = [p for p in range(len(old)) if group[p] == g]
+            home, first = P.emu_merge_home(P.load_emu(), [reg[ids[p]] for p in members])
+            assert first == 0 and m.cache_idx == old[members[0]].cache_idx
+            replaced[ids[members[0]]] = m.degree
+            self.single[(bundle_idx, m.cache_idx)] = m
+            for p in members[1:]:
+                dropped[ids[p]] = 1
+                del self.single[(bundle_idx, old[p].cache_idx)]
+            assert home == reg[ids[members[0]]][0]
+        self.check_renumbering(reg, dropped, replaced, [], new_id)          # (the merged BinBundle is on merge_home: its slot is the first member's)
+        return group, new_id, made
+
+
+def bins_of_degree(rng, t, degree, n_bins=60):
+    bins = [U.distinct(rng, t, int(rng.integers(0, degree + 1))) for _ in range(n_bins)]
+    bins[12] = U.distinct(rng, t, degree)
+    return bins
+
+
+# ---- build_bundle with slot -1 ------------------------------------------------------------------------------------------
+@DEVS
+def test_build_bundle_is_placed_by_the_rule(devs, tmp_path):
+    js = common.toy_json()
+    rng = np.random.default_rng(151)
+    t = U.toy_t()
+    T = Twin(js, devs, tmp_path)
+    load = [0] * T.world
+    plan = [(0, 0, 10), (1, 0, 7), (0, 1, 3), (0, 2, 10), (1, 1, 2), (0, 3, 5), (0, 4, 0), (1, 2, 11)]
+    for k, (bidx, cidx, degree) in enumerate(plan):
+        assert T.build(bidx, cidx, bins_of_degree(rng, t, degree)) == k                 # registered last
+        slot = P.model_place_new_unit(bidx, NIDX, T.world, load)
+        assert slot == P.emu_place(P.load_emu(), bidx, NIDX, T.world, load)
+        load[slot] += degree + 64
+        assert tuple(T.M.bundle_info(k)) == (slot, bidx, cidx, degree)
+    assert T.M.bundle_count() == len(plan) == T.M.n_bundles
+    if T.world == 3:
+        assert [u[0] for u in T.registry()] == [0, 1, 2, 2, 1, 0, 2, 1]                   # index 0 over slots 0 and 2 by load, index 1 on slot 1
+    T.check_images()
+    # a slot of the caller's choice, and the refusals
+    last = T.world - 1
+    assert T.build(1, 9, bins_of_degree(rng, t, 4), slot=last) == len(plan) and T.M.bundle_info(len(plan)).slot == last
+    for bad in (T.world, -2, 99):
+        with pytest.raises(ValueError, match="slot"):
+            T.M.build_bundle(0, 20, [[1]], slot=bad)
+    with pytest.raises(ValueError, match="bundle_idx"):
+        T.M.build_bundle(NIDX, 0, [[1]])
+    with pytest.raises(ValueError):
+        T.M.bundle_info(len(plan) + 1)
+    assert T.M.bundle_count() == len(plan) + 1
+    T.check_images()
+    T.close()
+
+
+# ---- bin_counts and lookup ----------------------------------------------------------------------------------------------
+@DEVS
+def test_bin_counts_and_lookup_equal_the_single_context(devs, tmp_path):
+    js = common.toy_json()
+    rng = np.random.default_rng(152)
+    t = U.toy_t()
+    T = Twin(js, devs, tmp_path)
+    G, M = T.G, T.M
+    items, bins = L.toy_db(rng, t)                                                       # ragged, start bin 15 empty, root 0 in bin 7
+    items40, bins40 = L.make_db(rng, t, 40, lambda s: 3, range(0, 40, F))                # slots 40 .. 63 are not bins here
+    items2, bins2 = L.make_db(rng, t, 60, lambda s: int(rng.integers(1, 5)), range(0, 60, F))
+    slots = T.slots_of(0)
+    # registered out of cache order, on different slots where the index has two
+    order = [(0, 5, bins2, slots[0]), (1, 0, bins40, -1), (0, 1, bins, slots[-1]), (0, 3, bins40, slots[0])]
+    ids = [T.build(*o[:3], slot=o[3]) for o in order]
+    assert M.index_bundles(0) == [ids[2], ids[3], ids[0]] and M.index_bundles(1) == [ids[1]]
+    if T.world == 3:
+        assert [M.bundle_info(i).slot for i in M.index_bundles(0)] == [2, 0, 0]
+    for key, gb in T.single.items():
+        i = next(i for i, u in enumerate(T.registry()) if (u[1], u[2]) == key)
+        assert (M.bin_counts(i) == G.bin_counts(gb)).all()
+    assert [int(v) for v in M.bin_counts(ids[2])] == [len(b) for b in bins] + [NONE] * 4
+    assert [int(v) for v in M.bin_counts(ids[3])] == [3] * 40 + [NONE] * 24
+    entries = L.three_kinds(rng, t, items, bins, 8) + items40[:3] + items2[:4]
+    entries += [(15, [0] * F), (15, [1] * F), (38, [0] * F), (40, [1] * F), (55, items2[-1][1]), (36, items40[-1][1])]
+    entries += [(0, f) for _, f in [items[0] if k % 3 == 0 else L.absent_variant(rng, t, items[0], bins) for k in range(200)]]   # skewed
+    want_present, want_room = G.lookup(T.index(0), entries)
+    present, room = M.lookup(0, entries)
+    assert present.shape == (3, len(entries)) and (present == want_present).all() and (room == want_room).all()
+    assert [bool(v) for v in present[0][:24]] == [True] * 8 + [False] * 8 + [True] * 8     # the three kinds, in the ragged BinBundle
+    assert present[1].any() and present[2].any() and (room[1] == NONE).any()
+    present1, room1 = M.lookup(1, entries)
+    w1 = G.lookup(T.index(1), entries)
+    assert (present1 == w1[0]).all() and (room1 == w1[1]).all()
+    for bad, text in (((56, [1] * F), "bins_per_bundle"), ((0, [1, 2, t, 3, 4]), "not reduced")):
+        with pytest.raises(ValueError, match=text):
+            M.lookup(0, [bad])
+    with pytest.raises(ValueError, match="bundle_idx"):
+        M.lookup(NIDX, entries[:1])
+    # two BinBundles of one index with one cache_idx: every call that needs the cache order refuses, the others go on
+    dup = M.build_bundle(0, 3, bins2)
+    for call in (lambda: M.index_bundles(0), lambda: M.lookup(0, entries[:2]), lambda: M.apply_entries(0, inserts=entries[:1]),
+                 lambda: M.compact(0)):
+        with pytest.raises(ValueError, match="share cache_idx 3"):
+            call()
+    assert (M.bin_counts(dup) == G.bin_counts(T.single[(0, 5)])).all() and M.index_bundles(1) == [ids[1]]
+    assert M.remove_bundle(dup) == [0, 1, 2, 3, -1]
+    assert (M.lookup(0, entries)[0] == want_present).all()
+    T.check_images()
+    T.close()
+
+
+# ---- apply_entries ------------------------------------------------------------------------------------------------------
+def apply_scene(rng, t, x=None):
+    """bundle index 0: b0 (cache 0) with start bin 0 full, b1 (cache 2) with start bin 0 one below full, b2 (cache 5) holding one item; and
+    one batch that removes from b0 and b1, empties b2, meets a duplicate, a duplicate of its own and a not-found, fills b1's start bin 0
+    to max_items_per_bin - 1 and then brings 11 more entries for it: two appended BinBundles (10 + 1)"""
+    items0, bins0 = L.make_db(rng, t, 60, lambda s: 10 if s == 0 else 2, range(0, 60, F))
+    items1, bins1 = L.make_db(rng, t, 60, lambda s: 9 if s == 0 else 3, range(0, 60, F))
+    items2, bins2 = L.make_db(rng, t, 60, lambda s: 1 if s == 20 else 0, range(0, 60, F))
+    used = [set(bins0[s]) | set(bins1[s]) | set(bins2[s]) | ({int(x[s])} if x is not None else set()) for s in range(60)]
+    at = lambda items, s: [it for it in items if it[0] == s]
+
+    def new(s):
+        f = [U.distinct(rng, t, 1, avoid=used[s + j])[0] for j in range(F)]
+        for j in range(F):
+            used[s + j].add(f[j])
+        return (s, f)
+    member = [(25, [int(x[25 + j]) for j in range(F)])] if x is not None else []       # the query's own values: b1 takes them
+    inserts = [at(items0, 35)[0], new(10)] + member + [new(0)] + [new(0) for _ in range(11)]
+    inserts.append(inserts[-3])                                                         # placed earlier in this call
+    removes = [items2[0], at(items0, 30)[1], at(items1, 40)[0], L.absent_variant(rng, t, at(items0, 45)[0], bins0)]
+    return [bins0, bins1, bins2], inserts, removes
+
+
+def other_index(rng, t):
+    return [L.make_db(rng, t, 60, lambda s: int(rng.integers(1, 8)), range(0, 60, F))[1] for _ in range(2)]
+
+
+def build_apply_scene(T, rng, t, x=None):
+    """ids: 0 = (1, 0), 1 = b0, 2 = b1, 3 = (1, 1), 4 = b2; index 0 alternates over its slots"""
+    model, inserts, removes = apply_scene(rng, t, x)
+    others = other_index(rng, t)
+    s0 = T.slots_of(0)
+    ids = [T.build(1, 0, others[0]), T.build(0, 0, model[0], slot=s0[0]), T.build(0, 2, model[1], slot=s0[-1]), T.build(1, 1, others[1]),
+           T.build(0, 5, model[2], slot=s0[0])]
+    assert ids == [0, 1, 2, 3, 4]
+    return inserts, removes
+
+
+@DEVS
+def test_apply_entries_equals_the_single_context(devs, tmp_path):
+    E = apsu_amd.engine
+    js = common.toy_json()
+    rng = np.random.default_rng(153)
+    t = U.toy_t()
+    T = Twin(js, devs, tmp_path)
+    inserts, removes = build_apply_scene(T, rng, t)
+    res, r = T.apply(0, inserts, removes)
+    # the scene is what its description says (the single context's answer; T.apply held the handle's against it)
+    assert [int(v) for v in res.state] == [E.BUNDLE_REPLACED, E.BUNDLE_REPLACED, E.BUNDLE_EMPTY] and len(res.appended) == 2
+    assert [int(v) for v in res.ins_status] == [E.ENTRY_DUPLICATE] + [E.ENTRY_INSERTED] * 13 + [E.ENTRY_DUPLICATE]
+    assert [int(v) for v in r.ins_target] == [1, 2, 2] + [5] * 10 + [6, 5]               # old ids: 5, 6 = the appended BinBundles
+    assert [int(v) for v in res.rem_status] == [E.ENTRY_REMOVED] * 3 + [E.ENTRY_NOT_FOUND]
+    assert [int(v) for v in r.rem_target] == [4, 1, 2, NONE]
+    assert r.new_id == [0, 1, 2, 3, -1, 4, 5]
+    assert [(u[1], u[2], u[3]) for u in T.registry()][4:] == [(0, 6, 10), (0, 7, 1)]
+    assert int(T.M.bin_counts(2)[0]) == 10                                                # b1's start bin 0 at max_items_per_bin - 1
+    T.check_images()
+    # the same insertions again: only duplicates, nothing changes
+    before = T.snapshot()
+    res2, r2 = T.apply(0, inserts, None)
+    assert [int(v) for v in r2.ins_status] == [E.ENTRY_DUPLICATE] * len(inserts) and r2.n_appended == 0
+    assert r2.new_id == list(range(6)) and T.snapshot() == before
+    # the refusals that come before any GPU work leave the handle as it is, too
+    for ins, rem, text in (([inserts[1]], [inserts[1]], "removal list too"), ([(56, [1] * F)], [], "bins_per_bundle"), ([], [removes[1], removes[1]], "twice")):
+        with pytest.raises(ValueError, match=text):
+            T.M.apply_entries(0, inserts=ins, removes=rem)
+    with pytest.raises(ValueError, match="bundle_idx"):
+        T.M.apply_entries(NIDX, inserts=inserts[:1])
+    assert T.snapshot() == before
+    T.close()
+
+
+def query_inputs(S, nidx):
+    return [S.src[b][e] for b in range(nidx) for e in S.sources]
+
+
+def masks_for(S, count, seed):
+    vals = [ref.fill_uniform(seed + i, S.C.t, S.C.n) for i in range(count)]
+    return vals, [S.C.encode(v) for v in vals]
+
+
+def single_eval(T, S, rk, masks):
+    """HeContext.eval_bundles over the single context's BinBundles, row = the handle's id"""
+    G = T.G
+    pw = G.compute_powers(list(range(T.nidx)), [[S.src[b][e] for e in S.sources] for b in range(T.nidx)], rk)
+    order = [T.single[(u[1], u[2])] for u in T.registry()]
+    return G.eval_bundles(order, pw, rk, masks)
+
+
+@DEVS
+def test_a_refused_update_leaves_the_handle_as_it_was(devs, tmp_path):
+    js = common.toy_json()
+    S = common.make_scenario(js, {0: [], 1: []})
+    rng = np.random.default_rng(154)
+    t = S.C.t
+    T = Twin(js, devs, tmp_path)
+    M = T.M
+    itemsx, binsx = L.make_db(rng, t, 60, lambda s: 3, range(0, 60, F))
+    itemsy, binsy = L.make_db(rng, t, 60, lambda s: 3, range(0, 60, F))
+    s0 = T.slots_of(0)
+    T.build(0, 0, binsx, slot=s0[0])
+    T.build(1, 0, other_index(rng, t)[0])
+    T.build(0, 1, binsy, slot=s0[-1])
+    M.upload_relin_keys(S.rk)
+    flat = query_inputs(S, T.nidx)
+    _, masks = masks_for(S, 3, 70)
+    before = T.snapshot()
+    out_before = M.eval_all(flat, masks, S.C.n)
+    a, b = itemsy[0], itemsy[1]
+    shares_part_0 = (0, [a[1][0]] + b[1][1:])             # present in y (a false positive); y's bin 0 holds a's part once
+    assert M.lookup(0, [itemsx[4], a, shares_part_0])[0].tolist() == [[True, False, False], [False, True, True]]
+    # x is rebuilt (on another slot where the index has two) while y's division refuses the second removal of one value
+    for fresh in ([], [(30, U.distinct(rng, t, F, avoid=[v for k in range(30, 35) for v in binsx[k] + binsy[k]]))]):
+        with pytest.raises(ValueError, match="is not a root"):
+            M.apply_entries(0, inserts=fresh, removes=[itemsx[4], a, shares_part_0])
+        assert T.snapshot() == before
+        assert (M.eval_all(flat, masks, S.C.n) == out_before).all()
+    with pytest.raises(ValueError, match="is not a root"):                               # the single context refuses the same call
+        T.G.apply_entries(T.index(0), removes=[itemsx[4], a, shares_part_0])
+    # and the handle still takes the call without the offending entry
+    T.apply(0, None, [itemsx[4], a])
+    T.check_images()
+    T.close()
+
+
+# ---- compact, merge_bundles ---------------------------------------------------------------------------------------------
+@DEVS
+def test_compact_across_slots_equals_the_single_context(devs, tmp_path):
+    js = common.toy_json()
+    rng = np.random.default_rng(155)
+    t = U.toy_t()
+    T = Twin(js, devs, tmp_path)
+    M = T.M
+    full = [U.distinct(rng, t, 10) for _ in range(60)]                                   # every bin at max_items_per_bin - 1: nothing fits
+    parts = [full]
+    for c in (3, 4, 4, 2):                                                                # 3 + 4 fit (< 11), + 4 = 11 does not, + 2 does
+        avoid = MG.union(*parts)
+        parts.append([U.distinct(rng, t, int(rng.integers(0, c + 1)) if s != 12 else c, avoid=avoid[s]) for s in range(60)])
+    parts = [parts[i] for i in (1, 0, 2, 3, 4)]                                           # cache order: the full one second
+    others = other_index(rng, t)
+    s0 = T.slots_of(0)
+    # registered newest first, so the merged group's first member in cache order has the group's highest id; the group that merges
+    # (cache positions 0, 2, 4) lies on both of the index's slots
+    T.build(1, 0, others[0])
+    for k in (4, 3, 2, 1, 0):
+        T.build(0, 2 * k + 1, parts[k], slot=s0[(0, 0, 1, 1, 0)[k] % len(s0)])
+    T.build(1, 1, others[1])
+    assert M.index_bundles(0) == [5, 4, 3, 2, 1]
+    if T.world == 3:
+        assert [M.bundle_info(i).slot for i in M.index_bundles(0)] == [0, 0, 2, 2, 0]
+    group, new_id, made = T.compact(0)
+    assert group == [0, 1, 0, 2, 0] and made == 1
+    assert new_id == [0, -1, 1, -1, 2, 3, 4]                                              # ids 1 and 3 (cache 9 and 5) went into id 5 (cache 1)
+    assert tuple(M.bundle_info(3))[1:3] == (0, 1) and M.index_bundles(0) == [3, 2, 1]
+    T.check_images()
+    before = T.snapshot()
+    group, new_id, made = T.compact(0)                                                   # a second call merges nothing
+    assert made == 0 and new_id == list(range(5)) and T.snapshot() == before
+    T.compact(1)                                                                          # the other index, whatever its plan is
+    T.check_images()
+    T.close()
+
+
+@DEVS
+def test_merge_refusals_surface_and_leave_the_handle_unchanged(devs, tmp_path):
+    js = common.toy_json()
+    t = U.toy_t(js)
+    rng = np.random.default_rng(156)
+    T = Twin(js, devs, tmp_path)
+    M, G = T.M, T.G
+    A = U.rand_bins(rng, t, 60, 4, full_frac=0.0)
+    B = [U.distinct(rng, t, int(rng.integers(0, 4)), avoid=a) for a in A]
+    A[20], B[20] = U.distinct(rng, t, 6), U.distinct(rng, t, 5)                          # 6 + 5 = 11 reaches max_items_per_bin
+    s0 = T.slots_of(0)
+    a = T.build(0, 0, A, slot=s0[0])
+    b = T.build(0, 1, B, slot=s0[-1])
+    short = T.build(0, 2, B[:55], slot=s0[0])                                            # slots 55 .. 59 hold the zero polynomial here, bins there
+    empty = T.build(0, 3, [[] for _ in range(60)], slot=s0[-1])
+    other = T.build(1, 0, [[] for _ in range(60)])
+    before = T.snapshot()
+    for ids, text in (([a, b], r"bin 20\b"), ([empty, short], r"slot 55\b"), ([a, other], "bundle index"), ([a], "at least two"), ([], "at least two"),
+                      ([a, a], "twice"), ([a, 17], "no BinBundle")):
+        with pytest.raises(ValueError, match=text):
+            M.merge_bundles(ids)
+        assert T.snapshot() == before
+    with pytest.raises(ValueError, match=r"bin 20\b"):
+        G.merge_bundles([T.single[(0, 0)], T.single[(0, 1)]])                            # the single context's refusal, unchanged
+    # what may be merged is: across slots, given newest first -- the merged BinBundle takes the place and cache_idx of (0, 1)
+    want = G.merge_bundles([T.single[(0, 1)], T.single[(0, 3)]])
+    reg = T.registry()
+    new_id = M.merge_bundles([empty, b])
+    del T.single[(0, 3)]
+    T.single[(0, 1)] = want
+    T.check_renumbering(reg, [0, 0, 0, 1, 0], [-1, want.degree, -1, -1, -1], [], new_id)
+    assert new_id == [0, 1, 2, -1, 3] and tuple(M.bundle_info(1)) == (s0[-1], 0, 1, want.degree)
+    T.check_images()
+    T.close()
+
+
+# ---- move_bundle, remove_bundle -----------------------------------------------------------------------------------------
+@DEVS
+def test_move_and_remove(devs, tmp_path):
+    js = common.toy_json()
+    S = common.make_scenario(js, {0: [], 1: []})
+    rng = np.random.default_rng(157)
+    t = S.C.t
+    T = Twin(js, devs, tmp_path)
+    M = T.M
+    for k, (bidx, degree) in enumerate([(0, 10), (1, 4), (0, 2), (1, 11), (0, 0)]):       # Paterson-Stockmeyer and plain layouts, degree 0
+        T.build(bidx, k, bins_of_degree(rng, t, degree))
+    M.upload_relin_keys(S.rk)
+    rk = T.G.upload_relin_keys(S.rk)
+    flat = query_inputs(S, T.nidx)
+    _, masks = masks_for(S, 5, 80)
+    want = single_eval(T, S, rk, masks)
+    assert (M.eval_all(flat, masks, S.C.n) == want).all()
+    before = T.snapshot()
+    for i in range(5):
+        M.move_bundle(i, before[1][i][0])                                                 # to the slot it is on: nothing happens
+    assert T.snapshot() == before
+    for bad_id, bad_slot in ((5, 0), (-1, 0), (0, T.world), (0, -1)):
+        with pytest.raises(ValueError, match="slot|id"):
+            M.move_bundle(bad_id, bad_slot)
+    assert T.snapshot() == before
+    if T.world > 1:
+        # every BinBundle to the next slot (an index may leave its own devices: a device then computes the powers of both indices)
+        for i in range(5):
+            to = (before[1][i][0] + 1) % T.world
+            M.move_bundle(i, to)
+            assert T.registry()[i] == (to,) + before[1][i][1:]
+        count, reg, imgs = T.snapshot()
+        assert count == 5 and imgs == before[2]                                            # same ids, same bytes
+        assert [u[1:] for u in reg] == [u[1:] for u in before[1]] and [u[0] for u in reg] == [(u[0] + 1) % T.world for u in before[1]]
+        for _ in range(2):
+            assert (M.eval_all(flat, masks, S.C.n) == want).all()
+        assert (M.bin_counts(0) == T.G.bin_counts(T.single[(0, 0)])).all()
+    # remove: the survivors close up
+    with pytest.raises(ValueError):
+        M.remove_bundle(5)
+    reg = T.registry()
+    assert M.remove_bundle(1) == [0, -1, 1, 2, 3]
+    del T.single[(1, 1)]
+    assert T.registry() == reg[:1] + reg[2:] and M.n_bundles == 4
+    T.check_images()
+    keep = [0, 2, 3, 4]
+    assert (M.eval_all(flat, [masks[i] for i in keep], S.C.n) == want[keep]).all()
+    T.close()
+
+
+# ---- the query follows, and queued work ---------------------------------------------------------------------------------
+def device_eval(T, S, flat, masks, devs):
+    """eval_all into a buffer on the handle's first device; the caller compares it later"""
+    import torch
+    out_d = torch.zeros((len(masks), 2, S.C.n), dtype=torch.int64, device="cuda:%d" % devs[0])
+    T.M.eval_all(flat, masks, S.C.n, out_device_slot=0, out_ptr=out_d.data_ptr())
+    return out_d
+
+
+def read_back(out_d, shape):
+    import torch
+    torch.cuda.synchronize()
+    return out_d.cpu().numpy().view(np.uint64).reshape(shape)
+
+
+def check_query(T, S, rk, flat, devs, seed):
+    """eval_all with one mask per (new) id against HeContext.eval_bundles over the same BinBundles: twice (buffers are pooled), and once
+    into a device buffer"""
+    count = T.M.bundle_count()
+    vals, masks = masks_for(S, count, seed)
+    want = single_eval(T, S, rk, masks)
+    for _ in range(2):
+        assert (T.M.eval_all(flat, masks, S.C.n) == want).all()
+    assert (read_back(device_eval(T, S, flat, masks, devs), want.shape) == want).all()
+    return vals, masks, want
+
+
+@DEVS
+def test_the_query_follows_apply_and_compact(devs, tmp_path):
+    js = common.toy_json()
+    S = common.make_scenario(js, {0: [], 1: []})
+    rng = np.random.default_rng(158)
+    t, n = S.C.t, S.C.n
+    T = Twin(js, devs, tmp_path)
+    M = T.M
+    inserts, removes = build_apply_scene(T, rng, t, S.x[0])
+    M.upload_relin_keys(S.rk)
+    rk = T.G.upload_relin_keys(S.rk)
+    flat = query_inputs(S, T.nidx)
+    vals, masks, want = check_query(T, S, rk, flat, devs, 90)
+    # device-side results in flight, the maintenance call right behind them: the buffer holds the OLD database's answer
+    out_d = device_eval(T, S, flat, masks, devs)
+    res, r = T.apply(0, inserts, removes)
+    assert (read_back(out_d, want.shape) == want).all()
+    assert r.new_id == [0, 1, 2, 3, -1, 4, 5]
+    vals, masks, want = check_query(T, S, rk, flat, devs, 91)
+    # b1 (id 2) took the query's own values at start bin 25: those slots decrypt to the mask alone
+    got = S.C.decode(S.C.decrypt(S.sk, np.ascontiguousarray(want[2]), 0)[0])
+    assert (got[25:30] == vals[2][25:30]).all() and not (got[:25] == vals[2][:25]).all()
+    # nine of the ten entries of the first appended BinBundle leave again: the two appended BinBundles fit into one
+    leave = [e for e, tgt in zip(inserts, r.ins_target) if int(tgt) == 5][:9]
+    T.apply(0, None, leave)
+    vals, masks, want = check_query(T, S, rk, flat, devs, 92)
+    out_d = device_eval(T, S, flat, masks, devs)
+    group, new_id, made = T.compact(0)
+    assert (read_back(out_d, want.shape) == want).all()
+    assert group == [0, 1, 2, 2] and made == 1 and new_id == [0, 1, 2, 3, 4, -1]
+    T.check_images()
+    vals, masks, want = check_query(T, S, rk, flat, devs, 93)
+    got = S.C.decode(S.C.decrypt(S.sk, np.ascontiguousarray(want[2]), 0)[0])
+    assert (got[25:30] == vals[2][25:30]).all()
+    assert T.compact(0)[2] == 0
+    T.close()
+
+
+def test_apply_compact_and_query_on_1M_1024(tmp_path):
+    """one shipped set (n = 4096, 4095 bins, max_items_per_bin 125) over three slots of one device"""
+    devs = [0, 0, 0]
+    js = common.param_json("1M-1024-com")
+    S = common.make_scenario(js, {0: [], 1: []})
+    rng = np.random.default_rng(159)
+    t = S.C.t
+    T = Twin(js, devs, tmp_path)
+    M = T.M
+    starts = sorted(set([60, 4090, 0] + [int(v) * F for v in rng.choice(4095 // F, size=40, replace=False)]))
+    dbs = [L.make_db(rng, t, 4095, lambda s: int(rng.integers(2, 7)), starts) for _ in range(3)]
+    T.build(0, 0, dbs[0][1], slot=0)
+    T.build(1, 0, dbs[2][1])
+    T.build(0, 1, dbs[1][1], slot=2)
+    M.upload_relin_keys(S.rk)
+    rk = T.G.upload_relin_keys(S.rk)
+    flat = query_inputs(S, T.nidx)
+    used = [set(dbs[0][1][s]) | set(dbs[1][1][s]) for s in range(4095)]
+    fresh = [(s, [U.distinct(rng, t, 1, avoid=used[s + j])[0] for j in range(F)]) for s in starts[:20]]
+    fresh.append((60, [int(S.x[0][60 + j]) for j in range(F)]))                          # slots 60 .. 64: two tiles
+    res, r = T.apply(0, fresh + [dbs[0][0][0]], dbs[0][0][5:10] + dbs[1][0][5:10] + [L.absent_variant(rng, t, dbs[0][0][1], dbs[0][1])])
+    assert r.n_appended == 0 and r.new_id == [0, 1, 2] and [int(v) for v in r.rem_target] == [0] * 5 + [2] * 5 + [NONE]
+    assert [int(v) for v in r.ins_target] == [2] * 21 + [0]
+    T.check_images()
+    vals, masks, want = check_query(T, S, rk, flat, devs, 95)
+    group, new_id, made = T.compact(0)
+    assert group == [0, 0] and made == 1 and new_id == [0, 1, -1] and tuple(M.bundle_info(0))[:3] == (0, 0, 0)
+    T.check_images()
+    vals, masks, want = check_query(T, S, rk, flat, devs, 96)
+    got = S.C.decode(S.C.decrypt(S.sk, np.ascontiguousarray(want[0]), 0)[0])
+    assert (got[60:65] == vals[0][60:65]).all()
+    T.close()
