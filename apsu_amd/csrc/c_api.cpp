@@ -335,6 +335,18 @@ int apsu_he_db_compact(apsu_he_ctx *c, uint32_t bundle_idx, const apsu_he_bundle
     });
 }
 
+int apsu_he_bundle_bins(apsu_he_ctx *c, const apsu_he_bundle *b, uint64_t *roots, uint32_t *counts, uint32_t stride)
+{ return guarded([&] { REQUIRE(c && b && b->b && counts, "null argument"); c->eng->bundle_bins(*b->b, roots, counts, stride); }); }
+int apsu_he_debug_bundle_bins_form(apsu_he_ctx *c, const apsu_he_bundle *b, uint64_t *roots, uint32_t *counts, uint32_t stride, int form)
+{
+    return guarded([&] {
+        REQUIRE(c && b && b->b && counts, "null argument");
+        REQUIRE(form >= Engine::BINS_FORM_AUTO && form <= Engine::BINS_FORM_COMPOSED, "unknown form");
+        c->eng->bundle_bins(*b->b, roots, counts, stride, form);
+    });
+}
+int apsu_he_debug_bins_times(apsu_he_ctx *c, double *decode_ms, double *roots_ms, double *mult_ms)
+{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->bins_times(decode_ms, roots_ms, mult_ms); }); }
 int apsu_he_debug_merge_times(apsu_he_ctx *c, double *decode_ms, double *kernel_ms, double *encode_ms)
 { return guarded([&] { REQUIRE(c, "null argument"); c->eng->merge_times(decode_ms, kernel_ms, encode_ms); }); }
 int apsu_he_debug_lookup_times(apsu_he_ctx *c, double *decode_ms, double *kernels_ms)
@@ -665,6 +677,8 @@ int apsu_he_multi_db_index_bundles(apsu_he_multi *m, uint32_t bundle_idx, int *i
 }
 int apsu_he_multi_db_bin_counts(apsu_he_multi *m, int bundle_id, uint32_t *counts)
 { return guarded([&] { REQUIRE(m && counts, "null argument"); m->m->bin_counts(bundle_id, counts); }); }
+int apsu_he_multi_db_bundle_bins(apsu_he_multi *m, int bundle_id, uint64_t *roots, uint32_t *counts, uint32_t stride)
+{ return guarded([&] { REQUIRE(m && counts, "null argument"); m->m->bundle_bins(bundle_id, roots, counts, stride); }); }
 int apsu_he_multi_db_build_bundle(apsu_he_multi *m, int device_slot, uint32_t bundle_idx, uint32_t cache_idx, const uint64_t *roots,
                                   const uint32_t *counts, uint32_t bins, uint32_t stride, int *bundle_id)
 {

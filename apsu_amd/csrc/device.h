@@ -10,6 +10,7 @@
 #include "query_side.h"
 #include "bin_lookup.h"
 #include "bin_merge.h"
+#include "bin_roots.h"
 
 namespace apsu_he {
 
@@ -77,6 +78,21 @@ void launch_bins_lookup(const LookupWork *work, u32 n_work, const u64 *pts, cons
 // count of A + that of B + 1.  topsA / topsB: per tile of 64 slots the largest count, -1 for none (merge_tile_tops); A and B hold at
 // least top + 1 rows for every tile.
 void launch_bins_merge(const u64 *A, const int *topsA, const u64 *B, const int *topsB, Mod t, u64 *C, size_t n, u32 rows, hipStream_t st);
+// reading the bins back (Engine::bundle_bins; bin_roots.h, kernels_roots.hip).  occ: the slots of the n_occ occupied bins (count >= 1);
+// hits [n_occ][hstride] and found [n_occ] (zeroed beforehand): the distinct roots of each; mult [n_occ][hstride]: their multiplicities,
+// written for the bins with fewer distinct roots than items only.  step: g^i, i < n; pts: the forward transform mod t of the polynomial X.
+bool bin_roots_has_kernel(int logn);                 // is there a k_bin_roots for this ring size (else: the composition below)
+u32 bin_roots_wg_slots(int logn);                    // workgroups of k_bin_roots the current device holds at once
+// the persistent kernel: `wgs` workgroups over n_occ * grid.blocks work items, rows: [wgs][n] words of workspace
+void launch_bin_roots(int logn, const u64 *poly, const u32 *occ, const u32 *counts, u32 n_occ, RootsGrid grid, u32 cosets, u32 wgs, const NttTable *tabs,
+                      const int *modmap, const u32 *step, const u64 *pts, u64 g, u64 *rows, u32 *vrows, u64 *hits, u32 *found, u32 hstride, hipStream_t st);
+// the plain composition, per coset c: rows[r][i] = a_i c^i of bin occ[r]; launch_ntt forward mod t; the scan (first: with the test for the root 0)
+void launch_roots_gather(const u64 *poly, size_t n, const u32 *occ, const u32 *counts, u32 nrows, u64 c, Mod t, u64 *rows, hipStream_t st);
+void launch_roots_scan(const u64 *rows, size_t n, u32 nrows, const u64 *pts, u64 c, Mod t, bool first, const u64 *poly, const u32 *occ, const u32 *counts,
+                       u64 *hits, u32 *found, u32 hstride, hipStream_t st);
+// divides the columns of poly in place
+void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u32 n_occ, Mod t, const u64 *hits, const u32 *found, u32 *mult, u32 hstride,
+                       hipStream_t st);
 void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 void launch_gather_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 // N1: algebraize_item for `count` 16-byte items -> out[count][felts]; bpf = bits per field element, item_bits = felts * bpf

@@ -194,6 +194,14 @@ public:
     // polynomials, so n >= 2 BinBundles of one bundle index become ONE new BinBundle without anybody's roots: decode each, per-slot
     // products pairwise (k_bins_merge, bin_merge.h), the tail of the build.  The given BinBundles are only read.
     std::unique_ptr<Bundle> merge_bundles(const Bundle *const *bundles, uint32_t n_bundles, uint32_t cache_idx);
+    // N1, reading the bins back (include/apsu_he.h: apsu_he_bundle_bins; bin_roots.h): the roots of every bin's polynomial, found as the
+    // zeros of (t - 1) / n forward transforms mod t of the bin's scaled coefficients.  counts: n words (host), LOOKUP_NONE where the slot
+    // is not a bin; roots (host, may be null): bin s at roots[s * stride], ascending, a value of multiplicity m written m times.
+    // form: BINS_FORM_AUTO, or one of the two paths by name (the debug call of the tests).  `b` is only read.
+    enum { BINS_FORM_AUTO = 0, BINS_FORM_KERNEL = 1, BINS_FORM_COMPOSED = 2 };
+    void bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form = BINS_FORM_AUTO);
+    // device time of the last bundle_bins call: decode and counts, the root search, multiplicities and copy-back
+    void bins_times(double *decode_ms, double *roots_ms, double *mult_ms);
     // device time of the last merge_bundles call: the decodes and counts, the product kernels, the re-encode
     void merge_times(double *decode_ms, double *kernel_ms, double *encode_ms);
     struct CompactResult {
@@ -484,6 +492,11 @@ private:
     double lookup_decode_ms_ = 0, lookup_kernels_ms_ = 0;
     EventStamps merge_evs_;                            // merge_bundles' five time stamps
     double merge_ms_[3] = { 0, 0, 0 };
+    EventStamps bins_evs_;                             // bundle_bins' four time stamps
+    double bins_ms_[3] = { 0, 0, 0 };
+    void roots_tables();                               // the context's generator, step table and point table, made by the first bundle_bins
+    u64 roots_g_ = 0;
+    DevBuf d_roots_step_, d_roots_pts_;                // g^i (u32) and the forward transform mod t of the polynomial X, n words each
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
     // seed expansion of `count` objects of L limbs queued on the stream without a host wait (seed_expand, query_create, relin_keygen): false = the objects need the host's

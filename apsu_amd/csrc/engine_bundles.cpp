@@ -459,6 +459,124 @@ void Engine::lookup_bundles(const Bundle *const *bundles, uint32_t n_bundles, co
     lookup_reduce(flags.data(), counts.data(), n_bundles, n, start, count, F, present, room);
 }
 
+// ---- N1, reading the bins back (bin_roots.h): decode, k_bin_counts, k_bin_roots (or the per-coset composition), k_roots_mult, one sync,
+// then the host's sort per bin and the sum check
+void Engine::roots_tables()
+{
+    if (roots_g_) return;
+    const size_t n = hp_.n;
+    const u64 g = field_generator(hp_.t);
+    const std::vector<u32> step = roots_step_table(g, hp_.t, n);
+    d_roots_step_.alloc(n * sizeof(u32));
+    HIP_CHECK(hipMemcpy(d_roots_step_.p(), step.data(), n * sizeof(u32), hipMemcpyHostToDevice));
+    // the evaluation point of output position k is the transform of X at k: the output order is the launch's own
+    d_roots_pts_.alloc(n * sizeof(u64));
+    std::vector<u64> x(n, 0);
+    x[1] = 1;
+    HIP_CHECK(hipMemcpy(d_roots_pts_.p(), x.data(), n * sizeof(u64), hipMemcpyHostToDevice));
+    d_ntt(d_roots_pts_.u(), 1, map_ct() + hp_.plain_id(), 1, false, false);
+    sync();
+    roots_g_ = g;
+}
+
+void Engine::bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("bins");
+    const size_t n = hp_.n;
+    const u32 cosets = roots_coset_count(hp_.t, n);                    // (refuses a plain modulus with too many cosets)
+    if (b.degree >= n) throw std::logic_error("bins: a bin's polynomial of degree " + std::to_string(b.degree) + " does not fit one transform of " + std::to_string(n) + " points");
+    const bool has_kernel = bin_roots_has_kernel(hp_.logn);
+    if (form == BINS_FORM_KERNEL && !has_kernel) throw std::logic_error("bins: no persistent kernel for this ring size");
+    const bool kernel = form == BINS_FORM_COMPOSED ? false : has_kernel;
+    roots_tables();
+    const Mod t = make_mod(hp_.t);
+    const u32 *step = reinterpret_cast<const u32 *>(d_roots_step_.p());
+    const u64 *pts = d_roots_pts_.u();
+    std::vector<uint32_t> occ;
+    std::vector<u64> hits;
+    std::vector<uint32_t> found, mult;
+    uint32_t hstride = 0;
+    bins_evs_.reserve(4);
+    WITH_ARENA({
+        occ.clear();
+        hstride = 0;
+        bins_evs_.record(0, st_);
+        u64 *poly = ws((size_t)(b.degree + 1) * n);                    // [d][slot] slot values of the batched polynomial
+        uint32_t *dcounts = ws_as<uint32_t>(n);
+        const size_t mark = arena_off_;
+        decode_bundle(b, poly);
+        arena_off_ = mark;                                             // the decode's workspace is free again (stream order)
+        launch_bin_counts(poly, n, b.degree + 1, dcounts, st_);
+        HIP_CHECK(hipMemcpyAsync(counts, dcounts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        bins_evs_.record(1, st_);
+        sync();                                                        // which bins are occupied, and the lists' size, are decided on the host
+        for (size_t s = 0; s < n; s++)
+            if (counts[s] != LOOKUP_NONE && counts[s] >= 1) { occ.push_back((uint32_t)s); hstride = std::max(hstride, counts[s]); }
+        if (roots && stride < hstride) throw std::invalid_argument("bins: stride " + std::to_string(stride) + " is below the largest bin count " + std::to_string(hstride));
+        const u32 n_occ = (u32)occ.size();
+        if (n_occ) {
+            uint32_t *docc = ws_as<uint32_t>(n_occ), *dfound = ws_as<uint32_t>(n_occ), *dmult = ws_as<uint32_t>((size_t)n_occ * hstride);
+            u64 *dhits = ws((size_t)n_occ * hstride);
+            HIP_CHECK(hipMemcpyAsync(docc, occ.data(), n_occ * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemsetAsync(dfound, 0, n_occ * sizeof(uint32_t), st_));
+            if (kernel) {
+                const u32 slots = bin_roots_wg_slots(hp_.logn);
+                const RootsGrid grid = roots_grid(n_occ, cosets, slots);
+                const u32 wgs = (u32)std::min<u64>((u64)n_occ * grid.blocks, slots);
+                u64 *rows = ws((size_t)wgs * n);
+                u32 *vrows = ws_as<u32>((size_t)wgs * n);
+                launch_bin_roots(hp_.logn, poly, docc, dcounts, n_occ, grid, cosets, wgs, tabs(), map_ct() + hp_.plain_id(), step, pts, roots_g_, rows, vrows,
+                                 dhits, dfound, hstride, st_);
+            } else {
+                // limb rows of at most 64 MiB at a time, all cosets for one group of bins, then the next group
+                const u32 group = (u32)std::max<size_t>(1, std::min<size_t>(n_occ, ((size_t)64 << 20) / (n * sizeof(u64))));
+                u64 *rows = ws((size_t)group * n);
+                const u64 r1 = t.r1;
+                for (u32 r0 = 0; r0 < n_occ; r0 += group) {
+                    const u32 nr = std::min(group, n_occ - r0);
+                    u64 c = 1;
+                    for (u32 j = 0; j < cosets; j++) {
+                        launch_roots_gather(poly, n, docc + r0, dcounts, nr, c, t, rows, st_);
+                        d_ntt(rows, nr, map_ct() + hp_.plain_id(), 1, false, false);
+                        launch_roots_scan(rows, n, nr, pts, c, t, j == 0, poly, docc + r0, dcounts, dhits + (size_t)r0 * hstride, dfound + r0, hstride, st_);
+                        c = roots_mul(c, roots_g_, hp_.t, r1);
+                    }
+                }
+            }
+            bins_evs_.record(2, st_);
+            launch_roots_mult(poly, n, docc, dcounts, n_occ, t, dhits, dfound, dmult, hstride, st_);
+            hits.resize((size_t)n_occ * hstride); found.resize(n_occ); mult.resize((size_t)n_occ * hstride);
+            HIP_CHECK(hipMemcpyAsync(found.data(), dfound, n_occ * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+            HIP_CHECK(hipMemcpyAsync(mult.data(), dmult, mult.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+            HIP_CHECK(hipMemcpyAsync(hits.data(), dhits, hits.size() * sizeof(u64), hipMemcpyDeviceToHost, st_));
+        } else bins_evs_.record(2, st_);
+        bins_evs_.record(3, st_);
+        sync();
+    });
+    for (int i = 0; i < 3; i++) bins_ms_[i] = bins_evs_.ms(i, i + 1);
+    // host end: multiplicities (1 wherever a bin has as many distinct roots as items), the sum check, the sort; nothing is written to
+    // `roots` before every bin has passed
+    std::vector<std::vector<u64>> bins(occ.size());
+    for (size_t r = 0; r < occ.size(); r++) {
+        const u32 cnt = counts[occ[r]], nf = found[r];
+        u32 *m = mult.data() + r * hstride;
+        if (nf >= cnt) std::fill(m, m + std::min(nf, cnt), 1u);
+        roots_expand(occ[r], cnt, hits.data() + r * hstride, m, nf, bins[r]);
+    }
+    if (!roots) return;
+    for (size_t r = 0; r < occ.size(); r++) std::copy(bins[r].begin(), bins[r].end(), roots + (size_t)occ[r] * stride);
+}
+
+void Engine::bins_times(double *decode_ms, double *roots_ms, double *mult_ms)
+{
+    Enter g(this);
+    if (decode_ms) *decode_ms = bins_ms_[0];
+    if (roots_ms) *roots_ms = bins_ms_[1];
+    if (mult_ms) *mult_ms = bins_ms_[2];
+}
+
 // apply_entries and compact take the BinBundles of one bundle index, in cache order
 static void check_one_index_in_cache_order(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles)
 {

@@ -14,6 +14,7 @@
 #include "bin_update.h"
 #include "bin_lookup.h"
 #include "bin_merge.h"
+#include "bin_roots.h"
 #include "db_compact.h"
 #include "db_place.h"
 #include "multi_place.h"
@@ -81,6 +82,45 @@ template <int LOGN, bool INV, int C = 16> static void emu_ntt(u64 *data, const N
     else if (tab.wide_d4) emu_ntt_n<LOGN, INV, NTT_WIDE_NEAR, C>(data, tab, T);
     else emu_ntt_n<LOGN, INV, NTT_WIDE, C>(data, tab, T);
 }
+
+// forward transform whose load steps the bin's scaled coefficients to the next coset (k_bin_roots: SrcCoset through ntt_body's staged path)
+template <int LOGN, int PASS> static void emu_pass_coset(u64 *lds, u64 *glob, int T, const NttTable &tab, const SrcCoset &ops)
+{
+    if constexpr (PASS < plan_passes(LOGN, 16)) {
+        if constexpr (PASS == 0)
+            for (int tid = 0; tid < T; tid++)
+                for (int e = 2 * tid; e < (1 << LOGN); e += 2 * T) *reinterpret_cast<u64x2 *>(lds + lds_slot(e)) = src_load2(ops, glob, e, tab);
+        for (int tid = 0; tid < T; tid++) {
+            if constexpr (PASS == 0) ntt_pass<LOGN, false, NTT_NARROW, 0, 0, false, SrcCoset, true, TwInline, NoHook, 16>(lds, glob, tid, T, tab, ops);
+            else ntt_pass<LOGN, false, NTT_NARROW, PASS, 0, false, SrcPlain, false, TwInline, NoHook, 16>(lds, glob, tid, T, tab);
+        }
+        emu_pass_coset<LOGN, PASS + 1>(lds, glob, T, tab, ops);
+    }
+}
+template <int LOGN> static void emu_ntt_coset(u64 *row, const NttTable &tab, int T, const SrcCoset &ops)
+{
+    std::vector<u64> lds(lds_slots(1 << LOGN));
+    emu_pass_coset<LOGN, 0>(lds.data(), row, T, tab, ops);
+    for (int e = 0; e < (1 << LOGN); e++) row[e] = ntt_fwd_finish<NTT_NARROW>(lds[lds_slot(e)], tab);
+}
+
+// the product's transform tables for one modulus
+struct EmuTables {
+    std::vector<TwPair> fwd, dit, sc;
+    NttTable tab;
+    EmuTables(int logn, u64 q)
+    {
+        const size_t n = (size_t)1 << logn;
+        const HeParams hp = HeParams::Create(n, { q }, 65537 < q ? 65537 : 3);
+        const NttTablesHost &t = hp.ntt[0];
+        fwd.resize(n); dit.resize(n); sc.resize(n);
+        for (size_t k = 0; k < n; k++) {
+            fwd[k] = { t.fwd[k], t.fwd_q[k] };
+            dit[k] = { t.dit[k], t.dit_q[k] }; sc[k] = { t.scale[k], t.scale_q[k] };
+        }
+        tab = make_ntt_table(t, logn, fwd.data(), dit.data(), sc.data());
+    }
+};
 
 static thread_local std::string g_err;
 
@@ -562,6 +602,150 @@ int emu_bins_lookup(uint64_t t_, const uint64_t *poly, uint64_t n, uint32_t degr
             }
         }
         if (stats) { stats[0] = plan.work.size(); stats[1] = plan.rows(); stats[2] = widest; }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// ---- reading the bins back (bin_roots.h)
+uint64_t emu_field_generator(uint64_t t)
+{
+    try { return field_generator(t); } catch (const std::exception &e) { g_err = e.what(); return 0; }
+}
+
+// (t - 1) / n, or -1 with emu_last_error for a modulus the walk cannot serve
+int64_t emu_roots_coset_count(uint64_t t, uint64_t n)
+{
+    try { return (int64_t)roots_coset_count(t, n); } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+int emu_ntt_limb_c(int logn, int inverse, uint64_t q, uint64_t *data, int threads, int coeffs);
+// the point table: the forward transform mod t of the polynomial X, through the library transform's emulation
+int emu_roots_points(int logn, uint64_t t, uint64_t *pts)
+{
+    const size_t n = (size_t)1 << logn;
+    std::fill(pts, pts + n, 0);
+    pts[1] = 1;
+    return emu_ntt_limb_c(logn, 0, t, pts, (int)std::max<size_t>(64, n / 16), 16);
+}
+
+// the coset walk alone: out[j * n + k] = c_j pts[k], the evaluation point of output position k of coset j, j < (t - 1) / n
+int emu_roots_walk(int logn, uint64_t t, uint64_t *out)
+{
+    try {
+        const size_t n = (size_t)1 << logn;
+        const u32 cosets = roots_coset_count(t, n);
+        const u64 g = field_generator(t), r1 = (u64)((((unsigned __int128)1) << 64) / t);
+        std::vector<u64> pts(n);
+        if (emu_roots_points(logn, t, pts.data())) return -1;
+        u64 c = roots_coset_before(g, 0, t, r1);
+        for (u32 j = 0; j < cosets; j++) {
+            c = roots_mul(c, g, t, r1);
+            for (size_t k = 0; k < n; k++) out[(size_t)j * n + k] = roots_value(c, pts[k], t, r1);
+        }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// k_bin_roots and k_roots_mult on ONE bin, as the workgroups and the wave run them: col[rows] are the bin's coefficients mod t (the
+// count is the index of the highest non-zero one), `blocks` the number of coset blocks the bin's cosets are split into (each block a
+// work item of its own, with its own scaled load).  values / mult [cap]: the distinct roots in the order found and their
+// multiplicities; returns how many were found, -1 (emu_last_error) on a refusal.  cap >= count.
+int64_t emu_bin_roots(int logn, uint64_t t, const uint64_t *col_in, uint32_t rows, uint32_t blocks, uint64_t *values, uint32_t *mult, uint32_t cap)
+{
+    try {
+        const size_t n = (size_t)1 << logn;
+        const u32 cosets = roots_coset_count(t, n);
+        int top = (int)rows - 1;
+        while (top >= 0 && col_in[top] == 0) top--;
+        if (top < 0) throw std::invalid_argument("the zero polynomial is not a bin");
+        const u32 cnt = (u32)top;
+        if (cnt >= n) throw std::invalid_argument("degree does not fit one transform");
+        if (cap < cnt) throw std::invalid_argument("cap below the count");
+        if (!blocks || blocks > cosets) throw std::invalid_argument("blocks out of range");
+        const int T = (int)std::max<size_t>(64, n / 16);
+        const EmuTables et(logn, t);
+        const NttTable &tab = et.tab;
+        const u64 q = tab.q, r1 = tab.r1, g = field_generator(t);
+        const std::vector<u32> step = roots_step_table(g, t, n);
+        std::vector<u64> pts(n), col(col_in, col_in + rows);
+        if (emu_roots_points(logn, t, pts.data())) return -1;
+        RootsGrid grid;
+        grid.per_block = (cosets + blocks - 1) / blocks;
+        grid.blocks = (cosets + grid.per_block - 1) / grid.per_block;
+        u32 found = 0;
+        if (cnt >= 1) {                                              // an occupied bin: the work items of k_bin_roots
+            std::vector<u32> v(n);
+            std::vector<u64> row(n);
+            for (u32 blk = 0; blk < grid.blocks; blk++) {
+                const u32 j0 = blk * grid.per_block, j1 = std::min(cosets, j0 + grid.per_block);
+                u64 c = roots_coset_before(g, j0, q, r1);
+                for (int tid = 0; tid < T; tid++)
+                    for (int e = tid; e < (int)n; e += T) v[e] = (u32)e <= cnt ? (u32)roots_scaled_load(col[e], c, (u32)e, q, r1) : 0;
+                if (blk == 0 && roots_is_zero(col[0])) roots_append(&found, values, cnt, 0);
+                for (u32 j = j0; j < j1; j++) {
+                    c = roots_mul(c, g, q, r1);
+                    const SrcCoset ops{ v.data(), step.data() };
+                    switch (logn) {
+                        case 6: emu_ntt_coset<6>(row.data(), tab, T, ops); break;
+                        case 8: emu_ntt_coset<8>(row.data(), tab, T, ops); break;
+                        case 10: emu_ntt_coset<10>(row.data(), tab, T, ops); break;
+                        case 12: emu_ntt_coset<12>(row.data(), tab, T, ops); break;
+                        case 13: emu_ntt_coset<13>(row.data(), tab, T, ops); break;
+                        default: throw std::invalid_argument("unsupported logn");
+                    }
+                    for (int tid = 0; tid < T; tid++)
+                        for (int e = tid; e < (int)n; e += T)
+                            if (roots_is_zero(row[e])) roots_append(&found, values, cnt, roots_value(c, pts[e], q, r1));
+                }
+            }
+        }
+        // k_roots_mult: the wave of this bin
+        const u32 nf = std::min(found, cnt);
+        if (nf < cnt) {
+            u32 top_now = cnt;
+            for (u32 base = 0; base < nf; base += ROOTS_LANES) {
+                u64 r[ROOTS_LANES], b1s[ROOTS_LANES];
+                bool live[ROOTS_LANES];
+                for (u32 lane = 0; lane < ROOTS_LANES; lane++) {
+                    live[lane] = base + lane < nf;
+                    r[lane] = live[lane] ? values[base + lane] : 0;
+                    u64 b0 = 0, b1 = 0;
+                    for (int d = (int)cnt; d >= 0; d--) roots_deriv_step(b0, b1, r[lane], col[d], q, r1);
+                    b1s[lane] = b1;
+                    if (live[lane] && b1 != 0) mult[base + lane] = 1;
+                }
+                for (u32 l = 0; l < ROOTS_LANES; l++) {               // the ballot's bits, lowest first; lane 0 works
+                    if (!(live[l] && b1s[l] == 0)) continue;
+                    const u64 a = r[l];
+                    u32 m = 0;
+                    for (;;) {
+                        u64 rem = 0;
+                        for (int k = (int)top_now; k >= 0; k--) rem = roots_div_step(col[k], a, rem, q, r1);
+                        if (rem != 0 || top_now == 0) break;
+                        u64 sv = 0;
+                        for (int k = (int)top_now; k >= 0; k--) {
+                            const u64 pk = col[k];
+                            col[k] = sv;
+                            sv = roots_div_step(pk, a, sv, q, r1);
+                        }
+                        top_now--;
+                        m++;
+                    }
+                    mult[base + l] = m;
+                }
+            }
+        } else std::fill(mult, mult + nf, 1u);
+        return (int64_t)found;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// the host end of the call (roots_expand): out[count] = the sorted multiset, or -1 with the refusal in emu_last_error
+int emu_roots_expand(uint32_t slot, uint32_t count, const uint64_t *values, const uint32_t *mult, uint32_t found, uint64_t *out)
+{
+    try {
+        std::vector<u64> v;
+        roots_expand(slot, count, values, mult, found, v);
+        std::copy(v.begin(), v.end(), out);
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }

@@ -1,0 +1,182 @@
+// Reading the bins of a resident BinBundle back from its polynomials (Engine::bundle_bins), a translation unit of its own: the
+// transforms' object (kernels.hip) is built exactly as before.  Rules and lane arithmetic: bin_roots.h, which the CPU tier runs as well.
+// Input of every kernel here: poly[d][slot], the slot values mod t that Engine::decode_bundle produces; bin s is the column s, read
+// top down to its count.
+#include "device.h"
+#include "ntt_wg.h"
+#include "bin_roots.h"
+
+namespace apsu_he {
+
+#define KERNEL_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw_hip(e_, __FILE__, __LINE__); } while (0)
+void throw_hip(hipError_t e, const char *file, int line);
+
+// ---- the persistent kernel.  A work item is (occupied bin, block of consecutive cosets); a workgroup takes work items blockIdx.x,
+// blockIdx.x + gridDim.x, ...  It reads the bin's column ONCE, keeps the scaled coefficients v_i (32-bit words) in its own row of
+// `vrows` (32 KiB at n = 8192, read and written by this workgroup alone: L2-resident.  In LDS next to the transform's image they cost the
+// second workgroup per CU at n = 8192 -- 104 KiB -- and the search took 1.13 x (16M-4096) to 1.27 x (256M-4096) as long, profiles/r15_bundle_bins.txt), and for each coset of its block steps v to that coset while the transform loads it (SrcCoset), runs the workgroup
+// transform of ntt_wg.h in the throughput form (16 coefficients per lane), and tests the n outputs for zero.  The transform's closing
+// reduction leaves canonical residues in the workgroup's own row of `rows` (n words, written and read back by the same workgroup: it
+// stays in the L2); a zero at position k is the root c_j pts[k], appended to the bin's list through the bin's counter.  Nothing but
+// the hits goes to memory.  The root 0 lies in no coset: a_0 = 0 is tested by the bin's first block.
+// rows: [gridDim.x][n] u64, vrows: [gridDim.x][n] u32; hits: [n_occupied][hstride], found: [n_occupied] (zeroed); hstride >= every count.
+template <int LOGN, int T, int MINW>
+__global__ __launch_bounds__(T, MINW) void k_bin_roots(const u64 *__restrict__ poly, const u32 *__restrict__ occ, const u32 *__restrict__ counts, u32 n_work,
+                                                    RootsGrid grid, u32 cosets, const NttTable *__restrict__ tabs, const int *__restrict__ modmap,
+                                                    const u32 *__restrict__ step, const u64 *__restrict__ pts, u64 g, u64 *__restrict__ rows,
+                                                    u32 *__restrict__ vrows, u64 *__restrict__ hits, u32 *__restrict__ found, u32 hstride)
+{
+    constexpr int N = 1 << LOGN;
+    __shared__ __attribute__((aligned(16))) u64 lds[lds_slots(N)];
+    const int tid = threadIdx.x;
+    const NttTable tab = tabs[modmap[0] & NTT_MAP_MASK];
+    const u64 q = tab.q, r1 = tab.r1;
+    u64 *p = rows + (size_t)blockIdx.x * N;
+    u32 *v = vrows + (size_t)blockIdx.x * N;
+    for (u32 w = blockIdx.x; w < n_work; w += gridDim.x) {           // workgroup-uniform
+        const u32 rank = w / grid.blocks, blk = w - rank * grid.blocks;
+        const u32 s = occ[rank], cnt = counts[s];
+        const u32 j0 = blk * grid.per_block, j1 = min(cosets, j0 + grid.per_block);
+        u64 c = roots_coset_before(g, j0, q, r1);
+        u64 *list = hits + (size_t)rank * hstride;
+        __syncthreads();                                             // the transform before has read v
+        for (int e = tid; e < N; e += T) v[e] = (u32)e <= cnt ? (u32)roots_scaled_load(poly[(size_t)e * N + s], c, (u32)e, q, r1) : 0;
+        if (blk == 0 && tid == 0 && roots_is_zero(poly[s])) roots_append(found + rank, list, cnt, 0);
+        __syncthreads();
+        for (u32 j = j0; j < j1; j++) {
+            c = roots_mul(c, g, q, r1);                              // c_j
+            ntt_body<LOGN, false, NTT_NARROW, T, 0, false, SrcCoset>(lds, p, tab, tid, nullptr, SrcCoset{ v, step });
+            __syncthreads();                                         // the row is complete
+            for (int e = tid; e < N; e += T)
+                if (roots_is_zero(p[e])) roots_append(found + rank, list, cnt, roots_value(c, pts[e], q, r1));
+            __syncthreads();                                         // before the next transform writes the image and the row
+        }
+    }
+}
+
+// ---- the plain composition (rings without an LDS-resident transform form here, and the form the persistent kernel is tested
+// against): per coset one transposed-and-scaled gather into [bin][n] limb rows, the library's forward transform mod t, one scan.
+__global__ __launch_bounds__(EW_T) void k_roots_gather(const u64 *__restrict__ poly, size_t n, const u32 *__restrict__ occ, const u32 *__restrict__ counts,
+                                                       u64 c, Mod t, u64 *__restrict__ rows)
+{
+    const size_t i = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (i >= n) return;
+    const u32 s = occ[blockIdx.y], cnt = counts[s];
+    rows[(size_t)blockIdx.y * n + i] = i <= cnt ? roots_scaled_load(poly[i * n + s], c, (u32)i, t.q, t.r1) : 0;
+}
+
+__global__ __launch_bounds__(EW_T) void k_roots_scan(const u64 *__restrict__ rows, size_t n, const u64 *__restrict__ pts, u64 c, Mod t, int first,
+                                                     const u64 *__restrict__ poly, const u32 *__restrict__ occ, const u32 *__restrict__ counts,
+                                                     u64 *__restrict__ hits, u32 *__restrict__ found, u32 hstride)
+{
+    const size_t i = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    if (i >= n) return;
+    const u32 rank = blockIdx.y, s = occ[rank], cnt = counts[s];
+    u64 *list = hits + (size_t)rank * hstride;
+    if (first && i == 0 && roots_is_zero(poly[s])) roots_append(found + rank, list, cnt, 0);
+    if (roots_is_zero(rows[(size_t)rank * n + i])) roots_append(found + rank, list, cnt, roots_value(c, pts[i], t.q, t.r1));
+}
+
+// ---- multiplicities: one WAVE per occupied bin, which leaves at once unless the bin has fewer distinct roots than items.  Lane =
+// found root, 64 at a time: P(r) and P'(r) by one Horner walk down the column (every lane reads the same coefficient: one broadcast
+// load per row).  A root with P'(r) != 0 is simple.  For the others lane 0 divides the column by (x - r) in place as long as the
+// remainder is 0 (poly is the call's own decoded copy); dividing out one root's factors leaves every other root's multiplicity alone.
+// mult: [n_occupied][hstride], written for every found root of a bin with a deficit (the host takes 1 elsewhere).
+__global__ __launch_bounds__(256) void k_roots_mult(u64 *__restrict__ poly, size_t n, const u32 *__restrict__ occ, const u32 *__restrict__ counts, u32 n_occ,
+                                                    Mod t, const u64 *__restrict__ hits, const u32 *__restrict__ found, u32 *__restrict__ mult, u32 hstride)
+{
+    const u32 lane = threadIdx.x & 63;
+    const u32 rank = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (rank >= n_occ) return;
+    const u32 s = occ[rank], cnt = counts[s], nf = min(found[rank], cnt);
+    if (nf >= cnt) return;                                           // as many distinct roots as items: all simple
+    u64 *col = poly + s;
+    const u64 q = t.q, r1 = t.r1;
+    u32 top = cnt;                                                   // degree of what the column holds now (lane 0's)
+    for (u32 base = 0; base < nf; base += ROOTS_LANES) {
+        const bool live = base + lane < nf;
+        const u64 r = live ? hits[(size_t)rank * hstride + base + lane] : 0;
+        u64 b0 = 0, b1 = 0;
+        for (int d = (int)cnt; d >= 0; d--) roots_deriv_step(b0, b1, r, col[(size_t)d * n], q, r1);
+        if (live && b1 != 0) mult[(size_t)rank * hstride + base + lane] = 1;
+        unsigned long long multiple = __ballot(live && b1 == 0);
+        while (multiple) {                                           // wave-uniform
+            const int l = __ffsll(multiple) - 1;
+            multiple &= multiple - 1;
+            const u64 a = __shfl((unsigned long long)r, l, 64);
+            if (lane == 0) {
+                u32 m = 0;
+                for (;;) {
+                    u64 rem = 0;
+                    for (int k = (int)top; k >= 0; k--) rem = roots_div_step(col[(size_t)k * n], a, rem, q, r1);
+                    if (rem != 0 || top == 0) break;
+                    u64 sv = 0;
+                    for (int k = (int)top; k >= 0; k--) {
+                        const u64 pk = col[(size_t)k * n];
+                        col[(size_t)k * n] = sv;
+                        sv = roots_div_step(pk, a, sv, q, r1);
+                    }
+                    top--;
+                    m++;
+                }
+                mult[(size_t)rank * hstride + base + l] = m;
+            }
+            __threadfence_block();                                   // the other lanes' next walk reads what lane 0 wrote
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
+// ---- launches
+// workgroups a CU holds: two at n = 8192 (72 KiB of LDS each, 126 VGPRs: 4 waves per SIMD), two at 4096 (170 VGPRs: 2 waves per SIMD; a
+// budget of 168 or 128 registers spills there); resource report: profiles/r15_bundle_bins.txt
+static int roots_wgs_per_cu(int logn) { return logn >= 13 ? 2 : logn == 12 ? 2 : 8; }
+
+bool bin_roots_has_kernel(int logn) { return logn == 13 || logn == 12 || logn == 6; }
+
+u32 bin_roots_wg_slots(int logn)
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    return (u32)cus * (u32)roots_wgs_per_cu(logn);
+}
+
+void launch_bin_roots(int logn, const u64 *poly, const u32 *occ, const u32 *counts, u32 n_occ, RootsGrid grid, u32 cosets, u32 wgs, const NttTable *tabs,
+                      const int *modmap, const u32 *step, const u64 *pts, u64 g, u64 *rows, u32 *vrows, u64 *hits, u32 *found, u32 hstride, hipStream_t st)
+{
+    const u32 n_work = n_occ * grid.blocks;
+    if (!n_work) return;
+#define BR_CASE(LN, T, W) case LN: hipLaunchKernelGGL((k_bin_roots<LN, T, W>), dim3(wgs), dim3(T), 0, st, poly, occ, counts, n_work, grid, cosets, tabs, modmap, step, pts, g, rows, vrows, hits, found, hstride); break;
+    switch (logn) {
+        BR_CASE(13, 512, 4) BR_CASE(12, 256, 2) BR_CASE(6, 64, 4)
+        default: throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
+    }
+#undef BR_CASE
+    KERNEL_CHECK();
+}
+
+void launch_roots_gather(const u64 *poly, size_t n, const u32 *occ, const u32 *counts, u32 nrows, u64 c, Mod t, u64 *rows, hipStream_t st)
+{
+    if (!nrows) return;
+    hipLaunchKernelGGL(k_roots_gather, dim3((unsigned)((n + EW_T - 1) / EW_T), nrows), dim3(EW_T), 0, st, poly, n, occ, counts, c, t, rows);
+    KERNEL_CHECK();
+}
+
+void launch_roots_scan(const u64 *rows, size_t n, u32 nrows, const u64 *pts, u64 c, Mod t, bool first, const u64 *poly, const u32 *occ, const u32 *counts,
+                       u64 *hits, u32 *found, u32 hstride, hipStream_t st)
+{
+    if (!nrows) return;
+    hipLaunchKernelGGL(k_roots_scan, dim3((unsigned)((n + EW_T - 1) / EW_T), nrows), dim3(EW_T), 0, st, rows, n, pts, c, t, first ? 1 : 0, poly, occ, counts,
+                       hits, found, hstride);
+    KERNEL_CHECK();
+}
+
+void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u32 n_occ, Mod t, const u64 *hits, const u32 *found, u32 *mult, u32 hstride,
+                       hipStream_t st)
+{
+    if (!n_occ) return;
+    hipLaunchKernelGGL(k_roots_mult, dim3((n_occ + 3) / 4), dim3(256), 0, st, poly, n, occ, counts, n_occ, t, hits, found, mult, hstride);
+    KERNEL_CHECK();
+}
+
+}  // namespace apsu_he

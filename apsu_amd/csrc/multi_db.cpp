@@ -102,6 +102,13 @@ void MultiEngine::bin_counts(int id, uint32_t *counts)
     devs_[(size_t)where_[(size_t)id].first]->eng->bin_counts(bundle_locked(id), counts);
 }
 
+void MultiEngine::bundle_bins(int id, u64 *roots, uint32_t *counts, uint32_t stride)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    check_id(id);
+    devs_[(size_t)where_[(size_t)id].first]->eng->bundle_bins(bundle_locked(id), roots, counts, stride);
+}
+
 int MultiEngine::build_bundle(int slot, uint32_t bundle_idx, uint32_t cache_idx, const u64 *roots, const uint32_t *counts, uint32_t bins, uint32_t stride)
 {
     std::lock_guard<std::mutex> g(mu_);

@@ -138,6 +138,15 @@ def _entries(entries, felts_per_item):
 
 
 NOT_A_BIN = 0xFFFFFFFF
+
+
+def _bins_stride(counts):
+    held = counts[counts != NOT_A_BIN]
+    return max(int(held.max()) if held.size else 0, 1)
+
+
+def _bins_list(roots, counts):
+    return [None if c == NOT_A_BIN else roots[s, :int(c)].copy() for s, c in enumerate(counts)]
 ENTRY_INSERTED, ENTRY_DUPLICATE, ENTRY_REMOVED, ENTRY_NOT_FOUND = 0, 1, 2, 3
 BUNDLE_UNCHANGED, BUNDLE_REPLACED, BUNDLE_EMPTY = 0, 1, 2
 ApplyResult = collections.namedtuple("ApplyResult", "state bundles appended ins_status ins_target rem_status rem_target")
@@ -425,6 +434,27 @@ class HeContext:
         counts = np.empty(self.n, dtype=np.uint32)
         _check(load_library().apsu_he_bundle_bin_counts(self.h, bundle.h, C.c_void_p(counts.ctypes.data)))
         return counts
+
+    def bins(self, bundle, _form=0):
+        """-> the BinBundle's bins read back from its polynomials: a list of n entries, a sorted np.uint64 array per bin (a value of
+        multiplicity m appears m times), None for a slot that is not a bin (apsu_he_bundle_bins).  _form: tests only, names the path
+        (1: k_bin_roots, 2: the per-coset composition)."""
+        lib = load_library()
+        counts = np.empty(self.n, dtype=np.uint32)
+        _check(lib.apsu_he_bundle_bin_counts(self.h, bundle.h, C.c_void_p(counts.ctypes.data)))   # the stride to ask with
+        stride = _bins_stride(counts)
+        roots = np.zeros((self.n, stride), dtype=np.uint64)
+        if _form:
+            _check(lib.apsu_he_debug_bundle_bins_form(self.h, bundle.h, _p(roots), C.c_void_p(counts.ctypes.data), C.c_uint32(stride), C.c_int(_form)))
+        else:
+            _check(lib.apsu_he_bundle_bins(self.h, bundle.h, _p(roots), C.c_void_p(counts.ctypes.data), C.c_uint32(stride)))
+        return _bins_list(roots, counts)
+
+    def bins_times(self):
+        """-> (decode + counts ms, root search ms, multiplicities + copy-back ms): device time of the last bins call"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(load_library().apsu_he_debug_bins_times(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def lookup(self, bundles, entries):
         """entries ((felts [count][F], start_bins [count]) or (start_bin, felts) pairs) against resident BinBundles -> (present
@@ -874,6 +904,14 @@ class MultiContext:
         counts = np.empty(self.n, dtype=np.uint32)
         _check(load_library().apsu_he_multi_db_bin_counts(self.h, int(bundle_id), C.c_void_p(counts.ctypes.data)))
         return counts
+
+    def bins(self, bundle_id):
+        """HeContext.bins of BinBundle `bundle_id`, on its device (apsu_he_multi_db_bundle_bins)"""
+        counts = self.bin_counts(bundle_id)
+        stride = _bins_stride(counts)
+        roots = np.zeros((len(counts), stride), dtype=np.uint64)
+        _check(load_library().apsu_he_multi_db_bundle_bins(self.h, int(bundle_id), _p(roots), C.c_void_p(counts.ctypes.data), C.c_uint32(stride)))
+        return _bins_list(roots, counts)
 
     def build_bundle(self, bundle_idx, cache_idx, bins, slot=-1):
         """HeContext.build_bundle on `slot`, or (slot -1) on the slot the placement rule chooses -> the new id (registered last)"""

@@ -228,6 +228,36 @@ int apsu_he_db_apply_entries(apsu_he_ctx *ctx, uint32_t bundle_idx, const apsu_h
                              uint32_t *rem_status, uint32_t *rem_target);
 /* device time of the context's last call of the three above, summed over its BinBundles: the decode, and the kernels behind it */
 int apsu_he_debug_lookup_times(apsu_he_ctx *ctx, double *decode_ms, double *kernels_ms);
+/* N1, reading the bins back: the items of a resident BinBundle, read from its polynomials -- the one question apsu_he_bundles_lookup
+ * cannot answer, since it takes values the caller already knows.  With it a database that came from an image, a DB file or a
+ * reference-saved cache can be rebuilt for other parameters (apsu_he_db_build_bundle of the bins in another context), audited, or counted
+ * with exact multiplicities (the root test of the lookup cannot count them).
+ *  - counts[poly_modulus_degree]: items in bin s as apsu_he_bundle_bin_counts gives them, APSU_HE_NOT_A_BIN for a slot holding the zero
+ *    polynomial.
+ *  - roots[poly_modulus_degree * stride], may be NULL to get only the counts (the bins are found and checked all the same): bin s at
+ *    roots[s * stride], ascending, a value of multiplicity m written m times.  Words past a bin's count and rows of slots that are not
+ *    bins are left alone.
+ * For b = apsu_he_db_build_bundle(B), any update or merge of such BinBundles, and the same BinBundle loaded from an image or a DB file:
+ * the bins equal B bin by bin as sorted multisets, and apsu_he_db_build_bundle of them gives a byte-identical image.
+ * How: batching forces plain_modulus t = 1 (mod 2n), and the forward negacyclic transform mod t evaluates a polynomial at one coset of
+ * the subgroup of order n of F_t^*.  Scaling coefficient i by g^(j i) for a generator g moves it to coset j; the (t - 1) / n cosets tile
+ * F_t^*.  A bin's roots are the zeros of (t - 1) / n transforms (one workgroup per bin, persistent over the cosets, the bin's coefficients
+ * resident in LDS: k_bin_roots) plus a_0 = 0 for the root 0; multiplicities by the first derivative, and division where it vanishes.
+ * Refusals (nothing is written past the counts):
+ *  - roots given and stride below the largest count: APSU_HE_INVALID_ARGUMENT.
+ *  - a bin whose roots, counted with multiplicity, do not sum to its count: APSU_HE_INVALID_ARGUMENT; apsu_he_last_error names the first
+ *    such slot, its count and the number found.  Such a polynomial is not a product of linear factors: apsu_he_db_random_bundle makes
+ *    one, and so does a damaged image.
+ *  - (t - 1) / n > 65536: APSU_HE_LOGIC_ERROR, stating t and the coset count.  A property of the context, like q_0 <= 2 * plain_modulus;
+ *    every shipped parameter file stays under it (the largest has 8192 cosets).  A degree of poly_modulus_degree or more: likewise.
+ * Preconditions and locking are apsu_he_bundle_bin_counts's.  Synchronous; the BinBundle is only read.
+ * apsu_he_debug_bundle_bins_form: the same with the path named (0: the context's choice; 1: k_bin_roots, APSU_HE_LOGIC_ERROR for a ring
+ * size without one; 2: the per-coset composition gather + library transform + scan that serves those ring sizes) -- for the tests that
+ * hold the two against each other.  apsu_he_debug_bins_times: device time of the context's last such call: decode and counts, the root
+ * search, multiplicities and copy-back. */
+int apsu_he_bundle_bins(apsu_he_ctx *ctx, const apsu_he_bundle *bundle, uint64_t *roots, uint32_t *counts, uint32_t stride);
+int apsu_he_debug_bundle_bins_form(apsu_he_ctx *ctx, const apsu_he_bundle *bundle, uint64_t *roots, uint32_t *counts, uint32_t stride, int form);
+int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_ms, double *mult_ms);
 /* N1, compaction: the way back from many sparse BinBundles to few full ones.  The placement rule tries BinBundles newest first and
  * drops one only when it is empty, so after insertions and removals a bundle index keeps several half-empty BinBundles, and each costs
  * every query its fixed share: the high-power ciphertext products, a key switch, one result ciphertext, one block of PEQT / OT work.
@@ -463,6 +493,7 @@ int apsu_he_multi_db_update_bundle(apsu_he_multi *m, int bundle_id, const uint64
  * apsu_he_multi_db_bundle_info: where BinBundle `bundle_id` lies and what it is (every output may be NULL).
  * apsu_he_multi_db_index_bundles: the ids of one bundle index in cache order; *n = how many there are, the first min(*n, capacity) are written.
  * apsu_he_multi_db_bin_counts: apsu_he_bundle_bin_counts on the owning device.
+ * apsu_he_multi_db_bundle_bins: apsu_he_bundle_bins on the owning device, under the handle's lock.
  * apsu_he_multi_db_build_bundle: apsu_he_db_build_bundle on device_slot, or with device_slot = -1 on the slot the placement rule
  *   chooses; the new BinBundle is registered last (*bundle_id = the count before the call).
  * apsu_he_multi_db_remove_bundle: drops one BinBundle; new_id[count before the call].
@@ -481,6 +512,7 @@ int apsu_he_multi_db_bundle_count(apsu_he_multi *m, int *count);
 int apsu_he_multi_db_bundle_info(apsu_he_multi *m, int bundle_id, int *device_slot, uint32_t *bundle_idx, uint32_t *cache_idx, uint32_t *degree);
 int apsu_he_multi_db_index_bundles(apsu_he_multi *m, uint32_t bundle_idx, int *ids, int capacity, int *n);
 int apsu_he_multi_db_bin_counts(apsu_he_multi *m, int bundle_id, uint32_t *counts);
+int apsu_he_multi_db_bundle_bins(apsu_he_multi *m, int bundle_id, uint64_t *roots, uint32_t *counts, uint32_t stride);
 int apsu_he_multi_db_build_bundle(apsu_he_multi *m, int device_slot, uint32_t bundle_idx, uint32_t cache_idx, const uint64_t *roots,
                                   const uint32_t *counts, uint32_t bins, uint32_t stride, int *bundle_id);
 int apsu_he_multi_db_remove_bundle(apsu_he_multi *m, int bundle_id, int *new_id);
