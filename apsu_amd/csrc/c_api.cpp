@@ -1147,22 +1147,26 @@ std::string psu_params_to_json(const wire::PsuParamsWire &w)
     return j;
 }
 } // namespace
+// PSUParams::save (psu_params.cpp:182-238): the binary form of a parameter set
+static std::vector<uint8_t> psu_params_binary(const PSUParams &p, const HeParams &hp)
+{
+    sealio::EncryptionParameters e;
+    e.poly_modulus_degree = hp.n; e.coeff_modulus.assign(hp.key_q.begin(), hp.key_q.begin() + hp.K); e.plain_modulus = hp.t;
+    const std::vector<uint8_t> sp = sealio::save_encryption_parameters(e, sealio::COMPR_NONE);
+    wire::PsuParamsWire w;
+    w.felts_per_item = p.item_params.felts_per_item;
+    w.table_size = p.table_params.table_size; w.max_items_per_bin = p.table_params.max_items_per_bin; w.hash_func_count = p.table_params.hash_func_count;
+    w.ps_low_degree = p.query_params.ps_low_degree;
+    w.query_powers.assign(p.query_params.query_powers.begin(), p.query_params.query_powers.end());
+    w.seal_params = wire::Span{ sp.data(), sp.size() };
+    return wire::build_psu_params(w);
+}
 int apsu_he_wire_psu_params_save(const char *psu_params_json, uint8_t **out, size_t *out_size)
 {
     return guarded([&] {
         REQUIRE(psu_params_json && out && out_size, "null argument");
         const PSUParams p = PSUParams::Load(psu_params_json);
-        const HeParams hp = HeParams::FromPSUParams(p);
-        sealio::EncryptionParameters e;
-        e.poly_modulus_degree = hp.n; e.coeff_modulus.assign(hp.key_q.begin(), hp.key_q.begin() + hp.K); e.plain_modulus = hp.t;
-        const std::vector<uint8_t> sp = sealio::save_encryption_parameters(e, sealio::COMPR_NONE);
-        wire::PsuParamsWire w;
-        w.felts_per_item = p.item_params.felts_per_item;
-        w.table_size = p.table_params.table_size; w.max_items_per_bin = p.table_params.max_items_per_bin; w.hash_func_count = p.table_params.hash_func_count;
-        w.ps_low_degree = p.query_params.ps_low_degree;
-        w.query_powers.assign(p.query_params.query_powers.begin(), p.query_params.query_powers.end());
-        w.seal_params = wire::Span{ sp.data(), sp.size() };
-        wire_out(wire::build_psu_params(w), out, out_size);
+        wire_out(psu_params_binary(p, HeParams::FromPSUParams(p)), out, out_size);
     });
 }
 int apsu_he_wire_psu_params_load(const uint8_t *buf, size_t size, uint8_t **json_out_buf, size_t *json_size)
@@ -1295,6 +1299,164 @@ int apsu_he_db_upload_saved_bundle(apsu_he_ctx *c, const apsu_he_seal_ctx *sc, c
         } catch (...) { delete b; throw; }
         *out = b;
         if (consumed) *consumed = sb.consumed;
+    });
+}
+// ---- the way back: a saved database written (wire.h: build_bin_bundle, build_receiver_db_header; Engine::export_saved)
+int apsu_he_wire_saved_size_check(uint64_t bytes)
+{ return guarded([&] { wire::check_saved_size(bytes, "the buffer"); }); }
+int apsu_he_wire_build_bin_bundle(uint32_t bundle_idx, uint64_t mod, int stripped, int has_cache, const uint64_t *bin_felts, const uint64_t *bin_offsets,
+                                  size_t n_bins, const uint64_t *polyn_felts, const uint64_t *polyn_offsets, size_t n_polyns, const uint8_t *const *coeffs,
+                                  const size_t *coeff_sizes, uint32_t n_coeffs, uint8_t **out, size_t *out_size)
+{
+    return guarded([&] {
+        REQUIRE(out && out_size && (!n_coeffs || (coeffs && coeff_sizes)), "null argument");
+        wire::BinBundleParts p;
+        p.bundle_idx = bundle_idx; p.mod = mod; p.stripped = stripped != 0; p.has_cache = has_cache != 0;
+        p.bin_felts = bin_felts; p.bin_off = bin_offsets; p.n_bins = n_bins;
+        p.polyn_felts = polyn_felts; p.polyn_off = polyn_offsets; p.n_polyns = n_polyns;
+        for (uint32_t d = 0; d < n_coeffs; d++) p.coeffs.push_back(wire::Span{ coeffs[d], coeff_sizes[d] });
+        wire_out(wire::build_bin_bundle(p), out, out_size);
+    });
+}
+int apsu_he_wire_build_receiver_db_header(const uint8_t *psu_params, size_t psu_params_size, uint32_t label_byte_count, uint32_t nonce_byte_count,
+                                          uint64_t item_count, int compressed, int stripped, const uint8_t *oprf_key, size_t oprf_key_size,
+                                          const uint64_t *hashed_items, size_t n_hashed_items, uint32_t bin_bundle_count, uint8_t **out, size_t *out_size)
+{
+    return guarded([&] {
+        REQUIRE(out && out_size, "null argument");
+        wire::ReceiverDbHeaderParts h;
+        h.params = wire::Span{ psu_params, psu_params_size }; h.oprf_key = wire::Span{ oprf_key, oprf_key_size };
+        h.label_byte_count = label_byte_count; h.nonce_byte_count = nonce_byte_count; h.item_count = item_count;
+        h.compressed = compressed != 0; h.stripped = stripped != 0;
+        h.hashed_items = hashed_items; h.n_hashed_items = n_hashed_items; h.bin_bundle_count = bin_bundle_count;
+        wire_out(wire::build_receiver_db_header(h), out, out_size);
+    });
+}
+int apsu_he_wire_receiver_db_header_fields(const uint8_t *buf, size_t size, const uint8_t **psu_params, size_t *psu_params_size, const uint8_t **oprf_key,
+                                           size_t *oprf_key_size, const uint8_t **hashed_items, size_t *n_hashed_items, uint32_t *nonce_byte_count)
+{
+    return guarded([&] {
+        REQUIRE(buf, "null argument");
+        const wire::ReceiverDbHeader h = wire::parse_receiver_db_header(buf, size);
+        if (psu_params) *psu_params = h.params.p;
+        if (psu_params_size) *psu_params_size = h.params.n;
+        if (oprf_key) *oprf_key = h.oprf_key.p;
+        if (oprf_key_size) *oprf_key_size = h.oprf_key.n;
+        if (hashed_items) *hashed_items = h.hashed_items.p;
+        if (n_hashed_items) *n_hashed_items = (size_t)h.hashed_item_count;
+        if (nonce_byte_count) *nonce_byte_count = h.nonce_byte_count;
+    });
+}
+int apsu_he_wire_bin_bundle_rows(const uint8_t *buf, size_t size, int which, uint64_t *felts, size_t felt_capacity, uint64_t *offsets, size_t offset_capacity,
+                                 size_t *n_rows, size_t *n_felts)
+{
+    return guarded([&] {
+        REQUIRE(buf && (which == 0 || which == 1), "bad argument");
+        const wire::SavedBinBundle sb = wire::parse_bin_bundle(buf, size, which == 1);
+        const auto &m = which == 0 ? sb.item_bins : sb.matching_polyns;
+        size_t total = 0;
+        for (const auto &row : m) total += row.size();
+        if (n_rows) *n_rows = m.size();
+        if (n_felts) *n_felts = total;
+        if (offsets) {
+            REQUIRE(offset_capacity >= m.size() + 1, "output buffer too small");
+            offsets[0] = 0;
+            for (size_t i = 0; i < m.size(); i++) offsets[i + 1] = offsets[i] + m[i].size();
+        }
+        if (felts) {
+            REQUIRE(felt_capacity >= total, "output buffer too small");
+            size_t at = 0;
+            for (const auto &row : m) { std::copy(row.begin(), row.end(), felts + at); at += row.size(); }
+        }
+    });
+}
+int apsu_he_wire_bin_bundle_coeffs(const uint8_t *buf, size_t size, const uint8_t **data, size_t *data_sizes, uint32_t capacity, uint32_t *count)
+{
+    return guarded([&] {
+        REQUIRE(buf && count, "null argument");
+        const wire::SavedBinBundle sb = wire::parse_bin_bundle(buf, size);
+        *count = sb.has_cache ? (uint32_t)sb.batched_coeffs.size() : 0;
+        if (!data && !data_sizes) return;
+        REQUIRE(data && data_sizes && capacity >= *count, "output buffer too small");
+        for (uint32_t d = 0; d < *count; d++) { data[d] = sb.batched_coeffs[d].p; data_sizes[d] = sb.batched_coeffs[d].n; }
+    });
+}
+int apsu_he_wire_bin_bundle_extras(const uint8_t *buf, size_t size, int *has_cache, int32_t *label_bins, int32_t *felt_interp_polyns, int32_t *batched_interp_polyns)
+{
+    return guarded([&] {
+        REQUIRE(buf, "null argument");
+        const wire::SavedBinBundle sb = wire::parse_bin_bundle(buf, size);
+        if (has_cache) *has_cache = sb.has_cache ? 1 : 0;
+        if (label_bins) *label_bins = sb.has_label_bins ? (int32_t)sb.label_bins : -1;
+        if (felt_interp_polyns) *felt_interp_polyns = sb.has_felt_interp ? (int32_t)sb.felt_interp : -1;
+        if (batched_interp_polyns) *batched_interp_polyns = sb.has_batched_interp ? (int32_t)sb.batched_interp : -1;
+    });
+}
+namespace {
+// SEAL's parms_id of the level the NTT-form plaintexts of a BinBundle are at (bundle_layout.h: pt_level, the same for every degree)
+const uint64_t *saved_ntt_parms_id(const Engine &E, const apsu_he_seal_ctx *sc)
+{
+    const HeParams &hp = E.he();
+    const PSUParams *psu = E.psu();
+    REQUIRE(psu, "context was created without PSUParams");
+    REQUIRE(sc->n == hp.n && sc->K == (size_t)hp.K && sc->t == hp.t, "the SEAL context belongs to other parameters");
+    const int pt_level = bundle_layout(psu->query_params.ps_low_degree, 0, hp.first_chain_idx).pt_level;
+    return seal_level(sc, pt_level).parms_id;
+}
+// the caller's fields of a saved database's header, checked against what ReceiverDB::Load does with them
+wire::ReceiverDbHeaderParts saved_header(const std::vector<uint8_t> &params, uint32_t flags, const uint8_t *oprf_key, size_t oprf_key_size,
+                                         const uint64_t *hashed_items, size_t n_hashed_items, uint64_t item_count, const std::vector<uint8_t> &zero_key)
+{
+    const bool stripped = (flags & APSU_HE_SAVED_STRIPPED) != 0;
+    REQUIRE((oprf_key || !oprf_key_size) && (hashed_items || !n_hashed_items), "null argument");
+    // ReceiverDB::Load copies oprf_key_size = 32 bytes out of the vector whatever its length (receiver_db.cpp:1324-1335)
+    REQUIRE(oprf_key_size == 32 || (stripped && oprf_key_size == 0), "the OPRF key has 32 bytes (a stripped database may give none: 32 zero bytes are written)");
+    // ... and refuses an unstripped database whose item count is not the number of its hashed items (:1345-1352)
+    if (!stripped && item_count != n_hashed_items)
+        throw std::invalid_argument("item_count " + std::to_string(item_count) + " is not the number of hashed items " + std::to_string(n_hashed_items) +
+                                    ": ReceiverDB::Load refuses such a database unless it is stripped");
+    wire::ReceiverDbHeaderParts h;
+    h.params = wire::Span{ params.data(), params.size() };
+    h.oprf_key = oprf_key_size ? wire::Span{ oprf_key, oprf_key_size } : wire::Span{ zero_key.data(), zero_key.size() };
+    h.hashed_items = hashed_items; h.n_hashed_items = n_hashed_items; h.item_count = item_count;
+    return h;
+}
+} // namespace
+int apsu_he_bundle_export_saved(apsu_he_ctx *c, const apsu_he_seal_ctx *sc, const apsu_he_bundle *b, uint32_t flags, int compr_mode, uint8_t **out,
+                                size_t *out_size)
+{
+    return guarded([&] {
+        REQUIRE(c && sc && b && out && out_size, "null argument");
+        wire_out(c->eng->export_saved(*b->b, saved_ntt_parms_id(*c->eng, sc), flags, compr_mode), out, out_size);
+    });
+}
+int apsu_he_debug_export_times(apsu_he_ctx *c, double *ms6)
+{ return guarded([&] { REQUIRE(c && ms6, "null argument"); c->eng->export_times(ms6); }); }
+int apsu_he_db_export_saved(apsu_he_ctx *c, const apsu_he_seal_ctx *sc, const char *path, const apsu_he_bundle *const *bundles, int count, uint32_t flags,
+                            int compr_mode, const uint8_t *oprf_key, size_t oprf_key_size, const uint64_t *hashed_items, size_t n_hashed_items,
+                            uint64_t item_count)
+{
+    return guarded([&] {
+        REQUIRE(c && sc && path && count >= 0 && (bundles || !count), "null argument");
+        const uint64_t *pid = saved_ntt_parms_id(*c->eng, sc);
+        const std::vector<uint8_t> params = psu_params_binary(*c->eng->psu(), c->eng->he()), zero_key(32, 0);
+        const wire::ReceiverDbHeaderParts h = saved_header(params, flags, oprf_key, oprf_key_size, hashed_items, n_hashed_items, item_count, zero_key);
+        std::vector<Engine *> engs((size_t)count, c->eng.get());
+        std::vector<const Bundle *> bs((size_t)count);
+        for (int i = 0; i < count; i++) { REQUIRE(bundles[i], "null bundle"); bs[(size_t)i] = bundles[i]->b.get(); }
+        saved_db_export(path, engs.data(), bs.data(), (size_t)count, h, pid, flags, compr_mode);
+    });
+}
+int apsu_he_multi_db_export_saved(apsu_he_multi *m, const apsu_he_seal_ctx *sc, const char *path, uint32_t flags, int compr_mode, const uint8_t *oprf_key,
+                                  size_t oprf_key_size, const uint64_t *hashed_items, size_t n_hashed_items, uint64_t item_count)
+{
+    return guarded([&] {
+        REQUIRE(m && sc && path, "null argument");
+        Engine &E = m->m->engine(0);
+        const uint64_t *pid = saved_ntt_parms_id(E, sc);
+        const std::vector<uint8_t> params = psu_params_binary(m->m->psu(), m->m->he()), zero_key(32, 0);
+        const wire::ReceiverDbHeaderParts h = saved_header(params, flags, oprf_key, oprf_key_size, hashed_items, n_hashed_items, item_count, zero_key);
+        m->m->export_saved_db(path, h, pid, flags, compr_mode);
     });
 }
 int apsu_he_seal_relin_keys_load(const apsu_he_seal_ctx *c, const uint8_t *buf, size_t size, uint64_t *ksk, size_t capacity_words, size_t *words,

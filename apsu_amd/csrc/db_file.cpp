@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -70,6 +71,48 @@ void pad_to(std::FILE *f, uint64_t &pos, uint64_t target, const std::string &pat
     }
 }
 } // namespace
+
+void saved_db_export(const std::string &path, Engine *const *engines, const Bundle *const *bundles, size_t count, wire::ReceiverDbHeaderParts header,
+                     const uint64_t ntt_parms_id[4], uint32_t flags, int compr, double *file_ms)
+{
+    if (count && (!engines || !bundles)) throw std::invalid_argument("null argument");
+    if (count > 0xffffffffull) throw std::invalid_argument("too many BinBundles for one saved database");
+    for (size_t i = 0; i < count; i++)
+        if (!engines[i] || !bundles[i]) throw std::invalid_argument("null bundle");
+    // bundle-index-major, the caller's order within an index (ReceiverDB::save walks bin_bundles_[bundle_idx] in turn)
+    std::vector<size_t> order(count);
+    for (size_t i = 0; i < count; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return bundles[a]->bundle_idx < bundles[b]->bundle_idx; });
+    header.bin_bundle_count = (uint32_t)count;
+    header.compressed = compr != 0;
+    header.stripped = (flags & Engine::SAVED_STRIPPED) != 0;
+    const std::vector<uint8_t> head = wire::build_receiver_db_header(header);
+    const std::string tmp = path + ".tmp";
+    double ms = 0;
+    auto timed_write = [&](std::FILE *f, const std::vector<uint8_t> &buf) {
+        const auto t0 = std::chrono::steady_clock::now();
+        write_all(f, buf.data(), buf.size(), tmp);
+        ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    try {
+        {
+            File out;
+            out.f = std::fopen(tmp.c_str(), "wb");
+            if (!out.f) throw std::runtime_error("cannot create " + tmp + ": " + std::strerror(errno));
+            timed_write(out.f, head);
+            for (size_t k = 0; k < count; k++) {
+                const std::vector<uint8_t> one = engines[order[k]]->export_saved(*bundles[order[k]], ntt_parms_id, flags, compr);
+                timed_write(out.f, one);
+            }                                                          // (`one` is released before the next BinBundle is exported)
+            if (std::fflush(out.f) != 0) throw std::runtime_error("cannot write " + tmp + ": " + std::strerror(errno));
+        }
+        if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot move " + tmp + " to " + path + ": " + std::strerror(errno));
+    } catch (...) {
+        std::remove(tmp.c_str());                                      // a failing call leaves neither file
+        throw;
+    }
+    if (file_ms) *file_ms = ms;
+}
 
 void db_file_save(const std::string &path, Engine *const *engines, const Bundle *const *bundles, size_t count)
 {

@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "wire.h"
+
 namespace apsu_he {
 
 class Engine;
@@ -27,6 +29,14 @@ struct DbFileEntry {
 // Writes the file: every BinBundle is downloaded from its device once (Engine::save_bundle) and appended.  bundles[i] may live on
 // different engines of the same parameters (engines[i]): the shards of a multi-device DB go to one file.
 void db_file_save(const std::string &path, Engine *const *engines, const Bundle *const *bundles, size_t count);
+
+// The database in the reference's saved format (ReceiverDB::save, receiver_db.cpp:1182-1255; wire.h): the header, then every
+// BinBundle as Engine::export_saved gives it, bundle-index-major and in the given order within a bundle index.  `header` carries the
+// caller's fields (parameters, OPRF key, hashed items, item count); bin_bundle_count, compressed and stripped are set here from
+// count, compr and flags.  One BinBundle is exported, written and released before the next.  Writes path + ".tmp" and renames it; a
+// call that throws leaves neither file.  file_ms (may be null): host time spent writing.
+void saved_db_export(const std::string &path, Engine *const *engines, const Bundle *const *bundles, size_t count, wire::ReceiverDbHeaderParts header,
+                     const uint64_t ntt_parms_id[4], uint32_t flags, int compr, double *file_ms = nullptr);
 
 class DbFile {
 public:

@@ -11,6 +11,7 @@
 #include "bin_lookup.h"
 #include "bin_merge.h"
 #include "bin_roots.h"
+#include "bin_rows.h"
 
 namespace apsu_he {
 
@@ -93,6 +94,9 @@ void launch_roots_scan(const u64 *rows, size_t n, u32 nrows, const u64 *pts, u64
 // divides the columns of poly in place
 void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u32 n_occ, Mod t, const u64 *hits, const u32 *found, u32 *mult, u32 hstride,
                        hipStream_t st);
+// the bins' polynomials as ragged rows (Engine::export_saved; bin_rows.h): out[off[s] + d] = poly[d][s], d <= counts[s], s < bins.
+// off: rows_offsets' scan (bins + 1 words), tops: rows_tile_tops, both on the device; out holds off[bins] words.
+void launch_bins_rows(const u64 *poly, size_t n, u32 rows, const u32 *counts, const u64 *off, const int *tops, u32 bins, u64 *out, hipStream_t st);
 void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 void launch_gather_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 // N1: algebraize_item for `count` 16-byte items -> out[count][felts]; bpf = bits per field element, item_bits = felts * bpf

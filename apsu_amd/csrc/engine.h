@@ -200,6 +200,16 @@ public:
     // form: BINS_FORM_AUTO, or one of the two paths by name (the debug call of the tests).  `b` is only read.
     enum { BINS_FORM_AUTO = 0, BINS_FORM_KERNEL = 1, BINS_FORM_COMPOSED = 2 };
     void bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form = BINS_FORM_AUTO);
+    // N2 towards the reference (include/apsu_he.h: apsu_he_bundle_export_saved): the BinBundle as BinBundle::save writes it
+    // (wire.h: build_bin_bundle), read by the reference's BinBundle::load and by apsu_he_db_upload_saved_bundle.  ntt_parms_id: SEAL's
+    // parms_id of chain level b.pt_level (the engine does not hash parameters; the SEAL context of the C ABI does).  One decode serves
+    // the bins (bundle_bins), the bins' polynomials (k_bins_rows, bin_rows.h) and the coefficient-form plaintexts; the NTT-form ones
+    // are the stored rows, unpacked one degree at a time.  compr: sealio::COMPR_NONE or COMPR_ZSTD.  `b` is only read.
+    enum { SAVED_STRIPPED = 1, SAVED_NO_CACHE = 2 };
+    std::vector<uint8_t> export_saved(const Bundle &b, const u64 ntt_parms_id[4], uint32_t flags, int compr);
+    // time of the last export_saved call in ms: decode and counts, the root search and multiplicities, k_bins_rows (device, by events);
+    // the copies to the host, the plaintexts' serialisation, the buffer's assembly (host clock)
+    void export_times(double ms[6]);
     // device time of the last bundle_bins call: decode and counts, the root search, multiplicities and copy-back
     void bins_times(double *decode_ms, double *roots_ms, double *mult_ms);
     // device time of the last merge_bundles call: the decodes and counts, the product kernels, the re-encode
@@ -483,7 +493,9 @@ private:
     // (engine_bundles.cpp, like everything from here to unlift_exact_)
     void finish_bundle(Bundle &b, const u64 *raw);     // raw: [degree+1][n] coefficient-form plaintexts mod t (device)
     void encode_bundle(Bundle &b, const u64 *poly);    // poly: [degree+1][n] slot values -> BatchEncoder::encode, then finish_bundle
-    void decode_bundle(const Bundle &b, u64 *poly);    // the inverse: the stored coefficients back to slot values [degree+1][n] mod t
+    // the inverse: the stored coefficients back to slot values [degree+1][n] mod t.  coeff (may be null): [degree+1][n], the coefficient
+    // form mod t on the way there -- what BatchEncoder::encode made of each degree, before the forward transform mod t
+    void decode_bundle(const Bundle &b, u64 *poly, u64 *coeff = nullptr);
     // decode each BinBundle in turn through the arena; counts (may be null): [n_bundles][n]; flags (null when count == 0): [n_bundles][count * F]
     void lookup_impl(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count, uint32_t *counts,
                      unsigned char *flags);
@@ -494,6 +506,14 @@ private:
     double merge_ms_[3] = { 0, 0, 0 };
     EventStamps bins_evs_;                             // bundle_bins' four time stamps
     double bins_ms_[3] = { 0, 0, 0 };
+    // bundle_bins without the context's lock.  tap (may be null) is called once the counts are on the host and before the search
+    // divides the columns of poly: export_saved takes the bins' rows and the coefficient-form plaintexts there, from the same decode
+    struct BinsTap { virtual void after_counts(const u64 *poly, const u64 *coeff, const uint32_t *dcounts, const uint32_t *counts) = 0; virtual ~BinsTap() = default; };
+    void bins_impl(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form, BinsTap *tap);
+    // the coefficient-form rows of decode_bundle's `coeff` that a saved BinBundle carries as they are: a_0, then the a_{i h} by slot
+    void keep_coeff_rows(const Bundle &b, const u64 *coeff, DevBuf &keep);
+    EventStamps export_evs_;
+    double export_ms_[6] = { 0, 0, 0, 0, 0, 0 };
     void roots_tables();                               // the context's generator, step table and point table, made by the first bundle_bins
     u64 roots_g_ = 0;
     DevBuf d_roots_step_, d_roots_pts_;                // g^i (u32) and the forward transform mod t of the polynomial X, n words each

@@ -3,6 +3,11 @@
 // (engine.cpp) the arena, the streams and the transform launcher (engine_impl.h).
 #include "engine_impl.h"
 
+#include <chrono>
+
+#include "seal_codec.h"
+#include "wire.h"
+
 namespace apsu_he {
 
 static void bundle_shape(const BundleLayout &y, Bundle &b)
@@ -230,7 +235,7 @@ void Engine::encode_bundle(Bundle &b, const u64 *poly)
 // The inverse of encode_bundle, whoever made the BinBundle: coefficient d -> its stored form as in finish_bundle (a_0 raw; NTT-form
 // rows and the pre-lifted a_{i h}: limb 0, the residues mod q_0), inverse NTT over q_0, un-lift (bin_update.h; SEAL's un-lifted
 // monomials included), forward NTT mod t, slot gather -- BatchEncoder::decode.
-void Engine::decode_bundle(const Bundle &b, u64 *poly)
+void Engine::decode_bundle(const Bundle &b, u64 *poly, u64 *coeff)
 {
     const uint32_t degree = b.degree;
     const size_t n = hp_.n, Lpt = b.pt_level + 1;
@@ -249,6 +254,7 @@ void Engine::decode_bundle(const Bundle &b, u64 *poly)
         d_ntt(raw + n, degree, map_ct(), 1, true, data_primes_narrow_);
         launch_unlift(raw + n, (size_t)degree * n, hp_.t, hp_.key_q[0], st_);
     }
+    if (coeff) D2D(coeff, raw, (size_t)(degree + 1) * n);
     d_ntt(raw, degree + 1, map_ct() + hp_.plain_id(), 1, false, false);
     launch_gather_slots(raw, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), poly, n, (int)degree + 1, st_);
 }
@@ -483,6 +489,11 @@ void Engine::bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t
 {
     Enter g(this);
     TIER1_SLOTS();
+    bins_impl(b, roots, counts, stride, form, nullptr);
+}
+
+void Engine::bins_impl(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form, BinsTap *tap)
+{
     lookup_check("bins");
     const size_t n = hp_.n;
     const u32 cosets = roots_coset_count(hp_.t, n);                    // (refuses a plain modulus with too many cosets)
@@ -505,13 +516,15 @@ void Engine::bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t
         bins_evs_.record(0, st_);
         u64 *poly = ws((size_t)(b.degree + 1) * n);                    // [d][slot] slot values of the batched polynomial
         uint32_t *dcounts = ws_as<uint32_t>(n);
+        u64 *coeff = tap ? ws((size_t)(b.degree + 1) * n) : nullptr;
         const size_t mark = arena_off_;
-        decode_bundle(b, poly);
+        decode_bundle(b, poly, coeff);
         arena_off_ = mark;                                             // the decode's workspace is free again (stream order)
         launch_bin_counts(poly, n, b.degree + 1, dcounts, st_);
         HIP_CHECK(hipMemcpyAsync(counts, dcounts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
         bins_evs_.record(1, st_);
         sync();                                                        // which bins are occupied, and the lists' size, are decided on the host
+        if (tap) tap->after_counts(poly, coeff, dcounts, counts);
         for (size_t s = 0; s < n; s++)
             if (counts[s] != LOOKUP_NONE && counts[s] >= 1) { occ.push_back((uint32_t)s); hstride = std::max(hstride, counts[s]); }
         if (roots && stride < hstride) throw std::invalid_argument("bins: stride " + std::to_string(stride) + " is below the largest bin count " + std::to_string(hstride));
@@ -798,6 +811,168 @@ Engine::CompactResult Engine::compact(uint32_t bundle_idx, const Bundle *const *
         if (members.size() >= 2) res.merged[g] = merge_bundles(members.data(), (uint32_t)members.size(), members[0]->cache_idx);
     }
     return res;
+}
+
+// ---- N2 towards the reference: a resident BinBundle as BinBundle::save writes it (wire.h: build_bin_bundle; bin_rows.h)
+void Engine::keep_coeff_rows(const Bundle &b, const u64 *coeff, DevBuf &keep)
+{
+    const size_t n = hp_.n;
+    const size_t H = b.use_ps ? b.H : 0;
+    keep.alloc((H + 1) * n * sizeof(u64));
+    D2D(keep.u(), coeff, n);
+    for (const BundleRun &r : layout_of(b.degree).runs)
+        if (r.kind == COEFF_LIFTED)
+            for (uint32_t i = 0; i < r.count; i++) D2D(keep.u() + (1 + r.first_slot + i) * n, coeff + (size_t)(r.d0 + i) * n, n);
+}
+
+static double host_ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+std::vector<uint8_t> Engine::export_saved(const Bundle &b, const u64 ntt_parms_id[4], uint32_t flags, int compr)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("export_saved");
+    if (flags & ~(uint32_t)(SAVED_STRIPPED | SAVED_NO_CACHE)) throw std::invalid_argument("export_saved: unknown flag");
+    const bool stripped = (flags & SAVED_STRIPPED) != 0, cache = !(flags & SAVED_NO_CACHE);
+    if (stripped && !cache) throw std::invalid_argument("export_saved: a stripped BinBundle holds nothing but its cache, so STRIPPED and NO_CACHE together leave nothing to save");
+    if (compr != sealio::COMPR_NONE && compr != sealio::COMPR_ZSTD) throw std::invalid_argument("export_saved: compr_mode is none (0) or zstd (2)");
+    const size_t n = hp_.n;
+    const uint32_t bins = psu_.bins_per_bundle, max_items = psu_.table_params.max_items_per_bin, degree = b.degree;
+    // (unstripped, the same bound comes out of the bin counts below, with the bin's name)
+    if (stripped && degree + 1 > max_items)
+        throw std::invalid_argument("export_saved: the BinBundle has " + std::to_string(degree + 1) + " plaintexts, BinBundle::load accepts max_items_per_bin = " +
+                                    std::to_string(max_items) + " at most");
+    const BundleLayout y = layout_of(degree);
+    for (double &m : export_ms_) m = 0;
+    export_evs_.reserve(3);
+
+    std::vector<u64> rows, row_off, bin_felts, bin_off;
+    DevBuf keep;                                                       // a_0 and the a_{i h} in coefficient form mod t
+    double copy_ms = 0;
+    if (!stripped) {
+        // what the tap takes from bundle_bins' decode while the columns are whole
+        struct Tap : BinsTap {
+            Engine *e; const Bundle *b; uint32_t bins, max_items; bool cache;
+            std::vector<u64> *rows, *row_off; DevBuf *keep; double *copy_ms;
+            void after_counts(const u64 *poly, const u64 *coeff, const uint32_t *dcounts, const uint32_t *counts) override
+            {
+                const size_t n = e->hp_.n;
+                // a bin may hold max_items_per_bin - 1 items (receiver_db.cpp:388-389); build_bundle lets one more in, and its polynomial
+                // of max_items_per_bin + 1 coefficients is what BinBundle::load's cache check refuses
+                for (uint32_t s = 0; s < bins; s++)
+                    if (counts[s] != LOOKUP_NONE && counts[s] >= max_items)
+                        throw std::invalid_argument("bin " + std::to_string(s) + " holds " + std::to_string(counts[s]) + " items: a saved BinBundle has at most max_items_per_bin - 1 = " +
+                                                    std::to_string(max_items - 1) + " per bin (BinBundle::load refuses the cache otherwise)");
+                *row_off = rows_offsets(counts, bins, b->degree + 1);
+                if (!cache) return;
+                // BinBundle::load wants as many plaintexts as the longest matching polynomial has coefficients (bin_bundle.cpp:1356-1366): a
+                // BinBundle uploaded with plaintexts above every bin's count has more
+                uint32_t longest = 0;
+                for (uint32_t s = 0; s < bins; s++) longest = std::max(longest, counts[s]);
+                if (longest != b->degree)
+                    throw std::invalid_argument("export_saved: the BinBundle has degree " + std::to_string(b->degree) + " but its longest bin holds " + std::to_string(longest) +
+                                                " items: BinBundle::load refuses a cache whose plaintexts outnumber the longest matching polynomial's coefficients");
+                const std::vector<int> tops = rows_tile_tops(counts, n, bins);
+                const u64 total = row_off->back();
+                u64 *doff = e->ws(row_off->size()), *dout = e->ws(total + 1);
+                int *dtops = e->ws_as<int>(tops.size());
+                HIP_CHECK(hipMemcpyAsync(doff, row_off->data(), row_off->size() * sizeof(u64), hipMemcpyHostToDevice, e->st_));
+                HIP_CHECK(hipMemcpyAsync(dtops, tops.data(), tops.size() * sizeof(int), hipMemcpyHostToDevice, e->st_));
+                e->export_evs_.record(0, e->st_);
+                launch_bins_rows(poly, n, b->degree + 1, dcounts, doff, dtops, bins, dout, e->st_);
+                e->export_evs_.record(1, e->st_);
+                e->keep_coeff_rows(*b, coeff, *keep);
+                e->sync();
+                const auto t0 = std::chrono::steady_clock::now();
+                rows->resize(total);
+                if (total) HIP_CHECK(hipMemcpy(rows->data(), dout, total * sizeof(u64), hipMemcpyDeviceToHost));   // one contiguous copy
+                *copy_ms = host_ms_since(t0);
+                e->export_evs_.record(2, e->st_);
+            }
+        } tap;
+        tap.e = this; tap.b = &b; tap.bins = bins; tap.max_items = max_items; tap.cache = cache;
+        tap.rows = &rows; tap.row_off = &row_off; tap.keep = &keep; tap.copy_ms = &copy_ms;
+        const uint32_t stride = std::max<uint32_t>(1, degree);
+        std::vector<u64> roots(n * (size_t)stride);
+        std::vector<uint32_t> counts(n);
+        bins_impl(b, roots.data(), counts.data(), stride, BINS_FORM_AUTO, &tap);
+        double tap_ms = 0;
+        if (cache) { export_ms_[2] = export_evs_.ms(0, 1); tap_ms = export_evs_.ms(0, 2); }
+        export_ms_[0] = bins_ms_[0];
+        export_ms_[1] = std::max(0.0, bins_ms_[1] - tap_ms) + bins_ms_[2];
+        bin_off.assign((size_t)bins + 1, 0);
+        for (uint32_t s = 0; s < bins; s++) bin_off[s + 1] = bin_off[s] + counts[s];
+        bin_felts.resize(bin_off[bins]);
+        for (uint32_t s = 0; s < bins; s++) std::copy(roots.data() + (size_t)s * stride, roots.data() + (size_t)s * stride + counts[s], bin_felts.begin() + bin_off[s]);
+    } else {
+        // stripped: nothing but a_0 and the a_{i h} is decoded -- decode_bundle's steps up to the un-lift, on the H lifted slots alone
+        const size_t H = b.use_ps ? b.H : 0;
+        const int high = hp_.clamp_chain_idx(1);
+        keep.alloc((H + 1) * n * sizeof(u64));
+        D2D(keep.u(), b.a0.u(), n);
+        if (H) {
+            const size_t Lh = (size_t)high + 1, sb = b.packed ? b.lifted_slot_bytes : Lh * n * sizeof(u64);
+            launch_limb0_rows(dlevel(high), (int)Lh, b.lifted.p(), sb, b.packed, keep.u() + n, n, H, st_);
+            d_ntt(keep.u() + n, H, map_ct(), 1, true, data_primes_narrow_);
+            launch_unlift(keep.u() + n, H * n, hp_.t, hp_.key_q[0], st_);
+        }
+        sync();
+    }
+
+    // the plaintexts, one degree at a time: the whole dense BinBundle is never on the host
+    std::vector<std::vector<uint8_t>> blobs;
+    double ser_ms = 0;
+    if (cache) {
+        const size_t Lpt = (size_t)b.pt_level + 1;
+        blobs.resize((size_t)degree + 1);
+        std::vector<u64> host(std::max(Lpt, (size_t)1) * n);
+        DevBuf dense;
+        if (b.packed && b.ntt_count) dense.alloc(Lpt * n * sizeof(u64));
+        for (uint32_t d = 0; d <= degree; d++) {
+            const BundleWhere w = y.where(d);
+            const bool ntt = w.kind == COEFF_NTT;
+            const size_t words = ntt ? Lpt * n : n;
+            auto t0 = std::chrono::steady_clock::now();
+            if (!ntt) HIP_CHECK(hipMemcpy(host.data(), keep.u() + (w.kind == COEFF_RAW ? 0 : 1 + w.slot) * n, words * sizeof(u64), hipMemcpyDeviceToHost));
+            else if (b.packed) {
+                launch_unpack_rows(dlevel(b.pt_level), (int)Lpt, static_cast<const char *>(b.ntt.p()) + w.slot * b.ntt_slot_bytes, b.ntt_slot_bytes, dense.u(), n, 1, st_);
+                sync();
+                HIP_CHECK(hipMemcpy(host.data(), dense.p(), words * sizeof(u64), hipMemcpyDeviceToHost));
+            } else HIP_CHECK(hipMemcpy(host.data(), b.ntt.u() + w.slot * words, words * sizeof(u64), hipMemcpyDeviceToHost));
+            copy_ms += host_ms_since(t0);
+            t0 = std::chrono::steady_clock::now();
+            sealio::Plaintext pt;
+            if (ntt) std::copy(ntt_parms_id, ntt_parms_id + 4, pt.parms_id);
+            pt.coeff_count = words;
+            pt.data.assign(host.begin(), host.begin() + words);
+            blobs[d] = sealio::save_plaintext(pt, (uint8_t)compr);
+            ser_ms += host_ms_since(t0);
+        }
+    }
+    export_ms_[3] = copy_ms;
+    export_ms_[4] = ser_ms;
+
+    const auto t0 = std::chrono::steady_clock::now();
+    wire::BinBundleParts parts;
+    parts.bundle_idx = b.bundle_idx;
+    parts.mod = hp_.t;
+    parts.stripped = stripped;
+    parts.has_cache = cache;
+    parts.bin_felts = bin_felts.data(); parts.bin_off = bin_off.data(); parts.n_bins = stripped ? 0 : bins;
+    parts.polyn_felts = rows.data(); parts.polyn_off = row_off.data(); parts.n_polyns = stripped || !cache ? 0 : bins;
+    for (const auto &blob : blobs) parts.coeffs.push_back(wire::Span{ blob.data(), blob.size() });
+    std::vector<uint8_t> out = wire::build_bin_bundle(parts);           // (refuses a buffer over the 32-bit limit before it allocates)
+    export_ms_[5] = host_ms_since(t0);
+    return out;
+}
+
+void Engine::export_times(double ms[6])
+{
+    Enter g(this);
+    for (int i = 0; i < 6; i++) ms[i] = export_ms_[i];
 }
 
 // ---- N2: BinBundle image ------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@
 #include "bin_lookup.h"
 #include "bin_merge.h"
 #include "bin_roots.h"
+#include "bin_rows.h"
 #include "db_compact.h"
 #include "db_place.h"
 #include "multi_place.h"
@@ -877,6 +878,42 @@ int emu_merge_k() { return MERGE_K; }
 int emu_merge_counts(const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t max_items, uint32_t *sum)
 {
     try { merge_counts(a, b, n, max_items, sum); return 0; } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// k_bins_rows over poly[rows][n] as the workgroups run it (bin_rows.h): one workgroup per tile of 64 slots x 64 degrees, an explicit
+// loop over its waves and their 64 lanes, the padded LDS tile between the two phases.  counts: n words (emu_bin_counts' form);
+// out: at least off[bins] words, where off is rows_offsets' scan, also returned in off_out (bins + 1 words, may be null).
+// Returns off[bins], or -1 (emu_last_error).
+int64_t emu_bins_rows(const uint64_t *poly, uint64_t n, uint32_t rows, const uint32_t *counts, uint32_t bins, uint64_t *off_out, uint64_t *out)
+{
+    try {
+        if (bins > n) throw std::invalid_argument("more bins than slots");
+        const std::vector<u64> off = rows_offsets(counts, bins, rows);
+        const std::vector<int> tops = rows_tile_tops(counts, n, bins);
+        if (off_out) std::copy(off.begin(), off.end(), off_out);
+        const u32 dtiles = (rows + ROWS_TILE - 1) / ROWS_TILE;
+        std::vector<u64> tile(ROWS_LDS_WORDS);
+        for (size_t bx = 0; bx < tops.size(); bx++)
+            for (u32 by = 0; by < dtiles; by++) {
+                const size_t s0 = bx * ROWS_TILE;
+                const u32 d0 = by * ROWS_TILE;
+                const int top = tops[bx];
+                if ((int)d0 > top) continue;
+                std::fill(tile.begin(), tile.end(), ~(u64)0);      // (what a live store reads was loaded: anything else would show)
+                for (int wave = 0; wave < ROWS_WAVES; wave++)
+                    for (int dl = wave; dl < ROWS_TILE; dl += ROWS_WAVES)
+                        for (int lane = 0; lane < ROWS_TILE; lane++)
+                            if (rows_load_live(d0 + dl, s0 + lane, rows, n, top)) tile[rows_lds_at(dl, lane)] = poly[(size_t)(d0 + dl) * n + s0 + lane];
+                for (int wave = 0; wave < ROWS_WAVES; wave++)
+                    for (int sl = wave; sl < ROWS_TILE; sl += ROWS_WAVES) {
+                        const size_t s = s0 + sl;
+                        if (s >= bins) break;
+                        for (int lane = 0; lane < ROWS_TILE; lane++)
+                            if (rows_store_live(d0 + lane, s, counts[s], bins)) out[off[s] + d0 + lane] = tile[rows_lds_at(lane, sl)];
+                    }
+            }
+        return (int64_t)off[bins];
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
 // plan_compaction (db_compact.h).  counts [n_bundles][n]; group [n_bundles]; degree [n_bundles] (the first `return value` are written).

@@ -5,6 +5,7 @@
 #include "device.h"
 #include "ntt_wg.h"
 #include "bin_roots.h"
+#include "bin_rows.h"
 
 namespace apsu_he {
 
@@ -127,6 +128,29 @@ __global__ __launch_bounds__(256) void k_roots_mult(u64 *__restrict__ poly, size
     }
 }
 
+// ---- the bins' polynomials as ragged rows (Engine::export_saved; bin_rows.h): out[off[s] + d] = poly[d][s], d <= counts[s], for the
+// first `bins` slots.  One workgroup per tile of 64 slots x 64 degrees: row segments in (lane = slot), row segments out (lane =
+// degree), through a padded LDS tile.  tops: per tile of slots the largest count, -1 for none.  Nothing at or behind off[bins] is written.
+__global__ __launch_bounds__(ROWS_TILE * ROWS_WAVES) void k_bins_rows(const u64 *__restrict__ poly, size_t n, u32 rows, const u32 *__restrict__ counts,
+                                                                      const u64 *__restrict__ off, const int *__restrict__ tops, u32 bins,
+                                                                      u64 *__restrict__ out)
+{
+    __shared__ u64 tile[ROWS_LDS_WORDS];
+    const int lane = threadIdx.x & (ROWS_TILE - 1), wave = threadIdx.x / ROWS_TILE;
+    const size_t s0 = (size_t)blockIdx.x * ROWS_TILE;
+    const u32 d0 = blockIdx.y * ROWS_TILE;
+    const int top = tops[blockIdx.x];
+    if ((int)d0 > top) return;                                       // workgroup-uniform: no bin of this tile reaches these degrees
+    for (int dl = wave; dl < ROWS_TILE; dl += ROWS_WAVES)
+        if (rows_load_live(d0 + dl, s0 + lane, rows, n, top)) tile[rows_lds_at(dl, lane)] = poly[(size_t)(d0 + dl) * n + s0 + lane];
+    __syncthreads();
+    for (int sl = wave; sl < ROWS_TILE; sl += ROWS_WAVES) {
+        const size_t s = s0 + sl;
+        if (s >= bins) break;                                        // wave-uniform
+        if (rows_store_live(d0 + lane, s, counts[s], bins)) out[off[s] + d0 + lane] = tile[rows_lds_at(lane, sl)];
+    }
+}
+
 // ---- launches
 // workgroups a CU holds: two at n = 8192 (72 KiB of LDS each, 126 VGPRs: 4 waves per SIMD), two at 4096 (170 VGPRs: 2 waves per SIMD; a
 // budget of 168 or 128 registers spills there); resource report: profiles/r15_bundle_bins.txt
@@ -176,6 +200,14 @@ void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u
 {
     if (!n_occ) return;
     hipLaunchKernelGGL(k_roots_mult, dim3((n_occ + 3) / 4), dim3(256), 0, st, poly, n, occ, counts, n_occ, t, hits, found, mult, hstride);
+    KERNEL_CHECK();
+}
+
+void launch_bins_rows(const u64 *poly, size_t n, u32 rows, const u32 *counts, const u64 *off, const int *tops, u32 bins, u64 *out, hipStream_t st)
+{
+    if (!bins || !rows) return;
+    hipLaunchKernelGGL(k_bins_rows, dim3((unsigned)((n + ROWS_TILE - 1) / ROWS_TILE), (rows + ROWS_TILE - 1) / ROWS_TILE), dim3(ROWS_TILE * ROWS_WAVES), 0, st,
+                       poly, n, rows, counts, off, tops, bins, out);
     KERNEL_CHECK();
 }
 

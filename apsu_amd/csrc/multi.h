@@ -42,6 +42,9 @@ public:
     // appended to whatever is registered already.  Returns the number of BinBundles loaded.
     int load_file(const DbFile &f);
     void save_file(const std::string &path);                      // every registered BinBundle, in id order
+    // the database in the reference's saved format (db_file.h: saved_db_export): every bundle index in turn, index_bundles' order within
+    // it; each BinBundle is exported by the device that owns it, the file is written by the calling thread
+    void export_saved_db(const std::string &path, const wire::ReceiverDbHeaderParts &header, const uint64_t ntt_parms_id[4], uint32_t flags, int compr);
     int bundle_count() const { return (int)where_.size(); }
     int bundle_device(int id) const { return where_.at(id).first; }
     const Bundle &bundle(int id) const { const auto &w = where_.at(id); return *devs_[w.first]->bundles[w.second]; }

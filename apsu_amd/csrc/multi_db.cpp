@@ -95,6 +95,20 @@ std::vector<int> MultiEngine::index_bundles(uint32_t bundle_idx)
     return index_in_cache_order(registry_locked(), bundle_idx);
 }
 
+void MultiEngine::export_saved_db(const std::string &path, const wire::ReceiverDbHeaderParts &header, const uint64_t ntt_parms_id[4], uint32_t flags, int compr)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    std::vector<Engine *> engs;
+    std::vector<const Bundle *> bs;
+    const std::vector<RegUnit> reg = registry_locked();
+    for (uint32_t idx = 0; idx < psu_.bundle_idx_count; idx++)
+        for (int id : index_in_cache_order(reg, idx)) {
+            engs.push_back(devs_[(size_t)where_[(size_t)id].first]->eng.get());
+            bs.push_back(&bundle_locked(id));
+        }
+    saved_db_export(path, engs.data(), bs.data(), bs.size(), header, ntt_parms_id, flags, compr);
+}
+
 void MultiEngine::bin_counts(int id, uint32_t *counts)
 {
     std::lock_guard<std::mutex> g(mu_);

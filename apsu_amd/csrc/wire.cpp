@@ -18,14 +18,29 @@ namespace {
 // only requires that) and a vtable sits in front of its table (positive soffset), like in flatc's output.
 struct Writer {
     std::vector<uint8_t> b;
-    size_t pos() const { return b.size(); }
-    void align(size_t a) { while (b.size() % a) b.push_back(0); }
-    void u8(uint8_t v) { b.push_back(v); }
-    void u16(uint16_t v) { b.push_back((uint8_t)v); b.push_back((uint8_t)(v >> 8)); }
-    void u32(uint32_t v) { for (int i = 0; i < 4; i++) b.push_back((uint8_t)(v >> (8 * i))); }
-    void u64(uint64_t v) { for (int i = 0; i < 8; i++) b.push_back((uint8_t)(v >> (8 * i))); }
-    void bytes(const uint8_t *p, size_t n) { if (n) b.insert(b.end(), p, p + n); }
-    void patch32(size_t at, uint32_t v) { for (int i = 0; i < 4; i++) b[at + i] = (uint8_t)(v >> (8 * i)); }
+    // dry: nothing is stored, only the position moves -- the exact size of a buffer from its shapes, before anything is allocated
+    bool dry = false;
+    size_t len = 0;
+    size_t pos() const { return dry ? len : b.size(); }
+    void zeros(size_t n) { if (dry) len += n; else b.insert(b.end(), n, 0); }
+    void align(size_t a) { if (pos() % a) zeros(a - pos() % a); }
+    void u8(uint8_t v) { if (dry) len++; else b.push_back(v); }
+    void u16(uint16_t v) { u8((uint8_t)v); u8((uint8_t)(v >> 8)); }
+    void u32(uint32_t v) { for (int i = 0; i < 4; i++) u8((uint8_t)(v >> (8 * i))); }
+    void u64(uint64_t v) { for (int i = 0; i < 8; i++) u8((uint8_t)(v >> (8 * i))); }
+    void bytes(const uint8_t *p, size_t n) { if (dry) len += n; else if (n) b.insert(b.end(), p, p + n); }
+    // `n` 64-bit words, little-endian
+    void words(const uint64_t *p, size_t n)
+    {
+        if (dry) { len += 8 * n; return; }
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__
+        bytes(reinterpret_cast<const uint8_t *>(p), 8 * n);
+#else
+        for (size_t i = 0; i < n; i++) u64(p[i]);
+#endif
+    }
+    void patch32(size_t at, uint32_t v) { if (!dry) for (int i = 0; i < 4; i++) b[at + i] = (uint8_t)(v >> (8 * i)); }
+    void patch64(size_t at, uint64_t v) { if (!dry) for (int i = 0; i < 8; i++) b[at + i] = (uint8_t)(v >> (8 * i)); }
     // forward offset stored at `at`, pointing to the current position
     void link(size_t at) { patch32(at, (uint32_t)(pos() - at)); }
 };
@@ -38,21 +53,29 @@ struct TableWriter {
     size_t table_pos = 0;
     explicit TableWriter(Writer &w_) : w(w_) {}
     // sizes_in: inline byte size of every field id (1 u8, 4 u32 / offset, 4 k: a struct of k u32), 0 = not stored
-    void begin(const std::vector<uint16_t> &sizes_in)
+    // align8: the field ids whose inline data sits at an 8-aligned position (uint64 scalars, structs with a uint64 member)
+    void begin(const std::vector<uint16_t> &sizes_in, const std::vector<int> &align8 = {})
     {
         sizes = sizes_in;
+        std::vector<char> wide(sizes.size(), 0);
+        for (int id : align8) wide[(size_t)id] = 1;
         // trailing absent fields are trimmed from the vtable (flatc does the same)
         size_t nf = sizes.size();
         while (nf && !sizes[nf - 1]) nf--;
         // inline layout: soffset, then 4-byte fields, then 1-byte fields (largest first keeps everything aligned)
         std::vector<uint16_t> off(sizes.size(), 0);
         uint16_t cur = 4;
-        for (size_t i = 0; i < sizes.size(); i++) if (sizes[i] >= 4) { off[i] = cur; cur = (uint16_t)(cur + sizes[i]); }   // u32, offsets, structs of u32
+        if (!align8.empty()) {                                        // the 8-aligned fields first, behind the soffset and four bytes of padding
+            cur = 8;
+            for (size_t i = 0; i < sizes.size(); i++) if (sizes[i] && wide[i]) { off[i] = cur; cur = (uint16_t)(cur + (sizes[i] + 7) / 8 * 8); }
+        }
+        for (size_t i = 0; i < sizes.size(); i++) if (sizes[i] >= 4 && !wide[i]) { off[i] = cur; cur = (uint16_t)(cur + sizes[i]); }   // u32, offsets, structs of u32
         for (size_t i = 0; i < sizes.size(); i++) if (sizes[i] == 1) { off[i] = cur; cur += 1; }
         const uint16_t tbl_size = cur;
         const uint16_t vt_size = (uint16_t)(4 + 2 * nf);
         w.align(4);
-        if (vt_size % 4) w.u16(0);                                   // so that the table behind the vtable is 4-aligned
+        if (align8.empty()) { if (vt_size % 4) w.u16(0); }           // so that the table behind the vtable is 4-aligned
+        else while ((w.pos() + vt_size) % 8) w.u16(0);               // ... 8-aligned
         const size_t vt_pos = w.pos();
         w.u16(vt_size);
         w.u16(tbl_size);
@@ -60,12 +83,12 @@ struct TableWriter {
         table_pos = w.pos();
         w.u32((uint32_t)(table_pos - vt_pos));                        // soffset: vtable = table - soffset
         where.assign(sizes.size(), 0);
-        for (uint16_t o = 4; o < tbl_size; o++) w.u8(0);
+        w.zeros((size_t)tbl_size - 4);
         for (size_t i = 0; i < sizes.size(); i++) if (sizes[i]) where[i] = table_pos + off[i];
         w.align(4);
     }
     void set_u32(int id, uint32_t v) { w.patch32(where[id], v); }
-    void set_u8(int id, uint8_t v) { w.b[where[id]] = v; }
+    void set_u8(int id, uint8_t v) { if (!w.dry) w.b[where[id]] = v; }
     void link(int id) { w.align(4); w.link(where[id]); }              // the child starts here
 };
 
@@ -564,13 +587,14 @@ ReceiverDbHeader parse_receiver_db_header(const uint8_t *buf, size_t size)
         r.need(hv + 4, (size_t)len * 16);
         if (len && (hv + 4) % 8) r.bad();
         h.hashed_item_count = len;
+        h.hashed_items = Span{ r.b + hv + 4, (size_t)len * 16 };
     }
     h.bin_bundle_count = r.get_u32(t, 4, 0);
     return h;
 }
 
 // ================================================================================================ a saved BinBundle
-SavedBinBundle parse_bin_bundle(const uint8_t *buf, size_t size)
+SavedBinBundle parse_bin_bundle(const uint8_t *buf, size_t size, bool with_polyns)
 {
     // ReceiverDB::save writes the BinBundles one after the other: this one ends where its size prefix says
     if (!buf || size < 8) throw std::runtime_error("failed to load BinBundle: invalid buffer");
@@ -590,14 +614,176 @@ SavedBinBundle parse_bin_bundle(const uint8_t *buf, size_t size)
             out.item_bins.push_back(r.u64_vector(r.child(a, 0, true)));
         }
     }
+    if (const size_t v = r.child(t, 3, false)) { out.has_label_bins = true; out.label_bins = r.u32(v); }
     if (const size_t cpos = r.child(t, 4, false)) {
         const Reader::Table c = r.table(cpos);
-        (void)r.child(c, 0, true);                                                  // felt_matching_polyns: required, not needed here
+        if (!with_polyns) (void)r.child(c, 0, true);                                // felt_matching_polyns: required, not needed by the upload
+        else {
+            const Reader::Table m = r.table(r.child(c, 0, true));
+            for (size_t row : r.table_vector(r.child(m, 0, true))) {
+                const Reader::Table a = r.table(row);
+                out.matching_polyns.push_back(r.u64_vector(r.child(a, 0, true)));
+            }
+        }
+        if (const size_t v = r.child(c, 2, false)) { out.has_felt_interp = true; out.felt_interp = r.u32(v); }
+        if (const size_t v = r.child(c, 3, false)) { out.has_batched_interp = true; out.batched_interp = r.u32(v); }
         const Reader::Table bp = r.table(r.child(c, 1, true));                      // batched_matching_polyn
         for (size_t ppos : r.table_vector(r.child(bp, 0, true))) out.batched_coeffs.push_back(r.ciphertext(ppos));   // Plaintext { data } has Ciphertext's shape
         out.has_cache = true;
     }
     return out;
+}
+
+// ================================================================================================ the writers of a saved database
+void check_saved_size(uint64_t bytes, const char *what)
+{
+    if (bytes > SAVED_MAX_BYTES)
+        throw std::invalid_argument(std::string(what) + " would take " + std::to_string(bytes) + " bytes: a FlatBuffers buffer holds at most " +
+                                    std::to_string(SAVED_MAX_BYTES) + " (32-bit offsets)");
+}
+
+namespace {
+
+// [uint64] (or a vector of structs of uint64, `per` words each) at the current position; returns where its length word is
+size_t write_u64_vector(Writer &w, const uint64_t *v, size_t count, size_t per = 1)
+{
+    w.align(4);
+    if ((w.pos() + 4) % 8) w.u32(0);
+    const size_t at = w.pos();
+    w.u32((uint32_t)count);
+    w.words(v, count * per);
+    return at;
+}
+
+// an empty vector of tables; returns where it is
+size_t write_empty_vector(Writer &w)
+{
+    w.align(4);
+    const size_t at = w.pos();
+    w.u32(0);
+    return at;
+}
+
+// FEltMatrix { rows:[FEltArray { felts:[uint64] }] } from a flat ragged matrix; returns the table's position
+size_t write_felt_matrix(Writer &w, const uint64_t *felts, const uint64_t *off, size_t n_rows)
+{
+    TableWriter m(w);
+    m.begin({ 4 });
+    m.link(0);
+    w.u32((uint32_t)n_rows);
+    const size_t slots = w.pos();
+    w.zeros(4 * n_rows);
+    for (size_t i = 0; i < n_rows; i++) {
+        TableWriter a(w);
+        a.begin({ 4 });
+        w.patch32(slots + 4 * i, (uint32_t)(a.table_pos - (slots + 4 * i)));
+        const size_t at = write_u64_vector(w, felts + off[i], (size_t)(off[i + 1] - off[i]));
+        w.patch32(a.where[0], (uint32_t)(at - a.where[0]));
+    }
+    return m.table_pos;
+}
+
+void write_bin_bundle(Writer &w, const BinBundleParts &p)
+{
+    w.u32(0); w.u32(0);
+    TableWriter t(w);
+    t.begin({ (uint16_t)(p.bundle_idx ? 4 : 0), 8, 4, 4, (uint16_t)(p.has_cache ? 4 : 0), (uint16_t)(p.stripped ? 1 : 0) }, { 1 });
+    w.patch32(4, (uint32_t)(t.table_pos - 4));
+    if (p.bundle_idx) t.set_u32(0, p.bundle_idx);
+    w.patch64(t.where[1], p.mod);
+    if (p.stripped) t.set_u8(5, 1);
+    const size_t bins = write_felt_matrix(w, p.bin_felts, p.bin_off, p.stripped ? 0 : p.n_bins);
+    w.patch32(t.where[2], (uint32_t)(bins - t.where[2]));
+    const size_t labels = write_empty_vector(w);
+    w.patch32(t.where[3], (uint32_t)(labels - t.where[3]));
+    if (p.has_cache) {
+        TableWriter c(w);
+        c.begin({ 4, 4, 4, 4 });
+        w.patch32(t.where[4], (uint32_t)(c.table_pos - t.where[4]));
+        const size_t polyns = write_felt_matrix(w, p.polyn_felts, p.polyn_off, p.stripped ? 0 : p.n_polyns);
+        w.patch32(c.where[0], (uint32_t)(polyns - c.where[0]));
+        TableWriter bp(w);
+        bp.begin({ 4 });
+        w.patch32(c.where[1], (uint32_t)(bp.table_pos - c.where[1]));
+        bp.link(0);
+        write_ciphertext_vector(w, p.coeffs);                          // Plaintext { data } has Ciphertext's shape
+        const size_t fi = write_empty_vector(w);
+        w.patch32(c.where[2], (uint32_t)(fi - c.where[2]));
+        const size_t bi = write_empty_vector(w);
+        w.patch32(c.where[3], (uint32_t)(bi - c.where[3]));
+    }
+    w.align(4);
+}
+
+void write_receiver_db_header(Writer &w, const ReceiverDbHeaderParts &h)
+{
+    w.u32(0); w.u32(0);
+    TableWriter t(w);
+    t.begin({ 4, 24, 4, 4, (uint16_t)(h.bin_bundle_count ? 4 : 0) }, { 1 });
+    w.patch32(4, (uint32_t)(t.table_pos - 4));
+    w.patch32(t.where[1], h.label_byte_count);
+    w.patch32(t.where[1] + 4, h.nonce_byte_count);
+    w.patch64(t.where[1] + 8, h.item_count);
+    if (!w.dry) { w.b[t.where[1] + 16] = h.compressed ? 1 : 0; w.b[t.where[1] + 17] = h.stripped ? 1 : 0; }
+    if (h.bin_bundle_count) t.set_u32(4, h.bin_bundle_count);
+    t.link(0);
+    write_byte_vector(w, h.params);
+    t.link(2);
+    write_byte_vector(w, h.oprf_key);
+    const size_t hv = write_u64_vector(w, h.hashed_items, h.n_hashed_items, 2);
+    w.patch32(t.where[3], (uint32_t)(hv - t.where[3]));
+    w.align(4);
+}
+
+void check_bin_bundle_parts(const BinBundleParts &p)
+{
+    if (p.stripped && !p.has_cache) throw std::invalid_argument("a stripped BinBundle is saved with its cache (it holds nothing else)");
+    if (!p.stripped && p.n_bins && (!p.bin_off || (p.bin_off[p.n_bins] && !p.bin_felts))) throw std::invalid_argument("item_bins: null argument");
+    if (!p.stripped && p.has_cache && p.n_polyns && (!p.polyn_off || (p.polyn_off[p.n_polyns] && !p.polyn_felts)))
+        throw std::invalid_argument("felt_matching_polyns: null argument");
+    for (size_t i = 0; !p.stripped && i < p.n_bins; i++)
+        if (p.bin_off[i + 1] < p.bin_off[i]) throw std::invalid_argument("item_bins: offsets of row " + std::to_string(i) + " descend");
+    for (size_t i = 0; !p.stripped && p.has_cache && i < p.n_polyns; i++)
+        if (p.polyn_off[i + 1] < p.polyn_off[i]) throw std::invalid_argument("felt_matching_polyns: offsets of row " + std::to_string(i) + " descend");
+    for (const Span &c : p.coeffs)
+        if (!c.p && c.n) throw std::invalid_argument("batched_matching_polyn: null plaintext");
+}
+
+} // namespace
+
+uint64_t bin_bundle_bytes(const BinBundleParts &p)
+{
+    check_bin_bundle_parts(p);
+    Writer w;
+    w.dry = true;
+    write_bin_bundle(w, p);
+    return w.pos();
+}
+
+std::vector<uint8_t> build_bin_bundle(const BinBundleParts &p)
+{
+    const uint64_t total = bin_bundle_bytes(p);
+    check_saved_size(total, "the saved BinBundle");
+    Writer w;
+    w.b.reserve((size_t)total);
+    write_bin_bundle(w, p);
+    if (w.pos() != total) throw std::logic_error("build_bin_bundle: the size computed beforehand is not the size written");
+    return finish_size_prefixed(w);
+}
+
+std::vector<uint8_t> build_receiver_db_header(const ReceiverDbHeaderParts &h)
+{
+    if ((!h.params.p && h.params.n) || (!h.oprf_key.p && h.oprf_key.n) || (!h.hashed_items && h.n_hashed_items))
+        throw std::invalid_argument("ReceiverDB header: null argument");
+    Writer dry;
+    dry.dry = true;
+    write_receiver_db_header(dry, h);
+    check_saved_size(dry.pos(), "the saved ReceiverDB header");
+    Writer w;
+    w.b.reserve(dry.pos());
+    write_receiver_db_header(w, h);
+    if (w.pos() != dry.pos()) throw std::logic_error("build_receiver_db_header: the size computed beforehand is not the size written");
+    return finish_size_prefixed(w);
 }
 
 } // namespace wire

@@ -92,8 +92,28 @@ struct ReceiverDbHeader {
     uint64_t item_count = 0, hashed_item_count = 0;
     bool compressed = false, stripped = false;
     size_t consumed = 0;                                              // where the first BinBundle starts
+    Span hashed_items;                                                // hashed_item_count x { low_word, high_word }, little-endian, 8-aligned
 };
 ReceiverDbHeader parse_receiver_db_header(const uint8_t *buf, size_t size);
+
+// FlatBuffers offsets are 32 bit and flatbuffers::Verifier refuses a buffer of 2^31 bytes or more (FLATBUFFERS_MAX_BUFFER_SIZE):
+// throws std::invalid_argument naming `bytes` when a buffer of that size cannot be written.  Every builder below computes the exact
+// size of its buffer first (a dry run of the same code over the shapes, no allocation) and calls this before it allocates.
+constexpr uint64_t SAVED_MAX_BYTES = ((uint64_t)1 << 31) - 1;
+void check_saved_size(uint64_t bytes, const char *what);
+
+// The writer of that header (ReceiverDB::save, receiver_db.cpp:1182-1232).  Field order of the table as above; info is an inline struct
+// of 24 bytes at an 8-aligned position (label_byte_count u32, nonce_byte_count u32, item_count u64, compressed u8, stripped u8, 6 bytes
+// of padding), hashed_items a vector of 16-byte structs whose elements are 8-aligned.  hashed_items: [n_hashed_items][2] = low, high.
+struct ReceiverDbHeaderParts {
+    Span params, oprf_key;
+    uint32_t label_byte_count = 0, nonce_byte_count = 0, bin_bundle_count = 0;
+    uint64_t item_count = 0;
+    bool compressed = false, stripped = false;
+    const uint64_t *hashed_items = nullptr;
+    size_t n_hashed_items = 0;
+};
+std::vector<uint8_t> build_receiver_db_header(const ReceiverDbHeaderParts &h);
 
 // receiver/apsu/bin_bundle.fbs -- what ReceiverDB::save appends per BinBundle (BinBundle::save, bin_bundle.cpp:1085-1168; size-prefixed):
 //   BinBundle { bundle_idx:uint32; mod:uint64; item_bins:FEltMatrix (required); label_bins:[FEltMatrix]; cache:BinBundleCache; stripped:bool }
@@ -110,9 +130,33 @@ struct SavedBinBundle {
     std::vector<std::vector<uint64_t>> item_bins;        // [bin] -> field elements
     std::vector<Span> batched_coeffs;                    // cache.batched_matching_polyn.coeffs[d].data
     size_t consumed = 0;                                 // bytes of the buffer this BinBundle occupies (prefix included)
+    std::vector<std::vector<uint64_t>> matching_polyns;  // cache.felt_matching_polyns: [bin] -> coefficients, ascending (with_polyns only)
+    // the label side, which this path neither reads nor fills: is the vector there, and how many entries does it have
+    bool has_label_bins = false, has_felt_interp = false, has_batched_interp = false;
+    uint32_t label_bins = 0, felt_interp = 0, batched_interp = 0;
 };
 // throws std::runtime_error("failed to load BinBundle: invalid buffer")
-SavedBinBundle parse_bin_bundle(const uint8_t *buf, size_t size);
+// with_polyns: also copy the rows of cache.felt_matching_polyns out (the upload path never needs them; the field is verified either way)
+SavedBinBundle parse_bin_bundle(const uint8_t *buf, size_t size, bool with_polyns = false);
+
+// The writer (BinBundle::save, bin_bundle.cpp:1107-1169).  A ragged matrix arrives flat with n_rows + 1 offsets in words: row i is
+// felts[off[i] .. off[i + 1]).  What is written, in the table's field order: bundle_idx (left out when 0, the schema's default), mod
+// (8-aligned), item_bins (always: the field is required; no rows when stripped), label_bins (present, empty), cache unless has_cache
+// is false { felt_matching_polyns (required; no rows when stripped), batched_matching_polyn { coeffs[d] { data = coeffs[d] } },
+// felt_interp_polyns and batched_interp_polyns (present, empty) }, stripped (left out when false).  Every [uint64] has its length word
+// directly in front of 8-aligned elements.  stripped with has_cache false is refused (BinBundle::load: "stripped but no cache").
+struct BinBundleParts {
+    uint32_t bundle_idx = 0;
+    uint64_t mod = 0;
+    bool stripped = false, has_cache = true;
+    const uint64_t *bin_felts = nullptr, *bin_off = nullptr;          // item_bins
+    size_t n_bins = 0;
+    const uint64_t *polyn_felts = nullptr, *polyn_off = nullptr;      // cache.felt_matching_polyns
+    size_t n_polyns = 0;
+    std::vector<Span> coeffs;                                         // cache.batched_matching_polyn.coeffs[d].data
+};
+uint64_t bin_bundle_bytes(const BinBundleParts &p);                   // the exact size of build_bin_bundle's buffer, nothing allocated
+std::vector<uint8_t> build_bin_bundle(const BinBundleParts &p);
 
 } // namespace wire
 } // namespace apsu_he

@@ -213,3 +213,47 @@ def load_reference_db(blob, device=0):
     if at != len(blob):
         raise ValueError("trailing bytes behind the last BinBundle")
     return ctx, sc, bundles
+
+
+SAVED_STRIPPED, SAVED_NO_CACHE = 1, 2
+
+
+def _saved_flags(stripped, cache):
+    return (SAVED_STRIPPED if stripped else 0) | (0 if cache else SAVED_NO_CACHE)
+
+
+def export_saved_bundle(ctx, seal_ctx, bundle, stripped=False, cache=True, compr=COMPR_NONE):
+    """apsu_he_bundle_export_saved: a resident BinBundle -> the bytes BinBundle::save writes for it (bin_bundle.fbs), which
+    upload_saved_bundle and the reference's BinBundle::load read"""
+    out, size = u8p(), C.c_size_t()
+    _check(load_library().apsu_he_bundle_export_saved(ctx.h, seal_ctx.h, bundle.h, C.c_uint32(_saved_flags(stripped, cache)), int(compr),
+                                                      C.byref(out), C.byref(size)))
+    return _take(out, size)
+
+
+def export_saved_times(ctx):
+    """ms of the last export_saved_bundle: decode + counts, root search + multiplicities, k_bins_rows (device); copies to the host,
+    plaintext serialisation, buffer assembly (host)"""
+    ms = (C.c_double * 6)()
+    _check(load_library().apsu_he_debug_export_times(ctx.h, ms))
+    return dict(zip(("decode_counts", "bundle_bins", "bins_rows", "copies", "serialise", "assemble"), [float(v) for v in ms]))
+
+
+def export_saved_db(ctx_or_multi, seal_ctx, path, bundles=None, stripped=False, cache=True, compr=COMPR_NONE, oprf_key=b"", hashed_items=(),
+                    item_count=0):
+    """apsu_he_db_export_saved / apsu_he_multi_db_export_saved: the database as ReceiverDB::save writes it, into `path`.
+    ctx_or_multi: an HeContext with its `bundles`, or a MultiContext (bundles=None: everything registered on the handle).
+    hashed_items: [(low, high), ...]; the OPRF key and the hashed items are the caller's and are written as given."""
+    from .engine import MultiContext
+    hi = np.array([[int(a), int(b)] for a, b in hashed_items], dtype=np.uint64).reshape(-1, 2)
+    tail = (C.c_uint32(_saved_flags(stripped, cache)), int(compr), _buf(oprf_key), C.c_size_t(len(oprf_key)), hi.ctypes.data_as(u64p),
+            C.c_size_t(hi.shape[0]), C.c_uint64(int(item_count)))
+    L = load_library()
+    if isinstance(ctx_or_multi, MultiContext):
+        if bundles is not None:
+            raise ValueError("a MultiContext exports the BinBundles registered on it")
+        _check(L.apsu_he_multi_db_export_saved(ctx_or_multi.h, seal_ctx.h, os.fsencode(path), *tail))
+        return
+    bundles = list(bundles or [])
+    bh = (C.c_void_p * max(1, len(bundles)))(*[b.h for b in bundles])
+    _check(L.apsu_he_db_export_saved(ctx_or_multi.h, seal_ctx.h, os.fsencode(path), bh, len(bundles), *tail))

@@ -218,3 +218,94 @@ def receiver_db_header(buf):
                                                          C.byref(comp), C.byref(strip), C.byref(lab), C.byref(used)))
     return dict(params_json=_take(js, jn).decode(), item_count=items.value, bin_bundle_count=bbs.value, compressed=bool(comp.value),
                 stripped=bool(strip.value), label_byte_count=lab.value, consumed=used.value)
+
+
+def saved_size_check(nbytes):
+    """the bound every saved-database writer applies before it allocates: raises ApsuHeError naming the size above 2^31 - 1 bytes"""
+    _check(load_library().apsu_he_wire_saved_size_check(C.c_uint64(int(nbytes))))
+
+
+def _ragged(rows):
+    """[[felt, ...], ...] -> (flat uint64 array, offsets uint64 array of len(rows) + 1)"""
+    import numpy as np
+    off = np.zeros(len(rows) + 1, dtype=np.uint64)
+    if len(rows):
+        off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+    flat = np.array([int(v) for r in rows for v in r], dtype=np.uint64)
+    return flat, off
+
+
+def build_bin_bundle(bundle_idx, mod, item_bins=(), matching_polyns=(), coeffs=(), stripped=False, cache=True):
+    """BinBundle::save (bin_bundle.fbs): item_bins / matching_polyns are lists of rows of field elements, coeffs the SEAL-serialised
+    plaintexts of cache.batched_matching_polyn; label vectors are written present and empty"""
+    u64p = C.POINTER(C.c_uint64)
+    bf, bo = _ragged(item_bins)
+    pf, po = _ragged(matching_polyns)
+    keep = [_buf(c) for c in coeffs]
+    ptrs = (C.c_void_p * max(1, len(coeffs)))(*[C.addressof(k) for k in keep])
+    sizes = (C.c_size_t * max(1, len(coeffs)))(*[len(c) for c in coeffs])
+    out, size = u8p(), C.c_size_t()
+    _check(load_library().apsu_he_wire_build_bin_bundle(C.c_uint32(bundle_idx), C.c_uint64(mod), int(bool(stripped)), int(bool(cache)),
+                                                        bf.ctypes.data_as(u64p), bo.ctypes.data_as(u64p), C.c_size_t(len(item_bins)),
+                                                        pf.ctypes.data_as(u64p), po.ctypes.data_as(u64p), C.c_size_t(len(matching_polyns)),
+                                                        ptrs, sizes, C.c_uint32(len(coeffs)), C.byref(out), C.byref(size)))
+    return _take(out, size)
+
+
+def parse_bin_bundle(buf):
+    """one saved BinBundle, every field this library reads or writes -> dict(bundle_idx, mod, stripped, has_cache, item_bins,
+    matching_polyns (lists of lists), coeffs (list of bytes), label_bins, felt_interp_polyns, batched_interp_polyns (entries of the
+    vector, None where it is absent), consumed)"""
+    import numpy as np
+    L = load_library()
+    u64p = C.POINTER(C.c_uint64)
+    keep = _buf(buf)
+    n = C.c_size_t(len(buf))
+    info = bin_bundle_info(buf)
+
+    def rows(which):
+        nr, nf = C.c_size_t(), C.c_size_t()
+        _check(L.apsu_he_wire_bin_bundle_rows(keep, n, which, None, C.c_size_t(0), None, C.c_size_t(0), C.byref(nr), C.byref(nf)))
+        felts, off = np.zeros(max(1, nf.value), dtype=np.uint64), np.zeros(nr.value + 1, dtype=np.uint64)
+        _check(L.apsu_he_wire_bin_bundle_rows(keep, n, which, felts.ctypes.data_as(u64p), C.c_size_t(felts.size), off.ctypes.data_as(u64p),
+                                              C.c_size_t(off.size), C.byref(nr), C.byref(nf)))
+        return [[int(v) for v in felts[int(off[i]):int(off[i + 1])]] for i in range(nr.value)]
+
+    hc, lb, fi, bi = C.c_int(), C.c_int32(), C.c_int32(), C.c_int32()
+    _check(L.apsu_he_wire_bin_bundle_extras(keep, n, C.byref(hc), C.byref(lb), C.byref(fi), C.byref(bi)))
+    k = info["cache_coeffs"]
+    ptrs, sizes, cnt = (u8p * max(1, k))(), (C.c_size_t * max(1, k))(), C.c_uint32()
+    _check(L.apsu_he_wire_bin_bundle_coeffs(keep, n, ptrs, sizes, C.c_uint32(k), C.byref(cnt)))
+    coeffs = [C.string_at(ptrs[d], sizes[d]) for d in range(cnt.value)]
+    opt = lambda v: None if v.value < 0 else v.value
+    return dict(bundle_idx=info["bundle_idx"], mod=info["mod"], stripped=info["stripped"], has_cache=bool(hc.value), item_bins=rows(0),
+                matching_polyns=rows(1) if hc.value else [], coeffs=coeffs, label_bins=opt(lb), felt_interp_polyns=opt(fi),
+                batched_interp_polyns=opt(bi), consumed=info["consumed"])
+
+
+def build_receiver_db_header(psu_params, item_count=0, bin_bundle_count=0, compressed=False, stripped=False, oprf_key=b"", hashed_items=(),
+                             label_byte_count=0, nonce_byte_count=0):
+    """ReceiverDB::save's header (receiver_db.fbs): psu_params = psu_params_save's bytes, hashed_items = [(low, high), ...]"""
+    import numpy as np
+    hi = np.array([[int(a), int(b)] for a, b in hashed_items], dtype=np.uint64).reshape(-1, 2)
+    out, size = u8p(), C.c_size_t()
+    _check(load_library().apsu_he_wire_build_receiver_db_header(_buf(psu_params), C.c_size_t(len(psu_params)), C.c_uint32(label_byte_count),
+                                                                C.c_uint32(nonce_byte_count), C.c_uint64(item_count), int(bool(compressed)),
+                                                                int(bool(stripped)), _buf(oprf_key), C.c_size_t(len(oprf_key)),
+                                                                hi.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_size_t(hi.shape[0]),
+                                                                C.c_uint32(bin_bundle_count), C.byref(out), C.byref(size)))
+    return _take(out, size)
+
+
+def parse_receiver_db_header(buf):
+    """receiver_db_header's dict plus psu_params (bytes), oprf_key (bytes), hashed_items ([(low, high)]) and nonce_byte_count"""
+    import numpy as np
+    keep = _buf(buf)
+    d = receiver_db_header(buf)
+    pp, pn, kp, kn, hp, hn, nb = u8p(), C.c_size_t(), u8p(), C.c_size_t(), u8p(), C.c_size_t(), C.c_uint32()
+    _check(load_library().apsu_he_wire_receiver_db_header_fields(keep, C.c_size_t(len(buf)), C.byref(pp), C.byref(pn), C.byref(kp), C.byref(kn),
+                                                                C.byref(hp), C.byref(hn), C.byref(nb)))
+    words = np.frombuffer(C.string_at(hp, 16 * hn.value), dtype="<u8").reshape(-1, 2)
+    d.update(psu_params=C.string_at(pp, pn.value), oprf_key=C.string_at(kp, kn.value), hashed_items=[(int(a), int(b)) for a, b in words],
+             nonce_byte_count=nb.value)
+    return d

@@ -719,6 +719,73 @@ int apsu_he_wire_bin_bundle_info(const uint8_t *buf, size_t size, uint32_t *bund
                                  uint32_t *largest_bin, uint32_t *cache_coeffs, size_t *consumed);
 int apsu_he_db_upload_saved_bundle(apsu_he_ctx *ctx, const apsu_he_seal_ctx *seal_ctx, const uint8_t *buf, size_t size, uint32_t cache_idx,
                                    apsu_he_bundle **out, size_t *consumed);
+/* The way back: a resident database written in the reference's saved format, for the reference's receiver, a CPU fallback or its
+ * tools.  (Additive to ABI 7.)
+ *
+ * The host writers.  apsu_he_wire_build_bin_bundle: one BinBundle as BinBundle::save writes it (bin_bundle.cpp:1107-1169).  A ragged
+ * matrix arrives flat with n_rows + 1 offsets in words (row i = felts[offsets[i] .. offsets[i + 1])): the item bins, and the bins'
+ * matching polynomials (ascending, monic; [1] for an empty bin).  Written: bundle_idx, mod, item_bins (no rows when stripped),
+ * label_bins (present, empty), the cache unless has_cache is 0 { felt_matching_polyns (no rows when stripped), batched_matching_polyn
+ * with coeffs[d] = the SEAL-serialised Plaintext of degree d, felt_interp_polyns and batched_interp_polyns (present, empty) },
+ * stripped.  stripped without the cache is refused.  apsu_he_wire_build_receiver_db_header: the header ReceiverDB::save puts in front
+ * (receiver_db.cpp:1182-1232); hashed_items is [n][2] = low, high word.  Both compute the exact size of their buffer first and refuse
+ * one over 2^31 - 1 bytes (FlatBuffers offsets are 32 bit) before anything is allocated: APSU_HE_INVALID_ARGUMENT, the size named;
+ * apsu_he_wire_saved_size_check is that bound alone.  The readers next to them: apsu_he_wire_receiver_db_header_fields (pointers into
+ * buf), apsu_he_wire_bin_bundle_rows (which: 0 item_bins, 1 cache.felt_matching_polyns; felts / offsets NULL: only the counts),
+ * apsu_he_wire_bin_bundle_coeffs (every plaintext of the cache with one parse, pointers into buf; data NULL: only *count) and apsu_he_wire_bin_bundle_extras (entries of the label-side vectors, -1 where absent). */
+int apsu_he_wire_saved_size_check(uint64_t bytes);
+int apsu_he_wire_build_bin_bundle(uint32_t bundle_idx, uint64_t mod, int stripped, int has_cache, const uint64_t *bin_felts, const uint64_t *bin_offsets,
+                                  size_t n_bins, const uint64_t *polyn_felts, const uint64_t *polyn_offsets, size_t n_polyns, const uint8_t *const *coeffs,
+                                  const size_t *coeff_sizes, uint32_t n_coeffs, uint8_t **out, size_t *out_size);
+int apsu_he_wire_build_receiver_db_header(const uint8_t *psu_params, size_t psu_params_size, uint32_t label_byte_count, uint32_t nonce_byte_count,
+                                          uint64_t item_count, int compressed, int stripped, const uint8_t *oprf_key, size_t oprf_key_size,
+                                          const uint64_t *hashed_items, size_t n_hashed_items, uint32_t bin_bundle_count, uint8_t **out, size_t *out_size);
+int apsu_he_wire_receiver_db_header_fields(const uint8_t *buf, size_t size, const uint8_t **psu_params, size_t *psu_params_size, const uint8_t **oprf_key,
+                                           size_t *oprf_key_size, const uint8_t **hashed_items, size_t *n_hashed_items, uint32_t *nonce_byte_count);
+int apsu_he_wire_bin_bundle_rows(const uint8_t *buf, size_t size, int which, uint64_t *felts, size_t felt_capacity, uint64_t *offsets, size_t offset_capacity,
+                                 size_t *n_rows, size_t *n_felts);
+int apsu_he_wire_bin_bundle_coeffs(const uint8_t *buf, size_t size, const uint8_t **data, size_t *data_sizes, uint32_t capacity, uint32_t *count);
+int apsu_he_wire_bin_bundle_extras(const uint8_t *buf, size_t size, int *has_cache, int32_t *label_bins, int32_t *felt_interp_polyns,
+                                   int32_t *batched_interp_polyns);
+/* apsu_he_bundle_export_saved: a resident BinBundle -> that buffer (release with apsu_he_wire_buffer_free), such that
+ * apsu_he_db_upload_saved_bundle of it has the apsu_he_bundle_save image of `bundle`, bit for bit, under every flag setting.  One
+ * decode of the stored plaintexts serves everything: the item bins are apsu_he_bundle_bins', the matching polynomials are the
+ * decoded columns cut to the bins' counts (k_bins_rows: a transposition on the device, so they leave it with one contiguous copy),
+ * plaintext d is what the BatchedPlaintextPolyn ctor keeps (bin_bundle.cpp:366-430): coefficient form mod t with n coefficients and
+ * a zero parms_id for d = 0 and, with Paterson-Stockmeyer, d % (ps_low_degree + 1) == 0 -- the decode's values before its forward
+ * transform mod t -- else the stored rows [(pt_level + 1)][n] in NTT form under that level's parms_id; each is serialised by the
+ * codec above (compr_mode 0 none or 2 zstd), one degree at a time.  flags: APSU_HE_SAVED_STRIPPED = what strip() leaves (no item
+ * bins, no matching polynomials, stripped = true); APSU_HE_SAVED_NO_CACHE = the item bins alone; both together are refused.
+ * Refused with APSU_HE_INVALID_ARGUMENT, the bin named in apsu_he_last_error, `bundle` untouched: unless stripped, a polynomial that
+ * does not split into the bin's count of roots (apsu_he_bundle_bins' refusals: a BinBundle that was not built from bins), an unused
+ * slot among the bins, a degree above every bin's count (BinBundle::load wants as many plaintexts as the longest matching polynomial
+ * has coefficients; possible only for a BinBundle uploaded with plaintexts above its longest bin), and a bin of max_items_per_bin items (apsu_he_db_build_bundle allows it; BinBundle::load's cache check does
+ * not); a buffer over the 32-bit limit.  What BinBundle::load checks and this writer meets: mod = the field modulus; unstripped,
+ * exactly bins_per_bundle item bins of at most max_items_per_bin items and as many matching polynomials, the longest of at most
+ * max_items_per_bin coefficients, and as many plaintexts as the longest has coefficients; stripped, a cache of at most
+ * max_items_per_bin plaintexts; label sizes 0.  apsu_he_debug_export_times (next to apsu_he_debug_bins_times): the last call's times in ms -- decode and counts, root
+ * search and multiplicities, k_bins_rows (device); copies to the host, serialisation, assembly (host).
+ *
+ * apsu_he_db_export_saved: the whole database into one file: the header (its compressed = compr_mode != 0, its stripped from flags),
+ * then the BinBundles bundle-index-major, the caller's order kept within a bundle index, each exported, written and released before
+ * the next.  Written to path + ".tmp" and renamed; a failing call leaves neither file.  The OPRF key and the hashed items are the
+ * caller's (the engine never had them) and are written as given.  What ReceiverDB::Load checks (receiver_db.cpp:1257-1429) and the
+ * call therefore requires: the buffer verifies; the parameters load (they are the context's own, apsu_he_wire_psu_params_save's
+ * bytes); the OPRF key has 32 bytes, which Load copies whatever the vector's length (a stripped database may pass none: 32 zero
+ * bytes are written); unstripped, item_count equals the number of hashed items; bin_bundle_count BinBundles follow, each passing
+ * BinBundle::load with a bundle index below bundle_idx_count.  apsu_he_multi_db_export_saved: the same for the BinBundles of a
+ * multi-device handle, in apsu_he_multi_db_index_bundles' order within a bundle index; every BinBundle is exported by the device
+ * that owns it and the file is written by the calling thread. */
+#define APSU_HE_SAVED_STRIPPED 1u
+#define APSU_HE_SAVED_NO_CACHE 2u
+int apsu_he_bundle_export_saved(apsu_he_ctx *ctx, const apsu_he_seal_ctx *seal_ctx, const apsu_he_bundle *bundle, uint32_t flags, int compr_mode,
+                                uint8_t **out, size_t *out_size);
+int apsu_he_debug_export_times(apsu_he_ctx *ctx, double *ms6);
+int apsu_he_db_export_saved(apsu_he_ctx *ctx, const apsu_he_seal_ctx *seal_ctx, const char *path, const apsu_he_bundle *const *bundles, int count,
+                            uint32_t flags, int compr_mode, const uint8_t *oprf_key, size_t oprf_key_size,
+                            const uint64_t *hashed_items /* [n][2]: low, high */, size_t n_hashed_items, uint64_t item_count);
+int apsu_he_multi_db_export_saved(apsu_he_multi *m, const apsu_he_seal_ctx *seal_ctx, const char *path, uint32_t flags, int compr_mode,
+                                  const uint8_t *oprf_key, size_t oprf_key_size, const uint64_t *hashed_items, size_t n_hashed_items, uint64_t item_count);
 /* RelinKeys::load -> ksk[K-1][2][K][n] (ksk NULL: only *words); ::save (seeds[K-1][8] or NULL) */
 int apsu_he_seal_relin_keys_load(const apsu_he_seal_ctx *c, const uint8_t *buf, size_t size, uint64_t *ksk, size_t capacity_words, size_t *words,
                                  size_t *consumed);
