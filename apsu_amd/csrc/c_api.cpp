@@ -6,6 +6,7 @@
 #include <thread>
 #include <atomic>
 #include <cstdlib>
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include <string>
@@ -420,6 +421,35 @@ int apsu_he_decrypt_decode_budget(apsu_he_ctx *c, const uint64_t *sk_ntt, const 
         c->eng->decrypt_decode(sk_ntt, cts, cts_on_device != 0, count, values, blocks, reinterpret_cast<int *>(budget_bits));
     });
 }
+// ---- the plaintext answer and the self-test (bin_eval.h)
+static_assert(sizeof(apsu_he_self_test_report) == sizeof(SelfTestReport) && offsetof(apsu_he_self_test_report, min_budget_bits) == offsetof(SelfTestReport, min_budget_bits) &&
+              offsetof(apsu_he_self_test_report, plain_ms) == offsetof(SelfTestReport, plain_ms), "the report of the header is the engine's");
+static void report_out(const SelfTestReport &r, apsu_he_self_test_report *out) { std::memcpy(out, &r, sizeof(r)); }
+int apsu_he_bundles_eval_plain(apsu_he_ctx *c, const apsu_he_bundle *const *bundles, uint32_t n_bundles, const uint64_t *x, int x_on_device,
+                               const uint64_t *masks, int masks_on_device, uint64_t *out, int out_on_device, uint8_t *is_bin)
+{
+    return guarded([&] {
+        REQUIRE(c && ((x && out) || !n_bundles), "null argument");
+        const auto v = bundle_ptrs(bundles, n_bundles);
+        c->eng->bundles_eval_plain(v.data(), n_bundles, x, x_on_device != 0, masks, masks_on_device != 0, out, out_on_device != 0, is_bin);
+    });
+}
+int apsu_he_debug_eval_plain_times(apsu_he_ctx *c, double *decode_ms, double *counts_ms, double *kernel_ms)
+{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->eval_plain_times(decode_ms, counts_ms, kernel_ms); }); }
+int apsu_he_db_self_test(apsu_he_ctx *c, const apsu_he_bundle *const *bundles, uint32_t count, const uint64_t *seed, const uint64_t *x,
+                         apsu_he_self_test_report *report)
+{
+    return guarded([&] {
+        REQUIRE(c && seed && report, "null argument");
+        const auto v = bundle_ptrs(bundles, count);
+        report_out(c->eng->self_test(v.data(), count, seed, x), report);
+    });
+}
+int apsu_he_debug_self_test_times(apsu_he_ctx *c, double *ms5)
+{ return guarded([&] { REQUIRE(c && ms5, "null argument"); c->eng->self_test_times(ms5); }); }
+int apsu_he_multi_db_self_test(apsu_he_multi *m, const uint64_t *seed, apsu_he_self_test_report *report)
+{ return guarded([&] { REQUIRE(m && seed && report, "null argument"); report_out(m->m->self_test(seed), report); }); }
+
 // ---- N5: the querier's side
 int apsu_he_keygen(apsu_he_ctx *c, const uint64_t *seed, uint64_t *sk_ntt)
 { return guarded([&] { REQUIRE(c && seed && sk_ntt, "null argument"); c->eng->keygen(seed, sk_ntt); }); }

@@ -12,6 +12,7 @@
 #include "bin_merge.h"
 #include "bin_roots.h"
 #include "bin_rows.h"
+#include "bin_eval.h"
 
 namespace apsu_he {
 
@@ -97,6 +98,11 @@ void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u
 // the bins' polynomials as ragged rows (Engine::export_saved; bin_rows.h): out[off[s] + d] = poly[d][s], d <= counts[s], s < bins.
 // off: rows_offsets' scan (bins + 1 words), tops: rows_tile_tops, both on the device; out holds off[bins] words.
 void launch_bins_rows(const u64 *poly, size_t n, u32 rows, const u32 *counts, const u64 *off, const int *tops, u32 bins, u64 *out, hipStream_t st);
+// the plaintext answer (Engine::bundles_eval_plain; bin_eval.h): out[s] = P_s(x[s]) + mask[s] mod t over poly[rows][n], counts =
+// launch_bin_counts' output of the same array; mask and is_bin (1: the slot is a bin) may be null; *bad = 1 for a value >= t.  The comparison of the self-test:
+// got, want [count][n]; status[0] += mismatches, status[1] = min (position << 32 | slot) of one (EVAL_NO_MISMATCH beforehand).
+void launch_bins_eval(const u64 *poly, size_t n, u32 rows, const u32 *counts, const u64 *x, const u64 *mask, Mod t, u64 *out, unsigned char *is_bin, u32 *bad, hipStream_t st);
+void launch_eval_compare(const u64 *got, const u64 *want, size_t n, u32 count, u64 *status, hipStream_t st);
 void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 void launch_gather_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 // N1: algebraize_item for `count` 16-byte items -> out[count][felts]; bpf = bits per field element, item_bits = felts * bpf

@@ -148,6 +148,8 @@ Engine::~Engine()
     if (ev_main_) (void)hipEventDestroy(ev_main_);
     lookup_evs_.release();
     merge_evs_.release();
+    eval_evs_.release();
+    self_evs_.release();
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_side_) (void)hipEventDestroy(ev_side_);
     if (ev_intt_) (void)hipEventDestroy(ev_intt_);
@@ -1282,7 +1284,8 @@ void Engine::mask_generate_impl(uint32_t count, u64 *masks_dev, u64 *values_host
     });
 }
 
-void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_device, uint32_t count, u64 *values_host, u64 *blocks_host, int *budget_bits)
+void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_device, uint32_t count, u64 *values_host, u64 *blocks_host, int *budget_bits,
+                            bool sk_on_device, u64 *values_dev)
 {
     Enter g(this);
     if (!has_psu_) throw std::logic_error("context was created without PSUParams");
@@ -1291,12 +1294,16 @@ void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_devi
     const size_t n = hp_.n;
     const uint32_t items = psu_.items_per_bundle, felts = psu_.item_params.felts_per_item;
     const int tid = hp_.plain_id();
-    for (size_t k = 0; k < n; k++)
+    for (size_t k = 0; !sk_on_device && k < n; k++)
         if (sk_ntt_host[k] >= hp_.key_q[0]) throw std::invalid_argument("secret key is not reduced modulo q_0");
     TIER1_SLOTS();
     WITH_ARENA({
-        u64 *sk = ws(n);
-        H2D(sk, sk_ntt_host, n);
+        const u64 *sk = sk_ntt_host;                             // (sk_on_device: the engine's own key, used where it lies)
+        if (!sk_on_device) {
+            u64 *staged = ws(n);
+            H2D(staged, sk_ntt_host, n);
+            sk = staged;
+        }
         const u64 *ct = cts;
         if (!on_device) {
             u64 *c = ws((size_t)count * 2 * n);
@@ -1332,6 +1339,7 @@ void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_devi
             D2H(blocks_host, blk, (size_t)count * items * 2);
         }
         if (values_host) D2H(values_host, vals, (size_t)count * n);
+        if (values_dev) D2D(values_dev, vals, (size_t)count * n);
         sync();
         // Decryptor::invariant_noise_budget: floor(log2(q_0 / (2 |t x mod q_0|))), the whole of q_0 for a noiseless result
         for (uint32_t i = 0; budget_bits && i < count; i++) {
@@ -1408,7 +1416,7 @@ bool Engine::seeds_overflowed(int count)
     return h != 0;
 }
 
-void Engine::keygen(const u64 seed[8], u64 *sk_ntt_host)
+void Engine::keygen(const u64 seed[8], u64 *sk_ntt_host, bool sk_on_device)
 {
     Enter g(this);
     const size_t n = hp_.n;
@@ -1420,18 +1428,18 @@ void Engine::keygen(const u64 seed[8], u64 *sk_ntt_host)
         { PROF(P_OTHER, 0); launch_sample_ternary(master_seed(seed), small, n, st_); }
         { PROF(P_OTHER, 0); launch_small_lift(dkey(), small, sk, K, n, 1, st_); }
         d_ntt(sk, K, map_ct(), K, false, data_primes_narrow_);
-        HIP_CHECK(hipMemcpyAsync(sk_ntt_host, sk, (size_t)K * n * sizeof(u64), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipMemcpyAsync(sk_ntt_host, sk, (size_t)K * n * sizeof(u64), sk_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st_));
         sync();
     });
 }
 
-void Engine::relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_host, u64 *seeds_host, std::unique_ptr<RelinKeys> *resident)
+void Engine::relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_host, u64 *seeds_host, std::unique_ptr<RelinKeys> *resident, bool sk_on_device)
 {
     Enter g(this);
     if (!hp_.using_keyswitching) throw std::invalid_argument("parameters do not support key switching: the reference creates no relinearisation keys");
     const size_t n = hp_.n;
     const int K = hp_.K, nk = K - 1;
-    check_key_residues(sk_ntt_host, K);
+    if (!sk_on_device) check_key_residues(sk_ntt_host, K);
     const Blake2xbSeed master = master_seed(seed);
     std::vector<u64> seeds((size_t)nk * 8);
     for (int i = 0; i < nk; i++) blake2xb_stream_block(master, qs_seed_block((u64)i), seeds.data() + (size_t)i * 8);
@@ -1442,8 +1450,12 @@ void Engine::relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_ho
     for (int i = 0; i < nk; i++) a[i] = rk->data.u() + ((size_t)i * 2 + 1) * K * n;
     TIER1_SLOTS();
     WITH_ARENA({
-        u64 *sk = ws((size_t)K * n);
-        HIP_CHECK(hipMemcpyAsync(sk, sk_ntt_host, (size_t)K * n * sizeof(u64), hipMemcpyHostToDevice, st_));
+        const u64 *sk = sk_ntt_host;
+        if (!sk_on_device) {
+            u64 *staged = ws((size_t)K * n);
+            HIP_CHECK(hipMemcpyAsync(staged, sk_ntt_host, (size_t)K * n * sizeof(u64), hipMemcpyHostToDevice, st_));
+            sk = staged;
+        }
         signed char *small = reinterpret_cast<signed char *>(ws((size_t)nk * n / 8));
         u64 *e = ws((size_t)nk * K * n);
         bool on_device = queue_seed_expand(K, nk, seeds.data(), a.data());
@@ -1467,7 +1479,7 @@ void Engine::relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_ho
 }
 
 void Engine::query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint32_t *bundle_indices, int nb, const u64 *values, bool values_on_device,
-                          u64 *cts_dev, u64 *seeds_host)
+                          u64 *cts_dev, u64 *seeds_host, bool sk_on_device)
 {
     Enter g(this);
     if (!has_psu_) throw std::logic_error("context was created without PSUParams");
@@ -1480,7 +1492,7 @@ void Engine::query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint3
     if ((size_t)nb * S > 65535) throw std::invalid_argument("more than 65535 ciphertexts in one call");
     for (int b = 0; b < nb; b++)
         if (bundle_indices[b] >= psu_.bundle_idx_count) throw std::invalid_argument("bundle index out of range");
-    check_key_residues(sk_ntt_host, L);
+    if (!sk_on_device) check_key_residues(sk_ntt_host, L);
     if (!values_on_device)
         for (size_t i = 0; i < (size_t)nb * n; i++)
             if (values[i] >= hp_.t) throw std::invalid_argument("slot value is not reduced modulo the plain modulus");
@@ -1492,8 +1504,12 @@ void Engine::query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint3
     u32 flags_host = 0;
     TIER1_SLOTS();
     WITH_ARENA({
-        u64 *sk = ws((size_t)L * n);
-        HIP_CHECK(hipMemcpyAsync(sk, sk_ntt_host, (size_t)L * n * sizeof(u64), hipMemcpyHostToDevice, st_));
+        const u64 *sk = sk_ntt_host;
+        if (!sk_on_device) {
+            u64 *staged = ws((size_t)L * n);
+            HIP_CHECK(hipMemcpyAsync(staged, sk_ntt_host, (size_t)L * n * sizeof(u64), hipMemcpyHostToDevice, st_));
+            sk = staged;
+        }
         const u64 *vals = values;
         if (!values_on_device) {
             u64 *staged = ws((size_t)nb * n);

@@ -200,6 +200,23 @@ public:
     // form: BINS_FORM_AUTO, or one of the two paths by name (the debug call of the tests).  `b` is only read.
     enum { BINS_FORM_AUTO = 0, BINS_FORM_KERNEL = 1, BINS_FORM_COMPOSED = 2 };
     void bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form = BINS_FORM_AUTO);
+    // What a BinBundle answers in plaintext (include/apsu_he.h: apsu_he_bundles_eval_plain; bin_eval.h): out[b][s] = P_s(x[b][s]) + masks[b][s]
+    // mod t for the polynomial P_s that BinBundle b holds in slot s -- the value a querier decrypts there.  x, masks (may be null), out:
+    // [n_bundles][n] slot values, host or device as flagged; is_bin (may be null): [n_bundles][n] bytes on out's side, 0 where the slot
+    // holds the zero polynomial.  The BinBundles are only read.
+    void bundles_eval_plain(const Bundle *const *bundles, uint32_t n_bundles, const u64 *x, bool x_on_device, const u64 *masks, bool masks_on_device,
+                            u64 *out, bool out_on_device, unsigned char *is_bin);
+    // device time of the last bundles_eval_plain call, summed over its BinBundles: decode_bundle, k_bin_counts, k_bins_eval
+    void eval_plain_times(double *decode_ms, double *counts_ms, double *kernel_ms);
+    // The self-test (include/apsu_he.h: apsu_he_db_self_test): keygen, relin_keygen, query_create, compute_powers, the masks, eval_bundles and
+    // decrypt_decode on device buffers of the call, held slot for slot against bundles_eval_plain of the same values.  x_host (may be
+    // null: drawn from the seed): [distinct bundle indices, ascending][n].  For a handle that tests one database in parts (MultiEngine):
+    // query_indices = the bundle indices of the whole (ascending; x_host then follows them) and mask_positions[i] = the position of
+    // BinBundle i in the whole, so every part draws what one context would draw.  Positions in the report are positions in `bundles`.
+    SelfTestReport self_test(const Bundle *const *bundles, uint32_t count, const u64 seed[8], const u64 *x_host, const uint32_t *query_indices = nullptr,
+                             uint32_t n_query = 0, const uint32_t *mask_positions = nullptr);
+    // device time of the last self_test call: decode, k_bin_counts, k_bins_eval (summed over the BinBundles), the comparison, the homomorphic part
+    void self_test_times(double ms[5]);
     // N2 towards the reference (include/apsu_he.h: apsu_he_bundle_export_saved): the BinBundle as BinBundle::save writes it
     // (wire.h: build_bin_bundle), read by the reference's BinBundle::load and by apsu_he_db_upload_saved_bundle.  ntt_parms_id: SEAL's
     // parms_id of chain level b.pt_level (the engine does not hash parameters; the SEAL context of the C ABI does).  One decode serves
@@ -235,15 +252,18 @@ public:
     // the same with the reference's generator: SEAL's Blake2xb PRNG under `seed`, starting at its first_value-th 32-bit output
     void mask_generate_blake2xb(const u64 seed[8], u64 first_value, uint32_t count, u64 *masks_dev, u64 *values_host, u64 *blocks_host);
     // budget_bits (may be null): SEAL's invariant noise budget of every result
+    // sk_on_device: the key is device memory of this context (the self-test's, which never leaves the device) and is taken as it is, here
+    // and in the three calls below; values_dev (may be null): the slot values once more, [count][n] on the device
     void decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_device, uint32_t count, u64 *values_host, u64 *blocks_host,
-                        int *budget_bits = nullptr);
+                        int *budget_bits = nullptr, bool sk_on_device = false, u64 *values_dev = nullptr);
     // N5, the querier's side (query_side.h): Sender::reset_keys and create_query's HE half (sender/apsu/sender_osn.cpp:215-229,426-484)
-    void keygen(const u64 seed[8], u64 *sk_ntt_host);                                       // [K][n]
+    void keygen(const u64 seed[8], u64 *sk_ntt_host, bool sk_on_device = false);            // [K][n]
     // ksk_host [K-1][2][K][n], seeds_host [K-1][8] and resident may each be null
-    void relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_host, u64 *seeds_host, std::unique_ptr<RelinKeys> *resident);
+    void relin_keygen(const u64 *sk_ntt_host, const u64 seed[8], u64 *ksk_host, u64 *seeds_host, std::unique_ptr<RelinKeys> *resident,
+                      bool sk_on_device = false);
     // cts_dev: [nb * S][2][L][n] device words; seeds_host: [nb * S][8]
     void query_create(const u64 *sk_ntt_host, const u64 seed[8], const uint32_t *bundle_indices, int nb, const u64 *values, bool values_on_device,
-                      u64 *cts_dev, u64 *seeds_host);
+                      u64 *cts_dev, u64 *seeds_host, bool sk_on_device = false);
     // N3 on the device: c1 of `count` seeded objects at chain_idx (-1 / K - 1: the key level) = util::sample_poly_uniform under
     // SEAL's Blake2xb generator seeded with seeds[i][8], written to the DEVICE buffers dst[i] ([L][n] words each)
     void seed_expand(int chain_idx, int count, const u64 *seeds, u64 *const *dst);
@@ -506,6 +526,12 @@ private:
     double merge_ms_[3] = { 0, 0, 0 };
     EventStamps bins_evs_;                             // bundle_bins' four time stamps
     double bins_ms_[3] = { 0, 0, 0 };
+    // bundles_eval_plain's and self_test's shared middle: queued inside the caller's WITH_ARENA; four time stamps per BinBundle
+    void eval_plain_queue(const Bundle *const *bundles, uint32_t n_bundles, const u64 *const *xs, const u64 *const *masks, u64 *out, unsigned char *is_bin,
+                          u32 *bad);
+    void eval_plain_collect(uint32_t n_bundles);
+    EventStamps eval_evs_, self_evs_;
+    double eval_ms_[3] = { 0, 0, 0 }, self_ms_[5] = { 0, 0, 0, 0, 0 };
     // bundle_bins without the context's lock.  tap (may be null) is called once the counts are on the host and before the search
     // divides the columns of poly: export_saved takes the bins' rows and the coefficient-form plaintexts there, from the same decode
     struct BinsTap { virtual void after_counts(const u64 *poly, const u64 *coeff, const uint32_t *dcounts, const uint32_t *counts) = 0; virtual ~BinsTap() = default; };

@@ -1127,4 +1127,235 @@ size_t Engine::download_coeff(const Bundle &b, uint32_t d, u64 *out, size_t capa
     return words;
 }
 
+// ---- what a BinBundle answers in plaintext (bin_eval.h): decode, k_bin_counts, k_bins_eval, one BinBundle after the other through the
+// workspace as the lookup runs them.  Queues only: inside the caller's WITH_ARENA, which syncs.  xs / masks: per BinBundle a device
+// pointer to n slot values (masks, or an entry of it, may be null); out [n_bundles][n], is_bin [n_bundles][n] or null, bad: one zeroed
+// word that a value >= t raises -- all device memory.
+void Engine::eval_plain_queue(const Bundle *const *bundles, uint32_t n_bundles, const u64 *const *xs, const u64 *const *masks, u64 *out,
+                              unsigned char *is_bin, u32 *bad)
+{
+    const size_t n = hp_.n;
+    eval_evs_.reserve((size_t)4 * n_bundles);
+    uint32_t *dcounts = ws_as<uint32_t>(n);
+    const size_t mark = arena_off_;
+    for (uint32_t i = 0; i < n_bundles; i++) {
+        const Bundle &b = *bundles[i];
+        arena_off_ = mark;                                             // one BinBundle after the other through the same workspace (stream order)
+        eval_evs_.record(4 * i, st_);
+        u64 *poly = ws((size_t)(b.degree + 1) * n);                    // [d][slot] slot values of the batched polynomial
+        decode_bundle(b, poly);
+        eval_evs_.record(4 * i + 1, st_);
+        launch_bin_counts(poly, n, b.degree + 1, dcounts, st_);
+        eval_evs_.record(4 * i + 2, st_);
+        launch_bins_eval(poly, n, b.degree + 1, dcounts, xs[i], masks ? masks[i] : nullptr, make_mod(hp_.t), out + (size_t)i * n,
+                         is_bin ? is_bin + (size_t)i * n : nullptr, bad, st_);
+        eval_evs_.record(4 * i + 3, st_);
+    }
+}
+
+// after the caller's sync
+void Engine::eval_plain_collect(uint32_t n_bundles)
+{
+    eval_ms_[0] = eval_ms_[1] = eval_ms_[2] = 0;
+    for (uint32_t i = 0; i < n_bundles; i++)
+        for (int k = 0; k < 3; k++) eval_ms_[k] += eval_evs_.ms(4 * i + k, 4 * i + k + 1);
+}
+
+static void check_slot_values(const u64 *v, size_t rows, size_t n, u64 t, const char *what)
+{
+    for (size_t i = 0; i < rows * n; i++)
+        if (v[i] >= t)
+            throw std::invalid_argument(std::string(what) + " " + std::to_string(v[i]) + " (row " + std::to_string(i / n) + ", slot " + std::to_string(i % n) +
+                                        ") is not reduced modulo plain_modulus");
+}
+
+void Engine::bundles_eval_plain(const Bundle *const *bundles, uint32_t n_bundles, const u64 *x, bool x_on_device, const u64 *masks, bool masks_on_device,
+                                u64 *out, bool out_on_device, unsigned char *is_bin)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("eval_plain");
+    if (!n_bundles) return;
+    const size_t n = hp_.n, words = (size_t)n_bundles * n;
+    if (!x_on_device) check_slot_values(x, n_bundles, n, hp_.t, "slot value");
+    if (masks && !masks_on_device) check_slot_values(masks, n_bundles, n, hp_.t, "mask value");
+    u32 bad_host = 0;
+    WITH_ARENA({
+        const u64 *dx = x, *dm = masks;
+        if (!x_on_device) {
+            u64 *staged = ws(words);
+            HIP_CHECK(hipMemcpyAsync(staged, x, words * sizeof(u64), hipMemcpyHostToDevice, st_));
+            dx = staged;
+        }
+        if (masks && !masks_on_device) {
+            u64 *staged = ws(words);
+            HIP_CHECK(hipMemcpyAsync(staged, masks, words * sizeof(u64), hipMemcpyHostToDevice, st_));
+            dm = staged;
+        }
+        u64 *dout = out_on_device ? out : ws(words);
+        unsigned char *dbin = !is_bin ? nullptr : out_on_device ? is_bin : ws_as<unsigned char>(words);
+        u32 *bad = ws_as<u32>(1, 1);
+        HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(u64), st_));
+        std::vector<const u64 *> xs(n_bundles), ms(n_bundles);
+        for (uint32_t i = 0; i < n_bundles; i++) { xs[i] = dx + (size_t)i * n; ms[i] = dm ? dm + (size_t)i * n : nullptr; }
+        eval_plain_queue(bundles, n_bundles, xs.data(), ms.data(), dout, dbin, bad);
+        if (!out_on_device) {
+            HIP_CHECK(hipMemcpyAsync(out, dout, words * sizeof(u64), hipMemcpyDeviceToHost, st_));
+            if (is_bin) HIP_CHECK(hipMemcpyAsync(is_bin, dbin, words, hipMemcpyDeviceToHost, st_));
+        }
+        HIP_CHECK(hipMemcpyAsync(&bad_host, bad, sizeof(u32), hipMemcpyDeviceToHost, st_));
+        sync();
+    });
+    eval_plain_collect(n_bundles);
+    if (bad_host) throw std::invalid_argument("a slot or mask value on the device is not reduced modulo plain_modulus");
+}
+
+void Engine::eval_plain_times(double *decode_ms, double *counts_ms, double *kernel_ms)
+{
+    Enter g(this);
+    if (decode_ms) *decode_ms = eval_ms_[0];
+    if (counts_ms) *counts_ms = eval_ms_[1];
+    if (kernel_ms) *kernel_ms = eval_ms_[2];
+}
+
+// ---- the self-test (include/apsu_he.h: apsu_he_db_self_test): the querier's and the receiver's calls strung together on device buffers
+// of this call, then the plaintext answer and the comparison.  The context's lock is taken per step, as by a caller who made these calls
+// one by one; the BinBundles are only read.
+SelfTestReport Engine::self_test(const Bundle *const *bundles, uint32_t count, const u64 seed[8], const u64 *x_host, const uint32_t *query_indices,
+                                 uint32_t n_query, const uint32_t *mask_positions)
+{
+    SelfTestReport rep = self_test_empty();
+    std::vector<uint32_t> idx;
+    {
+        Enter g(this);
+        lookup_check("self_test");
+        if (!hp_.using_keyswitching) throw std::invalid_argument("parameters do not support key switching: the reference creates no relinearisation keys");
+        if (query_indices) idx.assign(query_indices, query_indices + n_query);
+        else {
+            for (uint32_t i = 0; i < count; i++) idx.push_back(bundles[i]->bundle_idx);
+            std::sort(idx.begin(), idx.end());
+            idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+        }
+        for (size_t k = 0; k < idx.size(); k++)
+            if (idx[k] >= psu_.bundle_idx_count || (k && idx[k] <= idx[k - 1])) throw std::invalid_argument("bundle indices are ascending, distinct and in range");
+        for (uint32_t i = 0; i < count; i++) {
+            if (!std::binary_search(idx.begin(), idx.end(), bundles[i]->bundle_idx)) throw std::invalid_argument("a BinBundle's bundle index is not among the query's");
+            if (mask_positions && mask_positions[i] >= SELF_TEST_MAX_OBJECTS) throw std::invalid_argument("too many BinBundles for one self-test");
+        }
+        if (count >= SELF_TEST_MAX_OBJECTS) throw std::invalid_argument("too many BinBundles for one self-test");
+    }
+    if (!count) return rep;
+    const size_t n = hp_.n;
+    const int K = hp_.K, L = hp_.first_chain_idx + 1, n_idx = (int)idx.size();
+    const size_t S = psu_.query_params.query_powers.size();
+    if (x_host) check_slot_values(x_host, idx.size(), n, hp_.t, "slot value");
+    Blake2xbSeed sd;
+    for (int i = 0; i < 8; i++) sd.w[i] = seed[i];
+    auto pos = [&](uint32_t i) { return mask_positions ? mask_positions[i] : i; };
+
+    DevBuf xs, mvals, menc, sk, cts, res, got, want;                   // allocated with the context's device current
+    std::unique_ptr<RelinKeys> rk;
+    std::unique_ptr<Powers> pw;
+    // the key material of the call is overwritten before its buffers are released, whichever way the call ends: the secret key, the
+    // relinearisation keys, and the workspace through which keygen and the key generation passed them
+    auto wipe = [&] {
+        try {
+            Enter g(this);
+            if (sk.bytes()) HIP_CHECK(hipMemsetAsync(sk.p(), 0, sk.bytes(), st_));
+            if (rk && rk->data.bytes()) HIP_CHECK(hipMemsetAsync(rk->data.p(), 0, rk->data.bytes(), st_));
+            if (arena_.bytes()) HIP_CHECK(hipMemsetAsync(arena_.p(), 0, arena_.bytes(), st_));
+            sync();
+        } catch (...) { }
+    };
+    try {
+        {
+            Enter g(this);
+            self_evs_.reserve(4);
+            xs.alloc(idx.size() * n * sizeof(u64)); mvals.alloc((size_t)count * n * sizeof(u64)); menc.alloc((size_t)count * n * sizeof(u64));
+            sk.alloc((size_t)K * n * sizeof(u64)); cts.alloc(idx.size() * S * 2 * L * n * sizeof(u64)); res.alloc((size_t)count * 2 * n * sizeof(u64));
+            got.alloc((size_t)count * n * sizeof(u64)); want.alloc((size_t)count * n * sizeof(u64));
+            if (x_host) HIP_CHECK(hipMemcpyAsync(xs.p(), x_host, xs.bytes(), hipMemcpyHostToDevice, st_));
+            else launch_fill_blake2xb(xs.u(), idx.size() * n, sd, SELF_TEST_X_FIRST, hp_.t, st_);
+            // the masks' slot values, position by position: the draws apsu_he_mask_generate_blake2xb encodes below
+            for (uint32_t i = 0; i < count; i++) launch_fill_blake2xb(mvals.u() + (size_t)i * n, n, sd, SELF_TEST_MASK_FIRST + (u64)pos(i) * n, hp_.t, st_);
+            self_evs_.record(0, st_);
+        }
+        keygen(seed, sk.u(), true);
+        relin_keygen(sk.u(), seed, nullptr, nullptr, &rk, true);
+        std::vector<u64> ct_seeds(idx.size() * S * 8);
+        query_create(sk.u(), seed, idx.data(), n_idx, xs.u(), true, cts.u(), ct_seeds.data(), true);
+        std::vector<const u64 *> src(idx.size() * S);
+        for (size_t c = 0; c < src.size(); c++) src[c] = cts.u() + c * 2 * L * n;
+        pw = compute_powers(idx.data(), n_idx, src.data(), true, rk.get());
+        for (uint32_t i = 0; i < count;) {                             // runs of consecutive positions continue one stream
+            uint32_t j = i + 1;
+            while (j < count && pos(j) == pos(j - 1) + 1) j++;
+            mask_generate_blake2xb(seed, SELF_TEST_MASK_FIRST + (u64)pos(i) * n, j - i, menc.u() + (size_t)i * n, nullptr, nullptr);
+            i = j;
+        }
+        std::vector<const u64 *> mptr(count), xptr(count), vptr(count);
+        for (uint32_t i = 0; i < count; i++) {
+            mptr[i] = menc.u() + (size_t)i * n;
+            vptr[i] = mvals.u() + (size_t)i * n;
+            xptr[i] = xs.u() + (size_t)(std::lower_bound(idx.begin(), idx.end(), bundles[i]->bundle_idx) - idx.begin()) * n;
+        }
+        eval_bundles(bundles, (int)count, *pw, rk.get(), mptr.data(), true, res.u(), true);
+        std::vector<int> budget(count);
+        decrypt_decode(sk.u(), res.u(), true, count, nullptr, nullptr, budget.data(), true, got.u());
+        u64 status[2] = { 0, EVAL_NO_MISMATCH };
+        u32 bad_host = 0;
+        {
+            Enter g(this);
+            TIER1_SLOTS();
+            WITH_ARENA({
+                self_evs_.record(1, st_);
+                u64 *dstatus = ws(2);
+                u32 *bad = ws_as<u32>(1, 1);
+                const u64 init[2] = { 0, EVAL_NO_MISMATCH };
+                HIP_CHECK(hipMemcpyAsync(dstatus, init, sizeof(init), hipMemcpyHostToDevice, st_));
+                HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(u64), st_));
+                eval_plain_queue(bundles, count, xptr.data(), vptr.data(), want.u(), nullptr, bad);
+                self_evs_.record(2, st_);
+                launch_eval_compare(got.u(), want.u(), n, count, dstatus, st_);
+                self_evs_.record(3, st_);
+                HIP_CHECK(hipMemcpyAsync(status, dstatus, sizeof(status), hipMemcpyDeviceToHost, st_));
+                HIP_CHECK(hipMemcpyAsync(&bad_host, bad, sizeof(u32), hipMemcpyDeviceToHost, st_));
+                sync();
+            });
+            eval_plain_collect(count);
+            if (bad_host) throw std::logic_error("self_test: a drawn value is not reduced modulo plain_modulus");
+            rep.bundles = count;
+            rep.slots = (u64)count * n;
+            rep.mismatches = status[0];
+            if (status[1] != EVAL_NO_MISMATCH) {
+                rep.first_bundle = (int32_t)(status[1] >> 32);
+                rep.first_slot = (uint32_t)status[1];
+                const size_t at = (size_t)rep.first_bundle * n + rep.first_slot;
+                HIP_CHECK(hipMemcpy(&rep.first_got, got.u() + at, sizeof(u64), hipMemcpyDeviceToHost));
+                HIP_CHECK(hipMemcpy(&rep.first_expected, want.u() + at, sizeof(u64), hipMemcpyDeviceToHost));
+            }
+            for (uint32_t i = 0; i < count; i++)
+                if (rep.min_budget_bundle < 0 || budget[i] < rep.min_budget_bits) { rep.min_budget_bits = budget[i]; rep.min_budget_bundle = (int32_t)i; }
+            rep.he_ms = self_evs_.ms(0, 1);
+            rep.plain_ms = self_evs_.ms(1, 3);
+            self_ms_[0] = eval_ms_[0]; self_ms_[1] = eval_ms_[1]; self_ms_[2] = eval_ms_[2];
+            self_ms_[3] = self_evs_.ms(2, 3);
+            self_ms_[4] = rep.he_ms;
+        }
+    } catch (...) {
+        wipe();
+        if (pw) recycle_powers(std::move(pw));
+        throw;
+    }
+    wipe();
+    recycle_powers(std::move(pw));
+    return rep;
+}
+
+void Engine::self_test_times(double ms[5])
+{
+    Enter g(this);
+    for (int i = 0; i < 5; i++) ms[i] = self_ms_[i];
+}
+
 } // namespace apsu_he

@@ -16,6 +16,7 @@
 #include "bin_merge.h"
 #include "bin_roots.h"
 #include "bin_rows.h"
+#include "bin_eval.h"
 #include "db_compact.h"
 #include "db_place.h"
 #include "multi_place.h"
@@ -605,6 +606,55 @@ int emu_bins_lookup(uint64_t t_, const uint64_t *poly, uint64_t n, uint32_t degr
         if (stats) { stats[0] = plan.work.size(); stats[1] = plan.rows(); stats[2] = widest; }
         return 0;
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// k_bins_eval over poly[rows][n] as the waves run it (bin_eval.h): one wave per tile of 64 slots, the tile's top from the counts of
+// emu_bin_counts, an explicit loop over its 64 lanes, rows from the top EVAL_ROWS at a time.  mask, is_bin and walked may be null;
+// out[n] and is_bin[n] must come in as 0xEE bytes (a word that no lane writes keeps them); walked[tiles] = the rows a tile read.
+// wide: 0 = the width the launch takes for t, 1 = the 128-bit step whatever t (both must agree wherever both are exact).
+// Returns 0, or -1 (emu_last_error) for a value that is not below t.
+int emu_bins_eval(uint64_t t_, const uint64_t *poly, uint64_t n, uint32_t rows, const uint64_t *x, const uint64_t *mask, int wide, uint64_t *out,
+                  unsigned char *is_bin, uint32_t *walked)
+{
+    try {
+        for (size_t s = 0; s < n; s++)
+            if (x[s] >= t_ || (mask && mask[s] >= t_)) throw std::invalid_argument("slot value is not reduced modulo the plain modulus");
+        const ModulusInfo mi(t_);
+        const Mod t{ t_, mi.ratio[0], mi.ratio[1] };
+        const bool narrow = !wide && merge_narrow(merge_bits(t_));
+        std::vector<u32> counts(n);
+        emu_bin_counts(poly, n, rows, counts.data());
+        const size_t tiles = (n + EVAL_LANES - 1) / EVAL_LANES;
+        for (size_t tile = 0; tile < tiles; tile++) {
+            int top = -1;
+            for (int lane = 0; lane < EVAL_LANES; lane++) {
+                const size_t slot = tile * EVAL_LANES + lane;
+                top = std::max(top, eval_count_top(slot < n ? counts[slot] : LOOKUP_NONE));
+            }
+            const int d0 = eval_walk_top(top, rows);
+            if (walked) walked[tile] = (uint32_t)(d0 + 1);
+            for (int lane = 0; lane < EVAL_LANES; lane++) {
+                const size_t slot = tile * EVAL_LANES + lane;
+                if (slot >= n) continue;
+                const u64 *col = poly + slot;
+                const u64 xs = x[slot];
+                const u64 acc = narrow ? eval_walk<true>(col, n, d0, xs, t) : eval_walk<false>(col, n, d0, xs, t);
+                out[slot] = eval_finish(acc, mask ? mask[slot] : 0, t);
+                if (is_bin) is_bin[slot] = eval_is_bin(counts[slot]) ? 1 : 0;
+            }
+        }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+int emu_eval_rows() { return EVAL_ROWS; }
+
+// self_test_reduce over `count` reports (bin_eval.h), each sizeof(SelfTestReport) bytes; emu_self_test_report_bytes gives the size
+int emu_self_test_report_bytes() { return (int)sizeof(SelfTestReport); }
+void emu_self_test_reduce(const void *parts, int count, void *out)
+{
+    SelfTestReport r = self_test_empty();
+    for (int i = 0; i < count; i++) self_test_reduce(r, static_cast<const SelfTestReport *>(parts)[i]);
+    *static_cast<SelfTestReport *>(out) = r;
 }
 
 // ---- reading the bins back (bin_roots.h)

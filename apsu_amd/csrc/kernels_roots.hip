@@ -2,10 +2,12 @@
 // transforms' object (kernels.hip) is built exactly as before.  Rules and lane arithmetic: bin_roots.h, which the CPU tier runs as well.
 // Input of every kernel here: poly[d][slot], the slot values mod t that Engine::decode_bundle produces; bin s is the column s, read
 // top down to its count.
+// Also here, on the same input: the plaintext answer of a BinBundle and the self-test's comparison (k_bins_eval, k_eval_compare; bin_eval.h).
 #include "device.h"
 #include "ntt_wg.h"
 #include "bin_roots.h"
 #include "bin_rows.h"
+#include "bin_eval.h"
 
 namespace apsu_he {
 
@@ -151,6 +153,45 @@ __global__ __launch_bounds__(ROWS_TILE * ROWS_WAVES) void k_bins_rows(const u64 
     }
 }
 
+// ---- what the BinBundle answers in plaintext (Engine::bundles_eval_plain, Engine::self_test; bin_eval.h): out[s] = P_s(x[s]) + mask[s] mod t
+// for every slot, P_s the column s of poly[rows][n].  Lane = slot: one WAVE per tile of 64 consecutive slots, rows d = top .. 0 with one
+// contiguous 512-byte segment per d, EVAL_ROWS of them loaded before their Horner steps; top = the largest count of the tile, the
+// maximum over the wave of k_bin_counts' output.  One point per slot, so a stored coefficient is read exactly once.  mask and is_bin
+// may be null.  A slot or mask value that is not below t raises *bad (a plain store of 1: whoever finds one writes the same word).
+// No LDS, no atomics; every word of out (and of is_bin) is written by exactly one lane.
+template <bool NARROW>
+__global__ __launch_bounds__(EVAL_LANES) void k_bins_eval(const u64 *__restrict__ poly, size_t n, u32 rows, const u32 *__restrict__ counts,
+                                                          const u64 *__restrict__ x, const u64 *__restrict__ mask, Mod t, u64 *__restrict__ out,
+                                                          unsigned char *__restrict__ is_bin, u32 *__restrict__ bad)
+{
+    const size_t slot = (size_t)blockIdx.x * EVAL_LANES + threadIdx.x;
+    const bool live = slot < n;                                   // (n < 64 only)
+    const u32 cnt = live ? counts[slot] : LOOKUP_NONE;
+    int top = eval_count_top(cnt);
+#pragma unroll
+    for (int m = EVAL_LANES / 2; m; m >>= 1) top = max(top, __shfl_xor(top, m, EVAL_LANES));
+    const u64 *col = poly + (live ? slot : 0);
+    const u64 xs = live ? x[slot] : 0;
+    const u64 acc = eval_walk<NARROW>(col, n, eval_walk_top(top, rows), xs, t);      // the top is wave-uniform
+    if (!live) return;
+    const u64 ms = mask ? mask[slot] : 0;
+    if (xs >= t.q || ms >= t.q) *bad = 1;
+    out[slot] = eval_finish(acc, ms, t);
+    if (is_bin) is_bin[slot] = eval_is_bin(cnt) ? 1 : 0;
+}
+
+// the self-test's comparison of what was decrypted with what the polynomials say: got, want [count][n].  One lane per slot (grid.y = the
+// BinBundle's position); status[0] += the workgroup's mismatches (one atomic per workgroup that has any), status[1] = min of
+// (position << 32 | slot) over the mismatches (EVAL_NO_MISMATCH beforehand).
+__global__ __launch_bounds__(EW_T) void k_eval_compare(const u64 *__restrict__ got, const u64 *__restrict__ want, size_t n, unsigned long long *__restrict__ status)
+{
+    const size_t i = (size_t)blockIdx.x * EW_T + threadIdx.x;
+    const bool bad = i < n && got[(size_t)blockIdx.y * n + i] != want[(size_t)blockIdx.y * n + i];
+    if (bad) atomicMin(status + 1, (unsigned long long)eval_mismatch_key(blockIdx.y, (u32)i));
+    const int total = __syncthreads_count(bad);
+    if (total && threadIdx.x == 0) atomicAdd(status, (unsigned long long)total);
+}
+
 // ---- launches
 // workgroups a CU holds: two at n = 8192 (72 KiB of LDS each, 126 VGPRs: 4 waves per SIMD), two at 4096 (170 VGPRs: 2 waves per SIMD; a
 // budget of 168 or 128 registers spills there); resource report: profiles/r15_bundle_bins.txt
@@ -208,6 +249,22 @@ void launch_bins_rows(const u64 *poly, size_t n, u32 rows, const u32 *counts, co
     if (!bins || !rows) return;
     hipLaunchKernelGGL(k_bins_rows, dim3((unsigned)((n + ROWS_TILE - 1) / ROWS_TILE), (rows + ROWS_TILE - 1) / ROWS_TILE), dim3(ROWS_TILE * ROWS_WAVES), 0, st,
                        poly, n, rows, counts, off, tops, bins, out);
+    KERNEL_CHECK();
+}
+
+void launch_bins_eval(const u64 *poly, size_t n, u32 rows, const u32 *counts, const u64 *x, const u64 *mask, Mod t, u64 *out, unsigned char *is_bin, u32 *bad, hipStream_t st)
+{
+    if (!n || !rows) return;
+    const dim3 grid((unsigned)((n + EVAL_LANES - 1) / EVAL_LANES));
+    if (merge_narrow(merge_bits(t.q))) hipLaunchKernelGGL((k_bins_eval<true>), grid, dim3(EVAL_LANES), 0, st, poly, n, rows, counts, x, mask, t, out, is_bin, bad);
+    else hipLaunchKernelGGL((k_bins_eval<false>), grid, dim3(EVAL_LANES), 0, st, poly, n, rows, counts, x, mask, t, out, is_bin, bad);
+    KERNEL_CHECK();
+}
+
+void launch_eval_compare(const u64 *got, const u64 *want, size_t n, u32 count, u64 *status, hipStream_t st)
+{
+    if (!n || !count) return;
+    hipLaunchKernelGGL(k_eval_compare, dim3((unsigned)((n + EW_T - 1) / EW_T), count), dim3(EW_T), 0, st, got, want, n, reinterpret_cast<unsigned long long *>(status));
     KERNEL_CHECK();
 }
 

@@ -64,6 +64,7 @@ public:
     std::vector<int> index_bundles(uint32_t bundle_idx);          // the ids of one bundle index in cache order (index_in_cache_order)
     void bin_counts(int id, uint32_t *counts);                    // Engine::bin_counts on the owning device
     void bundle_bins(int id, u64 *roots, uint32_t *counts, uint32_t stride);   // Engine::bundle_bins on the owning device
+    SelfTestReport self_test(const u64 seed[8]);                 // Engine::self_test of every device's BinBundles, the reports reduced (bin_eval.h)
     // Engine::build_bundle on `slot`, or with slot == -1 on the slot place_new_unit chooses; registered last.  Returns the id.
     int build_bundle(int slot, uint32_t bundle_idx, uint32_t cache_idx, const u64 *roots, const uint32_t *counts, uint32_t bins, uint32_t stride);
     void remove_bundle(int id, int *new_id);                      // new_id[bundle_count()] (may be null)

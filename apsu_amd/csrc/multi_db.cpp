@@ -123,6 +123,34 @@ void MultiEngine::bundle_bins(int id, u64 *roots, uint32_t *counts, uint32_t str
     devs_[(size_t)where_[(size_t)id].first]->eng->bundle_bins(bundle_locked(id), roots, counts, stride);
 }
 
+// Every device tests the BinBundles it owns, devices side by side, each with the query of the WHOLE database's bundle indices and the
+// mask draws of its BinBundles' ids: what one context holding all of them would draw.  Positions become ids before the reports are reduced.
+SelfTestReport MultiEngine::self_test(const u64 seed[8])
+{
+    std::lock_guard<std::mutex> g(mu_);
+    std::vector<uint32_t> idx;
+    for (const RegUnit &u : registry_locked()) idx.push_back(u.bundle_idx);
+    std::sort(idx.begin(), idx.end());
+    idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+    std::vector<SelfTestReport> parts(devs_.size(), self_test_empty());
+    run_all([&](Dev &d) {
+        std::vector<size_t> order(d.bundles.size());                  // by id: a part's first mismatch is then its lowest id's
+        for (size_t i = 0; i < order.size(); i++) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return d.ids[a] < d.ids[b]; });
+        std::vector<const Bundle *> bs;
+        std::vector<uint32_t> ids;
+        for (size_t i : order) { bs.push_back(d.bundles[i].get()); ids.push_back((uint32_t)d.ids[i]); }
+        // (a device that owns nothing still answers for its context: the refusals are every device's)
+        SelfTestReport r = d.eng->self_test(bs.data(), (uint32_t)bs.size(), seed, nullptr, idx.data(), (uint32_t)idx.size(), ids.data());
+        if (r.first_bundle >= 0) r.first_bundle = (int32_t)ids[(size_t)r.first_bundle];
+        if (r.min_budget_bundle >= 0) r.min_budget_bundle = (int32_t)ids[(size_t)r.min_budget_bundle];
+        parts[(size_t)d.slot] = r;
+    });
+    SelfTestReport rep = self_test_empty();
+    for (const SelfTestReport &r : parts) self_test_reduce(rep, r);
+    return rep;
+}
+
 int MultiEngine::build_bundle(int slot, uint32_t bundle_idx, uint32_t cache_idx, const u64 *roots, const uint32_t *counts, uint32_t bins, uint32_t stride)
 {
     std::lock_guard<std::mutex> g(mu_);

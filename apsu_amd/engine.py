@@ -155,6 +155,22 @@ BundleInfo = collections.namedtuple("BundleInfo", "slot bundle_idx cache_idx deg
 MultiApplyResult = collections.namedtuple("MultiApplyResult", "new_id n_appended ins_status ins_target rem_status rem_target")
 
 
+class _SelfTestReport(C.Structure):
+    _fields_ = [("bundles", C.c_uint32), ("reserved", C.c_uint32), ("slots", C.c_uint64), ("mismatches", C.c_uint64),
+                ("first_bundle", C.c_int32), ("first_slot", C.c_uint32), ("first_got", C.c_uint64), ("first_expected", C.c_uint64),
+                ("min_budget_bits", C.c_int32), ("min_budget_bundle", C.c_int32), ("he_ms", C.c_double), ("plain_ms", C.c_double)]
+
+
+SelfTestReport = collections.namedtuple("SelfTestReport", "bundles slots mismatches first_mismatch min_budget min_budget_bundle he_ms plain_ms")
+
+
+def _self_test_report(r):
+    """first_mismatch: None, or (BinBundle, slot, got, expected); min_budget_bundle: None when nothing was checked"""
+    first = None if r.first_bundle < 0 else (int(r.first_bundle), int(r.first_slot), int(r.first_got), int(r.first_expected))
+    return SelfTestReport(int(r.bundles), int(r.slots), int(r.mismatches), first, int(r.min_budget_bits),
+                          None if r.min_budget_bundle < 0 else int(r.min_budget_bundle), float(r.he_ms), float(r.plain_ms))
+
+
 class RelinKeys:
     def __init__(self, ctx, handle):
         self._ctx, self.h = ctx, handle
@@ -449,6 +465,48 @@ class HeContext:
         else:
             _check(lib.apsu_he_bundle_bins(self.h, bundle.h, _p(roots), C.c_void_p(counts.ctypes.data), C.c_uint32(stride)))
         return _bins_list(roots, counts)
+
+    def eval_plain(self, bundles, x, masks=None, want_is_bin=False):
+        """What resident BinBundles answer in plaintext (apsu_he_bundles_eval_plain): x [len(bundles)][n] slot values below t, masks the
+        same shape (slot values, not encoded plaintexts) or None -> out [len(bundles)][n] = P_slot(x) + mask mod t, the value a querier
+        decrypts; with want_is_bin also a bool array, False where the slot holds the zero polynomial."""
+        count = len(bundles)
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(count, self.n)
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(count, self.n)
+        out = np.empty((count, self.n), dtype=np.uint64)
+        is_bin = np.zeros((count, self.n), dtype=np.uint8) if want_is_bin else None
+        hs = (C.c_void_p * count)(*[b.h for b in bundles])
+        _check(load_library().apsu_he_bundles_eval_plain(self.h, hs, C.c_uint32(count), _p(x), 0, _p(masks) if masks is not None else None, 0,
+                                                         _p(out), 0, C.c_void_p(is_bin.ctypes.data) if want_is_bin else None))
+        return (out, is_bin.astype(bool)) if want_is_bin else out
+
+    def eval_plain_times(self):
+        """-> (decode ms, counts ms, k_bins_eval ms): device time of the last eval_plain call, summed over its BinBundles"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(load_library().apsu_he_debug_eval_plain_times(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def self_test(self, bundles, seed=None, x=None):
+        """One real query against resident BinBundles, wholly on the device, held slot for slot against eval_plain of the same values
+        (apsu_he_db_self_test) -> SelfTestReport.  x: [distinct bundle indices, ascending][n] slot values, None to draw them from the
+        seed.  Proves that the engine's evaluation, decryption and stored polynomials agree; cannot prove agreement with SEAL."""
+        sd = self._seed_words(seed)
+        count = len(bundles)
+        hs = (C.c_void_p * max(count, 1))(*[b.h for b in bundles])
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.uint64)
+            if x.size != len({b.bundle_idx for b in bundles}) * self.n:
+                raise ValueError("x must hold n slot values per distinct bundle index")
+        rep = _SelfTestReport()
+        _check(load_library().apsu_he_db_self_test(self.h, hs, C.c_uint32(count), _p(sd), _p(x) if x is not None else None, C.byref(rep)))
+        return _self_test_report(rep)
+
+    def self_test_times(self):
+        """-> (decode, counts, k_bins_eval, comparison, homomorphic part) ms: device time of the last self_test call"""
+        ms = (C.c_double * 5)()
+        _check(load_library().apsu_he_debug_self_test_times(self.h, ms))
+        return tuple(float(v) for v in ms)
 
     def bins_times(self):
         """-> (decode + counts ms, root search ms, multiplicities + copy-back ms): device time of the last bins call"""
@@ -912,6 +970,14 @@ class MultiContext:
         roots = np.zeros((len(counts), stride), dtype=np.uint64)
         _check(load_library().apsu_he_multi_db_bundle_bins(self.h, int(bundle_id), _p(roots), C.c_void_p(counts.ctypes.data), C.c_uint32(stride)))
         return _bins_list(roots, counts)
+
+    def self_test(self, seed=None):
+        """HeContext.self_test of every registered BinBundle, each device testing its own, devices side by side
+        (apsu_he_multi_db_self_test) -> SelfTestReport; BinBundles are named by id"""
+        sd = HeContext._seed_words(seed)
+        rep = _SelfTestReport()
+        _check(load_library().apsu_he_multi_db_self_test(self.h, _p(sd), C.byref(rep)))
+        return _self_test_report(rep)
 
     def build_bundle(self, bundle_idx, cache_idx, bins, slot=-1):
         """HeContext.build_bundle on `slot`, or (slot -1) on the slot the placement rule chooses -> the new id (registered last)"""

@@ -377,6 +377,69 @@ int apsu_he_decrypt_decode_budget(apsu_he_ctx *ctx, const uint64_t *sk_ntt, cons
  * bits [j*b, (j+1)*b) of item i's first item_bit_count bits, read as a little-endian bit string, b = bit_count(plain_modulus) - 1.
  * These are the roots apsu_he_db_build_bundle takes once the host has placed them into bins.  (ABI 4) */
 int apsu_he_algebraize_items(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint64_t *felts, int felts_on_device);
+/* N1, checking a resident database against plaintext (added after ABI 7, additive).  The image checksum protects bytes, not meaning:
+ * a BinBundle whose stored limbs do not describe one plaintext, one encoded under another ps_low_degree, one merged from a damaged
+ * input, or one held under parameters whose noise budget is too small passes it, and the first sign is a wrong union at the end of
+ * the protocol.  These two calls say, on the device, what a resident BinBundle should answer to a query and whether the engine's own
+ * homomorphic path answers that.
+ * apsu_he_bundles_eval_plain: out[b][s] = P_{b,s}(x[b][s]) + masks[b][s] mod plain_modulus, P_{b,s} the polynomial BinBundle b holds in
+ * slot s -- the value the querier who sent x[b] decrypts in that slot, and what decrypt(eval(query)) is checked against.
+ *  - x[n_bundles][n], n = poly_modulus_degree: slot values below plain_modulus; the caller repeats a bundle index's query for each of
+ *    its BinBundles.  masks[n_bundles][n]: slot values (what apsu_he_mask_generate* return in `values`), NOT the encoded plaintexts
+ *    that apsu_he_eval_bundles takes; NULL: no masks.  out[n_bundles][n].  Each is a host pointer, or a device pointer with its flag set.
+ *  - is_bin (may be NULL): [n_bundles][n] bytes on out's side, 1 where the slot is a bin, 0 where it holds the zero polynomial.  Such a
+ *    slot yields masks[b][s] alone, as the homomorphic path does.  A member of a bin (a root of its polynomial) yields the mask alone too.
+ *  - The BinBundles are decoded and evaluated one after the other through the context's workspace, as by apsu_he_bundles_lookup
+ *    (k_bins_eval: one Horner walk per slot with lane = slot, every stored coefficient read once, a tile of 64 slots walking from its
+ *    own largest count).  They are only read.
+ *  - A value >= plain_modulus, in x or masks, on the host or the device: APSU_HE_INVALID_ARGUMENT (a device-side value is found by
+ *    the kernel; out is then written but means nothing).
+ * Preconditions and locking are apsu_he_bundle_bin_counts's.  Synchronous.  Parameter sets without key switching are served.
+ * apsu_he_debug_eval_plain_times: device time of the context's last such call, summed over its BinBundles: decode, counts, k_bins_eval.
+ *
+ * apsu_he_db_self_test: one call that runs the whole loop on the device for `count` BinBundles of this context and compares.  In order:
+ * apsu_he_keygen; apsu_he_relin_keygen; apsu_he_query_create for the distinct bundle indices among `bundles`; apsu_he_compute_powers
+ * with device sources; apsu_he_mask_generate_blake2xb; apsu_he_eval_bundles with masks on the device; apsu_he_decrypt_decode_budget;
+ * apsu_he_bundles_eval_plain on the same slot and mask values; a comparison kernel, slot for slot.
+ *  - x (may be NULL): [distinct bundle indices, ascending][n] slot values below plain_modulus (host).  NULL: drawn mod plain_modulus
+ *    from the Blake2xb stream of `seed` like the masks, as 32-bit outputs u[p]: the i-th distinct bundle index takes
+ *    p = 2^37 + i n + [0, n) (stream blocks from 2^33), the mask of the BinBundle at position b takes p = 2^38 + b n + [0, n) (blocks
+ *    from 2^34).  The querier's ranges (above, apsu_amd/csrc/query_side.h) end below block 2^33, so one seed serves the whole call.
+ *    A drawn x is almost never an item of the database; pass items to have the test cover members (they decrypt to the mask alone).
+ *  - report: BinBundles and slots checked; mismatches; the first mismatch in (position in `bundles`, slot) order with the value
+ *    decrypted and the value expected, first_bundle = -1 for none; the smallest noise budget over the results and the first BinBundle
+ *    that has it; device time of the homomorphic part (key generation to decryption) and of the plain part (evaluation and comparison).
+ *  - APSU_HE_OK whenever the test ran: mismatches are a result, not an error.  A noise budget of 0 bits shows as mismatches too.
+ *  - The secret key and the relinearisation keys never leave device buffers of the call; those buffers, and the context's workspace
+ *    through which the key generation passed them, are overwritten with zeros before they are released, whichever way the call ends.
+ *    The seed is key material all the same.
+ *  - A parameter set without key switching: APSU_HE_INVALID_ARGUMENT, as from apsu_he_relin_keygen (apsu_he_bundles_eval_plain serves
+ *    those).  Other preconditions as above.  At most 2^20 - 1 BinBundles.  Synchronous; the context's lock is taken per step.
+ * What a clean report proves: the engine's own evaluation, its decryption and the stored polynomials agree with each other for these
+ * parameters -- upload, layout, Paterson-Stockmeyer split, key switching, noise.  What it cannot prove: agreement with SEAL.  Both
+ * sides are this engine's restatement of the reference; that stays unpinned.  Nor that the polynomials are the
+ * intended ones: a stored plaintext that is wrong but well-formed (another a_0, say) reads the same on both sides -- another database.
+ * apsu_he_debug_self_test_times: device time in ms of the context's last self-test: decode, counts, k_bins_eval (each summed over the
+ * BinBundles), the comparison, the homomorphic part.
+ * apsu_he_multi_db_self_test (declared with the handle's calls below): every device tests the BinBundles it owns, devices side by side,
+ * under the handle's lock; every device creates the query for the bundle indices of the whole handle and draws BinBundle id's mask at
+ * position id, so the draws are those of one context holding the BinBundles in id order.  The reports are reduced: counts summed, the
+ * first mismatch and the smallest budget named by BinBundle id (lowest id first), the times of the slowest device. */
+typedef struct {
+    uint32_t bundles, reserved;
+    uint64_t slots, mismatches;
+    int32_t first_bundle;            /* position in `bundles` (multi-device handle: BinBundle id); -1: no mismatch */
+    uint32_t first_slot;
+    uint64_t first_got, first_expected;
+    int32_t min_budget_bits, min_budget_bundle;   /* -1: nothing was checked */
+    double he_ms, plain_ms;
+} apsu_he_self_test_report;
+int apsu_he_bundles_eval_plain(apsu_he_ctx *ctx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, const uint64_t *x, int x_on_device,
+                               const uint64_t *masks, int masks_on_device, uint64_t *out, int out_on_device, uint8_t *is_bin);
+int apsu_he_debug_eval_plain_times(apsu_he_ctx *ctx, double *decode_ms, double *counts_ms, double *kernel_ms);
+int apsu_he_db_self_test(apsu_he_ctx *ctx, const apsu_he_bundle *const *bundles, uint32_t count, const uint64_t seed[8], const uint64_t *x,
+                         apsu_he_self_test_report *report);
+int apsu_he_debug_self_test_times(apsu_he_ctx *ctx, double *ms5);
 /* N2 for the whole database -- the counterpart of ReceiverDB::save / Load (receiver/apsu/receiver_db.cpp:1182-1429) for a DB
  * that lives in HBM as raw limb arrays: ONE file per parameter set = header with the parameter fingerprint, a table
  * (bundle index, cache index, degree, offset, size) and the BinBundle images above at 4096-byte aligned offsets.  The file is
@@ -494,6 +557,8 @@ int apsu_he_multi_db_update_bundle(apsu_he_multi *m, int bundle_id, const uint64
  * apsu_he_multi_db_index_bundles: the ids of one bundle index in cache order; *n = how many there are, the first min(*n, capacity) are written.
  * apsu_he_multi_db_bin_counts: apsu_he_bundle_bin_counts on the owning device.
  * apsu_he_multi_db_bundle_bins: apsu_he_bundle_bins on the owning device, under the handle's lock.
+ * apsu_he_multi_db_self_test: apsu_he_db_self_test of every device's BinBundles, see there; positions in the report are BinBundle ids.
+ *   Run on a device list that repeats one GPU; two distinct GPUs have not run it.
  * apsu_he_multi_db_build_bundle: apsu_he_db_build_bundle on device_slot, or with device_slot = -1 on the slot the placement rule
  *   chooses; the new BinBundle is registered last (*bundle_id = the count before the call).
  * apsu_he_multi_db_remove_bundle: drops one BinBundle; new_id[count before the call].
@@ -513,6 +578,7 @@ int apsu_he_multi_db_bundle_info(apsu_he_multi *m, int bundle_id, int *device_sl
 int apsu_he_multi_db_index_bundles(apsu_he_multi *m, uint32_t bundle_idx, int *ids, int capacity, int *n);
 int apsu_he_multi_db_bin_counts(apsu_he_multi *m, int bundle_id, uint32_t *counts);
 int apsu_he_multi_db_bundle_bins(apsu_he_multi *m, int bundle_id, uint64_t *roots, uint32_t *counts, uint32_t stride);
+int apsu_he_multi_db_self_test(apsu_he_multi *m, const uint64_t seed[8], apsu_he_self_test_report *report);
 int apsu_he_multi_db_build_bundle(apsu_he_multi *m, int device_slot, uint32_t bundle_idx, uint32_t cache_idx, const uint64_t *roots,
                                   const uint32_t *counts, uint32_t bins, uint32_t stride, int *bundle_id);
 int apsu_he_multi_db_remove_bundle(apsu_he_multi *m, int bundle_id, int *new_id);
