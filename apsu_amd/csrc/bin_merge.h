@@ -105,4 +105,35 @@ inline void merge_counts(const u32 *a, const u32 *b, size_t n, u32 max_items, u3
     }
 }
 
+// The host decisions of a merge of n_bundles >= 1 BinBundles (counts [n_bundles][n], degrees [n_bundles]).  Step k < n_bundles - 1
+// multiplies the product of BinBundles 0 .. k (counts: the running sums) by BinBundle k + 1:
+//   tops[(2 k) tiles ..] and tops[(2 k + 1) tiles ..]: merge_tile_tops of the two operands;
+//   rows[k]: the rows k_bins_merge writes = the largest count of either operand, summed, + 1.  The two need not be in the same slot, so
+//            rows[k] can exceed the step's degree + 1, and an early step can be the tallest;
+//   degree: the largest summed count of all.
+// Refusals, step by step and before anything else is decided for that step: merge_counts' (std::invalid_argument), then
+// std::logic_error where an operand's largest count exceeds its BinBundle's degree (the decoded array has no such row).
+struct MergeSteps { std::vector<u32> rows; std::vector<int> tops; u32 degree = 0; };
+inline MergeSteps merge_steps(const u32 *counts, const u32 *degrees, u32 n_bundles, size_t n, u32 max_items)
+{
+    const size_t tiles = (n + MERGE_LANES - 1) / MERGE_LANES;
+    const u32 steps = n_bundles - 1;
+    auto top_of = [](const std::vector<int> &t) { int m = 0; for (int v : t) m = v > m ? v : m; return (u32)m; };
+    MergeSteps ms;
+    ms.rows.resize(steps);
+    ms.tops.resize((size_t)2 * steps * tiles);
+    std::vector<u32> run(counts, counts + n), next(n);
+    for (u32 k = 0; k < steps; k++) {
+        const u32 *cb = counts + (size_t)(k + 1) * n;
+        merge_counts(run.data(), cb, n, max_items, next.data());
+        const std::vector<int> ta = merge_tile_tops(run.data(), n), tb = merge_tile_tops(cb, n);
+        if (top_of(tb) > degrees[k + 1] || (!k && top_of(ta) > degrees[0])) throw std::logic_error("merge: a bin count exceeds its BinBundle's degree");
+        for (size_t i = 0; i < tiles; i++) { ms.tops[(size_t)2 * k * tiles + i] = ta[i]; ms.tops[(size_t)(2 * k + 1) * tiles + i] = tb[i]; }
+        ms.rows[k] = top_of(ta) + top_of(tb) + 1;
+        run.swap(next);
+    }
+    ms.degree = top_of(merge_tile_tops(run.data(), n));
+    return ms;
+}
+
 }  // namespace apsu_he

@@ -3,7 +3,7 @@
 // mod t; with h = ps_low_degree + 1, the coefficients a_{i*h} (i >= 1) are kept in coefficient form -- here pre-lifted and transformed at
 // the high level, H = degree / h of them, slot i - 1; every other coefficient is in NTT form at pt_level, packed in ascending degree
 // order.  Without Paterson-Stockmeyer (ps_low_degree == 0) every d >= 1 is of the second kind.  No HIP in here: Engine::new_bundle
-// fills a Bundle from the layout, upload / finish / decode / download / load (engine_bundles.cpp) read kinds, slots and runs from it and
+// fills a Bundle from the layout, upload / finish / decode / download / load (engine_bundles.cpp) and the saved export (engine_db.cpp) read kinds, slots and runs from it and
 // nowhere else; tests/test_bundle_layout_cpu.py enumerates it through the CPU emulation library against a restatement of the rule.
 //
 // The evaluation (engine.cpp: ps_tables, eval_bundles_nks) relies on one consequence: the NTT-form coefficients of inner polynomial i,

@@ -346,12 +346,23 @@ int apsu_he_debug_bundle_bins_form(apsu_he_ctx *c, const apsu_he_bundle *b, uint
         c->eng->bundle_bins(*b->b, roots, counts, stride, form);
     });
 }
+// the six apsu_he_debug_*_times: the first spans of one entry of the context's clock (Engine::op_times), each to where the caller wants it
+static int read_op_times(apsu_he_ctx *c, Engine::Op op, std::initializer_list<double *> out)
+{
+    return guarded([&] {
+        REQUIRE(c, "null argument");
+        double ms[Engine::OP_SPANS];
+        c->eng->op_times(op, ms, (int)out.size());
+        int i = 0;
+        for (double *p : out) { if (p) *p = ms[i]; i++; }
+    });
+}
 int apsu_he_debug_bins_times(apsu_he_ctx *c, double *decode_ms, double *roots_ms, double *mult_ms)
-{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->bins_times(decode_ms, roots_ms, mult_ms); }); }
+{ return read_op_times(c, Engine::OP_BINS, { decode_ms, roots_ms, mult_ms }); }
 int apsu_he_debug_merge_times(apsu_he_ctx *c, double *decode_ms, double *kernel_ms, double *encode_ms)
-{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->merge_times(decode_ms, kernel_ms, encode_ms); }); }
+{ return read_op_times(c, Engine::OP_MERGE, { decode_ms, kernel_ms, encode_ms }); }
 int apsu_he_debug_lookup_times(apsu_he_ctx *c, double *decode_ms, double *kernels_ms)
-{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->lookup_times(decode_ms, kernels_ms); }); }
+{ return read_op_times(c, Engine::OP_LOOKUP, { decode_ms, kernels_ms }); }
 int apsu_he_algebraize_items(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t *felts, int felts_on_device)
 {
     return guarded([&] {
@@ -435,7 +446,7 @@ int apsu_he_bundles_eval_plain(apsu_he_ctx *c, const apsu_he_bundle *const *bund
     });
 }
 int apsu_he_debug_eval_plain_times(apsu_he_ctx *c, double *decode_ms, double *counts_ms, double *kernel_ms)
-{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->eval_plain_times(decode_ms, counts_ms, kernel_ms); }); }
+{ return read_op_times(c, Engine::OP_EVAL_PLAIN, { decode_ms, counts_ms, kernel_ms }); }
 int apsu_he_db_self_test(apsu_he_ctx *c, const apsu_he_bundle *const *bundles, uint32_t count, const uint64_t *seed, const uint64_t *x,
                          apsu_he_self_test_report *report)
 {
@@ -446,7 +457,7 @@ int apsu_he_db_self_test(apsu_he_ctx *c, const apsu_he_bundle *const *bundles, u
     });
 }
 int apsu_he_debug_self_test_times(apsu_he_ctx *c, double *ms5)
-{ return guarded([&] { REQUIRE(c && ms5, "null argument"); c->eng->self_test_times(ms5); }); }
+{ return guarded([&] { REQUIRE(c && ms5, "null argument"); c->eng->op_times(Engine::OP_SELF_TEST, ms5, 5); }); }
 int apsu_he_multi_db_self_test(apsu_he_multi *m, const uint64_t *seed, apsu_he_self_test_report *report)
 { return guarded([&] { REQUIRE(m && seed && report, "null argument"); report_out(m->m->self_test(seed), report); }); }
 
@@ -1461,7 +1472,7 @@ int apsu_he_bundle_export_saved(apsu_he_ctx *c, const apsu_he_seal_ctx *sc, cons
     });
 }
 int apsu_he_debug_export_times(apsu_he_ctx *c, double *ms6)
-{ return guarded([&] { REQUIRE(c && ms6, "null argument"); c->eng->export_times(ms6); }); }
+{ return guarded([&] { REQUIRE(c && ms6, "null argument"); c->eng->op_times(Engine::OP_EXPORT, ms6, 6); }); }
 int apsu_he_db_export_saved(apsu_he_ctx *c, const apsu_he_seal_ctx *sc, const char *path, const apsu_he_bundle *const *bundles, int count, uint32_t flags,
                             int compr_mode, const uint8_t *oprf_key, size_t oprf_key_size, const uint64_t *hashed_items, size_t n_hashed_items,
                             uint64_t item_count)

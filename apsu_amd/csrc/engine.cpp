@@ -146,10 +146,7 @@ Engine::~Engine()
     for (hipEvent_t e : phase_pool_) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : { query_start_, query_end_ }) if (e) (void)hipEventDestroy(e);
     if (ev_main_) (void)hipEventDestroy(ev_main_);
-    lookup_evs_.release();
-    merge_evs_.release();
-    eval_evs_.release();
-    self_evs_.release();
+    for (OpClock &c : clock_) c.evs.release();
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_side_) (void)hipEventDestroy(ev_side_);
     if (ev_intt_) (void)hipEventDestroy(ev_intt_);

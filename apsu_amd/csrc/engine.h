@@ -179,8 +179,18 @@ public:
     // a BinBundle of ANOTHER context with the same parameters (on src_device) as a BinBundle of this one: its three arrays go device to
     // device on this context's stream (hipMemcpyPeerAsync), no host image.  `src` is only read; the copy is complete on return.
     std::unique_ptr<Bundle> clone_bundle(const Bundle &src, int src_device);
-    // device time of the last bin_counts / lookup_bundles / apply_entries call, summed over its BinBundles: decode_bundle, the kernels behind it
-    void lookup_times(double *decode_ms, double *kernels_ms);
+    // The resident-database calls' clock: one entry per operation, written by that operation alone.  op_times: the first `count` spans
+    // in ms of the context's last such call (0 before the first):
+    //   OP_LOOKUP     (bin_counts / lookup_bundles / apply_entries / compact, summed over the BinBundles) decode_bundle, the kernels behind it
+    //   OP_BINS       (bundle_bins) decode and counts, the root search, multiplicities and copy-back
+    //   OP_MERGE      (merge_bundles) the decodes and counts, the product kernels, the re-encode
+    //   OP_EVAL_PLAIN (bundles_eval_plain, summed over the BinBundles) decode_bundle, k_bin_counts, k_bins_eval
+    //   OP_SELF_TEST  (self_test) decode, k_bin_counts, k_bins_eval (summed over the BinBundles), the comparison, the homomorphic part
+    //   OP_EXPORT     (export_saved) decode and counts, the root search and multiplicities, k_bins_rows (device, by events); the copies
+    //                 to the host, the plaintexts' serialisation, the buffer's assembly (host clock)
+    enum Op { OP_LOOKUP = 0, OP_BINS, OP_MERGE, OP_EVAL_PLAIN, OP_SELF_TEST, OP_EXPORT, OP_COUNT };
+    static constexpr int OP_SPANS = 6;
+    void op_times(Op op, double *ms, int count);
     struct ApplyResult {
         PlaceResult place;                                 // per-entry status and target, per-BinBundle state (db_place.h)
         std::vector<std::unique_ptr<Bundle>> replaced;     // [n_bundles]: the new BinBundle where state == PLACE_REPLACED, else null
@@ -206,8 +216,6 @@ public:
     // holds the zero polynomial.  The BinBundles are only read.
     void bundles_eval_plain(const Bundle *const *bundles, uint32_t n_bundles, const u64 *x, bool x_on_device, const u64 *masks, bool masks_on_device,
                             u64 *out, bool out_on_device, unsigned char *is_bin);
-    // device time of the last bundles_eval_plain call, summed over its BinBundles: decode_bundle, k_bin_counts, k_bins_eval
-    void eval_plain_times(double *decode_ms, double *counts_ms, double *kernel_ms);
     // The self-test (include/apsu_he.h: apsu_he_db_self_test): keygen, relin_keygen, query_create, compute_powers, the masks, eval_bundles and
     // decrypt_decode on device buffers of the call, held slot for slot against bundles_eval_plain of the same values.  x_host (may be
     // null: drawn from the seed): [distinct bundle indices, ascending][n].  For a handle that tests one database in parts (MultiEngine):
@@ -215,8 +223,6 @@ public:
     // BinBundle i in the whole, so every part draws what one context would draw.  Positions in the report are positions in `bundles`.
     SelfTestReport self_test(const Bundle *const *bundles, uint32_t count, const u64 seed[8], const u64 *x_host, const uint32_t *query_indices = nullptr,
                              uint32_t n_query = 0, const uint32_t *mask_positions = nullptr);
-    // device time of the last self_test call: decode, k_bin_counts, k_bins_eval (summed over the BinBundles), the comparison, the homomorphic part
-    void self_test_times(double ms[5]);
     // N2 towards the reference (include/apsu_he.h: apsu_he_bundle_export_saved): the BinBundle as BinBundle::save writes it
     // (wire.h: build_bin_bundle), read by the reference's BinBundle::load and by apsu_he_db_upload_saved_bundle.  ntt_parms_id: SEAL's
     // parms_id of chain level b.pt_level (the engine does not hash parameters; the SEAL context of the C ABI does).  One decode serves
@@ -224,13 +230,6 @@ public:
     // are the stored rows, unpacked one degree at a time.  compr: sealio::COMPR_NONE or COMPR_ZSTD.  `b` is only read.
     enum { SAVED_STRIPPED = 1, SAVED_NO_CACHE = 2 };
     std::vector<uint8_t> export_saved(const Bundle &b, const u64 ntt_parms_id[4], uint32_t flags, int compr);
-    // time of the last export_saved call in ms: decode and counts, the root search and multiplicities, k_bins_rows (device, by events);
-    // the copies to the host, the plaintexts' serialisation, the buffer's assembly (host clock)
-    void export_times(double ms[6]);
-    // device time of the last bundle_bins call: decode and counts, the root search, multiplicities and copy-back
-    void bins_times(double *decode_ms, double *roots_ms, double *mult_ms);
-    // device time of the last merge_bundles call: the decodes and counts, the product kernels, the re-encode
-    void merge_times(double *decode_ms, double *kernel_ms, double *encode_ms);
     struct CompactResult {
         CompactPlan plan;                                  // group per BinBundle, degree per group (db_compact.h)
         std::vector<std::unique_ptr<Bundle>> merged;       // [groups]: the new BinBundle of a group of two or more, else null
@@ -476,7 +475,7 @@ private:
     bool tier1_device_ = false;       // tier-1 operands are device memory and calls do not synchronise
     void tier1_done() { if (!tier1_device_ || prof_on_) sync(); }
     bool packed_rows_ = true;         // BinBundle plaintexts are kept bit-packed in HBM (EngineSwitches::packed_rows, with key switching only; Bundle::packed)
-    // ---- the resident database (engine_bundles.cpp); where a coefficient is stored: bundle_layout.h
+    // ---- the resident database (engine_bundles.cpp, engine_db.cpp); where a coefficient is stored: bundle_layout.h
     BundleLayout layout_of(uint32_t degree) const { return bundle_layout(psu_.query_params.ps_low_degree, degree, hp_.first_chain_idx); }
     std::unique_ptr<Bundle> new_bundle(uint32_t bundle_idx, uint32_t cache_idx, uint32_t degree, BundleLayout *layout = nullptr) const;   // the shape, no buffers yet
     size_t slot_bytes(int chain_idx, bool packed) const;          // bytes of one NTT-form plaintext at a level, either format
@@ -510,37 +509,44 @@ private:
     void ps_products_per_term(EvalCall &c, const EvalPlan &plan, PsBatch &g);
     u64 *ps_i0(EvalCall &c, const EvalPlan &plan, PsBatch &g);
     void ps_epilogue(EvalCall &c, PsBatch &g, const u64 *i0);
-    // (engine_bundles.cpp, like everything from here to unlift_exact_)
+    // (engine_bundles.cpp: these three)
     void finish_bundle(Bundle &b, const u64 *raw);     // raw: [degree+1][n] coefficient-form plaintexts mod t (device)
     void encode_bundle(Bundle &b, const u64 *poly);    // poly: [degree+1][n] slot values -> BatchEncoder::encode, then finish_bundle
     // the inverse: the stored coefficients back to slot values [degree+1][n] mod t.  coeff (may be null): [degree+1][n], the coefficient
     // form mod t on the way there -- what BatchEncoder::encode made of each degree, before the forward transform mod t
     void decode_bundle(const Bundle &b, u64 *poly, u64 *coeff = nullptr);
+    // ---- the calls on a resident database (engine_db.cpp, like everything from here to unlift_exact_)
+    // The context's preconditions in their one order: PSUParams, batching, decodable stored plaintexts (q_0 > 2 t), each including the
+    // ones before it; what (may be null): the call's name, for "more bins than batching slots"
+    enum { NEED_PSU = 1, NEED_BATCHING, NEED_DECODE };
+    void lookup_check(const char *what, int need = NEED_DECODE) const;
+    // The prologue of every such call, inside its WITH_ARENA: poly [degree+1][n] from the arena = decode_bundle(b) (coeff as there), the
+    // decode's workspace free again, then k_bin_counts into dcounts (device, n words; null: no counts).  evs (may be null): stamp `mid`
+    // goes between the decode and the counts.
+    u64 *decode_counted(const Bundle &b, uint32_t *dcounts, u64 *coeff = nullptr, EventStamps *evs = nullptr, size_t mid = 0);
+    struct OpClock { EventStamps evs; double ms[OP_SPANS] = {}; } clock_[OP_COUNT];          // op_times
     // decode each BinBundle in turn through the arena; counts (may be null): [n_bundles][n]; flags (null when count == 0): [n_bundles][count * F]
     void lookup_impl(const Bundle *const *bundles, uint32_t n_bundles, const u64 *felts, const uint32_t *start, size_t count, uint32_t *counts,
                      unsigned char *flags);
-    void lookup_check(const char *what) const;
-    EventStamps lookup_evs_;                           // three per BinBundle of a call: before decode, behind it, behind the kernels
-    double lookup_decode_ms_ = 0, lookup_kernels_ms_ = 0;
-    EventStamps merge_evs_;                            // merge_bundles' five time stamps
-    double merge_ms_[3] = { 0, 0, 0 };
-    EventStamps bins_evs_;                             // bundle_bins' four time stamps
-    double bins_ms_[3] = { 0, 0, 0 };
-    // bundles_eval_plain's and self_test's shared middle: queued inside the caller's WITH_ARENA; four time stamps per BinBundle
+    // bundles_eval_plain's and self_test's shared middle: queued inside the caller's WITH_ARENA; four time stamps per BinBundle from
+    // evs[first] on, summed into ms[3] (decode, counts, kernel) by eval_plain_collect after the caller's sync
     void eval_plain_queue(const Bundle *const *bundles, uint32_t n_bundles, const u64 *const *xs, const u64 *const *masks, u64 *out, unsigned char *is_bin,
-                          u32 *bad);
-    void eval_plain_collect(uint32_t n_bundles);
-    EventStamps eval_evs_, self_evs_;
-    double eval_ms_[3] = { 0, 0, 0 }, self_ms_[5] = { 0, 0, 0, 0, 0 };
-    // bundle_bins without the context's lock.  tap (may be null) is called once the counts are on the host and before the search
-    // divides the columns of poly: export_saved takes the bins' rows and the coefficient-form plaintexts there, from the same decode
-    struct BinsTap { virtual void after_counts(const u64 *poly, const u64 *coeff, const uint32_t *dcounts, const uint32_t *counts) = 0; virtual ~BinsTap() = default; };
-    void bins_impl(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form, BinsTap *tap);
+                          u32 *bad, EventStamps &evs, size_t first);
+    static void eval_plain_collect(const EventStamps &evs, size_t first, uint32_t n_bundles, double *ms);
+    // bundle_bins in stages, for export_saved to take the bins' rows and the coefficient-form plaintexts from the same decode between
+    // (a) and (b), while the columns of poly are whole.  (a) and (b) run inside the caller's WITH_ARENA, (c) behind it.
+    struct BinsCounted { u64 *poly, *coeff; uint32_t *dcounts; const uint32_t *counts; };      // device, device or null, device, host
+    struct BinsFound { std::vector<uint32_t> occ, found, mult; std::vector<u64> hits; uint32_t hstride = 0; };
+    bool bins_prepare(const Bundle &b, int form);      // the refusals and the context's tables; true: the persistent kernel
+    // (a) decode, counts, the sync: stamps 0 and 1 of evs around them
+    BinsCounted bins_counted(const Bundle &b, bool want_coeff, uint32_t *counts, EventStamps &evs);
+    // (b) root search, stamp s, multiplicities and copies (queued), stamp s + 1.  stride (may be null): refused below the largest count
+    void bins_search(const BinsCounted &c, bool kernel, const uint32_t *stride, EventStamps &evs, size_t s, BinsFound &f);
+    // (c) the host end: every bin's list checked and sorted, then written to roots (may be null)
+    void bins_finish(const BinsCounted &c, BinsFound &f, u64 *roots, uint32_t stride);
     // the coefficient-form rows of decode_bundle's `coeff` that a saved BinBundle carries as they are: a_0, then the a_{i h} by slot
     void keep_coeff_rows(const Bundle &b, const u64 *coeff, DevBuf &keep);
-    EventStamps export_evs_;
-    double export_ms_[6] = { 0, 0, 0, 0, 0, 0 };
-    void roots_tables();                               // the context's generator, step table and point table, made by the first bundle_bins
+    void roots_tables();                             // the context's generator, step table and point table, made by the first bundle_bins
     u64 roots_g_ = 0;
     DevBuf d_roots_step_, d_roots_pts_;                // g^i (u32) and the forward transform mod t of the polynomial X, n words each
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)

@@ -1,5 +1,6 @@
-// What the Engine's two translation units share and nobody else sees: engine.cpp (contexts, tier 1, ComputePowers, the evaluation,
-// the querier's side) and engine_bundles.cpp (the resident database: BinBundles made, changed, searched, merged, saved and loaded).
+// What the Engine's three translation units share and nobody else sees: engine.cpp (contexts, tier 1, ComputePowers, the evaluation,
+// the querier's side), engine_bundles.cpp (what makes, stores and converts a BinBundle: upload, build, encode and decode, images) and
+// engine_db.cpp (the calls on a resident database: update, lookup, bins, merge and compaction, export, plaintext evaluation, self-test).
 #pragma once
 #include "engine.h"
 
@@ -63,6 +64,15 @@ template <class T> T *Engine::ws_as(size_t count, size_t extra) { return reinter
 #define H2D(dst, src, words) HIP_CHECK(hipMemcpyAsync(dst, src, (words) * sizeof(u64), tier1_device_ ? hipMemcpyDefault : hipMemcpyHostToDevice, st_))
 #define D2H(dst, src, words) HIP_CHECK(hipMemcpyAsync(dst, src, (words) * sizeof(u64), tier1_device_ ? hipMemcpyDefault : hipMemcpyDeviceToHost, st_))
 #define D2D(dst, src, words) HIP_CHECK(hipMemcpyAsync(dst, src, (words) * sizeof(u64), hipMemcpyDeviceToDevice, st_))
+
+// Caller data mod t: every v[i] < t, else std::invalid_argument naming the first one that is not -- name(i, v[i]) says what it is
+inline std::string not_reduced(const std::string &subject) { return subject + " is not reduced modulo plain_modulus"; }
+template <class Name> void check_reduced(const u64 *v, size_t count, u64 t, Name name)
+{
+    for (size_t i = 0; i < count; i++)
+        if (v[i] >= t) throw std::invalid_argument(not_reduced(name(i, v[i])));
+}
+inline std::string field_element(size_t, u64) { return "field element"; }
 
 inline bool is_monomial(const u64 *pt, size_t count)           // SEAL's multiply_plain takes a monomial without lifting it
 {

@@ -930,6 +930,22 @@ int emu_merge_counts(const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t 
     try { merge_counts(a, b, n, max_items, sum); return 0; } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
+// merge_steps (bin_merge.h): rows[n_bundles - 1], tops[2 (n_bundles - 1) tiles], *degree.  Returns 0, -1 for merge_counts' refusals
+// (std::invalid_argument) or -3 for the logic error, the text in emu_last_error.
+int emu_merge_steps(const uint32_t *counts, const uint32_t *degrees, uint32_t n_bundles, uint64_t n, uint32_t max_items, uint32_t *rows, int *tops,
+                    uint32_t *degree)
+{
+    try {
+        if (!n_bundles) throw std::invalid_argument("no BinBundle");
+        const MergeSteps ms = merge_steps(counts, degrees, n_bundles, n, max_items);
+        std::copy(ms.rows.begin(), ms.rows.end(), rows);
+        std::copy(ms.tops.begin(), ms.tops.end(), tops);
+        *degree = ms.degree;
+        return 0;
+    } catch (const std::invalid_argument &e) { g_err = e.what(); return -1;
+    } catch (const std::exception &e) { g_err = e.what(); return -3; }
+}
+
 // k_bins_rows over poly[rows][n] as the workgroups run it (bin_rows.h): one workgroup per tile of 64 slots x 64 degrees, an explicit
 // loop over its waves and their 64 lanes, the padded LDS tile between the two phases.  counts: n words (emu_bin_counts' form);
 // out: at least off[bins] words, where off is rows_offsets' scan, also returned in off_out (bins + 1 words, may be null).

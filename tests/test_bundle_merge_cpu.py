@@ -336,3 +336,116 @@ def test_merge_counts_names_the_first_slot(emu):
     b[2] = 0
     assert emu.emu_merge_counts(vp(a), vp(b), C.c_uint64(5), 5, vp(out)) == -1
     assert "slot 2 " in emu.emu_last_error().decode()
+
+
+# ---------------------------------------------------------------------------------------------------------- merge_steps
+def run_steps(emu, counts, degrees, max_items):
+    """counts [n_bundles][n], degrees [n_bundles] -> (rows, tops [steps][2][tiles], degree), or (return code, the refusal's text)"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    nb, n = counts.shape
+    tiles = (n + 63) // 64
+    deg = np.ascontiguousarray(degrees, dtype=np.uint32)
+    rows, tops, degree = np.full(nb - 1, 99, dtype=np.uint32), np.full(2 * (nb - 1) * tiles, 99, dtype=np.int32), C.c_uint32(99)
+    rc = emu.emu_merge_steps(vp(counts), vp(deg), nb, C.c_uint64(n), max_items, vp(rows), vp(tops), C.byref(degree))
+    if rc != 0:
+        return rc, emu.emu_last_error().decode()
+    return [int(r) for r in rows], tops.reshape(nb - 1, 2, tiles).tolist(), degree.value
+
+
+def model_steps(counts, degrees, max_items):
+    """the definition in numpy: step k multiplies the product of BinBundles 0 .. k (its counts: the sums so far) by BinBundle k + 1.  The
+    step's refusals come first: slot by slot, a bin in one operand only or (max_items != 0) a sum that reaches max_items; then an
+    operand's largest count above its BinBundle's degree.  tops: per operand and tile of 64 slots the largest count, -1 without a bin;
+    rows = the two operands' largest counts + 1; degree = the largest count of the last sums."""
+    counts = np.asarray(counts, dtype=np.int64)
+    nb, n = counts.shape
+    tiles = (n + 63) // 64
+
+    def tile_tops(c):
+        return [max([int(v) for v in c[64 * k:64 * (k + 1)] if v != NONE], default=-1) for k in range(tiles)]
+
+    run, rows, tops = counts[0].copy(), [], []
+    for k in range(nb - 1):
+        cb = counts[k + 1]
+        lone = (run == NONE) != (cb == NONE)
+        full = (run != NONE) & (cb != NONE) & (run + cb >= max_items) if max_items else np.zeros(n, dtype=bool)
+        if (lone | full).any():
+            s = int(np.argmax(lone | full))
+            return -1, ("slot %d " % s) if lone[s] else ("bin %d:" % s)
+        ta, tb = tile_tops(run), tile_tops(cb)
+        if max(tb + [0]) > degrees[k + 1] or (k == 0 and max(ta + [0]) > degrees[0]):
+            return -3, "merge: a bin count exceeds its BinBundle's degree"
+        tops.append([ta, tb])
+        rows.append(max(ta + [0]) + max(tb + [0]) + 1)
+        run = np.where(run == NONE, NONE, run + cb)
+    return rows, tops, max(tile_tops(run) + [0])
+
+
+def check_steps(emu, counts, degrees, max_items):
+    got, want = run_steps(emu, counts, degrees, max_items), model_steps(counts, degrees, max_items)
+    if isinstance(want[0], int):
+        assert got[0] == want[0] and want[1] in got[1], (got, want)
+    else:
+        assert got == want
+    return got
+
+
+def degrees_of(counts):
+    return [max([int(v) for v in c if v != NONE] + [0]) for c in counts]
+
+
+@pytest.mark.parametrize("n", [64, 128])
+@pytest.mark.parametrize("nb", [2, 3])
+def test_merge_steps_random_counts(emu, n, nb):
+    rng = np.random.default_rng(100 * n + nb)
+    for trial in range(20):
+        counts = rng.integers(0, 7, (nb, n)).astype(np.int64)
+        counts[:, rng.integers(0, n, 5)] = NONE           # the same slots are no bins in every input
+        if n == 128 and trial % 2:
+            counts[:, 64:] = NONE                          # a tile without a bin next to one with bins
+        rows, tops, degree = check_steps(emu, counts, degrees_of(counts), 0)
+        assert len(rows) == nb - 1 and degree <= 6 * nb
+        if n == 128 and trial % 2:
+            assert all(t[1] == -1 and t[0] >= 0 for step in tops for t in step)
+
+
+def test_merge_steps_rows_are_a_bound_over_tiles(emu):
+    # the largest counts of A and B in different slots of one tile: rows exceeds degree + 1, and with a third BinBundle of empty bins
+    # the first step is the tallest
+    a, b, c = [0] * 64, [0] * 64, [0] * 64
+    a[3], b[40] = 5, 5
+    rows, tops, degree = check_steps(emu, [a, b], [5, 5], 0)
+    assert (rows, tops, degree) == ([11], [[[5], [5]]], 5) and rows[0] > degree + 1
+    rows, tops, degree = check_steps(emu, [a, b, c], [5, 5, 0], 0)
+    assert (rows, degree) == ([11, 6], 5) and rows[0] > rows[1] and tops[1] == [[5], [0]]
+    # two tiles: each tile has its own tops, rows takes the largest of each operand wherever it lies
+    a, b = [1] * 128, [2] * 128
+    a[70], b[5] = 9, 4
+    rows, tops, degree = check_steps(emu, [a, b], [9, 4], 0)
+    assert (rows, tops, degree) == ([14], [[[1, 9], [4, 2]]], 11)
+    # a BinBundle whose degree is above every count (plaintexts above the longest bin) is no error
+    assert check_steps(emu, [a, b], [12, 4], 0) == (rows, tops, degree)
+
+
+def test_merge_steps_refusals_in_order(emu):
+    a = [2, 1, NONE, 3] + [0] * 60
+    b = [1, 1, NONE, 1] + [0] * 60
+    # the sum 3 + 1 = 4: max_items = 4 refuses it (a bin holds max_items - 1 at the most), 5 accepts it, 0 is no bound
+    assert check_steps(emu, [a, b], [3, 1], 4)[0] == -1 and "bin 3:" in run_steps(emu, [a, b], [3, 1], 4)[1]
+    assert check_steps(emu, [a, b], [3, 1], 5) == ([5], [[[3], [1]]], 4)
+    assert check_steps(emu, [a, b], [3, 1], 0) == ([5], [[[3], [1]]], 4)
+    # a slot that is a bin in one input only; an earlier slot's bound comes first
+    lone = list(b)
+    lone[2] = 0
+    assert check_steps(emu, [a, lone], [3, 1], 5)[0] == -1 and "slot 2 " in run_steps(emu, [a, lone], [3, 1], 5)[1]
+    assert "bin 0:" in run_steps(emu, [a, lone], [3, 1], 3)[1]
+    # a count above its BinBundle's degree, in either operand of the first step and in the new operand of a later one: the logic error,
+    # behind that step's merge_counts refusals
+    for degrees in ([2, 1], [3, 0]):
+        rc, msg = check_steps(emu, [a, b], degrees, 0)
+        assert rc == -3 and msg == "merge: a bin count exceeds its BinBundle's degree"
+    assert check_steps(emu, [a, b, b], [3, 1, 0], 0)[0] == -3
+    assert check_steps(emu, [a, lone], [2, 1], 5)[0] == -1
+    # the refusal of a later step: the sums so far count, 3 + 1 + 1 = 5
+    assert "bin 3:" in run_steps(emu, [a, b, b], [3, 1, 1], 5)[1]
+    assert check_steps(emu, [a, b, b], [3, 1, 1], 6) == ([5, 6], [[[3], [1]], [[4], [1]]], 5)

@@ -99,6 +99,69 @@ def test_toy_ring_full_stripped_and_no_cache(toy):
     assert ms["decode_counts"] > 0 and ms["bins_rows"] > 0 and ms["serialise"] > 0
 
 
+def two_toy_bundles(G, t):
+    """toy_bins (degree 10) and 60 bins with counts 0 .. 4 that merge with it: no summed count reaches max_items_per_bin = 11"""
+    B = toy_bins(t)
+    rng = np.random.default_rng(17)
+    B2 = [U.distinct(rng, t, min(4, 10 - len(x))) for x in B]
+    assert sorted({len(x) for x in B2}) == [0, 1, 2, 3, 4]
+    return G.build_bundle(0, 0, B), G.build_bundle(0, 1, B2)
+
+
+def resident_calls(G, sc, a, b, x):
+    """the staged calls, each the context's first of its kind -> (their results as bytes and lists, arena growths of the first export)"""
+    grown = G.debug_counters()["arena_grow"]
+    out = [seal.export_saved_bundle(G, sc, a)]
+    grown = G.debug_counters()["arena_grow"] - grown
+    out.append(seal.export_saved_bundle(G, sc, a, cache=False))
+    out.append([None if v is None else v.tolist() for v in G.bins(a)])
+    out.append(G.save_bundle(G.merge_bundles([a, b])).tobytes())
+    res, is_bin = G.eval_plain([a, b], x, want_is_bin=True)
+    return out + [res.tobytes(), is_bin.tobytes()], grown
+
+
+def test_staged_calls_under_arena_retry(monkeypatch):
+    """every call that runs bundle_bins' stages or the shared prologue inside its arena body gives the same bytes when the body runs
+    twice: a context without a workspace grows it on the way, the overflow comes wherever the call first needs more"""
+    js = common.toy_json()
+    t = U.toy_t(js)
+    sc = seal.SealContext(js)
+    x = np.random.default_rng(18).integers(0, t, (2, 64), dtype=np.uint64)
+    G0 = apsu_amd.HeContext(js)
+    want, _ = resident_calls(G0, sc, *two_toy_bundles(G0, t), x)
+    G0.close()
+    monkeypatch.setenv("APSU_HE_ARENA_BYTES", "0")                     # (read when a context is created)
+    G = apsu_amd.HeContext(js)
+    got, grown = resident_calls(G, sc, *two_toy_bundles(G, t), x)
+    assert grown > 0, "the first export's body did not run twice"
+    assert got == want
+    G.close()
+    sc.close()
+
+
+def test_each_clock_is_its_own(toy):
+    js, G, sc, t = toy
+    a, b = two_toy_bundles(G, t)
+    x = np.random.default_rng(19).integers(0, t, (2, G.n), dtype=np.uint64)
+    G.bins(a)
+    bins_ms = G.bins_times()
+    assert all(v > 0 for v in bins_ms)
+    seal.export_saved_bundle(G, sc, a)
+    ms = seal.export_saved_times(G)
+    assert all(ms[k] > 0 for k in ("decode_counts", "bundle_bins", "bins_rows", "copies", "serialise"))
+    entry = (1, [toy_bins(t)[1 + j][0] for j in range(5)])
+    assert G.lookup([a], [entry])[0][0][0]
+    assert all(v > 0 for v in G.lookup_times())
+    assert G.bins_times() == bins_ms                                   # the export's bins and the lookup left bundle_bins' clock alone
+    G.eval_plain([a, b], x)
+    eval_ms = G.eval_plain_times()
+    assert all(v > 0 for v in eval_ms)
+    assert G.self_test([a, b]).mismatches == 0
+    assert all(v > 0 for v in G.self_test_times())
+    assert G.eval_plain_times() == eval_ms                             # the self-test's plaintext answer has its own copy
+    assert G.bins_times() == bins_ms
+
+
 def test_toy_ring_after_update_merge_and_image_round_trip(toy):
     js, G, sc, t = toy
     rng = np.random.default_rng(7)
