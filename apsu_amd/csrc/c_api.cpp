@@ -346,6 +346,19 @@ int apsu_he_debug_bundle_bins_form(apsu_he_ctx *c, const apsu_he_bundle *b, uint
         c->eng->bundle_bins(*b->b, roots, counts, stride, form);
     });
 }
+int apsu_he_debug_run_step(apsu_he_ctx *c, const apsu_he_step_args *args)
+{
+    return guarded([&] {
+        REQUIRE(c && args, "null argument");
+        static_assert((int)APSU_HE_STEP_LIFT + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY, "step ids of the header and the engine");
+        Engine::StepArgs a{};
+        a.step = args->step; a.chain_idx = args->chain_idx; a.flags = args->flags;
+        a.terms = args->terms; a.polys = args->polys; a.batch = args->batch; a.e0 = args->e0; a.n_ext = args->n_ext;
+        for (int i = 0; i < 6; i++) { a.in[i] = args->in[i]; a.in_words[i] = args->in_words[i]; }
+        for (int i = 0; i < 2; i++) { a.out[i] = args->out[i]; a.out_words[i] = args->out_words[i]; }
+        c->eng->debug_run_step(a);
+    });
+}
 // the six apsu_he_debug_*_times: the first spans of one entry of the context's clock (Engine::op_times), each to where the caller wants it
 static int read_op_times(apsu_he_ctx *c, Engine::Op op, std::initializer_list<double *> out)
 {

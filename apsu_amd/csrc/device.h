@@ -17,6 +17,17 @@
 namespace apsu_he {
 
 // ---- launch wrappers (all asynchronous on `st`) --------------------------------------------
+// INPUT CONTRACTS of the element-wise launchers ("contract:" lines below; tests/test_gpu_kernel_steps.py feeds every launcher exactly
+// up to its contract through Engine::debug_run_step, which refuses what lies beyond it).
+//   canonical: a word in [0, m) for the modulus m of its limb (or [0, t) for a plaintext coefficient).
+//   RAW:       what an inverse transform leaves where the limb's map entry carries NTT_MAP_RAW -- no twist, no closing reduction; the
+//              word w stands for the residue w n^-1 psi^-k mod m at coefficient k.  What the transform can actually leave
+//              (ntt_core.h, the last inverse pass, `OUT == IO_GLOBAL && !(INV && RAW)`): for a wide modulus (not ntt_is_narrow) the
+//              butterflies keep values in [0, 2^64) by csub_top alone, so ANY 64-bit word; for a narrow modulus, which runs without
+//              range control, below (2^K b0 + 4 (logn - K)) m, with K the stages of the first inverse pass and b0 = 1 for a canonical
+//              source or ntt_lazy_bound_q(tab) for the tensor fold's last word (ntt_lazy_input_ok) -- under 2^64 by the narrow
+//              criterion, and nothing tighter is argued.  Every RAW consumer therefore takes ANY 64-bit word: its first operation on
+//              the word is a Shoup product (mul_shoup / mul_shoup_lazy, modmath.h: exact for any 64-bit x, m < 2^63).
 // NTT over `count` consecutive limb polynomials of n coefficients; limb g uses
 // tabs[modmap[g % period] & NTT_MAP_MASK].  An inverse transform of a limb whose map entry carries NTT_MAP_RAW (dev_consts.h) writes
 // its result WITHOUT the final twist n^-1 psi^-k and without the final reduction (consumers: the unrolled BEHZ finish kernels).
@@ -29,19 +40,26 @@ void launch_ntt(int logn, bool inverse, u64 *data, size_t count, const NttTable 
 void launch_ntt_gather(int logn, const u64 *const *src, u64 *data, size_t count, const NttTable *tabs, const int *modmap, int period,
                        hipStream_t st, bool nored, size_t latency_limbs, bool narrow);
 // out = a (.) b per limb; a:[batch][polys][L][n], b:[batch][L][n] (b_batch_stride may be 0)
+// contract: ct and pt canonical (one 128-bit product per word, Barrett-reduced)
 void launch_dyadic_plain(const DevLevel *lv, const u64 *ct, const u64 *pt, u64 *out, int polys, size_t n, int batch,
                          size_t pt_batch_stride, hipStream_t st);
 void launch_add(const DevLevel *lv, u64 *acc, const u64 *x, int polys, size_t n, int batch, hipStream_t st);
+// contract (launch_add, launch_add_many, launch_sum_jobs): every word canonical -- one conditional subtraction per addition
 // acc[b] += sum_{i<terms} x[b][i]   (x: [batch][terms][polys][L][n]; acc: [batch] stride acc_stride words)
 void launch_add_many(const DevLevel *lv, u64 *acc, size_t acc_stride, const u64 *x, int terms, int polys, size_t n,
                      int batch, hipStream_t st);
 struct SumJob { const u64 *src; u64 *dst; int terms; int pad; };
 void launch_sum_jobs(const DevLevel *lv, int L, const SumJob *jobs, int polys, size_t n, int njobs, hipStream_t st);
+// launch_sum_jobs: two coefficients per lane (n even, src and dst 16-byte aligned)
 struct PlainJob { u64 *ct; const u64 *pt; };        // ct: c0 limbs [L][n] ; pt: n coefficients mod t
+// contract (launch_add_plain, launch_lift): pt canonical mod t (m < t < 2^61: the 128-by-64 division of the scaling takes the
+// shift-subtract branch only for t > 2^32), ct canonical
 void launch_add_plain(const DevLevel *lv, const PlainJob *jobs, size_t n, int batch, hipStream_t st);
 void launch_lift(const DevLevel *lv, const u64 *pt, u64 *out, size_t n, int batch, const unsigned char *no_lift,
                  hipStream_t st);
 // drop last limb: ct c at in + c*in_stride holds `polys` polys [L][n] -> out packed [c][polys][L-1][n]
+// contract (launch_modswitch, launch_modswitch_jobs): every limb canonical; L >= 2.  The dropped prime may be narrower or wider than
+// the kept ones: (last + half) mod q_last is reduced into each kept prime by barrett64
 void launch_modswitch(const DevLevel *lv, const u64 *in, size_t in_stride, int polys, u64 *out, size_t n, int cts,
                       hipStream_t st);
 void launch_clear_bits(u64 *ct, size_t words, int bits, hipStream_t st);
@@ -129,12 +147,17 @@ void launch_rlk_finish(const DevKey *key, int K, const u64 *s, const u64 *e, u64
 void launch_flag_monomial(const u64 *pt, size_t n, int batch, unsigned char *flag, hipStream_t st);
 // BEHZ
 // ct c at in + c*in_stride holds `polys` polys [L][n]; out packed [c][polys][E][n]
+// contract: every limb canonical (the q limbs are copied to the output as they are)
 void launch_behz_ext(const DevLevel *lv, int L, int nB, const u64 *in, size_t in_stride, int polys, u64 *out, size_t n, int cts,
                      hipStream_t st);
 // mod_switch_to_next + extension in one pass (input: L + 1 limbs per polynomial at level lv + 1); false = not available for this size
 // raw: `in` comes from an inverse NTT that left out its twist (NTT_MAP_RAW); needs lv[1].drop_tw / last_tw
+// contract: L == nB <= 3 (behz_unrolled), else declined.  raw = false: all L + 1 limbs canonical.  raw = true: all L + 1 limbs RAW, any
+// 64-bit word (the dropped limb is made canonical by one exact Shoup product, the kept ones enter a + 2q - b with a, b in [0, 2q))
 bool launch_drop_behz_ext(const DevLevel *lv, int L, int nB, const u64 *in, size_t in_stride, int polys, u64 *out, size_t n, int cts,
                           hipStream_t st, bool raw = false);
+// contract (launch_tensor, launch_tensor_conv, launch_tensor_sum): every operand limb canonical modulo its ext modulus (q limbs < 2^60,
+// Bsk limbs < 2^61: a product is below 2^122, launch_tensor_sum folds its 128-bit sums every 8 terms = 16 products)
 struct TensorJob { const u64 *a, *b; u64 *d; };   // a,b: [2][E][n] ext-NTT ; d: [3][E][n]
 void launch_tensor(const DevLevel *lv, const TensorJob *jobs, size_t n, int batch, hipStream_t st);
 // operands of any size: a: [sa][E][n], b: [sb][E][n] ext-NTT ; d: [sa + sb - 1][E][n]   (no key switching: products are never relinearised)
@@ -151,14 +174,22 @@ void launch_tensor_sum(const DevLevel *lv, int E, const TensorSumJob *jobs, size
 void launch_intt_tensor(int logn, const TensorJob *jobs, int njobs, int limbs, size_t src_ps, u64 *plain, size_t n_plain,
                         const NttTable *tabs, const int *modmap, int period, hipStream_t st, size_t latency_limbs = 0);
 struct FinishSumJob { const u64 *dq, *bs; u64 *out; int terms; int pad; };   // out: [3][L][n] = sum of the finished terms
+// contract (launch_behz_finish_sum, launch_behz_finish): for L == nB <= 3 (behz_unrolled) dq / bs / d are RAW, any 64-bit word (the twist
+// is part of fin_q / fin_b), and ONLY RAW; every other level takes canonical limbs.  An accumulated-into `out` is canonical.
+// launch_behz_finish_sum adds the per-term canonical residues of a q limb as plain integers: terms * q_widest < 2^63 (plan_eval,
+// p.summed; the kernels themselves need terms * q_j < 2^64)
 void launch_behz_finish_sum(const DevLevel *lv, int L, int nB, const FinishSumJob *jobs, size_t n, int njobs, hipStream_t st);
 // finish: out[3][L][n] (+)= sum over `terms` consecutive products d[term][3][E][n] (coeff form)
 struct FinishJob { const u64 *d; u64 *out; int terms; int pad; };
 void launch_behz_finish(const DevLevel *lv, int L, int nB, const FinishJob *jobs, bool accumulate, size_t n, int njobs, hipStream_t st);
 // key switching
+// contract: tdec limb (I, J) canonical modulo m_I (the key moduli of this level, then the special prime), rk canonical: at most DMAXL
+// products below 2^120 per 128-bit sum
 void launch_ks_inner(const DevKey *key, int L, const u64 *tdec, const u64 *rk, u64 *acc, size_t n, int batch,
                      hipStream_t st);
 // raw: acc comes from an inverse NTT that left out its twist (L <= 4; needs key->md_tw / p_tw)
+// contract: ct canonical.  raw = false: acc canonical (the special limb below p).  raw = true: all L + 1 limbs of acc RAW, any 64-bit
+// word; L <= 4.  ext / n_ext: only for L == nB <= 3 (the caller checks)
 void launch_ks_moddown(const DevKey *key, int L, const u64 *acc, u64 *ct, size_t ct_stride, size_t n, int batch,
                        hipStream_t st, const DevLevel *lv = nullptr, u64 *ext = nullptr, int n_ext = 0, bool raw = false);
 // k_mac over njobs MacJobs (mac_core.h) in the form (kara: three products; packed: bit-packed plaintexts) and on the grid of a MacPlan (mac_plan.h)
@@ -172,6 +203,7 @@ void launch_pack_rows(const DevLevel *lv, int L, const u64 *dense, void *packed,
 void launch_unpack_rows(const DevLevel *lv, int L, const void *packed, size_t slot_bytes, u64 *dense, size_t n, size_t slots, hipStream_t st);
 // Fused tail of eval / eval_patstock (bin_bundle.cpp:159-171, 345-357): (c0,c1) (+ optional exact addends) + Delta*a0 +
 // Delta*mask, drop limbs down to the last level, clear the irrelevant bits, write the 2n-word result.
+// contract: ct, add1, add2 canonical at level lvl; a0 and mask canonical mod t; with a key, ks_acc RAW (any 64-bit word) and lvl + 1 <= 4
 struct EpiJob { const u64 *ct; const u64 *add1; const u64 *add2; const u64 *a0; const u64 *mask; u64 *out;
                 const u64 *ks_acc = nullptr; };   // round 6: RAW key-switch sums [2][L+1][n] whose mod-down the epilogue performs (launch_eval_epilogue with a key)
 void launch_eval_epilogue(const DevLevel *levels, int lvl, const EpiJob *jobs, size_t ct_poly_stride, int clear_bits, size_t n,
@@ -180,6 +212,8 @@ void launch_eval_epilogue(const DevLevel *levels, int lvl, const EpiJob *jobs, s
 // acc[p][m] += (S[p][m] + terms*half - sum_t ((V[t][p] + half) mod q_last)) * q_last^-1  mod q_m
 struct I0Job { const u64 *s; const u64 *v; u64 *acc; int terms; int store; };   // s:[2][L-1][n] v:[terms][2][n] acc:[2][L-1][n] (store: = instead of +=)
 // raw: s and v come from an inverse NTT that left out its twist (needs lv_low->drop_tw / last_tw)
+// contract: L >= 2 at lv_low; (terms + 1) * q_last < 2^64 (plan_eval, p.i0_fast); acc canonical unless stored.  raw = false: s and v
+// canonical.  raw = true: s and v RAW, any 64-bit word
 void launch_i0_finish(const DevLevel *lv_low, const I0Job *jobs, size_t n, int njobs, hipStream_t st, bool raw = false);
 
 } // namespace apsu_he

@@ -337,6 +337,23 @@ public:
     void download_power(const Powers &pw, uint32_t bundle_idx, uint32_t power, u64 *out, size_t capacity_words, int *chain_idx,
                         int *is_ntt);
     int device() const { return device_; }
+    // test hook (engine_steps.cpp; include/apsu_he.h: apsu_he_debug_run_step): ONE launch_* call of device.h on host arrays in that
+    // launcher's documented layout, with this context's own constant blocks.  Step ids, flags and the argument block mirror the C ABI's.
+    // Refuses (std::invalid_argument, nothing launched) whatever the launcher's input contract does not admit.
+    enum Step { STEP_LEVEL_INFO = 0, STEP_BEHZ_EXT, STEP_DROP_BEHZ_EXT, STEP_TENSOR, STEP_TENSOR_CONV, STEP_TENSOR_SUM, STEP_BEHZ_FINISH,
+                STEP_BEHZ_FINISH_SUM, STEP_KS_INNER, STEP_KS_MODDOWN, STEP_MODSWITCH, STEP_MODSWITCH_JOBS, STEP_I0_FINISH, STEP_EVAL_EPILOGUE,
+                STEP_ADD_MANY, STEP_SUM_JOBS, STEP_ADD_PLAIN, STEP_DYADIC_PLAIN, STEP_LIFT, STEP_COUNT };
+    enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8 };
+    struct StepArgs {
+        int step, chain_idx;
+        uint32_t flags;
+        int terms, polys, batch, e0, n_ext;
+        const u64 *in[6];
+        size_t in_words[6];
+        u64 *out[2];
+        size_t out_words[2];
+    };
+    void debug_run_step(const StepArgs &a);
     // Staging of apsu_he_run_query_request (c_api.cpp) kept across calls: a device buffer and a page-locked host buffer of at least
     // `bytes` (grown on demand; hipHostMalloc / hipMalloc per query cost milliseconds).  The caller holds wire_mutex() for the whole query.
     std::mutex &wire_mutex() { return wire_mu_; }

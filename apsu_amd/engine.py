@@ -164,6 +164,19 @@ class _SelfTestReport(C.Structure):
 SelfTestReport = collections.namedtuple("SelfTestReport", "bundles slots mismatches first_mismatch min_budget min_budget_bundle he_ms plain_ms")
 
 
+class _StepArgs(C.Structure):          # apsu_he_step_args
+    _fields_ = [("step", C.c_int32), ("chain_idx", C.c_int32), ("flags", C.c_uint32), ("terms", C.c_int32), ("polys", C.c_int32),
+                ("batch", C.c_int32), ("e0", C.c_int32), ("n_ext", C.c_int32), ("inp", u64p * 6), ("in_words", C.c_size_t * 6),
+                ("out", u64p * 2), ("out_words", C.c_size_t * 2)]
+
+
+# apsu_he_debug_run_step: the step ids (APSU_HE_STEP_*) by name, and the flags
+STEPS = {name: i for i, name in enumerate((
+    "level_info", "behz_ext", "drop_behz_ext", "tensor", "tensor_conv", "tensor_sum", "behz_finish", "behz_finish_sum", "ks_inner",
+    "ks_moddown", "modswitch", "modswitch_jobs", "i0_finish", "eval_epilogue", "add_many", "sum_jobs", "add_plain", "dyadic_plain", "lift"))}
+STEP_RAW, STEP_ACCUMULATE, STEP_STORE, STEP_KEY = 1, 2, 4, 8
+
+
 def _self_test_report(r):
     """first_mismatch: None, or (BinBundle, slot, got, expected); min_budget_bundle: None when nothing was checked"""
     first = None if r.first_bundle < 0 else (int(r.first_bundle), int(r.first_slot), int(r.first_got), int(r.first_expected))
@@ -465,6 +478,30 @@ class HeContext:
         else:
             _check(lib.apsu_he_bundle_bins(self.h, bundle.h, _p(roots), C.c_void_p(counts.ctypes.data), C.c_uint32(stride)))
         return _bins_list(roots, counts)
+
+    def debug_run_step(self, step, chain_idx, ins=(), outs=(), flags=0, terms=0, polys=0, batch=1, e0=0, n_ext=0):
+        """tests only: ONE element-wise launch on host arrays (apsu_he_debug_run_step; the layouts are in include/apsu_he.h).  step: a
+        name of STEPS; ins: up to six uint64 arrays or None; outs: up to two uint64 arrays, written (and read, where the step adds
+        into its output).  A refusal raises ValueError with the library's reason."""
+        a = _StepArgs()
+        a.step, a.chain_idx, a.flags = STEPS[step], chain_idx, flags
+        a.terms, a.polys, a.batch, a.e0, a.n_ext = terms, polys, batch, e0, n_ext
+        for i, x in enumerate(ins):
+            if x is not None:
+                a.inp[i], a.in_words[i] = _p(x), x.size
+        for i, x in enumerate(outs):
+            if x is not None:
+                a.out[i], a.out_words[i] = _p(x), x.size
+        _check(load_library().apsu_he_debug_run_step(self.h, C.byref(a)))
+
+    def level_info(self, chain_idx):
+        """tests only: the moduli of a chain level as the context holds them -> dict(L, nB, unrolled, K, q, B, m_sk, p, clear_bits)"""
+        out = np.zeros(64, dtype=np.uint64)
+        self.debug_run_step("level_info", chain_idx, outs=[out])
+        v = [int(x) for x in out]
+        L, nB = v[0], v[1]
+        return dict(L=L, nB=nB, unrolled=bool(v[2]), K=v[3], q=v[4:4 + L], B=v[4 + L:4 + L + nB], m_sk=v[4 + L + nB], p=v[5 + L + nB],
+                    clear_bits=v[6 + L + nB])
 
     def eval_plain(self, bundles, x, masks=None, want_is_bin=False):
         """What resident BinBundles answer in plaintext (apsu_he_bundles_eval_plain): x [len(bundles)][n] slot values below t, masks the

@@ -258,6 +258,57 @@ int apsu_he_debug_lookup_times(apsu_he_ctx *ctx, double *decode_ms, double *kern
 int apsu_he_bundle_bins(apsu_he_ctx *ctx, const apsu_he_bundle *bundle, uint64_t *roots, uint32_t *counts, uint32_t stride);
 int apsu_he_debug_bundle_bins_form(apsu_he_ctx *ctx, const apsu_he_bundle *bundle, uint64_t *roots, uint32_t *counts, uint32_t stride, int form);
 int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_ms, double *mult_ms);
+/* One element-wise kernel on caller-chosen words (added after ABI 7, additive; the ABI stays 7).  TEST-ONLY, synchronous, not for
+ * callers: it exists for the tests that hold each kernel against a big-integer model of the same step at the inputs where the
+ * kernel's range argument is tight -- inputs no public call can steer, since in a query they come out of transforms and base
+ * conversions.  The call copies the host arrays to the device, builds the job structs, calls the very launch function the engine
+ * calls for that step with the context's own constant blocks of chain level chain_idx (so the launcher's choice of kernel is part of
+ * what runs), waits, and copies the result back.  Layouts ([..][n] words, n = poly_modulus_degree; L limbs at chain_idx, nB auxiliary
+ * primes, nBsk = nB + 1, E = L + nBsk, K key primes; `batch` jobs):
+ *   LEVEL_INFO      out[0] = L, nB, unrolled (L == nB <= 3), K, q_0 .., B_0 .., m_sk, special prime (0 without key switching),
+ *                   irrelevant_bit_count -- the moduli the model needs (the auxiliary base is the engine's own choice)
+ *   BEHZ_EXT        in[0] [batch][polys][L][n] -> out[0] [batch][polys][E][n]
+ *   DROP_BEHZ_EXT   in[0] [batch][polys][L + 1][n] at chain_idx + 1 -> out[0] [batch][polys][E][n]          (RAW: in[0] raw words)
+ *   TENSOR          in[0], in[1] [batch][2][E][n] -> out[0] [batch][3][E][n]
+ *   TENSOR_CONV     in[0] [batch][sa][E][n], in[1] [batch][sb][E][n] -> out[0] [batch][sa + sb - 1][E][n]   (polys = sa, terms = sb)
+ *   TENSOR_SUM      in[0], in[1] [batch][terms][2][E][n] -> out[0] [batch][terms][3][L][n] (e0 == 0 only), out[1] [batch][3][nBsk][n]
+ *   BEHZ_FINISH     in[0] [batch][terms][3][E][n] -> out[0] [batch][3][L][n]   (ACCUMULATE: added to out[0]'s content; RAW: see below)
+ *   BEHZ_FINISH_SUM in[0] [batch][terms][3][L][n], in[1] [batch][3][nBsk][n] -> out[0] [batch][3][L][n]     (RAW: see below)
+ *   KS_INNER        in[0] [batch][L + 1][L][n], in[1] [K - 1][2][K][n] -> out[0] [batch][2][L + 1][n]
+ *   KS_MODDOWN      in[0] [batch][2][L + 1][n] added into out[0] [batch][polys][L][n] (polys 2 or 3); n_ext > 0: out[1] [n_ext][2][E][n],
+ *                   the BEHZ extension of the first n_ext results                                            (RAW: in[0] raw words)
+ *   MODSWITCH, MODSWITCH_JOBS   in[0] [batch][polys][L][n] -> out[0] [batch][polys][L - 1][n]
+ *   I0_FINISH       chain_idx = the level before the drop; in[0] [batch][2][L - 1][n], in[1] [batch][terms][2][n] -> out[0]
+ *                   [batch][2][L - 1][n] (STORE: written, else added to its content)                  (RAW: in[0], in[1] raw words)
+ *   EVAL_EPILOGUE   in[0] [batch][2][L][n], in[1] a0 [batch][n], in[2] mask [batch][n], in[3] / in[4] addends [batch][2][L][n] or
+ *                   null, KEY: in[5] the RAW key-switch sums [batch][2][L + 1][n] -> out[0] [batch][2][n]
+ *   ADD_MANY        in[0] [batch][terms][polys][L][n] added into out[0] [batch][polys][L][n];  SUM_JOBS: the same sums written
+ *   ADD_PLAIN       in[0] [batch][n] mod t, scaled and added into out[0] [batch][L][n] (c0)
+ *   DYADIC_PLAIN    in[0] [batch][polys][L][n], in[1] [batch][L][n] -> out[0] [batch][polys][L][n]
+ *   LIFT            in[0] [batch][n] mod t, in[1] null or [batch] words (non-zero: not lifted) -> out[0] [batch][L][n]
+ * RAW: the operand is what an inverse transform leaves when its limb's map entry carries the RAW mark -- any 64-bit word w, standing
+ * for the residue w n^-1 psi^-k at coefficient k.  The finish of a level with L == nB <= 3 takes ONLY such input (flag required there,
+ * refused elsewhere).  Every other operand is a canonical residue of its limb (or of plain_modulus).
+ * Refusals, all APSU_HE_INVALID_ARGUMENT with the reason in apsu_he_last_error and nothing launched: an unknown step; a chain_idx that
+ * is no data level; an array whose size is not the layout's; a word that is not canonical where the step needs a canonical one; RAW
+ * where the launcher has no RAW form (DROP_BEHZ_EXT and the fused extension of KS_MODDOWN exist for L == nB <= 3 only, RAW KS_MODDOWN
+ * and the KEY epilogue up to L = 4); a term count beyond the bound the engine checks on the host -- terms * q_widest < 2^63 for
+ * BEHZ_FINISH_SUM, (terms + 1) * q_last < 2^64 for I0_FINISH. */
+enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEHZ_EXT, APSU_HE_STEP_TENSOR, APSU_HE_STEP_TENSOR_CONV,
+       APSU_HE_STEP_TENSOR_SUM, APSU_HE_STEP_BEHZ_FINISH, APSU_HE_STEP_BEHZ_FINISH_SUM, APSU_HE_STEP_KS_INNER, APSU_HE_STEP_KS_MODDOWN,
+       APSU_HE_STEP_MODSWITCH, APSU_HE_STEP_MODSWITCH_JOBS, APSU_HE_STEP_I0_FINISH, APSU_HE_STEP_EVAL_EPILOGUE, APSU_HE_STEP_ADD_MANY,
+       APSU_HE_STEP_SUM_JOBS, APSU_HE_STEP_ADD_PLAIN, APSU_HE_STEP_DYADIC_PLAIN, APSU_HE_STEP_LIFT };
+enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8 };
+typedef struct {
+    int32_t step, chain_idx;
+    uint32_t flags;
+    int32_t terms, polys, batch, e0, n_ext;
+    const uint64_t *in[6];
+    size_t in_words[6];
+    uint64_t *out[2];
+    size_t out_words[2];
+} apsu_he_step_args;
+int apsu_he_debug_run_step(apsu_he_ctx *ctx, const apsu_he_step_args *args);
 /* N1, compaction: the way back from many sparse BinBundles to few full ones.  The placement rule tries BinBundles newest first and
  * drops one only when it is empty, so after insertions and removals a bundle index keeps several half-empty BinBundles, and each costs
  * every query its fixed share: the high-power ciphertext products, a key switch, one result ciphertext, one block of PEQT / OT work.
