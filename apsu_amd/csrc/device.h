@@ -79,24 +79,52 @@ struct SeedJob { Blake2xbSeed seed; u64 *dst; };
 void launch_seed_expand(const SeedJob *jobs, int njobs, const DevLevel *lv, int L, const u64 *max_multiple, size_t n, u32 *rej, int *overflow,
                         hipStream_t st);
 // N1: BinBundle build (polyn_with_roots per bin, BatchEncoder scatter, monomial detection)
+// INPUT CONTRACTS of the resident-database launchers ("contract:" lines from here to launch_eval_compare; tests/test_gpu_db_kernel_steps.py
+// feeds every one exactly up to its contract through Engine::debug_run_step, which refuses what lies beyond it).  All of them work on
+// poly[rows][n] words, column s = the polynomial of bin (slot) s mod t, coefficient d in row d; "residue" = a word in [0, t), t < 2^60.
+// contract: 1 <= bins <= n; counts[s] <= stride and <= max_deg; roots[s][r] a residue for r < counts[s] (the words behind a bin's count
+// are not read).  poly holds max_deg + 1 rows, all written (zeroed first).  max_deg / 64 + 1 register slots choose the instance: 1, 2, 4, 8,
+// 16, 24, 32, 48, 64, 96, 128, and beyond 128 slots (max_deg >= 8192) the serial kernel.
 void launch_polyn_with_roots(const u64 *roots, const u32 *counts, u32 bins, u32 stride, u32 max_deg, Mod t, u64 *poly, size_t n,
                              hipStream_t st);
 // BinBundle update (Engine::update_bundle): limb 0 of stored plaintext slots, the un-lift, the per-bin polynomial update on the
 // columns of poly[rows][n] (status: two words, both ~0 beforehand), the degree of the batched polynomial (out: one word, 0 beforehand)
 void launch_limb0_rows(const DevLevel *lv, int L, const void *src, size_t slot_bytes, bool packed, u64 *out, size_t n, size_t count, hipStream_t st);
+// contract (launch_unlift): q0 > 2 t; every word is a value below t or a lifted one in [q0 - t, q0) (bin_unlift; anything between the two
+// ranges has no meaning and would wrap)
 void launch_unlift(u64 *x, size_t words, u64 t, u64 q0, hipStream_t st);
+// contract (launch_bins_update): rows >= 1; touched[w] < n, no bin named twice (one wave per entry, in place); ins / rem are indexed by
+// the BIN: ins[s * ins_stride + r], r < ins_counts[s] <= ins_stride, residues (likewise rem; a null counts array = no such list).  A
+// touched column holds residues in all its rows; its count c is the index of its highest non-zero row, and c - rem_counts[s] + ins_counts[s] <=
+// rows - 1 (the host sizes the array: the kernels do not check, and the serial one would write behind it; the engine's rows = degree +
+// most insertions + 1 is on the safe side of this).  Columns not named are neither read
+// nor written.  (rows + 63) / 64 register slots choose the instance as in the build; above 128 slots (rows > 8192) the serial kernel.
+// For 48 slots and more the removal is a loop over single slots, up to 32 the recursion bins_remove_slots.
+// Outcome per touched bin: the updated column, zero above the new count, and counts_out[w] = the new count; OR the zero polynomial:
+// status[1] = min(bin), nothing written; OR removal r leaves a remainder: status[0] = min(bin << 32 | r), counts_out[w] not written, the
+// column untouched by the wave-per-bin instances and UNSPECIFIED after the serial one (which divides in place; the engine discards the
+// array on either status).
 void launch_bins_update(const u32 *touched, u32 n_touched, const u64 *ins, const u32 *ins_counts, u32 ins_stride, const u64 *rem,
                         const u32 *rem_counts, u32 rem_stride, Mod t, u64 *poly, size_t n, u32 rows, u32 *counts_out, u64 *status, hipStream_t st);
+// contract (launch_poly_degree, launch_bin_counts): rows >= 1; any words (tested for zero only).  poly_degree: max over the slots of the
+// highest non-zero row, row 0 not counted (*out 0 beforehand: the result is >= what it held)
 void launch_poly_degree(const u64 *poly, size_t n, u32 rows, u64 *out, hipStream_t st);
 // find and place (Engine::lookup_bundles; bin_lookup.h): per-slot counts of poly[rows][n] (LOOKUP_NONE: the zero polynomial), and the
 // root test of the planned points (lookup_plan with LOOKUP_R rows per work item) -> flags[part], one byte each
 constexpr int LOOKUP_R = 8;                          // points per lane of k_bins_lookup (resource report: profiles/r10_bundle_lookup.txt)
 void launch_bin_counts(const u64 *poly, size_t n, u32 rows, u32 *counts, hipStream_t st);
+// contract (launch_bins_lookup): poly holds degree + 1 rows of residues, ALL read by every work item (rows above a slot's count must be
+// 0 for the answer to be about the bin); pts residues in every cell of a row a work item names (cells without a point are evaluated
+// too); work[w]: tile < ceil(n / 64), 1 <= nrows <= LOOKUP_R, row0 + nrows <= the plan's rows; idx: LOOKUP_NONE or a part below the size
+// of flags, no part twice.  flags[part] is written for exactly the parts named; the others keep their bytes.
 void launch_bins_lookup(const LookupWork *work, u32 n_work, const u64 *pts, const u32 *idx, Mod t, const u64 *poly, size_t n, u32 degree,
                         unsigned char *flags, hipStream_t st);
 // merge (Engine::merge_bundles; bin_merge.h): C[rows][n] = the per-slot products of A's and B's polynomials mod t, rows = the largest
 // count of A + that of B + 1.  topsA / topsB: per tile of 64 slots the largest count, -1 for none (merge_tile_tops); A and B hold at
 // least top + 1 rows for every tile.
+// contract: rows >= 1 (any number: C is the product cut off at `rows` rows, zero from topA + topB + 1 on); -1 <= tops[tile] < the rows its
+// array holds; rows 0 .. top of a tile are residues; rows above a tile's top are NOT read and may hold anything -- so an operand is, per
+// tile, the polynomial of its rows 0 .. top.  The lazy sums are exact for residues only (bin_merge.h: merge_fold_exact).
 void launch_bins_merge(const u64 *A, const int *topsA, const u64 *B, const int *topsB, Mod t, u64 *C, size_t n, u32 rows, hipStream_t st);
 // reading the bins back (Engine::bundle_bins; bin_roots.h, kernels_roots.hip).  occ: the slots of the n_occ occupied bins (count >= 1);
 // hits [n_occ][hstride] and found [n_occ] (zeroed beforehand): the distinct roots of each; mult [n_occ][hstride]: their multiplicities,
@@ -104,6 +132,10 @@ void launch_bins_merge(const u64 *A, const int *topsA, const u64 *B, const int *
 bool bin_roots_has_kernel(int logn);                 // is there a k_bin_roots for this ring size (else: the composition below)
 u32 bin_roots_wg_slots(int logn);                    // workgroups of k_bin_roots the current device holds at once
 // the persistent kernel: `wgs` workgroups over n_occ * grid.blocks work items, rows: [wgs][n] words of workspace
+// contract (launch_bin_roots, launch_roots_gather / _scan, launch_roots_mult): t < 2^32 with (t - 1) / n <= ROOTS_MAX_COSETS cosets; poly
+// residues; counts[s] = the index of the highest non-zero row of column s, 1 <= counts[s] < n for every s in occ (degree < n: one
+// transform holds the polynomial); rows above a count are not read; hstride >= every count of occ; found zeroed.  At most counts[s]
+// values are written to a bin's list, found[rank] counts them; nothing is written to hits or mult at or behind found[rank].
 void launch_bin_roots(int logn, const u64 *poly, const u32 *occ, const u32 *counts, u32 n_occ, RootsGrid grid, u32 cosets, u32 wgs, const NttTable *tabs,
                       const int *modmap, const u32 *step, const u64 *pts, u64 g, u64 *rows, u32 *vrows, u64 *hits, u32 *found, u32 hstride, hipStream_t st);
 // the plain composition, per coset c: rows[r][i] = a_i c^i of bin occ[r]; launch_ntt forward mod t; the scan (first: with the test for the root 0)
@@ -115,10 +147,17 @@ void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u
                        hipStream_t st);
 // the bins' polynomials as ragged rows (Engine::export_saved; bin_rows.h): out[off[s] + d] = poly[d][s], d <= counts[s], s < bins.
 // off: rows_offsets' scan (bins + 1 words), tops: rows_tile_tops, both on the device; out holds off[bins] words.
+// contract: rows >= 1, 1 <= bins <= n; counts[s] < rows and not LOOKUP_NONE for s < bins (rows_offsets refuses the rest), counts behind
+// `bins` are not read; any words in poly (copied, no arithmetic); rows above a bin's count are read into the tile but not stored.
+// Exactly the words out[0 .. off[bins]) are written.
 void launch_bins_rows(const u64 *poly, size_t n, u32 rows, const u32 *counts, const u64 *off, const int *tops, u32 bins, u64 *out, hipStream_t st);
 // the plaintext answer (Engine::bundles_eval_plain; bin_eval.h): out[s] = P_s(x[s]) + mask[s] mod t over poly[rows][n], counts =
 // launch_bin_counts' output of the same array; mask and is_bin (1: the slot is a bin) may be null; *bad = 1 for a value >= t.  The comparison of the self-test:
 // got, want [count][n]; status[0] += mismatches, status[1] = min (position << 32 | slot) of one (EVAL_NO_MISMATCH beforehand).
+// contract (launch_bins_eval): rows >= 1; poly residues; counts any words: a tile walks rows min(largest count of the tile, rows - 1) .. 0
+// of ALL its slots (so rows above a slot's own count are read, and must be 0 for the answer to be about the bin), a tile of LOOKUP_NONE
+// alone reads nothing.  x and mask: any word; one that is not a residue raises *bad, and out of that slot is then unspecified, every
+// other slot's as always.  contract (launch_eval_compare): count <= 65535 (a grid dimension); any words.
 void launch_bins_eval(const u64 *poly, size_t n, u32 rows, const u32 *counts, const u64 *x, const u64 *mask, Mod t, u64 *out, unsigned char *is_bin, u32 *bad, hipStream_t st);
 void launch_eval_compare(const u64 *got, const u64 *want, size_t n, u32 count, u64 *status, hipStream_t st);
 void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);

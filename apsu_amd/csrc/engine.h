@@ -342,8 +342,11 @@ public:
     // Refuses (std::invalid_argument, nothing launched) whatever the launcher's input contract does not admit.
     enum Step { STEP_LEVEL_INFO = 0, STEP_BEHZ_EXT, STEP_DROP_BEHZ_EXT, STEP_TENSOR, STEP_TENSOR_CONV, STEP_TENSOR_SUM, STEP_BEHZ_FINISH,
                 STEP_BEHZ_FINISH_SUM, STEP_KS_INNER, STEP_KS_MODDOWN, STEP_MODSWITCH, STEP_MODSWITCH_JOBS, STEP_I0_FINISH, STEP_EVAL_EPILOGUE,
-                STEP_ADD_MANY, STEP_SUM_JOBS, STEP_ADD_PLAIN, STEP_DYADIC_PLAIN, STEP_LIFT, STEP_COUNT };
-    enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8 };
+                STEP_ADD_MANY, STEP_SUM_JOBS, STEP_ADD_PLAIN, STEP_DYADIC_PLAIN, STEP_LIFT,
+                // the resident-database kernels (engine_db_steps.cpp): the mod-t launchers of device.h, same argument block
+                STEP_POLYN_WITH_ROOTS, STEP_BINS_UPDATE, STEP_BIN_COUNTS, STEP_POLY_DEGREE, STEP_BINS_LOOKUP, STEP_BINS_MERGE, STEP_BINS_ROWS,
+                STEP_BINS_EVAL, STEP_EVAL_COMPARE, STEP_ROOTS, STEP_UNLIFT, STEP_COUNT };
+    enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32 };
     struct StepArgs {
         int step, chain_idx;
         uint32_t flags;
@@ -354,6 +357,7 @@ public:
         size_t out_words[2];
     };
     void debug_run_step(const StepArgs &a);
+    void debug_run_db_step(const StepArgs &a);                    // its database half (the caller holds the lock)
     // Staging of apsu_he_run_query_request (c_api.cpp) kept across calls: a device buffer and a page-locked host buffer of at least
     // `bytes` (grown on demand; hipHostMalloc / hipMalloc per query cost milliseconds).  The caller holds wire_mutex() for the whole query.
     std::mutex &wire_mutex() { return wire_mu_; }

@@ -293,12 +293,45 @@ int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_
  * is no data level; an array whose size is not the layout's; a word that is not canonical where the step needs a canonical one; RAW
  * where the launcher has no RAW form (DROP_BEHZ_EXT and the fused extension of KS_MODDOWN exist for L == nB <= 3 only, RAW KS_MODDOWN
  * and the KEY epilogue up to L = 4); a term count beyond the bound the engine checks on the host -- terms * q_widest < 2^63 for
- * BEHZ_FINISH_SUM, (terms + 1) * q_last < 2^64 for I0_FINISH. */
+ * BEHZ_FINISH_SUM, (terms + 1) * q_last < 2^64 for I0_FINISH.
+ *
+ * The kernels of a resident database, from POLYN_WITH_ROOTS on (same entry, same argument block, no new symbol; chain_idx is not
+ * used).  They work modulo plain_modulus t on poly[rows][n], column s = the polynomial of bin (slot) s, coefficient d in row d.  Arrays of
+ * 32-bit words and of bytes (counts, touched, tops, idx, flags, is_bin) travel as one 64-bit word per entry; 0xFFFFFFFF is LOOKUP_NONE,
+ * a tile top of -1 is the word ~0.  "in/out": the array is copied up first, so a word the kernel does not write comes back as it went.
+ *   POLYN_WITH_ROOTS polys = bins, terms = stride, e0 = max_deg; in[0] roots [bins][stride], in[1] counts [bins] -> out[0] poly [max_deg + 1][n]
+ *   BINS_UPDATE      terms = rows, batch = bins, polys = ins_stride, e0 = rem_stride; in[0] touched [n_touched], in[1] ins [bins][ins_stride]
+ *                    + in[2] ins_counts [bins] or both null, in[3] rem [bins][rem_stride] + in[4] rem_counts [bins] or both null;
+ *                    out[0] poly [rows][n] in/out; out[1] counts_out [n_touched] in/out, then status[0] (lowest bin << 32 | position of a
+ *                    removal that left a remainder, else ~0), status[1] (lowest touched bin that is the zero polynomial, else ~0)
+ *   BIN_COUNTS       terms = rows; in[0] poly [rows][n] -> out[0] counts [n]
+ *   POLY_DEGREE      terms = rows; in[0] poly [rows][n] -> out[0] one word
+ *   BINS_LOOKUP      terms = degree; in[0] poly [degree + 1][n]; out[0] flags [parts] in/out.  polys = F, in[1] felts [count][F], in[2] start
+ *                    [count]: the plan is lookup_plan's.  PLAN: in[1] work [n_work][4] (tile, row0, nrows, 0), in[2] pts [rows][64], in[3] idx
+ *                    [rows][64] (a part or LOOKUP_NONE): the caller's own plan
+ *   BINS_MERGE       terms = rows; in[0] A [rowsA][n], in[1] topsA [n / 64], in[2] B [rowsB][n], in[3] topsB [n / 64] -> out[0] C [rows][n]
+ *   BINS_ROWS        terms = rows, polys = bins; in[0] poly [rows][n], in[1] counts [n] -> out[0] the ragged rows (off[bins] words or more)
+ *                    in/out, out[1] off [bins + 1]
+ *   BINS_EVAL        terms = rows; in[0] poly [rows][n], in[1] counts [n], in[2] x [n], in[3] mask [n] or null -> out[0] [n] in/out, out[1]
+ *                    is_bin [n] in/out, then the bad flag (one word)
+ *   EVAL_COMPARE     polys = count; in[0] got [count][n], in[1] want [count][n] -> out[0] mismatches, lowest (position << 32 | slot) or ~0
+ *   ROOTS            terms = rows, e0 = hstride, batch = workgroups of the persistent search (0: the engine's number); COMPOSED: the
+ *                    per-coset gather + transform + scan instead.  in[0] poly [rows][n]; the occupied bins are the columns whose highest
+ *                    non-zero row is >= 1, in slot order -> out[0] hits [n_occ][hstride] in/out, out[1] found [n_occ], mult [n_occ][hstride]
+ *                    in/out (written for the bins with fewer distinct roots than items only)
+ *   UNLIFT           in[0] residues of q_0 as stored -> out[0] values mod t, as many words
+ * Refused like the others, nothing launched: rows of 0; a word >= t where the launcher's contract (device.h) wants a residue; a count
+ * above its stride or, after the insertions, >= rows; a bin named twice in `touched`; a tile top outside -1 .. rows - 1; a work item or
+ * index entry outside its plan; for ROOTS a degree >= n or a plain modulus with more than 65536 cosets; for UNLIFT a word that is
+ * neither below t nor in q_0 - t .. q_0 - 1. */
 enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEHZ_EXT, APSU_HE_STEP_TENSOR, APSU_HE_STEP_TENSOR_CONV,
        APSU_HE_STEP_TENSOR_SUM, APSU_HE_STEP_BEHZ_FINISH, APSU_HE_STEP_BEHZ_FINISH_SUM, APSU_HE_STEP_KS_INNER, APSU_HE_STEP_KS_MODDOWN,
        APSU_HE_STEP_MODSWITCH, APSU_HE_STEP_MODSWITCH_JOBS, APSU_HE_STEP_I0_FINISH, APSU_HE_STEP_EVAL_EPILOGUE, APSU_HE_STEP_ADD_MANY,
-       APSU_HE_STEP_SUM_JOBS, APSU_HE_STEP_ADD_PLAIN, APSU_HE_STEP_DYADIC_PLAIN, APSU_HE_STEP_LIFT };
-enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8 };
+       APSU_HE_STEP_SUM_JOBS, APSU_HE_STEP_ADD_PLAIN, APSU_HE_STEP_DYADIC_PLAIN, APSU_HE_STEP_LIFT,
+       APSU_HE_STEP_POLYN_WITH_ROOTS, APSU_HE_STEP_BINS_UPDATE, APSU_HE_STEP_BIN_COUNTS, APSU_HE_STEP_POLY_DEGREE, APSU_HE_STEP_BINS_LOOKUP,
+       APSU_HE_STEP_BINS_MERGE, APSU_HE_STEP_BINS_ROWS, APSU_HE_STEP_BINS_EVAL, APSU_HE_STEP_EVAL_COMPARE, APSU_HE_STEP_ROOTS, APSU_HE_STEP_UNLIFT };
+enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8, APSU_HE_STEP_PLAN = 16,
+       APSU_HE_STEP_COMPOSED = 32 };
 typedef struct {
     int32_t step, chain_idx;
     uint32_t flags;
