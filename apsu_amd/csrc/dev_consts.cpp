@@ -48,7 +48,7 @@ void DeviceConstants::relocate(const TwPair *tw_base, const ShoupConst *fin_base
 static void build_transform_tables(const HeParams &hp, DeviceConstants &dc)
 {
     // the NTT keeps one limb in a workgroup's LDS: n = 2^logn coefficients with a compiled pass plan (ntt_core.h)
-    // (32768: the limb is split into two LDS-resident halves around one radix-2 stage over global memory, kernels.hip)
+    // (32768: the limb is split into two LDS-resident halves around one radix-2 stage over global memory, kernels_ntt.hip)
     const bool split_ntt = hp.logn == 15;
     if (plan_passes(hp.logn) == 0 && !split_ntt)
         throw std::invalid_argument("poly_modulus_degree " + std::to_string(hp.n) +

@@ -13,6 +13,7 @@
 
 namespace apsu_he {
 
+constexpr int EW_T = 256;           // threads per workgroup of the coefficient-parallel kernels
 constexpr int DMAXL = 8;            // limbs of q at a data level
 constexpr int DMAXB = DMAXL + 2;    // |Bsk|
 constexpr int DMAXE = DMAXL + DMAXB; // limbs of an extended (q u Bsk) polynomial

@@ -3,13 +3,11 @@
 // streams that share the same ciphertext powers (the inner polynomials of the BinBundles of one bundle index).  The HBM-resident plaintexts
 // are streamed exactly once (16-byte non-temporal loads); every power load is shared by MAC_G streams.  The arithmetic is in mac_core.h,
 // which the CPU tier runs as well: k_mac is the function defined there, the other kernels call theirs.
-#include "device.h"
+#include "launch_mac.h"
+#include "kernel_launch.h"
 #include <algorithm>
 
 namespace apsu_he {
-
-#define KERNEL_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw_hip(e_, __FILE__, __LINE__); } while (0)
-void throw_hip(hipError_t e, const char *file, int line);
 
 // (k_mac is defined in mac_core.h AS the kernel.  Do not wrap its body in a kernel here without comparing the gfx950 assembly with the
 //  recorded one again: a called body compiles to another instruction stream, profiles/r13_mac_core_refactor.txt)

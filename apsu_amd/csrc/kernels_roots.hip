@@ -1,18 +1,15 @@
 // Reading the bins of a resident BinBundle back from its polynomials (Engine::bundle_bins), a translation unit of its own: the
-// transforms' object (kernels.hip) is built exactly as before.  Rules and lane arithmetic: bin_roots.h, which the CPU tier runs as well.
+// transforms' object (kernels_ntt.hip) is built exactly as before.  Rules and lane arithmetic: bin_roots.h, which the CPU tier runs as well.
 // Input of every kernel here: poly[d][slot], the slot values mod t that Engine::decode_bundle produces; bin s is the column s, read
 // top down to its count.
 // Also here, on the same input: the plaintext answer of a BinBundle and the self-test's comparison (k_bins_eval, k_eval_compare; bin_eval.h).
-#include "device.h"
+#include "launch_roots.h"
+#include "kernel_launch.h"
 #include "ntt_wg.h"
-#include "bin_roots.h"
 #include "bin_rows.h"
 #include "bin_eval.h"
 
 namespace apsu_he {
-
-#define KERNEL_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) throw_hip(e_, __FILE__, __LINE__); } while (0)
-void throw_hip(hipError_t e, const char *file, int line);
 
 // ---- the persistent kernel.  A work item is (occupied bin, block of consecutive cosets); a workgroup takes work items blockIdx.x,
 // blockIdx.x + gridDim.x, ...  It reads the bin's column ONCE, keeps the scaled coefficients v_i (32-bit words) in its own row of

@@ -8,7 +8,6 @@
 
 namespace apsu_he {
 
-constexpr int EW_T = 256;                                         // threads per workgroup of the coefficient-parallel kernels
 constexpr int MAC_G = 4;                                          // streams per multiply-accumulate job
 constexpr int MAC_C = 2;                                          // coefficients per lane (one 16-byte load)
 

@@ -1,6 +1,6 @@
 // Which form of the LDS-resident transform a launch takes, as a pure function of the ring size, the kind of launch, its number of limbs,
 // the engine's latency_limbs setting and what the caller states about its moduli.  Every form gives the same bits, so the GPU parity
-// tests cannot see this choice: the launch wrappers of kernels.hip dispatch from ntt_form and nothing else, and tests/test_host_logic.py
+// tests cannot see this choice: the launch wrappers of kernels_ntt.hip dispatch from ntt_form and nothing else, and tests/test_host_logic.py
 // holds it to a table through the CPU emulation library.  No HIP in here.
 #pragma once
 #include <cstddef>
@@ -12,7 +12,7 @@ namespace apsu_he {
 // (profiles/r06_ntt_forms_n8192.txt, _n4096.txt); any other value = a launch of at most that many limbs takes the latency form
 // wherever the ring size has one, whatever its kind (tests force either form with it: APSU_HE_NTT_LATENCY_LIMBS).
 constexpr size_t NTT_FORM_AUTO = ~(size_t)0;
-constexpr int SPLIT_LOGN = 15;   // n = 32768: two LDS-resident half transforms around one radix-2 stage over global memory (kernels.hip)
+constexpr int SPLIT_LOGN = 15;   // n = 32768: two LDS-resident half transforms around one radix-2 stage over global memory (kernels_ntt.hip)
 
 enum NttKind { NTT_KIND_FORWARD, NTT_KIND_INVERSE, NTT_KIND_GATHER, NTT_KIND_TENSOR };
 struct NttForm {

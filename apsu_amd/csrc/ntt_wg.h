@@ -1,5 +1,5 @@
 // The workgroup body of the LDS-resident transform (device code only): the passes of ntt_core.h in execution order with the
-// synchronisation between them.  Shared by kernels.hip and tools/microbench/ntt_variants.hip.
+// synchronisation between them.  Shared by kernels_ntt.hip and tools/microbench/ntt_variants.hip.
 //
 // Synchronisation (round 4).  A pass whose butterfly blocks are at most 1024 coefficients long (LOGN - S <= 10) touches, in
 // wave w, exactly the coefficients [1024 w, 1024 w + 1024): 64 lanes x 16 coefficients.  Two consecutive passes of that kind

@@ -1,4 +1,4 @@
-"""The resident-database kernels (apsu_amd/csrc/kernels.hip from k_polyn_with_roots on, kernels_roots.hip) stated on Python integers,
+"""The resident-database kernels (apsu_amd/csrc/kernels_db.hip, kernels_roots.hip) stated on Python integers,
 each from its definition and not from the kernel's loop structure: product of linear factors and polynomial product through ONE
 big-integer multiplication (Kronecker substitution), synthetic division with its remainder, Horner, the per-slot convolution, a count
 as the index of the top non-zero coefficient, ragged rows, the multiset of roots with multiplicities (a search over the whole field).

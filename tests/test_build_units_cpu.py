@@ -1,0 +1,38 @@
+"""CPU tier: the build's dependencies are the ones the compiler wrote down (apsu_amd/csrc/Makefile, build/*.d), unit by unit.
+
+The device code is split by kernel family so that work on anything but the transforms does not pay for the transforms' object
+(kernels_ntt.o: minutes; every other unit: seconds).  That holds only while no header of another family is reachable from
+kernels_ntt.hip, and while every object that does read a header is remade with it.  Asked of make itself, on the built tree:
+`make -n -W <header> all` lists what an edit of that header would compile."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "apsu_amd", "csrc")
+EMU = "../libapsu_he_hostemu.so"
+
+
+def remade(header):
+    """the targets (objects under build/, libraries) whose commands make would run after an edit of `header`"""
+    dep = os.path.join(SRC, "build", "kernels_ntt.d")
+    assert os.path.exists(dep), ("%s is missing: build the tree first (python __graft_entry__.py, or make -C apsu_amd/csrc all), "
+                                 "the compile step writes the dependency files" % dep)
+    assert os.path.exists(os.path.join(SRC, header))
+    out = subprocess.run(["make", "-C", SRC, "-n", "-W", header, "all"], check=True, capture_output=True, text=True).stdout
+    return set(re.findall(r" -o (\S+)", out))
+
+
+@pytest.mark.parametrize("header, unit", [("bin_merge.h", "kernels_db.o"), ("bin_update.h", "kernels_db.o"),
+                                          ("mac_core.h", "kernels_mac.o"), ("query_side.h", "kernels_ew.o")])
+def test_family_header_spares_the_transforms(header, unit):
+    got = remade(header)
+    assert "build/" + unit in got, got
+    assert "build/kernels_ntt.o" not in got, got
+
+
+def test_transform_header_reaches_every_user():
+    got = remade("ntt_core.h")
+    assert {"build/kernels_ntt.o", "build/kernels_roots.o", EMU} <= got, got

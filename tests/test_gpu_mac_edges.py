@@ -1,7 +1,7 @@
 """GPU tier: k_mac, the BinBundle multiply-accumulate, at its worst case, bit for bit against the CPU oracle.
 
 k_mac sums the products of s-bit operand halves without carries and folds every `chunk` terms (engine.cpp, DevLevel::mac_chunk
-and mac_chunk_k; the fold count in kernels.hip).  Uniform random operands reach a quarter to a half of that bound; here every
+and mac_chunk_k; the fold count in mac_core.h).  Uniform random operands reach a quarter to a half of that bound; here every
 NTT-form operand the kernel reads is an extreme (both halves at their maximum, q - 1, alternating extremes), and the chains
 straddle each width's chunk.
 

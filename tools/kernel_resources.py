@@ -1,5 +1,5 @@
 """VGPRs / SGPRs / spills / LDS / scratch of the kernels in a gfx950 object file (runs without a GPU):
-python tools/kernel_resources.py apsu_amd/csrc/build/kernels.o [name-substring ...]"""
+python tools/kernel_resources.py apsu_amd/csrc/build/kernels_ntt.o [name-substring ...]"""
 import os, re, subprocess, sys, tempfile
 obj = os.path.abspath(sys.argv[1]); want = sys.argv[2:]
 llvm = "/opt/rocm/lib/llvm/bin"

@@ -2,7 +2,7 @@
 // inverse transform behind it, the way k_intt_tensor forms the BEHZ tensor product.  Same bits (87 GPU tests), but measured
 // with tools/ab_test.py on the whole 16M-4096 query: +0.073 +- 0.018 ms (+2.2 %), N = 8 shard +0.4 % (profiles/r03_ab_fusions.txt):
 // six operand streams per output and tdec read twice (once per key component) cost more than k_ks_inner's own pass.
-// To rebuild it: SrcKs goes next to SrcTensor in ntt_core.h, k_intt_ks / launch_intt_ks next to k_intt_tensor in kernels.hip, and
+// To rebuild it: SrcKs goes next to SrcTensor in ntt_core.h, k_intt_ks / launch_intt_ks next to k_intt_tensor in kernels_ntt.hip, and
 // Engine::d_relinearize calls launch_intt_ks(hp_.logn, tdec, rk.data.u(), acc, L, hp_.K, batch, tabs(), amap, st_) in place of
 // launch_ks_inner + d_ntt(acc, ...).
 #if 0
