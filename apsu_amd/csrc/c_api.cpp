@@ -350,8 +350,8 @@ int apsu_he_debug_run_step(apsu_he_ctx *c, const apsu_he_step_args *args)
 {
     return guarded([&] {
         REQUIRE(c && args, "null argument");
-        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
-                      (int)APSU_HE_STEP_COMPOSED == (int)Engine::STEP_COMPOSED, "step ids of the header and the engine");
+        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT == (int)Engine::STEP_UNLIFT && (int)APSU_HE_STEP_INTT_TENSOR + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
+                      (int)APSU_HE_STEP_COMPOSED == (int)Engine::STEP_COMPOSED && (int)APSU_HE_STEP_NORED == (int)Engine::STEP_NORED, "step ids of the header and the engine");
         Engine::StepArgs a{};
         a.step = args->step; a.chain_idx = args->chain_idx; a.flags = args->flags;
         a.terms = args->terms; a.polys = args->polys; a.batch = args->batch; a.e0 = args->e0; a.n_ext = args->n_ext;

@@ -22,7 +22,10 @@
 //              word w stands for the residue w n^-1 psi^-k mod m at coefficient k.  What the transform can actually leave
 //              (ntt_core.h, the last inverse pass, `OUT == IO_GLOBAL && !(INV && RAW)`): for a wide modulus (not ntt_is_narrow) the
 //              butterflies keep values in [0, 2^64) by csub_top alone, so ANY 64-bit word; for a narrow modulus, which runs without
-//              range control, below (2^K b0 + 4 (logn - K)) m, with K the stages of the first inverse pass and b0 = 1 for a canonical
-//              source or ntt_lazy_bound_q(tab) for the tensor fold's last word (ntt_lazy_input_ok) -- under 2^64 by the narrow
-//              criterion, and nothing tighter is argued.  Every RAW consumer therefore takes ANY 64-bit word: its first operation on
+//              range control, below (max(2^K b0, 2 b0 + 4 (K - 1)) + 4 (logn - K)) m, with K the stages of the first inverse pass and
+//              b0 = 1 for a canonical source or ntt_lazy_bound_q(tab) for the tensor fold's last word (ntt_lazy_input_ok).  The first
+//              pass: stage 1 is product-free (2 b0), a later stage doubles a product-free chain and adds 4 m to every other word, so it
+//              ends below the larger of 2^K b0 and 2 b0 + 4 (K - 1); every stage of the other passes adds 4 m.  That is under 2^64 by
+//              the narrow criterion (b0 = 1: at most 4 logn - 2) or by ntt_lazy_input_ok, and nothing tighter is argued.
+//              Every RAW consumer therefore takes ANY 64-bit word: its first operation on
 //              the word is a Shoup product (mul_shoup / mul_shoup_lazy, modmath.h: exact for any 64-bit x, m < 2^63).

@@ -345,8 +345,10 @@ public:
                 STEP_ADD_MANY, STEP_SUM_JOBS, STEP_ADD_PLAIN, STEP_DYADIC_PLAIN, STEP_LIFT,
                 // the resident-database kernels (engine_db_steps.cpp): the mod-t launchers of device.h, same argument block
                 STEP_POLYN_WITH_ROOTS, STEP_BINS_UPDATE, STEP_BIN_COUNTS, STEP_POLY_DEGREE, STEP_BINS_LOOKUP, STEP_BINS_MERGE, STEP_BINS_ROWS,
-                STEP_BINS_EVAL, STEP_EVAL_COMPARE, STEP_ROOTS, STEP_UNLIFT, STEP_COUNT };
-    enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32 };
+                STEP_BINS_EVAL, STEP_EVAL_COMPARE, STEP_ROOTS, STEP_UNLIFT,
+                // the transforms (engine_ntt_steps.cpp): the launchers of launch_ntt.h with a caller-given limb-to-modulus map
+                STEP_NTT_INFO, STEP_NTT, STEP_NTT_GATHER, STEP_INTT_TENSOR, STEP_COUNT };
+    enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32, STEP_INVERSE = 64, STEP_NORED = 128 };
     struct StepArgs {
         int step, chain_idx;
         uint32_t flags;
@@ -358,6 +360,7 @@ public:
     };
     void debug_run_step(const StepArgs &a);
     void debug_run_db_step(const StepArgs &a);                    // its database half (the caller holds the lock)
+    void debug_run_ntt_step(const StepArgs &a);                   // its transform half (the caller holds the lock)
     // Staging of apsu_he_run_query_request (c_api.cpp) kept across calls: a device buffer and a page-locked host buffer of at least
     // `bytes` (grown on demand; hipHostMalloc / hipMalloc per query cost milliseconds).  The caller holds wire_mutex() for the whole query.
     std::mutex &wire_mutex() { return wire_mu_; }

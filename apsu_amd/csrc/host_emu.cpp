@@ -31,7 +31,7 @@
 using namespace apsu_he;
 
 // inverse transform whose first pass forms the dyadic tensor product while it loads (k_intt_tensor)
-template <int LOGN, int MODE, int PASS, int C = 16> static void emu_pass_tensor(u64 *lds, u64 *glob, int T, const NttTable &tab, const SrcTensor &ops)
+template <int LOGN, int MODE, int PASS, int C = 16, bool RAW = false> static void emu_pass_tensor(u64 *lds, u64 *glob, int T, const NttTable &tab, const SrcTensor &ops)
 {
     if constexpr (PASS < plan_passes(LOGN, C)) {
         if constexpr (PASS == 0)           // as in ntt_body: products staged into the LDS image with coalesced loads
@@ -39,15 +39,21 @@ template <int LOGN, int MODE, int PASS, int C = 16> static void emu_pass_tensor(
                 for (int e = 2 * tid; e < (1 << LOGN); e += 2 * T) *reinterpret_cast<u64x2 *>(lds + lds_slot(e)) = src_load2(ops, glob, e, tab);
         for (int tid = 0; tid < T; tid++) {
             if constexpr (PASS == 0) ntt_pass<LOGN, true, MODE, 0, false, false, SrcTensor, true, TwInline, NoHook, C>(lds, glob, tid, T, tab, ops);   // (the source's input bound rides along, as in ntt_body)
-            else ntt_pass<LOGN, true, MODE, PASS, 0, false, SrcPlain, false, TwInline, NoHook, C>(lds, glob, tid, T, tab);
+            else ntt_pass<LOGN, true, MODE, PASS, 0, RAW, SrcPlain, false, TwInline, NoHook, C>(lds, glob, tid, T, tab);
         }
-        emu_pass_tensor<LOGN, MODE, PASS + 1, C>(lds, glob, T, tab, ops);
+        emu_pass_tensor<LOGN, MODE, PASS + 1, C, RAW>(lds, glob, T, tab, ops);
     }
 }
 
-template <int LOGN, int C = 16> static void emu_intt_tensor(u64 *out, const NttTable &tab, int T, const SrcTensor &ops)
+template <int LOGN, int C = 16> static void emu_intt_tensor(u64 *out, const NttTable &tab, int T, const SrcTensor &ops, bool raw = false)
 {
     std::vector<u64> lds(lds_slots(1 << LOGN));
+    if (raw) {                                                    // NTT_MAP_RAW: no twist, no closing reduction
+        if (tab.narrow) emu_pass_tensor<LOGN, NTT_NARROW, 0, C, true>(lds.data(), out, T, tab, ops);
+        else if (tab.wide_d4) emu_pass_tensor<LOGN, NTT_WIDE_NEAR, 0, C, true>(lds.data(), out, T, tab, ops);
+        else emu_pass_tensor<LOGN, NTT_WIDE, 0, C, true>(lds.data(), out, T, tab, ops);
+        return;
+    }
     if (tab.narrow) emu_pass_tensor<LOGN, NTT_NARROW, 0, C>(lds.data(), out, T, tab, ops);
     else if (tab.wide_d4) emu_pass_tensor<LOGN, NTT_WIDE_NEAR, 0, C>(lds.data(), out, T, tab, ops);
     else emu_pass_tensor<LOGN, NTT_WIDE, 0, C>(lds.data(), out, T, tab, ops);
@@ -83,6 +89,55 @@ template <int LOGN, bool INV, int C = 16> static void emu_ntt(u64 *data, const N
     if (tab.narrow) emu_ntt_n<LOGN, INV, NTT_NARROW, C>(data, tab, T);
     else if (tab.wide_d4) emu_ntt_n<LOGN, INV, NTT_WIDE_NEAR, C>(data, tab, T);
     else emu_ntt_n<LOGN, INV, NTT_WIDE, C>(data, tab, T);
+}
+
+// One limb as k_ntt / k_ntt_gather run it, with the template arguments the kernels pass to ntt_body: RED 1 / 2 = forward transform of a limb
+// gathered from `src` (reduced on load / taken as it is), RAW = the inverse leaves out its twist and its closing reduction
+template <int LOGN, bool INV, int MODE, int PASS, int RED, bool RAW, int C> static void emu_pass_ex(u64 *lds, const u64 *src, u64 *glob, int T, const NttTable &tab)
+{
+    if constexpr (PASS < plan_passes(LOGN, C)) {
+        if constexpr (PASS == 0 && RED != 0) {                    // forward only: pass 0 just reads, from the source limb
+            for (int tid = 0; tid < T; tid++) ntt_pass<LOGN, INV, MODE, 0, RED, false, SrcPlain, false, TwInline, NoHook, C>(lds, const_cast<u64 *>(src), tid, T, tab);
+        } else if constexpr (PASS == 0 && INV) {                  // SrcStaged: coalesced loads into the LDS image, the first pass from there
+            for (int tid = 0; tid < T; tid++)
+                for (int e = 2 * tid; e < (1 << LOGN); e += 2 * T) *reinterpret_cast<u64x2 *>(lds + lds_slot(e)) = src_load2(SrcStaged(), glob, e, tab);
+            for (int tid = 0; tid < T; tid++) ntt_pass<LOGN, true, MODE, 0, 0, false, SrcStaged, true, TwInline, NoHook, C>(lds, glob, tid, T, tab, SrcStaged());
+        } else if constexpr (PASS == 0) {
+            for (int tid = 0; tid < T; tid++) ntt_pass<LOGN, INV, MODE, 0, 0, false, SrcPlain, false, TwInline, NoHook, C>(lds, glob, tid, T, tab);
+        } else
+            for (int tid = 0; tid < T; tid++) ntt_pass<LOGN, INV, MODE, PASS, 0, RAW, SrcPlain, false, TwInline, NoHook, C>(lds, glob, tid, T, tab);
+        emu_pass_ex<LOGN, INV, MODE, PASS + 1, RED, RAW, C>(lds, src, glob, T, tab);
+    }
+}
+template <int LOGN, bool INV, int MODE, int RED, bool RAW, int C> static void emu_ntt_ex_n(const u64 *src, u64 *data, const NttTable &tab, int T)
+{
+    constexpr int N = 1 << LOGN;
+    std::vector<u64> lds(lds_slots(N));
+    emu_pass_ex<LOGN, INV, MODE, 0, RED, RAW, C>(lds.data(), src, data, T, tab);
+    if (!INV) for (int e = 0; e < N; e++) data[e] = ntt_fwd_finish<MODE>(lds[lds_slot(e)], tab);
+}
+template <int LOGN, int C> static void emu_ntt_ex(int inverse, int red, int raw, const u64 *src, u64 *data, const NttTable &tab, int T)
+{
+    // the kernels' wave-uniform branches: k_ntt (RED 0; RAW from the map entry), k_ntt_gather (RED 2 for a narrow modulus of a `nored` launch, else 1)
+    if (inverse) {
+        if (raw) {
+            if (tab.narrow) emu_ntt_ex_n<LOGN, true, NTT_NARROW, 0, true, C>(src, data, tab, T);
+            else if (tab.wide_d4) emu_ntt_ex_n<LOGN, true, NTT_WIDE_NEAR, 0, true, C>(src, data, tab, T);
+            else emu_ntt_ex_n<LOGN, true, NTT_WIDE, 0, true, C>(src, data, tab, T);
+        } else {
+            if (tab.narrow) emu_ntt_ex_n<LOGN, true, NTT_NARROW, 0, false, C>(src, data, tab, T);
+            else if (tab.wide_d4) emu_ntt_ex_n<LOGN, true, NTT_WIDE_NEAR, 0, false, C>(src, data, tab, T);
+            else emu_ntt_ex_n<LOGN, true, NTT_WIDE, 0, false, C>(src, data, tab, T);
+        }
+    } else if (red == 0) {
+        if (tab.narrow) emu_ntt_ex_n<LOGN, false, NTT_NARROW, 0, false, C>(src, data, tab, T);
+        else if (tab.wide_d4) emu_ntt_ex_n<LOGN, false, NTT_WIDE_NEAR, 0, false, C>(src, data, tab, T);
+        else emu_ntt_ex_n<LOGN, false, NTT_WIDE, 0, false, C>(src, data, tab, T);
+    } else if (tab.narrow) {
+        if (red == 2) emu_ntt_ex_n<LOGN, false, NTT_NARROW, 2, false, C>(src, data, tab, T);
+        else emu_ntt_ex_n<LOGN, false, NTT_NARROW, 1, false, C>(src, data, tab, T);
+    } else if (tab.wide_d4) emu_ntt_ex_n<LOGN, false, NTT_WIDE_NEAR, 1, false, C>(src, data, tab, T);
+    else emu_ntt_ex_n<LOGN, false, NTT_WIDE, 1, false, C>(src, data, tab, T);
 }
 
 // forward transform whose load steps the bin's scaled coefficients to the next coset (k_bin_roots: SrcCoset through ntt_body's staged path)
@@ -161,6 +216,39 @@ int emu_ntt_limb_c(int logn, int inverse, uint64_t q, uint64_t *data, int thread
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
+// The same with the kernels' other template arguments (tests/test_ntt_step_model_cpu.py): red 0 = in place on data; 1 / 2 = the forward
+// transform of `src` (another modulus' residues reduced on load / any words taken as they are: k_ntt_gather with nored 0 / 1) written to
+// data; raw = the inverse transform without its twist and closing reduction (NTT_MAP_RAW).  Refused: red with an inverse transform or
+// without a source, raw with a forward one, red 2 for a modulus that is not narrow (the kernel reduces there).
+int emu_ntt_limb_ex(int logn, int inverse, uint64_t q, const uint64_t *src, uint64_t *data, int threads, int coeffs, int red, int raw)
+{
+    try {
+        if (coeffs != 16 && !(coeffs == 8 && plan_has_latency_form(logn))) throw std::invalid_argument("no pass schedule for this ring size and coefficients per work item");
+        if (red < 0 || red > 2 || (red && (inverse || !src)) || (raw && !inverse)) throw std::invalid_argument("red is for a forward transform with a source, raw for an inverse one");
+        const EmuTables et(logn, q);
+        if (red == 2 && !et.tab.narrow) throw std::invalid_argument("an unreduced gather needs a narrow modulus");
+        if (coeffs == 8) {
+            if (logn == 13) emu_ntt_ex<13, 8>(inverse, red, raw, src, data, et.tab, threads); else emu_ntt_ex<12, 8>(inverse, red, raw, src, data, et.tab, threads);
+            return 0;
+        }
+#define CASE(L) case L: emu_ntt_ex<L, 16>(inverse, red, raw, src, data, et.tab, threads); break;
+        switch (logn) { CASE(14) CASE(13) CASE(12) CASE(11) CASE(10) CASE(8) CASE(6) default: throw std::invalid_argument("unsupported logn"); }
+#undef CASE
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+// ntt_reduce128_lazy on explicit (hi, lo) pairs, then ntt_lazy_bound_q and ntt_lazy_input_ok(logn) in out[count], out[count + 1];
+// returns fold_k, 0 when the modulus does not admit the fold
+int emu_reduce128_lazy(uint64_t q, int logn, const uint64_t *hi, const uint64_t *lo, uint64_t *out, int count)
+{
+    const NttTable tab = make_ntt_table(q, logn);
+    if (!ntt_fold128_ok(tab.fold_k, tab.fold_c)) return 0;
+    for (int i = 0; i < count; i++) out[i] = ntt_reduce128_lazy(hi[i], lo[i], tab);
+    out[count] = ntt_lazy_bound_q(tab);
+    out[count + 1] = plan_passes(logn, 16) ? (u64)ntt_lazy_input_ok(tab, logn) : 0;
+    return (int)tab.fold_k;
+}
+
 // INTT(x0*y0 (+ x1*y1)) of one limb through the fused loader; x1 = y1 = NULL for a single product.  Returns -2 when the
 // modulus does not admit the 128-bit fold reduction (the engine then keeps the separate tensor kernel).
 int emu_intt_tensor_limb_c(int logn, uint64_t q, const uint64_t *x0, const uint64_t *y0, const uint64_t *x1, const uint64_t *y1,
@@ -186,15 +274,16 @@ int emu_intt_tensor_limb_c(int logn, uint64_t q, const uint64_t *x0, const uint6
         const NttTable tab = make_ntt_table(t, logn, fwd.data(), dit.data(), sc.data());
         if (!ntt_fold128_ok(tab.fold_k, tab.fold_c)) return -2;
         // coeffs | 0x100: the products enter as the fold's last word (< 4q) where the engine would take them so (k_intt_tensor: ntt_lazy_input_ok)
-        const bool lazy = (coeffs & 0x100) != 0;
+        // coeffs | 0x200: the limb's map entry carries NTT_MAP_RAW
+        const bool lazy = (coeffs & 0x100) != 0, raw = (coeffs & 0x200) != 0;
         coeffs &= 0xff;
         if (lazy && !ntt_lazy_input_ok(tab, logn)) return -3;
         const SrcTensor ops{ x0, y0, x1, y1, lazy };
         if (coeffs == 8) {
-            if (logn == 13) emu_intt_tensor<13, 8>(out, tab, threads, ops); else emu_intt_tensor<12, 8>(out, tab, threads, ops);
+            if (logn == 13) emu_intt_tensor<13, 8>(out, tab, threads, ops, raw); else emu_intt_tensor<12, 8>(out, tab, threads, ops, raw);
             return 0;
         }
-#define CASE(L) case L: emu_intt_tensor<L>(out, tab, threads, ops); break;
+#define CASE(L) case L: emu_intt_tensor<L>(out, tab, threads, ops, raw); break;
         switch (logn) { CASE(14) CASE(13) CASE(12) CASE(11) CASE(10) CASE(8) CASE(6) default: throw std::invalid_argument("unsupported logn"); }
 #undef CASE
         return 0;

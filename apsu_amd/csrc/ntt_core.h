@@ -458,7 +458,7 @@ HD void ntt_pass16(u64 *lds, u64 *__restrict__ glob, int w, const NttTable &tab,
                         // wherever the row's low bits are zero -- all of stage 1, half of stage 2, a quarter of stage 3 ... (15 of the 32
                         // butterflies of a radix-16 pass): (x, y) -> (x + y, x - y + M) needs no product.  M is the multiple of q that bounds
                         // y there: both operands are sums of `bit` inputs, each below b0 q (b0 = 1 for canonical input,
-                        // ntt_lazy_bound_q for the tensor fold's last word).  Narrow moduli only (no range control to keep: the values stay below (2^K b0 + 4 (log n - K)) q,
+                        // ntt_lazy_bound_q for the tensor fold's last word).  Narrow moduli only (no range control to keep: the values stay below (max(2^K b0, 2 b0 + 4 (K - 1)) + 4 (log n - K)) q -- device.h, RAW --,
                         // inside the narrow criterion for b0 = 1 and checked by ntt_lazy_input_ok for b0 = 4); -3 ... -7 % on inverse
                         // launches over the data primes (tools/microbench/ntt_forms.hip, profiles/r06_ntt_trivial_twiddles.txt).
                         // Wide moduli (61-bit BEHZ primes, values anywhere in 64 bits): only stage 1 behind the tensor loader -- both operands are

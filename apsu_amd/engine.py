@@ -175,8 +175,9 @@ STEPS = {name: i for i, name in enumerate((
     "level_info", "behz_ext", "drop_behz_ext", "tensor", "tensor_conv", "tensor_sum", "behz_finish", "behz_finish_sum", "ks_inner",
     "ks_moddown", "modswitch", "modswitch_jobs", "i0_finish", "eval_epilogue", "add_many", "sum_jobs", "add_plain", "dyadic_plain", "lift",
     "polyn_with_roots", "bins_update", "bin_counts", "poly_degree", "bins_lookup", "bins_merge", "bins_rows", "bins_eval", "eval_compare", "roots",
-    "unlift"))}
-STEP_RAW, STEP_ACCUMULATE, STEP_STORE, STEP_KEY, STEP_PLAN, STEP_COMPOSED = 1, 2, 4, 8, 16, 32
+    "unlift", "ntt_info", "ntt", "ntt_gather", "intt_tensor"))}
+STEP_RAW, STEP_ACCUMULATE, STEP_STORE, STEP_KEY, STEP_PLAN, STEP_COMPOSED, STEP_INVERSE, STEP_NORED = 1, 2, 4, 8, 16, 32, 64, 128
+STEP_MAP_RAW = 1 << 30                 # in a map entry of an inverse transform step: that limb comes back RAW
 
 
 def _self_test_report(r):

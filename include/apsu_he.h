@@ -323,15 +323,37 @@ int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_
  * Refused like the others, nothing launched: rows of 0; a word >= t where the launcher's contract (device.h) wants a residue; a count
  * above its stride or, after the insertions, >= rows; a bin named twice in `touched`; a tile top outside -1 .. rows - 1; a work item or
  * index entry outside its plan; for ROOTS a degree >= n or a plain modulus with more than 65536 cosets; for UNLIFT a word that is
- * neither below t nor in q_0 - t .. q_0 - 1. */
+ * neither below t nor in q_0 - t .. q_0 - 1.
+ *
+ * The transforms, from NTT_INFO on (same entry, no new symbol; chain_idx is not used): launch_ntt, launch_ntt_gather and
+ * launch_intt_tensor with the context's own tables and its own APSU_HE_NTT_LATENCY_LIMBS setting, so the choice of the launch form
+ * and the split path at n = 32768 are part of what runs.  The caller gives the limb-to-modulus map the launcher reads: logical limb g
+ * takes entry g % period, a modulus id (0 .. K-1 the key primes, K + i the i-th auxiliary prime, then plain_modulus where it
+ * supports batching), plus APSU_HE_STEP_MAP_RAW in an inverse map: that limb comes back RAW (above).
+ *   NTT_INFO        -> out[0]: log2 n, K, the number of auxiliary primes, batching (0 / 1), then the modulus of every modulus id
+ *   NTT             in[0] [count][n] canonical, in[1] map [period]; INVERSE: the inverse transform -> out[0] [count][n]
+ *   NTT_GATHER      in[0] sources [nsrc][n], in[1] the source of every output limb [count], in[2] map [period], in[3] max_src (one word,
+ *                   NORED only) -> out[0] [count][n].  A source word is any 64-bit word; with NORED it is not reduced on load and must
+ *                   be below max_src
+ *   INTT_TENSOR     batch = njobs, terms = limbs, polys = stride (limbs between an operand's two polynomials, >= limbs; 0: limbs),
+ *                   e0 = dgap (limbs between the outputs of two jobs, >= 3 limbs; 0: 3 limbs);
+ *                   in[0] a [njobs][2][stride][n], in[1] b the same, both canonical, in[2] plain [n_plain][n] canonical or null, in[3] map
+ *                   [period] over (job, polynomial of 3, limb) and then the plain limbs -> out[0] [njobs][dgap][n] in/out, job j's first
+ *                   [3][limbs][n] = the inverse transforms of a0 b0, a0 b1 + a1 b0, a1 b1; out[1] [n_plain][n] the inverse transforms of the plain limbs
+ * Refused like the others, nothing launched: a modulus id out of range; MAP_RAW in a forward map; NORED at n = 32768, with a target
+ * for which max_src + 4 log2(n) q exceeds 2^64 or which is not narrow, or with a source word at or above max_src; a word that is not
+ * canonical where canonical is asked; the three outputs of one operand limb under different moduli; INTT_TENSOR at n = 32768; sizes
+ * that do not match (at most 4096 limbs per launch). */
 enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEHZ_EXT, APSU_HE_STEP_TENSOR, APSU_HE_STEP_TENSOR_CONV,
        APSU_HE_STEP_TENSOR_SUM, APSU_HE_STEP_BEHZ_FINISH, APSU_HE_STEP_BEHZ_FINISH_SUM, APSU_HE_STEP_KS_INNER, APSU_HE_STEP_KS_MODDOWN,
        APSU_HE_STEP_MODSWITCH, APSU_HE_STEP_MODSWITCH_JOBS, APSU_HE_STEP_I0_FINISH, APSU_HE_STEP_EVAL_EPILOGUE, APSU_HE_STEP_ADD_MANY,
        APSU_HE_STEP_SUM_JOBS, APSU_HE_STEP_ADD_PLAIN, APSU_HE_STEP_DYADIC_PLAIN, APSU_HE_STEP_LIFT,
        APSU_HE_STEP_POLYN_WITH_ROOTS, APSU_HE_STEP_BINS_UPDATE, APSU_HE_STEP_BIN_COUNTS, APSU_HE_STEP_POLY_DEGREE, APSU_HE_STEP_BINS_LOOKUP,
-       APSU_HE_STEP_BINS_MERGE, APSU_HE_STEP_BINS_ROWS, APSU_HE_STEP_BINS_EVAL, APSU_HE_STEP_EVAL_COMPARE, APSU_HE_STEP_ROOTS, APSU_HE_STEP_UNLIFT };
+       APSU_HE_STEP_BINS_MERGE, APSU_HE_STEP_BINS_ROWS, APSU_HE_STEP_BINS_EVAL, APSU_HE_STEP_EVAL_COMPARE, APSU_HE_STEP_ROOTS, APSU_HE_STEP_UNLIFT,
+       APSU_HE_STEP_NTT_INFO, APSU_HE_STEP_NTT, APSU_HE_STEP_NTT_GATHER, APSU_HE_STEP_INTT_TENSOR };
 enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8, APSU_HE_STEP_PLAN = 16,
-       APSU_HE_STEP_COMPOSED = 32 };
+       APSU_HE_STEP_COMPOSED = 32, APSU_HE_STEP_INVERSE = 64, APSU_HE_STEP_NORED = 128 };
+#define APSU_HE_STEP_MAP_RAW ((uint64_t)1 << 30)   /* in a map entry of an inverse transform */
 typedef struct {
     int32_t step, chain_idx;
     uint32_t flags;

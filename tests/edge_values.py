@@ -74,6 +74,25 @@ def fill(kind, q, n, rng=None, s=None):
     raise ValueError(kind)
 
 
+def fill_below(kind, bound, n):
+    """one limb of n words below `bound`, which need not be a modulus (the unreduced gather's max_src, tests/ntt_step_model.py):
+    max: every word bound - 1;  alternating: bound - 1 and 0 in turn;  sprinkled: random below bound with bound - 1 sprinkled in"""
+    top = int(bound) - 1
+    if kind == "max":
+        return np.full(n, top, dtype=np.uint64)
+    if kind == "alternating":
+        out = np.zeros(n, dtype=np.uint64)
+        out[::2] = top
+        return out
+    if kind == "sprinkled":
+        rng = np.random.default_rng([n, int(bound) % 65521])
+        out = rng.integers(0, int(bound), n, dtype=np.uint64)
+        out[rng.random(n) < 0.25] = top
+        out[:2] = (top, 0)
+        return out
+    raise ValueError(kind)
+
+
 def fill_poly(kind, qs, n, rng=None):
     """[len(qs)][n]: limb j filled with `kind` modulo qs[j]"""
     return np.stack([fill(kind, q, n, rng) for q in qs])
@@ -99,7 +118,8 @@ def raw_bound(m, logn):
     c = (1 << k) - m
     b0 = 5 + (((c << 32) + 4 * c * c) >> (k - 1))                           # ntt_lazy_bound_q
     K = PLAN_K_FIRST_INVERSE.get(logn, 0)
-    return min(1 << 64, ((b0 << K) + 4 * (logn - K)) * m)
+    # (the first pass ends below max(2^K b0, 2 b0 + 4 (K - 1)) m; with b0 >= 5 that is 2^K b0)
+    return min(1 << 64, (max(b0 << K, 2 * b0 + 4 * (K - 1)) + 4 * (logn - K)) * m)
 
 
 def canonical_edges(m, extra=()):
