@@ -336,6 +336,48 @@ int apsu_he_db_compact(apsu_he_ctx *c, uint32_t bundle_idx, const apsu_he_bundle
     });
 }
 
+// handles for the engine's BinBundles, all or none: nothing below throws except the allocation of the handles, which come first
+static void wrap_bundles(std::vector<std::unique_ptr<Bundle>> &made, apsu_he_bundle **out)
+{
+    std::vector<std::unique_ptr<apsu_he_bundle>> hs(made.size());
+    for (auto &h : hs) h = std::make_unique<apsu_he_bundle>();
+    for (size_t i = 0; i < hs.size(); i++) { hs[i]->b = std::move(made[i]); out[i] = hs[i].release(); }
+}
+
+int apsu_he_bundle_split(apsu_he_ctx *c, const apsu_he_bundle *b, uint32_t parts, const uint32_t *cache_idx, apsu_he_bundle **out)
+{
+    return guarded([&] {
+        REQUIRE(c && b && b->b && out, "null argument");
+        auto made = c->eng->split_bundle(*b->b, parts, cache_idx);
+        wrap_bundles(made, out);
+    });
+}
+
+int apsu_he_bundle_adopt(apsu_he_ctx *dst, apsu_he_ctx *src, const apsu_he_bundle *b, uint32_t cache_idx, apsu_he_bundle **out)
+{
+    return guarded([&] {
+        REQUIRE(dst && src && b && b->b && out, "null argument");
+        std::vector<std::unique_ptr<Bundle>> made;
+        made.push_back(dst->eng->adopt_bundle(*src->eng, *b->b, cache_idx));
+        wrap_bundles(made, out);
+    });
+}
+
+int apsu_he_db_rebase(apsu_he_ctx *dst, apsu_he_ctx *src, const apsu_he_bundle *const *bundles, uint32_t n_bundles, apsu_he_bundle **out,
+                      uint32_t *origin, uint32_t *cache_idx, uint32_t capacity, uint32_t *n_out)
+{
+    return guarded([&] {
+        REQUIRE(dst && src && n_out && ((out && origin) || !capacity), "null argument");
+        const auto v = bundle_ptrs(bundles, n_bundles);
+        Engine::RebaseResult r = dst->eng->rebase_from(*src->eng, v.data(), n_bundles);
+        *n_out = (uint32_t)r.bundles.size();
+        if (r.bundles.size() > capacity)
+            throw std::invalid_argument("rebase: " + std::to_string(r.bundles.size()) + " BinBundles come out, the caller has room for " + std::to_string(capacity));
+        for (size_t i = 0; i < r.bundles.size(); i++) { origin[i] = r.origin[i]; if (cache_idx) cache_idx[i] = r.bundles[i]->cache_idx; }
+        wrap_bundles(r.bundles, out);
+    });
+}
+
 int apsu_he_bundle_bins(apsu_he_ctx *c, const apsu_he_bundle *b, uint64_t *roots, uint32_t *counts, uint32_t stride)
 { return guarded([&] { REQUIRE(c && b && b->b && counts, "null argument"); c->eng->bundle_bins(*b->b, roots, counts, stride); }); }
 int apsu_he_debug_bundle_bins_form(apsu_he_ctx *c, const apsu_he_bundle *b, uint64_t *roots, uint32_t *counts, uint32_t stride, int form)
@@ -350,7 +392,7 @@ int apsu_he_debug_run_step(apsu_he_ctx *c, const apsu_he_step_args *args)
 {
     return guarded([&] {
         REQUIRE(c && args, "null argument");
-        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT == (int)Engine::STEP_UNLIFT && (int)APSU_HE_STEP_INTT_TENSOR + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
+        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT == (int)Engine::STEP_UNLIFT && (int)APSU_HE_STEP_INTT_TENSOR == (int)Engine::STEP_INTT_TENSOR && (int)APSU_HE_STEP_ROOTS_SPLIT + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
                       (int)APSU_HE_STEP_COMPOSED == (int)Engine::STEP_COMPOSED && (int)APSU_HE_STEP_NORED == (int)Engine::STEP_NORED, "step ids of the header and the engine");
         Engine::StepArgs a{};
         a.step = args->step; a.chain_idx = args->chain_idx; a.flags = args->flags;
@@ -360,7 +402,7 @@ int apsu_he_debug_run_step(apsu_he_ctx *c, const apsu_he_step_args *args)
         c->eng->debug_run_step(a);
     });
 }
-// the six apsu_he_debug_*_times: the first spans of one entry of the context's clock (Engine::op_times), each to where the caller wants it
+// the seven apsu_he_debug_*_times: the first spans of one entry of the context's clock (Engine::op_times), each to where the caller wants it
 static int read_op_times(apsu_he_ctx *c, Engine::Op op, std::initializer_list<double *> out)
 {
     return guarded([&] {
@@ -373,6 +415,8 @@ static int read_op_times(apsu_he_ctx *c, Engine::Op op, std::initializer_list<do
 }
 int apsu_he_debug_bins_times(apsu_he_ctx *c, double *decode_ms, double *roots_ms, double *mult_ms)
 { return read_op_times(c, Engine::OP_BINS, { decode_ms, roots_ms, mult_ms }); }
+int apsu_he_debug_split_times(apsu_he_ctx *c, double *decode_ms, double *roots_ms, double *split_ms, double *build_ms)
+{ return read_op_times(c, Engine::OP_SPLIT, { decode_ms, roots_ms, split_ms, build_ms }); }
 int apsu_he_debug_merge_times(apsu_he_ctx *c, double *decode_ms, double *kernel_ms, double *encode_ms)
 { return read_op_times(c, Engine::OP_MERGE, { decode_ms, kernel_ms, encode_ms }); }
 int apsu_he_debug_lookup_times(apsu_he_ctx *c, double *decode_ms, double *kernels_ms)

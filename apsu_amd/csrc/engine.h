@@ -188,7 +188,8 @@ public:
     //   OP_SELF_TEST  (self_test) decode, k_bin_counts, k_bins_eval (summed over the BinBundles), the comparison, the homomorphic part
     //   OP_EXPORT     (export_saved) decode and counts, the root search and multiplicities, k_bins_rows (device, by events); the copies
     //                 to the host, the plaintexts' serialisation, the buffer's assembly (host clock)
-    enum Op { OP_LOOKUP = 0, OP_BINS, OP_MERGE, OP_EVAL_PLAIN, OP_SELF_TEST, OP_EXPORT, OP_COUNT };
+    //   OP_SPLIT      (split_bundle) decode and counts, the root search and multiplicities, k_roots_split, the parts' builds
+    enum Op { OP_LOOKUP = 0, OP_BINS, OP_MERGE, OP_EVAL_PLAIN, OP_SELF_TEST, OP_EXPORT, OP_SPLIT, OP_COUNT };
     static constexpr int OP_SPANS = 6;
     void op_times(Op op, double *ms, int count);
     struct ApplyResult {
@@ -210,6 +211,21 @@ public:
     // form: BINS_FORM_AUTO, or one of the two paths by name (the debug call of the tests).  `b` is only read.
     enum { BINS_FORM_AUTO = 0, BINS_FORM_KERNEL = 1, BINS_FORM_COMPOSED = 2 };
     void bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t stride, int form = BINS_FORM_AUTO);
+    // N1, splitting (include/apsu_he.h: apsu_he_bundle_split; bin_split.h): the inverse of merge_bundles.  bundle_bins' decode, counts and
+    // root search, then k_roots_split sorts and cuts every bin's list on the device and the tail of the build makes each part from
+    // the device-resident lists: no root reaches the host, which knows every part's counts and degree from the counts alone.  Part p
+    // holds positions [split_cut(c, k, p), split_cut(c, k, p + 1)) of every bin's sorted list, keeps b's bundle_idx and takes
+    // cache_idx[p] (null: b's own and the numbers behind it).  `b` is only read.
+    std::vector<std::unique_ptr<Bundle>> split_bundle(const Bundle &b, uint32_t k, const uint32_t *cache_idx);
+    // N1, moving (apsu_he_bundle_adopt, apsu_he_db_rebase; db_rebase.h), called on the DESTINATION: a BinBundle of `src`, a context on
+    // the same device whose parameters are rebase_compatible with this one's, becomes a BinBundle of this context with the given
+    // cache_idx -- the coefficient half of src's decode, then this context's finish_bundle.  No slot transform, no roots.  The two
+    // contexts' locks are taken one after the other, never together.  `b` is only read.
+    std::unique_ptr<Bundle> adopt_bundle(Engine &src, const Bundle &b, uint32_t cache_idx);
+    struct RebaseResult { std::vector<std::unique_ptr<Bundle>> bundles; std::vector<uint32_t> origin; };
+    // bin_counts per BinBundle in src -> rebase_plan -> adopt_bundle, or split_bundle in src and adopt_bundle of each part (the parts
+    // are released).  All or nothing.  origin[i]: the position in `bundles` that output i came from.
+    RebaseResult rebase_from(Engine &src, const Bundle *const *bundles, uint32_t n_bundles);
     // What a BinBundle answers in plaintext (include/apsu_he.h: apsu_he_bundles_eval_plain; bin_eval.h): out[b][s] = P_s(x[b][s]) + masks[b][s]
     // mod t for the polynomial P_s that BinBundle b holds in slot s -- the value a querier decrypts there.  x, masks (may be null), out:
     // [n_bundles][n] slot values, host or device as flagged; is_bin (may be null): [n_bundles][n] bytes on out's side, 0 where the slot
@@ -347,7 +363,9 @@ public:
                 STEP_POLYN_WITH_ROOTS, STEP_BINS_UPDATE, STEP_BIN_COUNTS, STEP_POLY_DEGREE, STEP_BINS_LOOKUP, STEP_BINS_MERGE, STEP_BINS_ROWS,
                 STEP_BINS_EVAL, STEP_EVAL_COMPARE, STEP_ROOTS, STEP_UNLIFT,
                 // the transforms (engine_ntt_steps.cpp): the launchers of launch_ntt.h with a caller-given limb-to-modulus map
-                STEP_NTT_INFO, STEP_NTT, STEP_NTT_GATHER, STEP_INTT_TENSOR, STEP_COUNT };
+                STEP_NTT_INFO, STEP_NTT, STEP_NTT_GATHER, STEP_INTT_TENSOR,
+                // behind the existing ids, which stay: k_roots_split (engine_db_steps.cpp)
+                STEP_ROOTS_SPLIT, STEP_COUNT };
     enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32, STEP_INVERSE = 64, STEP_NORED = 128 };
     struct StepArgs {
         int step, chain_idx;
@@ -539,6 +557,12 @@ private:
     // the inverse: the stored coefficients back to slot values [degree+1][n] mod t.  coeff (may be null): [degree+1][n], the coefficient
     // form mod t on the way there -- what BatchEncoder::encode made of each degree, before the forward transform mod t
     void decode_bundle(const Bundle &b, u64 *poly, u64 *coeff = nullptr);
+    // its coefficient half: raw [degree+1][n] = what finish_bundle was given, the coefficient-form plaintexts mod t
+    void decode_coeff(const Bundle &b, u64 *raw);
+    // adopt_bundle's source side, under this context's lock: decode_coeff into a buffer of the call's own, complete on return
+    void export_coeff(const Bundle &b, DevBuf &raw);
+    // the tail of build_bundle: device root lists [bins][stride] and counts [bins] -> the stored BinBundle b (queued)
+    void build_from_roots(Bundle &b, const u64 *droots, const uint32_t *dcounts, uint32_t bins, uint32_t stride);
     // ---- the calls on a resident database (engine_db.cpp, like everything from here to unlift_exact_)
     // The context's preconditions in their one order: PSUParams, batching, decodable stored plaintexts (q_0 > 2 t), each including the
     // ones before it; what (may be null): the call's name, for "more bins than batching slots"
@@ -566,6 +590,10 @@ private:
     BinsCounted bins_counted(const Bundle &b, bool want_coeff, uint32_t *counts, EventStamps &evs);
     // (b) root search, stamp s, multiplicities and copies (queued), stamp s + 1.  stride (may be null): refused below the largest count
     void bins_search(const BinsCounted &c, bool kernel, const uint32_t *stride, EventStamps &evs, size_t s, BinsFound &f);
+    // its device half: the launches alone (f.occ and f.hstride are set; null pointers where no bin is occupied), what they leave
+    // on the device for launch_roots_split or for bins_search's three copies
+    struct BinsDevice { uint32_t *occ, *found, *mult; u64 *hits; };
+    BinsDevice bins_search_device(const BinsCounted &c, bool kernel, const uint32_t *stride, EventStamps &evs, size_t s, BinsFound &f);
     // (c) the host end: every bin's list checked and sorted, then written to roots (may be null)
     void bins_finish(const BinsCounted &c, BinsFound &f, u64 *roots, uint32_t stride);
     // the coefficient-form rows of decode_bundle's `coeff` that a saved BinBundle carries as they are: a_0, then the a_{i h} by slot

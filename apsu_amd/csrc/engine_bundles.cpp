@@ -205,13 +205,19 @@ std::unique_ptr<Bundle> Engine::build_bundle(uint32_t bundle_idx, uint32_t cache
             H2D(droots, roots, (size_t)bins * stride);
             HIP_CHECK(hipMemcpyAsync(dcounts, counts, bins * sizeof(uint32_t), hipMemcpyHostToDevice, st_));
         }
-        u64 *poly = ws((size_t)(degree + 1) * n);                  // [d][slot] slot values of the batched polynomial
-        launch_polyn_with_roots(droots, dcounts, bins, stride, degree, make_mod(hp_.t), poly, n, st_);
-        encode_bundle(*b, poly);
+        build_from_roots(*b, droots, dcounts, bins, stride);
         sync();
     });
     pack_bundle(*b);
     return b;
+}
+
+void Engine::build_from_roots(Bundle &b, const u64 *droots, const uint32_t *dcounts, uint32_t bins, uint32_t stride)
+{
+    const size_t n = hp_.n;
+    u64 *poly = ws((size_t)(b.degree + 1) * n);                    // [d][slot] slot values of the batched polynomial
+    launch_polyn_with_roots(droots, dcounts, bins, stride, b.degree, make_mod(hp_.t), poly, n, st_);
+    encode_bundle(b, poly);
 }
 
 // the tail of build_bundle and update_bundle: slot values [degree+1][n] of the batched polynomial -> the stored BinBundle
@@ -231,10 +237,20 @@ void Engine::encode_bundle(Bundle &b, const u64 *poly)
 void Engine::decode_bundle(const Bundle &b, u64 *poly, u64 *coeff)
 {
     const uint32_t degree = b.degree;
+    const size_t n = hp_.n;
+    u64 *raw = ws((size_t)(degree + 1) * n);
+    decode_coeff(b, raw);
+    if (coeff) D2D(coeff, raw, (size_t)(degree + 1) * n);
+    d_ntt(raw, degree + 1, map_ct() + hp_.plain_id(), 1, false, false);
+    launch_gather_slots(raw, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), poly, n, (int)degree + 1, st_);
+}
+
+void Engine::decode_coeff(const Bundle &b, u64 *raw)
+{
+    const uint32_t degree = b.degree;
     const size_t n = hp_.n, Lpt = b.pt_level + 1;
     const int high = hp_.clamp_chain_idx(1);
     const size_t Lh = high + 1;
-    u64 *raw = ws((size_t)(degree + 1) * n);
     D2D(raw, b.a0.u(), n);
     for (const BundleRun &r : layout_of(degree).runs) {                  // the runs finish_bundle wrote
         const bool ntt = r.kind == COEFF_NTT;
@@ -247,9 +263,6 @@ void Engine::decode_bundle(const Bundle &b, u64 *poly, u64 *coeff)
         d_ntt(raw + n, degree, map_ct(), 1, true, data_primes_narrow_);
         launch_unlift(raw + n, (size_t)degree * n, hp_.t, hp_.key_q[0], st_);
     }
-    if (coeff) D2D(coeff, raw, (size_t)(degree + 1) * n);
-    d_ntt(raw, degree + 1, map_ct() + hp_.plain_id(), 1, false, false);
-    launch_gather_slots(raw, reinterpret_cast<const uint32_t *>(d_slot_map_.p()), poly, n, (int)degree + 1, st_);
 }
 
 std::unique_ptr<Bundle> Engine::clone_bundle(const Bundle &src, int src_device)

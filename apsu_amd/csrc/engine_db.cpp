@@ -1,10 +1,11 @@
-// See engine.h.  The calls on a resident database: a BinBundle updated, searched, listed, merged, exported in the reference's saved format,
-// evaluated in plaintext and self-tested.  Each decodes what engine_bundles.cpp stored (decode_counted) and, where it makes a new
+// See engine.h.  The calls on a resident database: a BinBundle updated, searched, listed, merged, split, moved to another context, exported
+// in the reference's saved format, evaluated in plaintext and self-tested.  Each decodes what engine_bundles.cpp stored (decode_counted) and, where it makes a new
 // BinBundle, ends in that file's encode_bundle.  One clock for all of them (op_times), one place for the context's refusals (lookup_check).
 #include "engine_impl.h"
 
 #include <chrono>
 
+#include "db_rebase.h"
 #include "seal_codec.h"
 #include "wire.h"
 
@@ -277,6 +278,20 @@ Engine::BinsCounted Engine::bins_counted(const Bundle &b, bool want_coeff, uint3
 
 void Engine::bins_search(const BinsCounted &c, bool kernel, const uint32_t *stride, EventStamps &evs, size_t s, BinsFound &f)
 {
+    const BinsDevice d = bins_search_device(c, kernel, stride, evs, s, f);
+    const u32 n_occ = (u32)f.occ.size();
+    if (n_occ) {
+        f.hits.resize((size_t)n_occ * f.hstride); f.found.resize(n_occ); f.mult.resize((size_t)n_occ * f.hstride);
+        HIP_CHECK(hipMemcpyAsync(f.found.data(), d.found, n_occ * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipMemcpyAsync(f.mult.data(), d.mult, f.mult.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipMemcpyAsync(f.hits.data(), d.hits, f.hits.size() * sizeof(u64), hipMemcpyDeviceToHost, st_));
+    }
+    evs.record(s + 1, st_);
+}
+
+Engine::BinsDevice Engine::bins_search_device(const BinsCounted &c, bool kernel, const uint32_t *stride, EventStamps &evs, size_t s, BinsFound &f)
+{
+    BinsDevice d{ nullptr, nullptr, nullptr, nullptr };
     const size_t n = hp_.n;
     const u32 cosets = roots_coset_count(hp_.t, n);
     const Mod t = make_mod(hp_.t);
@@ -318,12 +333,9 @@ void Engine::bins_search(const BinsCounted &c, bool kernel, const uint32_t *stri
         }
         evs.record(s, st_);
         launch_roots_mult(c.poly, n, docc, c.dcounts, n_occ, t, dhits, dfound, dmult, hstride, st_);
-        f.hits.resize((size_t)n_occ * hstride); f.found.resize(n_occ); f.mult.resize((size_t)n_occ * hstride);
-        HIP_CHECK(hipMemcpyAsync(f.found.data(), dfound, n_occ * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipMemcpyAsync(f.mult.data(), dmult, f.mult.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipMemcpyAsync(f.hits.data(), dhits, f.hits.size() * sizeof(u64), hipMemcpyDeviceToHost, st_));
+        d = BinsDevice{ docc, dfound, dmult, dhits };
     } else evs.record(s, st_);
-    evs.record(s + 1, st_);
+    return d;
 }
 
 // multiplicities (1 wherever a bin has as many distinct roots as items), the sum check, the sort; nothing is written to `roots` before
@@ -358,6 +370,141 @@ void Engine::bundle_bins(const Bundle &b, u64 *roots, uint32_t *counts, uint32_t
     });
     for (int i = 0; i < 3; i++) clk.ms[i] = clk.evs.ms(i, i + 1);
     bins_finish(c, f, roots, stride);
+}
+
+// ---- N1, splitting (bin_split.h): bundle_bins' decode, counts and root search, k_roots_split, one sync and the failure word, then the
+// tail of the build per part on the device-resident lists
+std::vector<std::unique_ptr<Bundle>> Engine::split_bundle(const Bundle &b, uint32_t k, const uint32_t *cache_idx)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    if (k < 1) throw std::invalid_argument("split: a BinBundle is split into 1 part or more, not " + std::to_string(k));
+    const bool kernel = bins_prepare(b, BINS_FORM_AUTO);
+    const size_t n = hp_.n;
+    OpClock &clk = clock_[OP_SPLIT];
+    // stamps: 0, 1 around decode and counts (bins_counted); 2 in front of the root search, 3 behind it, 4 behind the multiplicities, 5
+    // behind k_roots_split, 6 behind the builds
+    clk.evs.reserve(7);
+    std::vector<uint32_t> counts(n);
+    std::vector<std::unique_ptr<Bundle>> parts;
+    WITH_ARENA({
+        parts.clear();                                                 // (the body runs again after an arena overflow)
+        BinsFound f;
+        const BinsCounted c = bins_counted(b, false, counts.data(), clk.evs);
+        uint32_t bins = 0, most = 0;
+        for (size_t s = 0; s < n; s++) {
+            if (counts[s] == LOOKUP_NONE) continue;
+            if (s != bins)
+                throw std::invalid_argument("split: slot " + std::to_string(s) + " is a bin but slot " + std::to_string(bins) + " is not: the parts are built from a prefix of the slots");
+            bins++;
+            most = std::max(most, counts[s]);
+        }
+        if (most >= 1 && k > most)
+            throw std::invalid_argument("split: " + std::to_string(k) + " parts, but the largest bin holds " + std::to_string(most) + " items: a part would be empty in every bin");
+        const SplitShape shape = split_shape(counts.data(), n, k, LOOKUP_NONE);
+        clk.evs.record(2, st_);
+        const BinsDevice d = bins_search_device(c, kernel, nullptr, clk.evs, 3, f);      // (divides the columns of poly)
+        clk.evs.record(4, st_);
+        const u32 n_occ = (u32)f.occ.size();
+        std::vector<u64> off(k);
+        size_t words = 0;
+        for (uint32_t p = 0; p < k; p++) { off[p] = words; words += (size_t)bins * shape.degree[p]; }
+        u64 *dout = ws(words + 1), *doff = ws(k), *dfail = ws(1);
+        u32 *dstride = ws_as<u32>(k, 1), *dpart_counts = ws_as<u32>((size_t)k * n, 1);
+        HIP_CHECK(hipMemcpyAsync(doff, off.data(), k * sizeof(u64), hipMemcpyHostToDevice, st_));
+        HIP_CHECK(hipMemcpyAsync(dstride, shape.degree.data(), k * sizeof(u32), hipMemcpyHostToDevice, st_));     // a part's stride is its degree
+        HIP_CHECK(hipMemsetAsync(dfail, 0xff, sizeof(u64), st_));
+        launch_roots_split(d.hits, d.found, d.mult, f.hstride, d.occ, c.dcounts, n_occ, k, dout, doff, dstride, dpart_counts, (u32)n, dfail, st_);
+        clk.evs.record(5, st_);
+        u64 failure = SPLIT_NO_FAILURE;
+        HIP_CHECK(hipMemcpyAsync(&failure, dfail, sizeof(u64), hipMemcpyDeviceToHost, st_));
+        sync();                                                        // nothing is built before every bin has passed
+        if (failure != SPLIT_NO_FAILURE) {
+            const uint32_t s = (uint32_t)(failure >> 32);
+            throw std::invalid_argument("bin " + std::to_string(s) + ": its polynomial of degree " + std::to_string(counts[s]) + " does not split into linear factors (" +
+                                        std::to_string((uint32_t)failure) + " roots found, counted with multiplicity)");
+        }
+        const size_t mark = arena_off_;
+        for (uint32_t p = 0; p < k; p++) {
+            arena_off_ = mark;                                         // one part after the other through the same workspace (stream order)
+            parts.push_back(new_bundle(b.bundle_idx, cache_idx ? cache_idx[p] : b.cache_idx + p, shape.degree[p]));
+            build_from_roots(*parts.back(), dout + off[p], dpart_counts + (size_t)p * n, bins, shape.degree[p]);
+        }
+        clk.evs.record(6, st_);
+        sync();
+    });
+    for (auto &p : parts) pack_bundle(*p);
+    const int span[4][2] = { { 0, 1 }, { 2, 4 }, { 4, 5 }, { 5, 6 } };
+    for (int i = 0; i < 4; i++) clk.ms[i] = clk.evs.ms(span[i][0], span[i][1]);
+    return parts;
+}
+
+// ---- N1, moving (db_rebase.h)
+void Engine::export_coeff(const Bundle &b, DevBuf &raw)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check(nullptr, NEED_DECODE);
+    raw.alloc((size_t)(b.degree + 1) * hp_.n * sizeof(u64));
+    WITH_ARENA({
+        decode_coeff(b, raw.u());
+        sync();
+    });
+}
+
+std::unique_ptr<Bundle> Engine::adopt_bundle(Engine &src, const Bundle &b, uint32_t cache_idx)
+{
+    // the parameters never change: read without either lock
+    if (!has_psu_ || !src.has_psu_) throw std::logic_error("context was created without PSUParams");
+    if (src.device_ != device_)
+        throw std::invalid_argument("adopt: the source context is on device " + std::to_string(src.device_) + ", this one on device " + std::to_string(device_) +
+                                    ": BinBundles move between contexts of one device");
+    const std::string why = rebase_compatible(src.psu_, psu_);
+    if (!why.empty()) throw std::invalid_argument("adopt: " + why);
+    const uint32_t max_items = psu_.table_params.max_items_per_bin;
+    if (b.degree > max_items)
+        throw std::invalid_argument("adopt: the BinBundle has degree " + std::to_string(b.degree) + ", above the destination's max_items_per_bin = " + std::to_string(max_items) +
+                                    ": split it into " + std::to_string(split_parts(b.degree, max_items)) + " parts in the source first");
+    DevBuf raw;                                                        // [degree+1][n] coefficient-form plaintexts mod t, this call's own
+    src.export_coeff(b, raw);                                          // the source's lock, released on return
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check(nullptr, NEED_BATCHING);
+    std::unique_ptr<Bundle> out;
+    WITH_ARENA({
+        out = new_bundle(b.bundle_idx, cache_idx, b.degree);
+        finish_bundle(*out, raw.u());
+        sync();
+    });
+    pack_bundle(*out);
+    return out;
+}
+
+Engine::RebaseResult Engine::rebase_from(Engine &src, const Bundle *const *bundles, uint32_t n_bundles)
+{
+    if (!has_psu_ || !src.has_psu_) throw std::logic_error("context was created without PSUParams");
+    const std::string why = rebase_compatible(src.psu_, psu_);
+    if (!why.empty()) throw std::invalid_argument("rebase: " + why);
+    const size_t n = src.hp_.n;
+    std::vector<uint32_t> counts(n), most(n_bundles, 0), index(n_bundles);
+    for (uint32_t i = 0; i < n_bundles; i++) {
+        src.bin_counts(*bundles[i], counts.data());
+        for (size_t s = 0; s < n; s++)
+            if (counts[s] != LOOKUP_NONE) most[i] = std::max(most[i], counts[s]);
+        index[i] = bundles[i]->bundle_idx;
+    }
+    const RebasePlan plan = rebase_plan(most.data(), index.data(), n_bundles, psu_.table_params.max_items_per_bin);
+    RebaseResult res;                                                  // (a refusal below releases every BinBundle made so far with it)
+    for (uint32_t i = 0; i < n_bundles; i++) {
+        const uint32_t first = plan.first[i];
+        if (plan.parts[i] == 1) res.bundles.push_back(adopt_bundle(src, *bundles[i], plan.cache_idx[first]));
+        else {
+            const std::vector<std::unique_ptr<Bundle>> parts = src.split_bundle(*bundles[i], plan.parts[i], nullptr);
+            for (uint32_t p = 0; p < plan.parts[i]; p++) res.bundles.push_back(adopt_bundle(src, *parts[p], plan.cache_idx[first + p]));
+        }
+    }
+    res.origin = plan.origin;
+    return res;
 }
 
 // apply_entries and compact take the BinBundles of one bundle index, in cache order

@@ -414,6 +414,54 @@ void Engine::debug_run_db_step(const StepArgs &a)
             down32(a.out[1], dfound, n_occ);
             down32(a.out[1] + n_occ, dmult, n_occ * hstride);
         } break;
+        case STEP_ROOTS_SPLIT: {
+            // polys = k, e0 = hstride; in[0] hits [n_occ][hstride], in[1] found [n_occ], in[2] mult [n_occ][hstride], in[3] counts [n] (the
+            // occupied bins: 1 <= count, not LOOKUP_NONE, in slot order), in[4] part_stride [k] -> out[0] the parts' lists, part p at
+            // n * (part_stride[0] + .. + part_stride[p - 1]) (in: poison), out[1] counts_out [k][n], the failure word
+            const size_t k = polys, hstride = e0;
+            need(k >= 1 && k < ROWS_MAX, "roots_split: k (polys) out of range");
+            need(hstride >= 1 && split_capacity((u32)std::min<size_t>(hstride, SPLIT_CAP_LARGE + 1)) != 0, "roots_split: hstride (e0) outside 1 .. 8192: no instance holds the list");
+            in_is(3, n, "roots_split: in[3] counts [n]");
+            fits32(a.in[3], n, "roots_split: in[3]");
+            std::vector<u64> occ;
+            for (size_t s = 0; s < n; s++)
+                if (a.in[3][s] != LOOKUP_NONE && a.in[3][s] >= 1) { need(a.in[3][s] <= hstride, "roots_split: a count exceeds hstride"); occ.push_back(s); }
+            const size_t n_occ = occ.size();
+            need(n_occ >= 1, "roots_split: no occupied bin");
+            in_is(0, n_occ * hstride, "roots_split: in[0] hits [n_occ][hstride]");
+            in_is(1, n_occ, "roots_split: in[1] found [n_occ]");
+            in_is(2, n_occ * hstride, "roots_split: in[2] mult [n_occ][hstride]");
+            in_is(4, k, "roots_split: in[4] part_stride [k]");
+            fits32(a.in[1], n_occ, "roots_split: in[1]");
+            fits32(a.in[2], n_occ * hstride, "roots_split: in[2]");
+            fits32(a.in[4], k, "roots_split: in[4]");
+            std::vector<u64> off(k + 1, 0);
+            for (size_t p = 0; p < k; p++) { need(a.in[4][p] <= SPLIT_CAP_LARGE, "roots_split: a part_stride above 8192"); off[p + 1] = off[p] + n * a.in[4][p]; }
+            for (size_t r = 0; r < n_occ; r++) {
+                const u64 c = a.in[3][occ[r]], nf = a.in[1][r], read = std::min(nf, c);
+                for (size_t i = 0; i < read; i++) need(a.in[0][r * hstride + i] < std::min<u64>(t, (u64)1 << 32), "roots_split: a value that is read is not below min(plain_modulus, 2^32)");
+                if (nf < c)
+                    for (size_t i = 0; i < read; i++) need(a.in[2][r * hstride + i] <= SPLIT_MULT_MAX, "roots_split: a multiplicity that is read exceeds SPLIT_MULT_MAX");
+                for (size_t p = 0; p < k; p++)
+                    need(split_cut((u32)c, (u32)k, (u32)p + 1) - split_cut((u32)c, (u32)k, (u32)p) <= a.in[4][p], "roots_split: a part_stride is below a bin's share of that part");
+            }
+            out_is(0, off[k], "roots_split: out[0] the parts' lists, n * part_stride[p] words each");
+            out_is(1, k * n + 1, "roots_split: out[1] counts_out [k][n], failure");
+            const u64 *dhits = up(a.in[0], a.in_words[0]);
+            const u32 *dfound = up32(a.in[1], n_occ), *dmult = up32(a.in[2], n_occ * hstride), *dcounts = up32(a.in[3], n), *docc = up32(occ.data(), n_occ);
+            const u32 *dstride = up32(a.in[4], k);
+            const u64 *doff = up(off.data(), k);
+            u64 *o = up(a.out[0], a.out_words[0]);
+            u32 *dco = ws_as<u32>(k * n, 1);
+            HIP_CHECK(hipMemsetAsync(dco, 0xee, k * n * sizeof(u32), st_));   // (the launcher zeroes them)
+            u64 *fail = ws(1);
+            HIP_CHECK(hipMemsetAsync(fail, 0xff, sizeof(u64), st_));
+            sync();                                                    // (occ and off are this block's own)
+            launch_roots_split(dhits, dfound, dmult, (u32)hstride, docc, dcounts, (u32)n_occ, (u32)k, o, doff, dstride, dco, (u32)n, fail, st_);
+            down(a.out[0], o, a.out_words[0]);
+            down32(a.out[1], dco, k * n);
+            down(a.out[1] + k * n, fail, 1);
+        } break;
         default: refuse("unknown step");
         }
         sync();

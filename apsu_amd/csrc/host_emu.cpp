@@ -17,6 +17,8 @@
 #include "bin_roots.h"
 #include "bin_rows.h"
 #include "bin_eval.h"
+#include "bin_split.h"
+#include "db_rebase.h"
 #include "db_compact.h"
 #include "db_place.h"
 #include "multi_place.h"
@@ -887,6 +889,54 @@ int emu_roots_expand(uint32_t slot, uint32_t count, const uint64_t *values, cons
         roots_expand(slot, count, values, mult, found, v);
         std::copy(v.begin(), v.end(), out);
         return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// ---- splitting and moving (bin_split.h, db_rebase.h)
+uint32_t emu_split_cut(uint32_t c, uint32_t k, uint32_t p) { return split_cut(c, k, p); }
+uint32_t emu_split_part_of(uint32_t c, uint32_t k, uint32_t pos) { return split_part_of(c, k, pos); }
+uint32_t emu_split_capacity(uint32_t hstride) { return split_capacity(hstride); }
+// the number of parts, or -1 with emu_last_error
+int64_t emu_split_parts(uint32_t max_count, uint32_t limit)
+{
+    try { return (int64_t)split_parts(max_count, limit); } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// k_roots_split as its workgroups run it, one after the other: the launcher's arguments on host arrays (launch_roots.h: launch_roots_split,
+// the zeroing of counts_out included).  *failure: SPLIT_NO_FAILURE beforehand, as on the device.  Returns 0, -1 for what the launcher refuses.
+int emu_roots_split(const uint64_t *hits, const uint32_t *found, const uint32_t *mult, uint32_t hstride, const uint32_t *occ, const uint32_t *counts,
+                    uint32_t n_occ, uint32_t k, uint64_t *out, const uint64_t *part_off, const uint32_t *part_stride, uint32_t *counts_out, uint32_t cstride,
+                    uint64_t *failure)
+{
+    try {
+        split_emulate(hits, found, mult, hstride, occ, counts, n_occ, k, out, part_off, part_stride, counts_out, cstride, failure);
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// rebase_compatible of two parameter files: 1 compatible, 0 not (the reason in emu_last_error), -1 a file that does not load
+int emu_rebase_compatible(const char *src_json, const char *dst_json)
+{
+    try {
+        const std::string why = rebase_compatible(PSUParams::Load(src_json), PSUParams::Load(dst_json));
+        g_err = why;
+        return why.empty() ? 1 : 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+// rebase_plan: parts [n_bundles], first [n_bundles]; cache_idx / origin [capacity].  Returns the number of output BinBundles, -1 on a
+// refusal, -2 when capacity is too small.
+int64_t emu_rebase_plan(const uint32_t *max_count, const uint32_t *bundle_idx, uint32_t n_bundles, uint32_t dst_max_items, uint32_t *parts, uint32_t *first,
+                        uint32_t *cache_idx, uint32_t *origin, uint64_t capacity)
+{
+    try {
+        const RebasePlan plan = rebase_plan(max_count, bundle_idx, n_bundles, dst_max_items);
+        if (plan.cache_idx.size() > capacity) return -2;
+        std::copy(plan.parts.begin(), plan.parts.end(), parts);
+        std::copy(plan.first.begin(), plan.first.end(), first);
+        std::copy(plan.cache_idx.begin(), plan.cache_idx.end(), cache_idx);
+        std::copy(plan.origin.begin(), plan.origin.end(), origin);
+        return (int64_t)plan.cache_idx.size();
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 

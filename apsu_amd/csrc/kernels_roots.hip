@@ -8,6 +8,7 @@
 #include "ntt_wg.h"
 #include "bin_rows.h"
 #include "bin_eval.h"
+#include "bin_split.h"
 
 namespace apsu_he {
 
@@ -189,6 +190,76 @@ __global__ __launch_bounds__(EW_T) void k_eval_compare(const u64 *__restrict__ g
     if (total && threadIdx.x == 0) atomicAdd(status, (unsigned long long)total);
 }
 
+// ---- the bins of a BinBundle cut into k parts on the device (Engine::split_bundle; bin_split.h): behind k_roots_mult, one WORKGROUP per
+// occupied bin.  The bin's distinct roots and multiplicities become 64-bit keys in LDS (CAP of them, the rest sentinels), a bitonic
+// network sorts them, every work item then takes CAP / T consecutive keys into registers and the key array's first words serve the
+// workgroup scan of the multiplicities.  A bin whose multiplicities do not add up to its count reports split_failure by atomicMin and
+// writes nothing; every other bin writes each part's items to the part's row of the bin and each part's count.  Words behind a part's
+// count, and rows and counts of slots that are not in occ, are not written.  LDS: CAP keys, dynamic (64 KiB in the largest instance).
+template <int CAP, int T>
+__global__ __launch_bounds__(T) void k_roots_split(const u64 *__restrict__ hits, const u32 *__restrict__ found, const u32 *__restrict__ mult, u32 hstride,
+                                                   const u32 *__restrict__ occ, const u32 *__restrict__ counts, u32 k, u64 *__restrict__ out,
+                                                   const u64 *__restrict__ part_off, const u32 *__restrict__ part_stride, u32 *__restrict__ counts_out,
+                                                   u32 cstride, unsigned long long *__restrict__ failure)
+{
+    constexpr int PER = CAP / T, WAVES = T / 64;
+    static_assert(PER * T == CAP && WAVES * 64 == T && CAP >= 2 * WAVES, "k_roots_split: the instance's shape");
+    __shared__ __attribute__((aligned(16))) u64 key[CAP];
+    const u32 tid = threadIdx.x, rank = blockIdx.x;
+    const u32 slot = occ[rank], cnt = counts[slot], nf = found[rank];
+    const u64 *list = hits + (size_t)rank * hstride;
+    const u32 *ml = mult + (size_t)rank * hstride;
+    for (u32 i = tid; i < (u32)CAP; i += T) key[i] = i < hstride ? split_load(list, ml, i, nf, cnt) : SPLIT_SENTINEL;
+    __syncthreads();
+    for (u32 size = 2; size <= (u32)CAP; size <<= 1)
+        for (u32 j = size >> 1; j; j >>= 1) {
+            for (u32 i = tid; i < (u32)CAP / 2; i += T) {
+                u32 lo, hi;
+                split_pair(i, j, lo, hi);
+                u64 a = key[lo], b = key[hi];
+                split_exchange(a, b, split_ascending(lo, size));
+                key[lo] = a;
+                key[hi] = b;
+            }
+            __syncthreads();
+        }
+    u64 mine[PER];
+    u32 sum = 0;
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        mine[e] = key[tid * PER + e];
+        sum = split_combine(sum, split_key_mult(mine[e]));
+    }
+    __syncthreads();                                                 // the keys are in registers: the array's first words become the scan's
+    u32 incl = sum;                                                  // inclusive scan over the wave, then over the waves' totals
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u32 up = __shfl_up(incl, d, 64);
+        if ((int)(tid & 63) >= d) incl = split_combine(incl, up);
+    }
+    u32 *wave_total = reinterpret_cast<u32 *>(key);
+    if ((tid & 63) == 63) wave_total[tid >> 6] = incl;
+    __syncthreads();
+    u32 before = 0, total = 0;
+    for (int w = 0; w < WAVES; w++) {
+        const u32 x = wave_total[w];
+        if (w < (int)(tid >> 6)) before = split_combine(before, x);
+        total = split_combine(total, x);
+    }
+    if (!split_bin_ok(nf, cnt, total)) {                             // workgroup-uniform
+        if (tid == 0) atomicMin(failure, (unsigned long long)split_failure(slot, nf, cnt, total));
+        return;
+    }
+    u32 pos = split_combine(before, incl - sum);
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+        const u32 m = split_key_mult(mine[e]);
+        split_write(out, part_off, part_stride, slot, cnt, k, pos, m, split_key_value(mine[e]));
+        pos = split_combine(pos, m);
+    }
+    for (u32 p = tid; p < k; p += T) counts_out[(size_t)p * cstride + slot] = split_cut(cnt, k, p + 1) - split_cut(cnt, k, p);
+}
+
 // ---- launches
 // workgroups a CU holds: two at n = 8192 (72 KiB of LDS each, 126 VGPRs: 4 waves per SIMD), two at 4096 (170 VGPRs: 2 waves per SIMD; a
 // budget of 168 or 128 registers spills there); resource report: profiles/r15_bundle_bins.txt
@@ -238,6 +309,21 @@ void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u
 {
     if (!n_occ) return;
     hipLaunchKernelGGL(k_roots_mult, dim3((n_occ + 3) / 4), dim3(256), 0, st, poly, n, occ, counts, n_occ, t, hits, found, mult, hstride);
+    KERNEL_CHECK();
+}
+
+void launch_roots_split(const u64 *hits, const u32 *found, const u32 *mult, u32 hstride, const u32 *occ, const u32 *counts, u32 n_occ, u32 k, u64 *out,
+                        const u64 *part_off, const u32 *part_stride, u32 *counts_out, u32 cstride, u64 *failure, hipStream_t st)
+{
+    const u32 cap = split_capacity(hstride);
+    if (!k || !cap) throw_hip(hipErrorInvalidValue, __FILE__, __LINE__);
+    { hipError_t e_ = hipMemsetAsync(counts_out, 0, (size_t)k * cstride * sizeof(u32), st); if (e_ != hipSuccess) throw_hip(e_, __FILE__, __LINE__); }
+    if (!n_occ) return;
+#define RS_CASE(CAP) case CAP: hipLaunchKernelGGL((k_roots_split<CAP, CAP == SPLIT_CAP_SMALL ? 64 : CAP == SPLIT_CAP_MID ? 256 : 1024>), dim3(n_occ), dim3(split_threads(CAP)), 0, st, hits, found, mult, hstride, occ, counts, k, out, part_off, part_stride, counts_out, cstride, reinterpret_cast<unsigned long long *>(failure)); break;
+    switch (cap) {
+        RS_CASE(SPLIT_CAP_SMALL) RS_CASE(SPLIT_CAP_MID) RS_CASE(SPLIT_CAP_LARGE)
+    }
+#undef RS_CASE
     KERNEL_CHECK();
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "dev_consts.h"
 #include "bin_roots.h"
+#include "bin_split.h"
 
 namespace apsu_he {
 
@@ -25,6 +26,19 @@ void launch_roots_scan(const u64 *rows, size_t n, u32 nrows, const u64 *pts, u64
 // divides the columns of poly in place
 void launch_roots_mult(u64 *poly, size_t n, const u32 *occ, const u32 *counts, u32 n_occ, Mod t, const u64 *hits, const u32 *found, u32 *mult, u32 hstride,
                        hipStream_t st);
+// the bins cut into k parts on the device (Engine::split_bundle; bin_split.h), behind launch_roots_mult on the same hits / found / mult.
+// out: the parts' root lists in one buffer, part p at out + part_off[p] as [slot][part_stride[p]] words; counts_out [k][cstride]: part
+// p's count of slot s at counts_out[p * cstride + s]; part_off, part_stride: k words each, on the device; failure: one word,
+// SPLIT_NO_FAILURE beforehand.  The instance (256 / 2048 / 8192 keys of LDS, 64 / 256 / 1024 work items) follows from hstride.
+// contract: k >= 1; 1 <= hstride <= SPLIT_CAP_LARGE; occ: n_occ distinct slots below cstride, 1 <= counts[s] <= hstride for each;
+// hits below min(found, count) are values below 2^32; mult is read only where found < count, there below min(found, count), every word
+// <= SPLIT_MULT_MAX; part_stride[p] >= split_cut(c, k, p + 1) - split_cut(c, k, p) for every occupied count c, and part p's array holds
+// (largest slot of occ + 1) * part_stride[p] words.  counts_out is zeroed here, all k * cstride words.  A bin with found > count, or
+// whose multiplicities do not add up to its count, lowers *failure to split_failure (atomicMin) and has nothing written: no root, and
+// its counts stay 0.  For every other bin exactly the words out[part_off[p] + s * part_stride[p] + i], i < its count in part p, are
+// written, and its k counts.
+void launch_roots_split(const u64 *hits, const u32 *found, const u32 *mult, u32 hstride, const u32 *occ, const u32 *counts, u32 n_occ, u32 k, u64 *out,
+                        const u64 *part_off, const u32 *part_stride, u32 *counts_out, u32 cstride, u64 *failure, hipStream_t st);
 // the bins' polynomials as ragged rows (Engine::export_saved; bin_rows.h): out[off[s] + d] = poly[d][s], d <= counts[s], s < bins.
 // off: rows_offsets' scan (bins + 1 words), tops: rows_tile_tops, both on the device; out holds off[bins] words.
 // contract: rows >= 1, 1 <= bins <= n; counts[s] < rows and not LOOKUP_NONE for s < bins (rows_offsets refuses the rest), counts behind

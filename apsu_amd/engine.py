@@ -175,7 +175,7 @@ STEPS = {name: i for i, name in enumerate((
     "level_info", "behz_ext", "drop_behz_ext", "tensor", "tensor_conv", "tensor_sum", "behz_finish", "behz_finish_sum", "ks_inner",
     "ks_moddown", "modswitch", "modswitch_jobs", "i0_finish", "eval_epilogue", "add_many", "sum_jobs", "add_plain", "dyadic_plain", "lift",
     "polyn_with_roots", "bins_update", "bin_counts", "poly_degree", "bins_lookup", "bins_merge", "bins_rows", "bins_eval", "eval_compare", "roots",
-    "unlift", "ntt_info", "ntt", "ntt_gather", "intt_tensor"))}
+    "unlift", "ntt_info", "ntt", "ntt_gather", "intt_tensor", "roots_split"))}
 STEP_RAW, STEP_ACCUMULATE, STEP_STORE, STEP_KEY, STEP_PLAN, STEP_COMPOSED, STEP_INVERSE, STEP_NORED = 1, 2, 4, 8, 16, 32, 64, 128
 STEP_MAP_RAW = 1 << 30                 # in a map entry of an inverse transform step: that limb comes back RAW
 
@@ -618,6 +618,52 @@ class HeContext:
         deg = C.c_uint32()
         _check(load_library().apsu_he_bundle_degree(h, C.byref(deg)))
         return Bundle(self, h, bundles[0].bundle_idx, cache_idx, deg.value)
+
+    def _wrap_new(self, h, bundle_idx, cache_idx):
+        h = C.c_void_p(h)
+        deg = C.c_uint32()
+        _check(load_library().apsu_he_bundle_degree(h, C.byref(deg)))
+        return Bundle(self, h, bundle_idx, cache_idx, deg.value)
+
+    def split_bundle(self, bundle, parts, cache_idx=None):
+        """one BinBundle -> `parts` new Bundles, the inverse of merge_bundles: part p holds the positions [p c // parts,
+        (p + 1) c // parts) of every bin's sorted list of c items (apsu_he_bundle_split).  cache_idx: one per part, default the
+        input's and the numbers behind it.  No root reaches the host; the input stays valid."""
+        parts = int(parts)
+        ci = None if cache_idx is None else np.ascontiguousarray(cache_idx, dtype=np.uint32)
+        if ci is not None and len(ci) != parts:
+            raise ValueError("split_bundle: one cache_idx per part")
+        hs = (C.c_void_p * max(parts, 1))()
+        _check(load_library().apsu_he_bundle_split(self.h, bundle.h, C.c_uint32(max(parts, 0)), C.c_void_p(ci.ctypes.data) if ci is not None else None, hs))
+        return [self._wrap_new(hs[p], bundle.bundle_idx, int(ci[p]) if ci is not None else bundle.cache_idx + p) for p in range(parts)]
+
+    def adopt_bundle(self, src_ctx, bundle, cache_idx=None):
+        """a BinBundle of src_ctx, whose parameters agree with this context's in ring, plain modulus and table and item geometry, as
+        a new Bundle of this context with the same bins (apsu_he_bundle_adopt).  cache_idx: default the input's."""
+        cache_idx = bundle.cache_idx if cache_idx is None else int(cache_idx)
+        h = C.c_void_p()
+        _check(load_library().apsu_he_bundle_adopt(self.h, src_ctx.h, bundle.h, C.c_uint32(cache_idx), C.byref(h)))
+        return self._wrap_new(h.value, bundle.bundle_idx, cache_idx)
+
+    def rebase_from(self, src_ctx, bundles):
+        """the BinBundles of src_ctx moved to this context, split first where this context's max_items_per_bin asks for it
+        (apsu_he_db_rebase) -> (new Bundles, origin): origin[i] is the position in `bundles` that output i came from.  All or nothing."""
+        nb = len(bundles)
+        cap = sum(b.degree + 1 for b in bundles)
+        hs = (C.c_void_p * max(nb, 1))(*[b.h for b in bundles])
+        out = (C.c_void_p * max(cap, 1))()
+        origin, cache = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint32)
+        n_out = C.c_uint32()
+        _check(load_library().apsu_he_db_rebase(self.h, src_ctx.h, hs, nb, out, C.c_void_p(origin.ctypes.data), C.c_void_p(cache.ctypes.data), C.c_uint32(cap),
+                                                C.byref(n_out)))
+        m = n_out.value
+        return [self._wrap_new(out[i], bundles[origin[i]].bundle_idx, int(cache[i])) for i in range(m)], [int(o) for o in origin[:m]]
+
+    def split_times(self):
+        """-> (decode + counts, root search + multiplicities, k_roots_split, the parts' builds) ms: device time of the last split_bundle call"""
+        v = [C.c_double() for _ in range(4)]
+        _check(load_library().apsu_he_debug_split_times(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def merge_times(self):
         """-> (decode ms, kernel ms, encode ms): device time of the last merge_bundles call"""

@@ -320,10 +320,16 @@ int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_
  *                    non-zero row is >= 1, in slot order -> out[0] hits [n_occ][hstride] in/out, out[1] found [n_occ], mult [n_occ][hstride]
  *                    in/out (written for the bins with fewer distinct roots than items only)
  *   UNLIFT           in[0] residues of q_0 as stored -> out[0] values mod t, as many words
+ *   ROOTS_SPLIT      (numbered behind the transforms' steps) polys = k, e0 = hstride; in[0] hits [n_occ][hstride], in[1] found [n_occ],
+ *                    in[2] mult [n_occ][hstride], in[3] counts [n]; the occupied bins are the slots with a count of 1 or more that is not
+ *                    LOOKUP_NONE, in slot order; in[4] part_stride [k] -> out[0] the parts' root lists in/out, part p at the word
+ *                    n * (part_stride[0] + .. + part_stride[p - 1]) as [n][part_stride[p]]; out[1] counts_out [k][n], then the failure
+ *                    word (lowest slot << 32 | roots found with multiplicity of a bin that does not add up to its count, else ~0)
  * Refused like the others, nothing launched: rows of 0; a word >= t where the launcher's contract (device.h) wants a residue; a count
  * above its stride or, after the insertions, >= rows; a bin named twice in `touched`; a tile top outside -1 .. rows - 1; a work item or
  * index entry outside its plan; for ROOTS a degree >= n or a plain modulus with more than 65536 cosets; for UNLIFT a word that is
- * neither below t nor in q_0 - t .. q_0 - 1.
+ * neither below t nor in q_0 - t .. q_0 - 1; for ROOTS_SPLIT k < 1, an hstride outside 1 .. 8192 or below a count, a value that
+ * is read and is not below min(t, 2^32), a multiplicity that is read and exceeds 2^18, a part_stride below a bin's share of that part.
  *
  * The transforms, from NTT_INFO on (same entry, no new symbol; chain_idx is not used): launch_ntt, launch_ntt_gather and
  * launch_intt_tensor with the context's own tables and its own APSU_HE_NTT_LATENCY_LIMBS setting, so the choice of the launch form
@@ -350,7 +356,8 @@ enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEH
        APSU_HE_STEP_SUM_JOBS, APSU_HE_STEP_ADD_PLAIN, APSU_HE_STEP_DYADIC_PLAIN, APSU_HE_STEP_LIFT,
        APSU_HE_STEP_POLYN_WITH_ROOTS, APSU_HE_STEP_BINS_UPDATE, APSU_HE_STEP_BIN_COUNTS, APSU_HE_STEP_POLY_DEGREE, APSU_HE_STEP_BINS_LOOKUP,
        APSU_HE_STEP_BINS_MERGE, APSU_HE_STEP_BINS_ROWS, APSU_HE_STEP_BINS_EVAL, APSU_HE_STEP_EVAL_COMPARE, APSU_HE_STEP_ROOTS, APSU_HE_STEP_UNLIFT,
-       APSU_HE_STEP_NTT_INFO, APSU_HE_STEP_NTT, APSU_HE_STEP_NTT_GATHER, APSU_HE_STEP_INTT_TENSOR };
+       APSU_HE_STEP_NTT_INFO, APSU_HE_STEP_NTT, APSU_HE_STEP_NTT_GATHER, APSU_HE_STEP_INTT_TENSOR,
+       APSU_HE_STEP_ROOTS_SPLIT };
 enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8, APSU_HE_STEP_PLAN = 16,
        APSU_HE_STEP_COMPOSED = 32, APSU_HE_STEP_INVERSE = 64, APSU_HE_STEP_NORED = 128 };
 #define APSU_HE_STEP_MAP_RAW ((uint64_t)1 << 30)   /* in a map entry of an inverse transform */
@@ -401,6 +408,52 @@ int apsu_he_bundles_merge(apsu_he_ctx *ctx, const apsu_he_bundle *const *bundles
                           apsu_he_bundle **out);
 int apsu_he_db_compact(apsu_he_ctx *ctx, uint32_t bundle_idx, const apsu_he_bundle *const *bundles, uint32_t n_bundles, uint32_t *group,
                        apsu_he_bundle **merged, uint32_t *n_merged);
+/* N1, splitting and moving: the two maintenance steps that the calls above lacked.  Neither takes a root to the host.
+ * apsu_he_bundle_split: ONE BinBundle -> `parts` NEW BinBundles out[0 .. parts), the inverse of apsu_he_bundles_merge.  A bin holds the
+ * sorted multiset r_0 <= .. <= r_{c-1}; with cut(p) = floor(p c / parts), part p holds the positions [cut(p), cut(p + 1)) of it.
+ *  - Every part of every bin therefore has floor(c / parts) or ceil(c / parts) items; equal values may straddle a cut (the parts are
+ *    multisets); an empty bin is empty (the polynomial 1) in every part; a slot that is not a bin is not a bin in any part.
+ *  - Every part keeps the input's bundle index and takes cache_idx[p]; cache_idx NULL: the input's own for part 0 and the numbers
+ *    behind it.
+ *  - How: apsu_he_bundle_bins' decode, counts and root search; then k_roots_split, one workgroup per occupied bin, sorts the bin's
+ *    distinct roots (64-bit keys value << 32 | multiplicity in LDS, a bitonic network), scans the multiplicities and writes every
+ *    part's items to a list of that part on the device; then the tail of the build per part.  The host decides every part's counts
+ *    and degree from the input's counts alone.
+ *  - If b is build_bundle(B), any update or merge of such, or such a BinBundle loaded from an image, the image of part p
+ *    (apsu_he_bundle_save) is byte-identical to that of build_bundle of part p of B, and apsu_he_bundles_merge of the parts has b's image.
+ *  - Refused (APSU_HE_INVALID_ARGUMENT, apsu_he_last_error names the slot where there is one, no BinBundle is produced): parts < 1;
+ *    parts above the largest bin count when that count is 1 or more; bins that are not a prefix of the slots (the build makes
+ *    prefixes only); a bin whose polynomial does not split into linear factors (the first such slot, its count, the roots found,
+ *    as by apsu_he_bundle_bins).  APSU_HE_LOGIC_ERROR as there: a plain modulus with more than 65536 cosets, a degree >= n.
+ *  - The number of parts that brings every bin below a bound `limit` is the smallest k with ceil(largest count / k) < limit; with
+ *    limit = max_items_per_bin the parts take insertions and can be exported (apsu_he_bundle_export_saved refuses a bin at the bound).
+ * apsu_he_bundle_adopt, called on the DESTINATION context with the source context and one of ITS BinBundles -> *out, a NEW BinBundle
+ * of dst with the same bins, bundle index b's, cache index as given.  The two parameter sets must agree in poly_modulus_degree,
+ * plain_modulus, felts_per_item, table_size and hash_func_count (so every item lies in the same bin of the same bundle index);
+ * coeff_modulus_bits, ps_low_degree, query_powers and max_items_per_bin are free.  Between two such contexts a stored plaintext is
+ * the same polynomial mod plain_modulus, so the coefficient half of the source's decode and the destination's own build tail move
+ * it: no slot transform, no root search.
+ *  - The image in dst is byte-identical to dst's build_bundle of the same bins: level, Paterson-Stockmeyer layout, monomial flags
+ *    and the row format of dst's own APSU_HE_PACKED_ROWS.
+ *  - Refused (APSU_HE_INVALID_ARGUMENT): parameters that differ in one of the five fields (the message names the first); a degree
+ *    above dst's max_items_per_bin (the message says into how many parts to split first); contexts on different devices.
+ *    APSU_HE_LOGIC_ERROR: a source whose first coefficient prime is not above 2 * plain_modulus.
+ *  - The contexts' locks are taken one after the other, never both.
+ * apsu_he_db_rebase: the BinBundles of one call, from src to dst: apsu_he_bundle_bin_counts of each, then per BinBundle either
+ * apsu_he_bundle_adopt, or -- where its largest bin does not stay below dst's max_items_per_bin -- apsu_he_bundle_split in src into the
+ * smallest number of parts that does, apsu_he_bundle_adopt of each part and release of the parts.
+ *  - out[i], i < *n_out: the NEW BinBundles of dst in input order, the parts of one input consecutive; origin[i]: the position in
+ *    `bundles` it came from; cache_idx[i] (may be NULL): dense per bundle index, by position.  `capacity`: the room in out / origin /
+ *    cache_idx; *n_out is written even when it is too small (which is refused).
+ *  - All or nothing: on any refusal every BinBundle made so far is released and no handle is produced.
+ *  - It does not compact: where dst allows fuller bins, apsu_he_db_compact there does.
+ * Preconditions and locking otherwise are the update's.  The multi-device handle has no forms of these yet. */
+int apsu_he_bundle_split(apsu_he_ctx *ctx, const apsu_he_bundle *b, uint32_t parts, const uint32_t *cache_idx, apsu_he_bundle **out);
+int apsu_he_bundle_adopt(apsu_he_ctx *dst, apsu_he_ctx *src, const apsu_he_bundle *b, uint32_t cache_idx, apsu_he_bundle **out);
+int apsu_he_db_rebase(apsu_he_ctx *dst, apsu_he_ctx *src, const apsu_he_bundle *const *bundles, uint32_t n_bundles, apsu_he_bundle **out,
+                      uint32_t *origin, uint32_t *cache_idx, uint32_t capacity, uint32_t *n_out);
+/* device time of the context's last apsu_he_bundle_split: decode and counts, root search and multiplicities, k_roots_split, the builds */
+int apsu_he_debug_split_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_ms, double *split_ms, double *build_ms);
 /* device time of the context's last apsu_he_bundles_merge: the decodes and counts, the product kernels, the re-encode */
 int apsu_he_debug_merge_times(apsu_he_ctx *ctx, double *decode_ms, double *kernel_ms, double *encode_ms);
 /* "next" row N2: engine-native image of one BinBundle cache (256-byte header with a parameter
