@@ -428,6 +428,50 @@ int apsu_he_algebraize_items(apsu_he_ctx *c, const uint8_t *items, size_t count,
         c->eng->algebraize_items(items, count, items_on_device != 0, felts, felts_on_device != 0);
     });
 }
+int apsu_he_item_locations(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint32_t *locs, int locs_on_device)
+{
+    return guarded([&] {
+        REQUIRE(c && (!count || (items && locs)), "null argument");
+        c->eng->item_locations(items, count, items_on_device != 0, locs, locs_on_device != 0);
+    });
+}
+int apsu_he_items_bucket(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t *offsets, uint32_t *order, uint64_t *total)
+{
+    return guarded([&] {
+        REQUIRE(c && offsets && total && (!count || (items && order)), "null argument");
+        c->eng->items_bucket(items, count, items_on_device != 0, offsets, order, total);
+    });
+}
+int apsu_he_cuckoo_table(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t max_rounds, uint32_t *table_idx,
+                         uint32_t *item_loc, uint64_t *rounds)
+{
+    return guarded([&] {
+        REQUIRE(c && table_idx && (!count || (items && item_loc)), "null argument");
+        c->eng->cuckoo_table(items, count, items_on_device != 0, max_rounds, table_idx, item_loc, rounds);
+    });
+}
+int apsu_he_query_values(apsu_he_ctx *c, const uint8_t *table_items, int on_device, uint64_t *values, int values_on_device)
+{
+    return guarded([&] {
+        REQUIRE(c && table_items && values, "null argument");
+        c->eng->query_values(table_items, on_device != 0, values, values_on_device != 0);
+    });
+}
+int apsu_he_debug_item_locations(apsu_he_ctx *c, const uint8_t *items, size_t count, uint32_t hash_func_count, uint32_t table_size, uint32_t *locs)
+{
+    return guarded([&] {
+        REQUIRE(c && (!count || (items && locs)), "null argument");
+        c->eng->debug_item_locations(items, count, hash_func_count, table_size, locs);
+    });
+}
+int apsu_he_debug_cuckoo_insert(apsu_he_ctx *c, const uint8_t *items, const uint32_t *locs, size_t count, uint32_t hash_func_count, uint32_t table_size,
+                                uint64_t max_rounds, int form, uint32_t *table_idx, uint32_t *item_loc, uint64_t *rounds)
+{
+    return guarded([&] {
+        REQUIRE(c && table_idx && (!count || (items && locs && item_loc)), "null argument");
+        c->eng->debug_cuckoo_insert(items, locs, count, hash_func_count, table_size, max_rounds, form, table_idx, item_loc, rounds);
+    });
+}
 int apsu_he_bundle_download(apsu_he_ctx *c, const apsu_he_bundle *b, uint32_t degree, uint64_t *out, size_t capacity_words,
                             size_t *words, int *kind)
 {

@@ -256,6 +256,23 @@ public:
     // N1, one step earlier: algebraize_item (common/apsu/util/db_encoding.cpp:209-256,360-366) for `count` hashed items of 16 bytes:
     // out[count][felts_per_item], felt j = bits [j*b, (j+1)*b) of the item's first item_bit_count bits, b = bit_count(t) - 1
     void algebraize_items(const unsigned char *items, size_t count, bool items_on_device, u64 *out, bool out_on_device);
+    // N1, cuckoo hashing for both parties (include/apsu_he.h: apsu_he_item_locations ... apsu_he_query_values; cuckoo.h, engine_cuckoo.cpp).
+    // item_locations: locs[count][hash_func_count] of `count` items of 16 bytes (k_cuckoo_locations).  items_bucket: the same
+    // locations, then the stable grouping by location on the host (cuckoo_bucket): offsets[table_size + 1], order[count * hash_func_count]
+    // (host).  cuckoo_table: the querier's table by the engine's rule (k_cuckoo_insert): table_idx[table_size], item_loc[count], rounds
+    // (host; rounds may be null); an item without a slot after max_rounds: std::runtime_error naming the lowest one and the fill rate.
+    // query_values: table_items [table_size][16], the table after the caller's OPRF -> values[bundle_idx_count][n] as query_create reads them.
+    void item_locations(const unsigned char *items, size_t count, bool items_on_device, uint32_t *locs, bool locs_on_device);
+    void items_bucket(const unsigned char *items, size_t count, bool items_on_device, u64 *offsets, uint32_t *order, u64 *total);
+    void cuckoo_table(const unsigned char *items, size_t count, bool items_on_device, u64 max_rounds, uint32_t *table_idx, uint32_t *item_loc, u64 *rounds);
+    void query_values(const unsigned char *table_items, bool on_device, u64 *values, bool values_on_device);
+    // test hook: k_cuckoo_insert alone on caller-given items and locations locs[count][H] (host), any context.  form: where the table
+    // lives -- the engine's choice, LDS (std::logic_error where table_size slots do not fit), or device memory
+    enum { CUCKOO_FORM_AUTO = 0, CUCKOO_FORM_LDS = 1, CUCKOO_FORM_GLOBAL = 2 };
+    // test hook: k_cuckoo_locations alone with a caller-given function count and table size (host pointers), any context
+    void debug_item_locations(const unsigned char *items, size_t count, uint32_t H, uint32_t T, uint32_t *locs);
+    void debug_cuckoo_insert(const unsigned char *items, const uint32_t *locs, size_t count, uint32_t H, uint32_t T, u64 max_rounds, int form,
+                             uint32_t *table_idx, uint32_t *item_loc, u64 *rounds);
     // N2: engine-native image of a BinBundle cache (raw limb arrays), replacing the flatbuffers +
     // SEAL-serialised blobs of ReceiverDB::save/Load (receiver_db.cpp:1182-1429) for the GPU-resident DB.
     size_t bundle_image_size(const Bundle &b) const;
@@ -603,6 +620,13 @@ private:
     DevBuf d_roots_step_, d_roots_pts_;                // g^i (u32) and the forward transform mod t of the polynomial X, n words each
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
+    // ---- cuckoo hashing (engine_cuckoo.cpp)
+    DevBuf d_cuckoo_tabs_;                             // [hash_func_count][16][256] words, made by the first call that hashes
+    void cuckoo_tables_ready();
+    const unsigned char *cuckoo_items(const unsigned char *items, size_t count, bool on_device);     // 16-byte aligned device memory (inside WITH_ARENA)
+    // inside the caller's WITH_ARENA: the launch, the status, then the copies to the host; throws for an unplaced item before any copy
+    void cuckoo_insert_run(const unsigned char *ditems, const uint32_t *dlocs, uint32_t count, uint32_t H, uint32_t T, u64 max_rounds, int form,
+                           uint32_t *table_idx, uint32_t *item_loc, u64 *rounds);
     // seed expansion of `count` objects of L limbs queued on the stream without a host wait (seed_expand, query_create, relin_keygen): false = the objects need the host's
     // sampler (seed_expand's rule) and nothing was queued; seeds_overflowed() after the final sync tells whether the device lists sufficed
     bool queue_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst);

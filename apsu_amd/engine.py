@@ -256,9 +256,12 @@ class HeContext:
                 with open(psu_params_json) as f:
                     psu_params_json = f.read()
             _check(L.apsu_he_create(psu_params_json.encode(), device, C.byref(h)))
-            self.felts_per_item = int(json.loads(psu_params_json)["item_params"]["felts_per_item"])
+            js = json.loads(psu_params_json)
+            self.felts_per_item = int(js["item_params"]["felts_per_item"])
+            self.table_size = int(js["table_params"]["table_size"])
+            self.hash_func_count = int(js["table_params"]["hash_func_count"])
         else:
-            self.felts_per_item = 0
+            self.felts_per_item = self.table_size = self.hash_func_count = 0
             q = np.array(coeff_modulus, dtype=np.uint64)
             _check(L.apsu_he_create_raw(C.c_uint64(n), _p(q), len(q), C.c_uint64(plain_modulus), device, C.byref(h)))
         self.h = h
@@ -703,6 +706,123 @@ class HeContext:
         out = np.empty((items.shape[0], self.felts_per_item), dtype=np.uint64)
         _check(load_library().apsu_he_algebraize_items(self.h, items.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(items.shape[0]), 0,
                                                        _p(out), 0))
+        return out
+
+    # ---- N1: cuckoo hashing for both parties (include/apsu_he.h: apsu_he_item_locations ... apsu_he_query_values)
+    def _table_params(self):
+        if not self.felts_per_item:
+            raise ApsuHeError("context was created without PSUParams")
+        return self.table_size, self.hash_func_count
+
+    @staticmethod
+    def _items16(items):
+        return np.ascontiguousarray(items, dtype=np.uint8).reshape(-1, 16)
+
+    def item_locations(self, items, count=None, locs=None):
+        """Kuku's LocFunc for items [count][16] uint8 -> locs [count][hash_func_count] uint32 (apsu_he_item_locations).  items / locs
+        may be device pointers (ints; `count` then says how many items): locs then stays on the device and None is returned."""
+        T, H = self._table_params()
+        on_dev = isinstance(items, int)
+        if not on_dev:
+            items = self._items16(items)
+            count = items.shape[0]
+        out = np.empty((count, H), dtype=np.uint32) if locs is None else None
+        _check(load_library().apsu_he_item_locations(self.h, C.c_void_p(items if on_dev else items.ctypes.data), C.c_size_t(count), 1 if on_dev else 0,
+                                                     C.c_void_p(out.ctypes.data if locs is None else int(locs)), 0 if locs is None else 1))
+        return out
+
+    def bucket_items(self, items):
+        """the database side's grouping -> (offsets [table_size + 1] uint64, order uint32): order[offsets[l]:offsets[l + 1]] = the items
+        with l among their locations, in input order, each once (apsu_he_items_bucket)"""
+        T, H = self._table_params()
+        items = self._items16(items)
+        offsets = np.zeros(T + 1, dtype=np.uint64)
+        order = np.zeros(max(items.shape[0] * H, 1), dtype=np.uint32)
+        total = C.c_uint64()
+        _check(load_library().apsu_he_items_bucket(self.h, C.c_void_p(items.ctypes.data), C.c_size_t(items.shape[0]), 0, _p(offsets),
+                                                   C.c_void_p(order.ctypes.data), C.byref(total)))
+        return offsets, order[:total.value].copy()
+
+    def bucket_entries(self, offsets):
+        """offsets of bucket_items -> per bundle index (lo, hi, start_bins): its entries are order[lo:hi] (contiguous, location by
+        location) and start_bins [hi - lo] uint32 = (location % items_per_bundle) * felts_per_item of each"""
+        T, _ = self._table_params()
+        ipb = int(self.info.items_per_bundle)
+        offsets = np.asarray(offsets, dtype=np.uint64)
+        sizes = np.diff(offsets).astype(np.int64)
+        out = []
+        for b in range(self.bundle_idx_count):
+            l0, l1 = b * ipb, (b + 1) * ipb
+            start = np.repeat(((np.arange(l0, l1) % ipb) * self.felts_per_item).astype(np.uint32), sizes[l0:l1])
+            out.append((int(offsets[l0]), int(offsets[l1]), start))
+        return out
+
+    def insert_items(self, bundles_by_index, items, oprf=None):
+        """Items into a resident database: bucket_items -> oprf(per location, the list of its items [k][16]) -> one list of [k][16] per
+        location, None: the items themselves -> algebraize_items -> apply_entries per bundle index.  bundles_by_index: {bundle index:
+        its Bundles in cache order} (missing: none yet).  -> {bundle index: ApplyResult} for the bundle indices that got entries."""
+        items = self._items16(items)
+        offsets, order = self.bucket_items(items)
+        per_loc = [items[order[int(offsets[l]):int(offsets[l + 1])]] for l in range(self.table_size)]
+        if oprf is not None:
+            per_loc = [self._items16(x) for x in oprf(per_loc)]
+            if [len(x) for x in per_loc] != np.diff(offsets).astype(np.int64).tolist():
+                raise ValueError("insert_items: oprf must return one item per item it was given, location by location")
+        hashed = np.concatenate(per_loc) if per_loc else np.zeros((0, 16), dtype=np.uint8)
+        felts = self.algebraize_items(hashed)
+        out = {}
+        for b, (lo, hi, start) in enumerate(self.bucket_entries(offsets)):
+            if hi > lo:
+                out[b] = self.apply_entries(list(bundles_by_index.get(b, [])), inserts=(felts[lo:hi], start), bundle_idx=b)
+        return out
+
+    def cuckoo_table(self, items, max_rounds=500):
+        """the querier's table by the engine's deterministic rule -> (table_idx [table_size] uint32: item or 0xFFFFFFFF, item_loc
+        [count] uint32: location, 0xFFFFFFFF for a repeated item, rounds); apsu_he_cuckoo_table.  An item without a slot after
+        max_rounds: ApsuHeError naming the lowest one and the fill rate."""
+        T, _ = self._table_params()
+        items = self._items16(items)
+        table_idx = np.zeros(T, dtype=np.uint32)
+        item_loc = np.zeros(max(items.shape[0], 1), dtype=np.uint32)
+        rounds = C.c_uint64()
+        _check(load_library().apsu_he_cuckoo_table(self.h, C.c_void_p(items.ctypes.data), C.c_size_t(items.shape[0]), 0, C.c_uint64(max_rounds),
+                                                   C.c_void_p(table_idx.ctypes.data), C.c_void_p(item_loc.ctypes.data), C.byref(rounds)))
+        return table_idx, item_loc[:items.shape[0]], rounds.value
+
+    def debug_item_locations(self, items, hash_func_count, table_size):
+        """test hook: k_cuckoo_locations with a caller-given function count and table size -> locs [count][hash_func_count]"""
+        items = self._items16(items)
+        out = np.empty((items.shape[0], hash_func_count), dtype=np.uint32)
+        _check(load_library().apsu_he_debug_item_locations(self.h, C.c_void_p(items.ctypes.data), C.c_size_t(items.shape[0]), C.c_uint32(hash_func_count),
+                                                           C.c_uint32(table_size), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def debug_cuckoo_insert(self, items, locs, table_size, max_rounds=500, form=0):
+        """test hook: the table rule on caller-given locations locs [count][H]; form 0 the engine's choice, 1 LDS, 2 device memory"""
+        items = self._items16(items)
+        locs = np.ascontiguousarray(locs, dtype=np.uint32)
+        if locs.ndim != 2 or locs.shape[0] != items.shape[0] or not locs.shape[1]:
+            raise ValueError("debug_cuckoo_insert: locs must be [count][H]")
+        table_idx = np.zeros(max(table_size, 1), dtype=np.uint32)
+        item_loc = np.zeros(max(items.shape[0], 1), dtype=np.uint32)
+        rounds = C.c_uint64()
+        _check(load_library().apsu_he_debug_cuckoo_insert(self.h, C.c_void_p(items.ctypes.data), C.c_void_p(locs.ctypes.data), C.c_size_t(items.shape[0]),
+                                                          C.c_uint32(locs.shape[1]), C.c_uint32(table_size), C.c_uint64(max_rounds), int(form),
+                                                          C.c_void_p(table_idx.ctypes.data), C.c_void_p(item_loc.ctypes.data), C.byref(rounds)))
+        return table_idx[:table_size], item_loc[:items.shape[0]], rounds.value
+
+    def query_values(self, table_items, values=None):
+        """table_items [table_size][16] uint8, the table after the caller's OPRF (or a device pointer) -> values [bundle_idx_count][n]
+        as query_create reads them; values: a device pointer to write them to instead (None is returned).  apsu_he_query_values"""
+        T, _ = self._table_params()
+        on_dev = isinstance(table_items, int)
+        if not on_dev:
+            table_items = self._items16(table_items)
+            if table_items.shape[0] != T:
+                raise ValueError("query_values: table_items must hold table_size items")
+        out = np.empty((self.bundle_idx_count, self.n), dtype=np.uint64) if values is None else None
+        _check(load_library().apsu_he_query_values(self.h, C.c_void_p(table_items if on_dev else table_items.ctypes.data), 1 if on_dev else 0,
+                                                   _p(out) if values is None else C.c_void_p(int(values)), 0 if values is None else 1))
         return out
 
     def save_db_file(self, path, bundles):

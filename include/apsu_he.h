@@ -180,8 +180,8 @@ int apsu_he_bundle_update(apsu_he_ctx *ctx, const apsu_he_bundle *old, const uin
  * -- item_bins_, the cuckoo filters, hashed_items_ -- is asked of the resident polynomials instead, so a database that came from an
  * image, a DB file or a reference-saved cache can have items inserted and removed without anybody knowing its bins.
  * An ENTRY is what preprocess_unlabeled_data emits per cuckoo location (receiver_db.cpp:292-299): felts_per_item field elements
- * f_0 .. f_{F-1} (each < plain_modulus) and a start bin s, s + F <= bins_per_bundle; part j belongs to bin s + j.  Cuckoo locations,
- * OPRF and apsu_he_algebraize_items stay with the caller.
+ * f_0 .. f_{F-1} (each < plain_modulus) and a start bin s, s + F <= bins_per_bundle; part j belongs to bin s + j.  The OPRF stays
+ * with the caller; the cuckoo locations and their entries are apsu_he_items_bucket's, the field elements apsu_he_algebraize_items'.
  *  - A bin's COUNT is the index of the highest non-zero coefficient of its polynomial (the update's definition).  A slot that holds
  *    the zero polynomial is not a bin: APSU_HE_NOT_A_BIN.
  *  - An entry is PRESENT in a BinBundle iff P_{s+j}(f_j) = 0 mod plain_modulus for every j and every s + j is a bin.  That is
@@ -494,7 +494,8 @@ int apsu_he_decrypt_decode(apsu_he_ctx *ctx, const uint64_t *sk_ntt, const uint6
  * create_relin_keys); apsu_he_query_create replaces the prepare_data / encrypt_data blocks of Sender::create_query (:426-484:
  * PlaintextPowers, BatchEncoder::encode, Encryptor::encrypt_symmetric; plaintext_powers.cpp:41-46,51-99);
  * apsu_he_decrypt_decode_budget is apsu_he_decrypt_decode with the invariant noise budget ResultPackage::extract also reports
- * (common/apsu/network/result_package.cpp:175-213).  Cuckoo hashing, OPRF and algebraization (apsu_he_algebraize_items) stay with the caller.
+ * (common/apsu/network/result_package.cpp:175-213).  The OPRF stays with the caller; the cuckoo table and its slot values are
+ * apsu_he_cuckoo_table's and apsu_he_query_values' (below).
  *
  * Randomness.  SEAL draws through std::uniform_int_distribution and its bootstrap generator, which no restatement can pin; the
  * streams here are the engine's own.  Every draw of a call is a function of u[0], u[1], ...: the 32-bit outputs of SEAL's Blake2xb
@@ -536,6 +537,60 @@ int apsu_he_decrypt_decode_budget(apsu_he_ctx *ctx, const uint64_t *sk_ntt, cons
  * bits [j*b, (j+1)*b) of item i's first item_bit_count bits, read as a little-endian bit string, b = bit_count(plain_modulus) - 1.
  * These are the roots apsu_he_db_build_bundle takes once the host has placed them into bins.  (ABI 4) */
 int apsu_he_algebraize_items(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint64_t *felts, int felts_on_device);
+/* N1, cuckoo hashing for both parties (added after ABI 7, additive): where an item goes (receiver_db.cpp:57-79,262-300) and the
+ * querier's table (sender_osn.cpp:329-460), without Kuku.  Both parties must agree on the location function bit for bit.
+ *
+ * Kuku 2.x LocFunc [Kuku-recall]: restated from memory and UNPINNED, like the SEAL object layer -- no Kuku source and no known-answer
+ * vector has been held against it.  item_type is 16 bytes, location_type uint32_t.  The seed of function f is make_item(f, 0): f as 8
+ * little-endian bytes, then 8 zero bytes.  tab_f[16][256] (uint32) = the 16384 bytes of blake2xb(out = 16384, in = the 16 seed bytes,
+ * no key) read as little-endian words: root hash under the parameter block {digest 64, key 0, fanout 1, depth 1, xof_length 16384},
+ * then 256 expansion nodes {digest 64, key 0, fanout 0, depth 0, leaf_length 64, node_offset i, xof_length 16384, node_depth 0,
+ * inner_length 64} over the root.  loc_f(item) = (tab_f[0][item[0]] ^ tab_f[1][item[1]] ^ ... ^ tab_f[15][item[15]]) % table_size for
+ * f < hash_func_count, both from the context's PSUParams (a context without them: APSU_HE_LOGIC_ERROR).
+ *
+ * apsu_he_item_locations: locs[count][hash_func_count] of items[count][16]; each a host pointer, or a device pointer with its flag.
+ * apsu_he_items_bucket (the database side): the locations on the device, then a stable counting sort by location on the host.
+ *   offsets[table_size + 1], order[count * hash_func_count] (host; *total = offsets[table_size] words of order are written): bucket l =
+ *   order[offsets[l] .. offsets[l + 1]) lists the items that have l among their locations, in input order; an item whose functions
+ *   collide on l appears once (the unordered_set of all_locations).  That is oprf_in of receiver_db.cpp:264-289 flattened, hence the
+ *   order in which the reference emits entries.  Every listed item is one ENTRY of apsu_he_db_apply_entries: its (OPRF'd) item through
+ *   apsu_he_algebraize_items, bundle index l / items_per_bundle, start bin (l % items_per_bundle) * felts_per_item.  The buckets of
+ *   one bundle index are contiguous in order: offsets[b * items_per_bundle] .. offsets[(b + 1) * items_per_bundle].
+ *
+ * apsu_he_cuckoo_table (the querier's side).  The reference inserts sequentially with a random walk under its own generator; the
+ * protocol needs only that every item sits at one of its own locations, so the table is built by the engine's own deterministic,
+ * order-independent rule.  Item i starts with function index h_i = 0 and is active.  Rounds r = 0 .. max_rounds - 1 (the reference's
+ * cuckoo_table_insert_attempts is 500; max_rounds outside [1, 2^32], the round's share of the key: APSU_HE_INVALID_ARGUMENT):
+ *   propose  every active item takes the 64-bit minimum on slot[loc_{h_i}(i)] with the key ((max_rounds - 1 - r) << 32) | i.  An empty
+ *            slot holds ~0, so a newer round beats any older occupant and within a round the lowest index wins.
+ *   settle   (after a barrier) every item that is not a duplicate reads its slot.  Its own key: it is placed.  Otherwise, the winner's
+ *            16 bytes equal its own: it is a DUPLICATE of the winner for good (the lowest index of equal items survives; the
+ *            reference's "skipping repeated insertion").  Otherwise h_i = (h_i + 1) % hash_func_count and it is active again.
+ *   The build is done when no item is active.  An item still active after max_rounds: APSU_HE_RUNTIME_ERROR, the message names the
+ *   lowest such item and the fill rate, and nothing is written.
+ *   table_idx[table_size]: the item of each slot or 0xFFFFFFFF; item_loc[count]: the location of each item, 0xFFFFFFFF for a duplicate;
+ *   *rounds (may be NULL): rounds run.  Outputs are host memory.  One workgroup (k_cuckoo_insert); the slots live in LDS up to 8184 of
+ *   them and in the context's workspace beyond, with the same result.  With uniformly random locations (NOT Kuku's, which nobody has
+ *   measured) every shipped (set size, table_size) pair with three functions finished within 37 rounds over 60 seeds each, fill <= 0.676.
+ * apsu_he_query_values: table_items[table_size][16] = the table after the caller's OPRF (the caller fills the slots from table_idx;
+ *   an empty slot holds what the caller's protocol puts there, { 0, 0 } in the reference) -> values[bundle_idx_count][n]: slot
+ *   b * items_per_bundle + k, algebraized as by apsu_he_algebraize_items, fills positions k * felts_per_item .. + felts_per_item - 1 of
+ *   row b; positions from bins_per_bundle to n are 0 (sender_osn.cpp:433-460 and BatchEncoder's padding).  Exactly what
+ *   apsu_he_query_create(values_on_device) reads.
+ * apsu_he_debug_item_locations / apsu_he_debug_cuckoo_insert: test hooks on host arrays -- the location kernel with a caller-given
+ *   function count and table size; the table rule on caller-given items[count][16] and locs[count][hash_func_count] (the tests steer
+ *   collisions no item set can steer).  form: 0 the engine's choice, 1 LDS (a table that does not fit: APSU_HE_LOGIC_ERROR), 2 workspace.
+ * All are synchronous and serialised on the context like every other call. */
+int apsu_he_item_locations(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint32_t *locs, int locs_on_device);
+int apsu_he_items_bucket(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint64_t *offsets, uint32_t *order,
+                         uint64_t *total);
+int apsu_he_cuckoo_table(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint64_t max_rounds, uint32_t *table_idx,
+                         uint32_t *item_loc, uint64_t *rounds);
+int apsu_he_query_values(apsu_he_ctx *ctx, const uint8_t *table_items, int table_items_on_device, uint64_t *values, int values_on_device);
+int apsu_he_debug_item_locations(apsu_he_ctx *ctx, const uint8_t *items, size_t count, uint32_t hash_func_count, uint32_t table_size,
+                                 uint32_t *locs);
+int apsu_he_debug_cuckoo_insert(apsu_he_ctx *ctx, const uint8_t *items, const uint32_t *locs, size_t count, uint32_t hash_func_count,
+                                uint32_t table_size, uint64_t max_rounds, int form, uint32_t *table_idx, uint32_t *item_loc, uint64_t *rounds);
 /* N1, checking a resident database against plaintext (added after ABI 7, additive).  The image checksum protects bytes, not meaning:
  * a BinBundle whose stored limbs do not describe one plaintext, one encoded under another ps_low_degree, one merged from a damaged
  * input, or one held under parameters whose noise budget is too small passes it, and the first sign is a wrong union at the end of
