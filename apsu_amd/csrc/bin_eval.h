@@ -2,7 +2,7 @@
 // the arithmetic of one lane and the pure host functions, no HIP in here.  With poly[d][slot] the decoded array of a BinBundle
 // (Engine::decode_bundle; rows above a slot's count are 0) the querier who sent x decrypts, in slot s,
 //   out[s] = P_s(x[s]) + mask[s]  mod t,   P_s = the column s,
-// one point per slot.  The kernels run the lane functions below, the CPU emulation (host_emu.cpp: emu_bins_eval) the same loop
+// one point per slot.  The kernels run the lane functions below, the CPU emulation (emu/db.cpp: emu_bins_eval) the same loop
 // structure with an explicit loop over the 64 lanes (tests/test_bundle_eval_cpu.py).
 //
 // k_bins_eval has lane = slot: a wave owns a tile of 64 consecutive slots and walks the rows d = top .. 0, one contiguous 512-byte row

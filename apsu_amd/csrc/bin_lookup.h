@@ -1,6 +1,6 @@
 // Asking a resident BinBundle's polynomials questions (Engine::lookup_bundles, k_bin_counts, k_bins_lookup): the arithmetic of one lane
 // and the pure host functions, no HIP in here.  The kernels run the lane functions on the decoded poly[d][slot] (Engine::decode_bundle),
-// the CPU emulation (host_emu.cpp: emu_bin_counts, emu_bins_lookup) runs the kernels' loop structure with an explicit loop over the 64
+// the CPU emulation (emu/db.cpp: emu_bin_counts, emu_bins_lookup) runs the kernels' loop structure with an explicit loop over the 64
 // lanes (tests/test_bundle_lookup_cpu.py).
 //
 // An entry is felts_per_item field elements f_0 .. f_{F-1} and a start bin s; part j belongs to bin (slot) s + j.  Part j is found iff

@@ -2,7 +2,7 @@
 // functions, no HIP in here.  The union of two bins is the product of their polynomials, so with A[dA + 1][n] and B[dB + 1][n] the
 // decoded arrays of two BinBundles (Engine::decode_bundle; rows above a slot's count are 0) the merged one is, per slot s,
 //   C[k][s] = sum_{i + j = k} A[i][s] B[j][s]  mod t,   k <= dA + dB.
-// The kernel runs the lane functions below, the CPU emulation (host_emu.cpp: emu_bins_merge) the same loop structure with an explicit
+// The kernel runs the lane functions below, the CPU emulation (emu/db.cpp: emu_bins_merge) the same loop structure with an explicit
 // loop over the 64 lanes (tests/test_bundle_merge_cpu.py).
 //
 // k_bins_merge has lane = slot: a wave owns a tile of 64 consecutive slots and a block of MERGE_K consecutive output rows

@@ -1,6 +1,6 @@
 // Reading a resident BinBundle's bins back from its polynomials (Engine::bundle_bins, k_bin_roots, k_roots_mult): the rules and the
 // arithmetic of one lane, no HIP in here.  The kernels (kernels_roots.hip) run these functions on the GPU, the CPU emulation
-// (host_emu.cpp: emu_bin_roots) steps them over the lanes of a workgroup (tests/test_bundle_roots_cpu.py).
+// (emu/roots.cpp: emu_bin_roots) steps them over the lanes of a workgroup (tests/test_bundle_roots_cpu.py).
 //
 // Batching forces t = 1 (mod 2n).  The forward negacyclic transform mod t evaluates a polynomial of degree below n at the n points
 // psi^odd, one coset psi <w> of the subgroup <w> of order n of F_t^*.  Scaling coefficient i by c^i moves the evaluation to the coset

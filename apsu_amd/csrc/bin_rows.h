@@ -4,7 +4,7 @@
 // read from row 0 to row count[s]: ascending and monic, [1] for an empty bin.  A saved BinBundle (bin_bundle.fbs:
 // cache.felt_matching_polyns) wants these columns as rows of their own length, one behind the other:
 //   out[off[s] + d] = poly[d][s],  d <= count[s],  off = the exclusive scan of count[s] + 1 over the bins.
-// The kernel runs the functions below, the CPU emulation (host_emu.cpp: emu_bins_rows) the same loop structure with an explicit loop
+// The kernel runs the functions below, the CPU emulation (emu/db.cpp: emu_bins_rows) the same loop structure with an explicit loop
 // over the workgroup's waves and their 64 lanes (tests/test_saved_db_writer_cpu.py).
 //
 // k_bins_rows is a transposition through LDS and nothing else: no arithmetic, no atomics.  A workgroup of ROWS_WAVES waves owns a

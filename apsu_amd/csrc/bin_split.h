@@ -1,5 +1,5 @@
 // Splitting the bins of a resident BinBundle (Engine::split_bundle, k_roots_split): the rules and the arithmetic of one work item, no HIP
-// in here.  The kernel (kernels_roots.hip) runs these functions on the GPU, the CPU emulation (host_emu.cpp: emu_roots_split) steps them
+// in here.  The kernel (kernels_roots.hip) runs these functions on the GPU, the CPU emulation (emu/roots.cpp: emu_roots_split) steps them
 // over the work items of a workgroup (tests/test_bundle_split_cpu.py).
 //
 // The contract of a split into k parts.  A bin holds the sorted multiset r_0 <= ... <= r_{c-1}; part p holds the positions

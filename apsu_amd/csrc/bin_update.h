@@ -1,5 +1,5 @@
 // The arithmetic of the BinBundle update (Engine::update_bundle, k_bins_update), as functions of one lane's values: no HIP in here.
-// The kernel runs them with wave shuffles in between, the CPU emulation (host_emu.cpp: emu_bin_update) with an explicit loop over the
+// The kernel runs them with wave shuffles in between, the CPU emulation (emu/db.cpp: emu_bin_update) with an explicit loop over the
 // 64 lanes, so the scan and the carry between register slots can be stepped through where a debugger reaches them
 // (tests/test_bundle_update_cpu.py).
 //

@@ -1,5 +1,5 @@
 // Cuckoo hashing (N1, both parties): where an item goes, the querier's table, and the database side's grouping by location.
-// Pure functions shared by the kernels (kernels_cuckoo.hip), the engine's host steps and the CPU test tier (host_emu.cpp); an
+// Pure functions shared by the kernels (kernels_cuckoo.hip), the engine's host steps and the CPU test tier (emu/cuckoo.cpp); an
 // independent Python model is tests/cuckoo_model.py.  Contracts: include/apsu_he.h (apsu_he_item_locations, apsu_he_cuckoo_table).
 //
 // The location function is Kuku 2.x's LocFunc, restated from memory [Kuku-recall] and UNPINNED, like the SEAL object layer: no Kuku

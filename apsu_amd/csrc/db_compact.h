@@ -1,5 +1,5 @@
 // Which BinBundles of one bundle index are merged (Engine::compact, apsu_he_db_compact), as a pure function of their bin counts.  No
-// HIP in here; the CPU tier reaches it through the emulation library (host_emu.cpp: emu_plan_compaction,
+// HIP in here; the CPU tier reaches it through the emulation library (emu/db.cpp: emu_plan_compaction,
 // tests/test_bundle_merge_cpu.py).
 //
 // The placement rule (db_place.h) tries BinBundles newest first and drops one only when it is empty, so after insertions and removals

@@ -1,6 +1,6 @@
 // The placement rule of the database-level step (Engine::apply_entries), as pure functions of what the lookup found: which BinBundle
 // of one bundle index an entry is removed from or inserted into, and when a new BinBundle is appended.  No HIP in here; the CPU tier
-// reaches it through the emulation library (host_emu.cpp: emu_place_entries, tests/test_bundle_lookup_cpu.py).
+// reaches it through the emulation library (emu/db.cpp: emu_place_entries, tests/test_bundle_lookup_cpu.py).
 //
 // It restates ReceiverDB::remove's and ReceiverDB::insert_or_assign's loops (receiver_db.cpp:349-434,524-567) over counts and
 // root tests instead of the host-side item lists the reference keeps:

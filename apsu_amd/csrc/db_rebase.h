@@ -1,5 +1,5 @@
 // Moving the BinBundles of a resident database to other parameters (Engine::adopt_bundle, rebase), as pure functions.  No HIP in here;
-// the CPU tier reaches them through the emulation library (host_emu.cpp: emu_rebase_compatible, emu_rebase_plan,
+// the CPU tier reaches them through the emulation library (emu/db.cpp: emu_rebase_compatible, emu_rebase_plan,
 // tests/test_bundle_split_cpu.py).
 //
 // Two parameter sets hold the same database in the same bins when the ring, the plain modulus and the table and item geometry agree:

@@ -1,6 +1,6 @@
 // The multiply-accumulate family's arithmetic, written once: the per-lane bodies of k_mac, k_term_product, k_pack_rows and
 // k_unpack_rows (kernels_mac.hip), the bit-packed row extraction, and the rules for the operand split and the carry-free chunks.
-// The gfx950 kernels run these functions and host_emu.cpp steps the same functions over every lane of a grid on the CPU
+// The gfx950 kernels run these functions and emu/mac.cpp steps the same functions over every lane of a grid on the CPU
 // (tests/test_mac_core_cpu.py), as ntt_core.h does for the transforms.
 #pragma once
 #include <stddef.h>
@@ -106,7 +106,7 @@ HD u64 packed_coeff(const u32 *row, size_t c, u32 w)
 // ---- k_mac, one lane (block indices bx, by, bz; thread tx).  For hipcc this function IS the kernel, not a body that a kernel calls: the
 // compiler optimises a called body on its own before it inlines it, and k_mac's instruction stream then differs from the recorded one
 // (operand order, block layout; profiles/r13_mac_core_refactor.txt), where no timing can tell whether that matters.  For a host compiler
-// it is a plain function that takes the lane's position as arguments; host_emu.cpp steps it over every lane of a grid.
+// it is a plain function that takes the lane's position as arguments; emu/mac.cpp steps it over every lane of a grid.
 #if defined(__HIPCC__)
 #define MAC_LANE_FN __global__ __launch_bounds__(EW_T, 1) void
 #define MAC_LANE_AT

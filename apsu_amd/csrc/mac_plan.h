@@ -1,6 +1,6 @@
 // One pure function from the streams of a multiply-accumulate launch to the launch: the jobs, the profile units, the form
 // (three products or four, packed rows or dense) and the grid.  No HIP: the engine launches what it returns (Engine::d_mac), and the
-// CPU tier enumerates it (host_emu.cpp, tests/test_mac_core_cpu.py).
+// CPU tier enumerates it (emu/mac.cpp, tests/test_mac_core_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -1,6 +1,6 @@
 // The rules of a resident database behind the multi-device handle (MultiEngine, multi.h), as pure functions: where a new BinBundle
 // goes, what every BinBundle's id is after BinBundles were dropped, replaced, merged or appended, and on which device a merge is made.
-// No HIP in here; the CPU tier reaches it through the emulation library (host_emu.cpp: emu_place_new_unit, emu_registry_after,
+// No HIP in here; the CPU tier reaches it through the emulation library (emu/db.cpp: emu_place_new_unit, emu_registry_after,
 // emu_index_in_cache_order, emu_merge_home; tests/test_multi_place_cpu.py).  MultiEngine reads these and spells the rules nowhere else.
 //
 //   * place_new_unit: the candidates of a bundle index are the devices partition_units' first pass gives it (sharding.cpp, devs_of):

@@ -1,7 +1,7 @@
 // Querier side (N5): the pure device functions of key generation and query encryption -- where every random draw sits in the
 // generator's output, the word -> value maps of the two samplers, and the exponentiation of PlaintextPowers
 // (sender/apsu/plaintext_powers.cpp:51-99).  __host__ __device__, so that the CPU test tier runs the same code against Python
-// (host_emu.cpp: emu_qs_*).
+// (emu/query.cpp: emu_qs_*).
 //
 // One generator per call: SEAL's Blake2xb generator (blake2x.h) under the caller's 64-byte seed, u[0], u[1], ... its 32-bit
 // outputs.  A 64-byte stream block holds 16 of them; a 64-bit draw is w = u[p] + 2^32 u[p + 1] at an even position p, i.e. one

@@ -7,26 +7,21 @@ runs the tensor-on-load inverse through the workgroup emulation with lazy and wi
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import common
+import emu_lib
 from oracle import ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 u64p = C.POINTER(C.c_uint64)
 PARAM_FILES = sorted(f[:-5] for f in os.listdir(common.PARAM_DIR) if f.endswith(".json"))
 
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
+    lib = emu_lib.load()
     lib.emu_aux_base.argtypes = [C.c_char_p, C.c_int, u64p, C.c_int]
     return lib
 
@@ -162,7 +157,6 @@ def test_extension_launch_form_follows_the_base(emu):
     transform (6 840 limbs) takes the 8-wave build with the narrow base and the 16-coefficient form with SEAL's; narrowness does not
     change the inverse or the tensor-on-load forms, and launches of at most 256 limbs keep the latency form either way"""
     emu.emu_ntt_form.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int)]
-    emu.emu_ntt_form.restype = None
     auto = 2 ** 64 - 1
     FWD, INV, GATHER, TENSOR = range(4)
     out = (C.c_int * 4)()

@@ -33,6 +33,14 @@ def test_family_header_spares_the_transforms(header, unit):
     assert "build/kernels_ntt.o" not in got, got
 
 
+@pytest.mark.parametrize("header, units", [("cuckoo.h", {"build/emu/cuckoo.o", "build/kernels_cuckoo.o"}), ("mac_core.h", {"build/emu/mac.o"})])
+def test_family_header_spares_the_transform_emulation(header, units):
+    """the emulation library is in units by family too (apsu_amd/csrc/emu/): the transforms' unit is its long one"""
+    got = remade(header)
+    assert units | {EMU} <= got, got
+    assert "build/emu/ntt.o" not in got and "build/kernels_ntt.o" not in got, got
+
+
 def test_transform_header_reaches_every_user():
     got = remade("ntt_core.h")
     assert {"build/kernels_ntt.o", "build/kernels_roots.o", EMU} <= got, got

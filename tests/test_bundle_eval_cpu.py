@@ -11,7 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_bundle_merge_cpu import T32, T33, T60, is_prime, param_moduli, vp
+import emu_lib
+from emu_lib import vp
+from test_bundle_merge_cpu import T32, T33, T60, is_prime, param_moduli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 128                                                   # two tiles of 64 slots
@@ -20,15 +22,7 @@ TABLE = (40961, 65537, 1032193, T32, T33, T60)            # the issue's list: th
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    if not hasattr(lib, "emu_bins_eval"):                 # a library from before this feature: rebuild it
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "-B", "../libapsu_he_hostemu.so"])
-        lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    return lib
+    return emu_lib.load()
 
 
 def all_moduli():

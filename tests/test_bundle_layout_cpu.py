@@ -5,15 +5,14 @@ partition 1 .. degree, neighbours differ in kind, the slots of a kind count up w
 inner polynomial i of the evaluation starts at slot i * l of the NTT-form coefficients."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import common
+import emu_lib
 from oracle import ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
 REFUSAL = "ps_low_degree == 1 leaves coefficient-form plaintexts that eval() cannot multiply"
@@ -22,12 +21,7 @@ ALL_PARAM_FILES = sorted(f[:-5] for f in os.listdir(common.PARAM_DIR) if f.endsw
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    return lib
+    return emu_lib.load()
 
 
 def restated(ps, degree, first_chain_idx):

@@ -4,15 +4,14 @@ emulation library (emu_bins_lookup, emu_bin_counts) and held to plain Python Hor
 (apsu_amd/csrc/db_place.h through emu_place_entries) held to a Python restatement of the reference's loops
 (ReceiverDB::remove / insert_or_assign, receiver_db.cpp:349-434,524-567).  All comparisons are exact integers."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_lib
+from emu_lib import vp
 from test_bundle_update_cpu import T, poly_from_roots
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 u64p = C.POINTER(C.c_uint64)
 NONE = 0xFFFFFFFF
 R = 8                                                     # device.h: LOOKUP_R
@@ -22,20 +21,7 @@ UNCHANGED, REPLACED, EMPTY = 0, 1, 2
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    if not hasattr(lib, "emu_bins_lookup"):               # a library from before this feature: rebuild it
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "-B", "../libapsu_he_hostemu.so"])
-        lib = C.CDLL(so)
-        lib.emu_last_error.restype = C.c_char_p
-    return lib
-
-
-def vp(a):
-    return C.c_void_p(a.ctypes.data)
+    return emu_lib.load()
 
 
 # ---------------------------------------------------------------------------------------------------------------- lookup

@@ -6,11 +6,12 @@ import ctypes as C
 import glob
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_lib
+from emu_lib import vp
 from oracle import ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,26 +22,9 @@ T33 = 4294967311                                          # 2^32 + 15, the first
 T60 = (1 << 60) - 93                                      # the widest prime below 2^60
 
 
-def load_emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    if not hasattr(lib, "emu_bins_merge"):                # a library from before this feature: rebuild it
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "-B", "../libapsu_he_hostemu.so"])
-        lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    lib.emu_merge_fold_interval.restype = C.c_uint32
-    return lib
-
-
 @pytest.fixture(scope="module")
 def emu():
-    return load_emu()
-
-
-def vp(a):
-    return C.c_void_p(a.ctypes.data)
+    return emu_lib.load()
 
 
 def is_prime(p):

@@ -6,38 +6,21 @@ import ctypes as C
 import glob
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+import emu_lib
+from emu_lib import vp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = [(7681, 6), (769, 6), (257, 6), (12289, 8)]          # (t, log2 n) with t = 1 (mod 2n): 120, 12, 4 and 48 cosets
 # (a ring of 32 slots has no workgroup transform form, so (193, 32) cannot be run through the lanes; (257, 64) takes its place)
 
 
-def load_emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    if not hasattr(lib, "emu_bin_roots"):                 # a library from before this feature: rebuild it
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "-B", "../libapsu_he_hostemu.so"])
-        lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    lib.emu_field_generator.restype = C.c_uint64
-    lib.emu_roots_coset_count.restype = C.c_int64
-    lib.emu_bin_roots.restype = C.c_int64
-    return lib
-
-
 @pytest.fixture(scope="module")
 def emu():
-    return load_emu()
-
-
-def vp(a):
-    return C.c_void_p(a.ctypes.data)
+    return emu_lib.load()
 
 
 def prime_factors(m):

@@ -10,9 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import emu_lib
+from emu_lib import vp
 import split_model as M
 from oracle import ref
-from test_bundle_merge_cpu import vp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = 65537
@@ -20,19 +21,7 @@ T = 65537
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    if not hasattr(lib, "emu_roots_split"):               # a library from before this feature: rebuild it
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "-B", "../libapsu_he_hostemu.so"])
-        lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    lib.emu_split_parts.restype = C.c_int64
-    lib.emu_rebase_plan.restype = C.c_int64
-    for f in ("emu_split_cut", "emu_split_part_of", "emu_split_capacity"):
-        getattr(lib, f).restype = C.c_uint32
-    return lib
+    return emu_lib.load()
 
 
 # --------------------------------------------------------------------------------------------- the rules

@@ -2,13 +2,12 @@
 i % 64, register slot i / 64, removal as a suffix scan over the 64 lanes with a carry between slots -- stepped lane by lane by the
 CPU emulation library (emu_bin_update) and held to plain integer polynomial arithmetic mod t."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import emu_lib
+
 u64p = C.POINTER(C.c_uint64)
 T = 0x1C001                                               # 114689 = 14 * 2^13 + 1, a 17-bit batching prime
 COUNTS = [0, 1, 62, 63, 64, 65, 127, 128, 129, 200]
@@ -16,12 +15,7 @@ COUNTS = [0, 1, 62, 63, 64, 65, 127, 128, 129, 200]
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_bin_update.restype = C.c_int64
-    lib.emu_bin_unlift.restype = C.c_uint64
+    lib = emu_lib.load()
     lib.emu_bin_unlift.argtypes = [C.c_uint64] * 3
     return lib
 

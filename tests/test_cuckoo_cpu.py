@@ -1,26 +1,18 @@
 """CPU tier of the cuckoo hashing (apsu_amd/csrc/cuckoo.h through libapsu_he_hostemu.so) against the independent model
 tests/cuckoo_model.py: the location functions' tables, the locations, the table rule and the database side's grouping."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cuckoo_cases
 import cuckoo_model as M
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import emu_lib
 
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    return lib
+    return emu_lib.load()
 
 
 def _vp(a):

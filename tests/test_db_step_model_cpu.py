@@ -11,8 +11,9 @@ import pytest
 import common
 import db_step_model as M
 from db_step_model import NONE, U, ints
+import emu_lib
+from emu_lib import vp
 from oracle import ref
-from test_bundle_merge_cpu import load_emu, vp
 
 WIDTHS = [17, 28, 30, 31, 32, 33, 41, 50, 58]
 RINGS = [64, 256]
@@ -40,11 +41,7 @@ def oracle(n, bits):
 
 @pytest.fixture(scope="module")
 def emu():
-    lib = load_emu()
-    lib.emu_bin_update.restype = C.c_int64
-    lib.emu_bins_rows.restype = C.c_int64
-    lib.emu_bin_roots.restype = C.c_int64
-    return lib
+    return emu_lib.load()
 
 
 def directed_roots(rng, t, count):

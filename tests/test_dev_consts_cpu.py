@@ -15,9 +15,9 @@ import pytest
 
 import common
 import edge_values as ev
+import emu_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "dev_consts_parent.json")))
 ALL_PARAM_FILES = sorted(f[:-5] for f in os.listdir(common.PARAM_DIR) if f.endswith(".json"))
 RAW = 1 << 30
@@ -26,11 +26,7 @@ MT = 1 << 32
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(SO)
-    lib.emu_last_error.restype = C.c_char_p
-    lib.emu_device_constants.restype = C.c_int64
+    lib = emu_lib.load()
     lib.emu_device_constants.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_char_p, C.c_void_p, C.c_uint64]
     lib.emu_ntt_table.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p]
     return lib
@@ -393,7 +389,9 @@ SWITCHES = {
 }
 CHILD = """
 import ctypes, json, os, sys
-lib = ctypes.CDLL(sys.argv[1])
+sys.path.insert(0, sys.argv[1])
+import emu_lib
+lib = emu_lib.load()
 name, values = sys.argv[2], json.loads(sys.argv[3])
 out = (ctypes.c_int64 * 10)()
 res = {}
@@ -408,7 +406,7 @@ print(json.dumps(res))
 
 def read_in_child(name, values):
     env = {k: v for k, v in os.environ.items() if not k.startswith("APSU_HE_")}
-    r = subprocess.run([sys.executable, "-c", CHILD, SO, name, json.dumps(values)], capture_output=True, text=True, env=env, timeout=60)
+    r = subprocess.run([sys.executable, "-c", CHILD, os.path.join(ROOT, "tests"), name, json.dumps(values)], capture_output=True, text=True, env=env, timeout=60)
     assert r.returncode == 0, r.stderr
     return {k: dict(zip(SWITCH_FIELDS, v)) for k, v in json.loads(r.stdout).items()}
 

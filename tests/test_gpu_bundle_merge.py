@@ -13,6 +13,7 @@ import torch
 
 import apsu_amd
 import common
+import emu_lib
 import test_bundle_merge_cpu as M
 import test_gpu_bundle_update as U
 from oracle import ref
@@ -302,7 +303,7 @@ def test_compact_four_sparse_and_one_full():
     res = G.compact(0, gb)
     group = [int(g) for g in res.group]
     assert group == [0, 1, 0, 2, 0]
-    assert M.run_plan(M.load_emu(), counts[:, :60], 11)[0] == group          # the groups are the planner's
+    assert M.run_plan(emu_lib.load(), counts[:, :60], 11)[0] == group          # the groups are the planner's
     degrees = [max(len(b) for b in union(*[parts[i] for i in range(5) if group[i] == g])) for g in range(3)]
     assert M.plan_errors([[int(v) for v in c] for c in counts], 11, group, degrees) == []
     assert len(res.merged) == 3 and res.merged[1] is None and res.merged[2] is None          # groups of one: untouched

@@ -12,6 +12,7 @@ import pytest
 
 import apsu_amd
 import common
+import emu_lib
 import test_gpu_bundle_lookup as L
 import test_gpu_bundle_merge as MG
 import test_gpu_bundle_update as U
@@ -125,7 +126,7 @@ class Twin:
         return res, r
 
     def check_renumbering(self, reg, dropped, replaced, appended, new_id):
-        want_new_id, want_reg = P.emu_registry_after(P.load_emu(), reg, dropped, replaced, appended)
+        want_new_id, want_reg = P.emu_registry_after(emu_lib.load(), reg, dropped, replaced, appended)
         assert (want_new_id, want_reg) == P.model_registry_after(reg, dropped, replaced, appended)
         assert new_id == want_new_id
         assert self.registry() == want_reg and self.M.n_bundles == len(want_reg)
@@ -143,7 +144,7 @@ class Twin:
             if m is None:
                 continue
             members = [p for p in range(len(old)) if group[p] == g]
-            home, first = P.emu_merge_home(P.load_emu(), [reg[ids[p]] for p in members])
+            home, first = P.emu_merge_home(emu_lib.load(), [reg[ids[p]] for p in members])
             assert first == 0 and m.cache_idx == old[members[0]].cache_idx
             replaced[ids[members[0]]] = m.degree
             self.single[(bundle_idx, m.cache_idx)] = m
@@ -173,7 +174,7 @@ def test_build_bundle_is_placed_by_the_rule(devs, tmp_path):
     for k, (bidx, cidx, degree) in enumerate(plan):
         assert T.build(bidx, cidx, bins_of_degree(rng, t, degree)) == k                 # registered last
         slot = P.model_place_new_unit(bidx, NIDX, T.world, load)
-        assert slot == P.emu_place(P.load_emu(), bidx, NIDX, T.world, load)
+        assert slot == P.emu_place(emu_lib.load(), bidx, NIDX, T.world, load)
         load[slot] += degree + 64
         assert tuple(T.M.bundle_info(k)) == (slot, bidx, cidx, degree)
     assert T.M.bundle_count() == len(plan) == T.M.n_bundles

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import common
+import emu_lib
 from oracle import ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,12 +19,7 @@ u64p = C.POINTER(C.c_uint64)
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    return lib
+    return emu_lib.load()
 
 
 CONFIGS = ["100K-1", "1M-1024-com", "16M-4096", "256M-4096"]
@@ -506,7 +502,6 @@ def test_ntt_launch_form_table(emu):
     256 limbs at n = 8192 (above: the 8-wave build for narrow forward and for every gathered launch), at n = 4096 always but the inverse
     above 1 024 limbs.  Every form gives the same bits, so the GPU parity tests cannot see this choice."""
     emu.emu_ntt_form.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int)]
-    emu.emu_ntt_form.restype = None
     out = (C.c_int * 4)()
     for logn in (6, 8, 10, 11, 12, 13, 14, 15):
         for kind in (FWD, INV, GATHER, TENSOR):

@@ -9,12 +9,13 @@ import ctypes as C
 import functools
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import edge_values as ev
+import emu_lib
+from emu_lib import vp
 from oracle import ref
 from test_gpu_mac_edges import LONG_CHAIN, WIDTHS, chain_lengths
 
@@ -36,22 +37,9 @@ class TermJob(C.Structure):
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    if not hasattr(lib, "emu_mac_plan"):                  # a library from before this feature: rebuild it
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "-B", "../libapsu_he_hostemu.so"])
-        lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    lib.emu_packed_coeff.restype = C.c_uint64
-    lib.emu_packed_row_bits.restype = C.c_uint32
+    lib = emu_lib.load()
     assert lib.emu_mac_job_bytes() == C.sizeof(MacJob) == 112
     return lib
-
-
-def vp(a):
-    return C.c_void_p(a.ctypes.data)
 
 
 def u32(v):

@@ -11,22 +11,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import emu_lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "apsu_amd", "csrc")
 
 
-def load_emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", SRC, "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    return lib
-
-
 @pytest.fixture(scope="module")
 def emu():
-    return load_emu()
+    return emu_lib.load()
 
 
 def ptr(a):

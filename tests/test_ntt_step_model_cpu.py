@@ -3,7 +3,7 @@ to the kernels' form tables.
 
   the definition   out[i] = a(psi^(2 brv(i) + 1)): complete at n <= 256 (oracle/pymodel.py Model.ntt), Horner at sampled indices above
   the C oracle     transform_to_ntt / transform_from_ntt on the data primes of the GPU test's contexts, every ring size
-  the emulation    emu_ntt_limb, emu_ntt_limb_c, emu_ntt_limb_ex and emu_intt_tensor_limb_c (apsu_amd/csrc/host_emu.cpp: the pass functions
+  the emulation    emu_ntt_limb, emu_ntt_limb_c, emu_ntt_limb_ex and emu_intt_tensor_limb_c (apsu_amd/csrc/emu/ntt.cpp: the pass functions
                    the kernels run, RED 0 / 1 / 2, RAW on and off, both per-lane forms) on every directed case of the GPU test that fits
                    one limb: the fills, the reduced-gather edges, the unreduced gather at its boundary, the solved lazy operands, the RAW
                    bound and congruence
@@ -14,9 +14,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import emu_lib
+from emu_lib import vp
 import ntt_step_model as M
 from oracle import pymodel, ref
-from test_bundle_merge_cpu import load_emu, vp
 
 EMU_LOGNS = [l for l in M.LOGNS if l < M.SPLIT_LOGN]
 # a wide-near modulus per ring: a 61-bit prime behind the ones an emulation context takes for its own auxiliary base
@@ -25,10 +26,7 @@ SEAL61 = {logn: pymodel.get_primes(2 << logn, 61, 8)[-1] for logn in EMU_LOGNS}
 
 @pytest.fixture(scope="module")
 def emu():
-    lib = load_emu()
-    if not hasattr(lib, "emu_ntt_limb_ex"):
-        pytest.fail("libapsu_he_hostemu.so is older than the sources: rebuild it")
-    return lib
+    return emu_lib.load()
 
 
 def moduli(logn):
@@ -138,8 +136,7 @@ def test_fold_word_against_the_emulation(emu):
 def context_moduli(logn, narrow_aux):
     """the 13 moduli of the GPU test's context of this ring, as the engine's parameter code picks them (emu_device_constants): the five
     coefficient primes, the seven auxiliary primes of the narrow or of SEAL's base, the plain modulus"""
-    emu = load_emu()
-    emu.emu_device_constants.restype = C.c_int64
+    emu = emu_lib.load()
     lay = np.zeros(5, dtype=np.uint64)
     emu.emu_dev_layout(vp(lay))
     step = int(lay[0]) * (2 if logn == M.SPLIT_LOGN else 1)

@@ -3,7 +3,6 @@ k_plain_powers run) through libapsu_he_hostemu.so against a Python restatement o
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import common  # noqa: E402
+import emu_lib  # noqa: E402
 import query_side_model as M  # noqa: E402
 
 u64p = C.POINTER(C.c_uint64)
@@ -22,11 +22,7 @@ RINGS = [64, 4096, 8192]
 
 @pytest.fixture(scope="module")
 def emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "apsu_amd", "csrc"), "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    lib.emu_qs_block.restype = C.c_uint64
+    lib = emu_lib.load()
     lib.emu_qs_block.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
     return lib
 

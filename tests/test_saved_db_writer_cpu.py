@@ -12,6 +12,8 @@ import pytest
 
 import common
 from apsu_amd import wire
+import emu_lib
+from emu_lib import vp
 from test_wire_framing import FbBuilder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -265,26 +267,9 @@ def test_the_size_bound():
 
 
 # --------------------------------------------------------------------------------------------- k_bins_rows on the CPU
-def load_emu():
-    so = os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so")
-    if not os.path.exists(so):
-        subprocess.check_call(["make", "-C", SRC, "-s", "../libapsu_he_hostemu.so"])
-    lib = C.CDLL(so)
-    if not hasattr(lib, "emu_bins_rows"):                 # a library from before this feature: rebuild it
-        subprocess.check_call(["make", "-C", SRC, "-s", "-B", "../libapsu_he_hostemu.so"])
-        lib = C.CDLL(so)
-    lib.emu_last_error.restype = C.c_char_p
-    lib.emu_bins_rows.restype = C.c_int64
-    return lib
-
-
 @pytest.fixture(scope="module")
 def emu():
-    return load_emu()
-
-
-def vp(a):
-    return C.c_void_p(a.ctypes.data)
+    return emu_lib.load()
 
 
 def decoded_array(n, degree, counts, seed):

@@ -6,7 +6,8 @@ Median of --reps after --warmup.  Writes --out (and prints it)."""
 import argparse, ctypes as C, os, re, statistics, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import numpy as np, torch, apsu_amd
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np, torch, apsu_amd, emu_lib
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=20)
@@ -44,7 +45,7 @@ def measure(ctx, fn):
 
 
 rng = np.random.default_rng(24)
-emu = C.CDLL(os.path.join(ROOT, "apsu_amd", "libapsu_he_hostemu.so"))
+emu = emu_lib.load()
 ctx = apsu_amd.HeContext(params("16M-4096"))
 T, H = ctx.table_size, ctx.hash_func_count
 say(f"median (min .. max) of {args.reps} in ms; {torch.cuda.get_device_name(0)}")
