@@ -6,7 +6,7 @@
 // fills a Bundle from the layout, upload / finish / decode / download / load (engine_bundles.cpp) and the saved export (engine_db.cpp) read kinds, slots and runs from it and
 // nowhere else; tests/test_bundle_layout_cpu.py enumerates it through the CPU emulation library against a restatement of the rule.
 //
-// The evaluation (engine.cpp: ps_tables, eval_bundles_nks) relies on one consequence: the NTT-form coefficients of inner polynomial i,
+// The evaluation (engine_eval.cpp: ps_tables; engine_nks.cpp: eval_bundles_nks) relies on one consequence: the NTT-form coefficients of inner polynomial i,
 // a_{i*h+1} .. a_{i*h+l} with l = ps_low_degree, start at slot i * l -- each block of h degrees holds l of them and one a_{i*h}.
 #pragma once
 #include <algorithm>

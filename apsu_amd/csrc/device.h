@@ -9,7 +9,6 @@
 #include "launch_behz.h"
 #include "launch_mac.h"
 // the pure rules host code reads next to the launchers
-#include "eval_plan.h"
 #include "query_side.h"
 #include "bin_merge.h"
 #include "bin_rows.h"

@@ -1,4 +1,4 @@
-// CPU emulation, the host's rules: parameters, device constant blocks, the powers' graph, scheduling, the evaluation's forms, the stored
+// CPU emulation, the host's rules: parameters, device constant blocks, the powers' graph and its schedules, scheduling, the evaluation's forms, the stored
 // layout of a BinBundle, the transform's launch form, the switches.  No kernel code in here: pure functions of the host, enumerated by tests.
 #include <cstring>
 #include <set>
@@ -11,6 +11,7 @@
 #include "eval_plan.h"
 #include "params.h"
 #include "powers_dag.h"
+#include "powers_sched.h"
 #include "sched_policy.h"
 
 using namespace apsu_he;
@@ -173,6 +174,70 @@ int emu_powers_dag(const uint32_t *sources, int ns, const uint32_t *targets, int
         i++;
     }
     return (int)d.depth();
+}
+
+// The rules of ComputePowers (powers_sched.h), for tests/test_powers_sched_cpu.py.  Every call configures the PowersDag of the given
+// sets itself and returns -1 where that fails (or a rule refuses: emu_last_error).
+static PowersDag dag_of(const uint32_t *sources, int ns, const uint32_t *targets, int nt)
+{
+    PowersDag d;
+    if (!d.configure(std::set<uint32_t>(sources, sources + ns), std::set<uint32_t>(targets, targets + nt))) throw std::invalid_argument("PowersDag::configure failed");
+    return d;
+}
+// which: 0 the whole DAG's schedule, 1 the low half's, 2 the high half's (both empty unless the walk splits).  out = split_ok, then each
+// list behind its length: slot_power, slot_of, levels (s0, s1, sp each), nodes (slot, parent slots each), low_powers, high_powers.
+// Returns the words of `out` (the first `cap` are written).
+int emu_powers_sched(const uint32_t *sources, int ns, const uint32_t *targets, int nt, uint32_t ps_low_degree, int which, int64_t *out, int cap)
+{
+    return guarded([&]() -> int {
+        const PowersScheds r = powers_scheds(dag_of(sources, ns, targets, nt), ps_low_degree);
+        const PowersSched &s = which == 0 ? r.all : which == 1 ? r.low : r.high;
+        std::vector<int64_t> v{ r.split_ok };
+        auto put = [&](const auto &list) { v.push_back((int64_t)list.size()); for (auto x : list) v.push_back((int64_t)x); };
+        put(s.slot_power); put(s.slot_of);
+        v.push_back((int64_t)s.levels.size());
+        for (const PowersSched::Level &l : s.levels) v.insert(v.end(), { l.s0, l.s1, l.sp });
+        v.push_back((int64_t)s.nodes.size());
+        for (const auto &nd : s.nodes) v.insert(v.end(), { nd[0], nd[1], nd[2] });
+        put(s.low_powers); put(s.high_powers);
+        for (size_t i = 0; i < v.size() && (int)i < cap; i++) out[i] = v[i];
+        return (int)v.size();
+    });
+}
+// out = products, oversize, stored, then size[0 .. the largest target power]
+int emu_power_sizes(const uint32_t *sources, int ns, const uint32_t *targets, int nt, uint32_t ps_low_degree, int using_keyswitching, uint32_t *out, int cap)
+{
+    return guarded([&]() -> int {
+        const PowersDag d = dag_of(sources, ns, targets, nt);
+        const PowerSizes z = power_sizes(powers_scheds(d, ps_low_degree).all, using_keyswitching != 0, d.depth());
+        std::vector<uint32_t> v{ z.products, z.oversize, z.stored };
+        v.insert(v.end(), z.size.begin(), z.size.end());
+        for (size_t i = 0; i < v.size() && (int)i < cap; i++) out[i] = v[i];
+        return (int)v.size();
+    });
+}
+// out = result_polys, then result_size_for(degree) for degree = 0 .. max_items_per_bin
+int emu_result_size(const uint32_t *sources, int ns, const uint32_t *targets, int nt, uint32_t ps_low_degree, int using_keyswitching,
+                    uint32_t max_items_per_bin, uint32_t *out, int cap)
+{
+    return guarded([&]() -> int {
+        const PowersDag d = dag_of(sources, ns, targets, nt);
+        const bool ks = using_keyswitching != 0;
+        const PowerSizes z = power_sizes(powers_scheds(d, ps_low_degree).all, ks, d.depth());
+        std::vector<uint32_t> v{ result_polys(z, ps_low_degree, ks, max_items_per_bin) };
+        for (uint32_t deg = 0; deg <= max_items_per_bin; deg++) v.push_back(result_size_for(z, ps_low_degree, deg, ks));
+        for (size_t i = 0; i < v.size() && (int)i < cap; i++) out[i] = v[i];
+        return (int)v.size();
+    });
+}
+// out = low, idx; -1 where the power is refused ("power not available")
+int emu_power_place(uint32_t ps_low_degree, uint32_t power, uint32_t n_low, uint32_t n_high, uint32_t *out)
+{
+    return guarded([&]() -> int {
+        const PowerPlace at = power_place(ps_low_degree, power, n_low, n_high);
+        out[0] = at.low; out[1] = at.idx;
+        return 0;
+    });
 }
 
 int emu_create_powers_set(uint32_t ps_low, uint32_t target, uint32_t *out, int cap)

@@ -21,6 +21,7 @@
 #include "db_place.h"
 #include "db_compact.h"
 #include "powers_dag.h"
+#include "powers_sched.h"
 #include "bundle_layout.h"
 
 namespace apsu_he {
@@ -104,6 +105,7 @@ struct Powers {
 };
 
 struct PsBatch;
+struct EvalPlan;                     // eval_plan.h (engine_eval.cpp)
 
 // time stamps of a resident-database call on the engine's stream: events created before the call's first stamp (outside the timed
 // spans), elapsed times read after the call's sync
@@ -316,10 +318,9 @@ public:
     // (receiver_osn.cpp:416,430-432 ; bin_bundle.cpp:308-310), so powers and results have more than two polynomials.
     // power_size: polynomials of a target power after ComputePowers; result_size: of one BinBundle's result;
     // result_polys: the largest result_size over all degrees = polynomials per row of eval_bundles' output (2 with key switching).
-    static constexpr uint32_t CT_SIZE_MAX = 16;          // SEAL_CIPHERTEXT_SIZE_MAX: Ciphertext::resize throws beyond it
+    // The numbers are powers_sched.h's (power_sizes, result_size_for, result_polys; CT_SIZE_MAX), made at creation.
     uint32_t power_size(uint32_t power) const;
     uint32_t result_size(const Bundle &b) const;
-    uint32_t result_size_for(uint32_t degree) const;
     uint32_t result_polys() const { return result_polys_; }
 
     // introspection for tests
@@ -403,10 +404,10 @@ public:
 
 private:
     // arena (bump allocator reset per top-level operation)
-    u64 *ws(size_t words);
+    u64 *ws(size_t words);                                               // engine_impl.h
     template <class T> T *ws_as(size_t count, size_t extra_words = 0);   // engine_impl.h
     void ws_reset(size_t need_bytes_hint = 0);
-    template <class T> const T *upload_jobs(const std::vector<T> &v);
+    template <class T> const T *upload_jobs(const std::vector<T> &v);   // engine_impl.h
 
     const DevLevel *dlevel(int chain_idx) const { return d_levels_.u() ? reinterpret_cast<const DevLevel *>(d_levels_.p()) + chain_idx : nullptr; }
     const LevelConstants &hlevel(int chain_idx) const { return hp_.level[chain_idx]; }
@@ -415,9 +416,8 @@ private:
     const int *map_ct() const { return reinterpret_cast<const int *>(d_map_ct_.p()); }
     const int *map_ext(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ext_.p()) + chain_idx * DMAXE; }
     // the same map for the inverse transform in front of a finish kernel: NTT_MAP_RAW set where that level's finish takes
-    // the twist into its own constants (fast_finish), identical to map_ext otherwise
+    // the twist into its own constants (behz_unrolled), identical to map_ext otherwise
     const int *map_ext_fin(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ext_fin_.p()) + chain_idx * DMAXE; }
-    bool fast_finish(int chain_idx) const { return behz_unrolled(hp_.level[chain_idx].L, hp_.level[chain_idx].nB); }
     const int *map_ks(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ks_.p()) + chain_idx * (DMAXL + 1) * DMAXL; }
     const int *map_ksacc(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ksacc_.p()) + chain_idx * (DMAXL + 1); }
     const int *map_ksacc_raw(int chain_idx) const { return reinterpret_cast<const int *>(d_map_ksacc_raw_.p()) + chain_idx * (DMAXL + 1); }
@@ -444,10 +444,7 @@ private:
     std::unique_ptr<Powers> compute_powers_nks(const uint32_t *bundle_indices, int nb, const u64 *const *src, bool on_device);
     void eval_bundles_nks(const Bundle *const *bundles, int count, const Powers &pw, const u64 *const *masks, bool masks_on_device,
                           u64 *out, bool out_on_device, u64 *const *out_rows);
-    bool nks_ = false;                // no key switching AND the PowersDag has products
-    bool nks_oversize_ = false;       // some product exceeds CT_SIZE_MAX polynomials: ComputePowers throws like SEAL's multiply
-    std::vector<uint32_t> nks_size_;  // polynomials per target power (index = power; 0 = no target)
-    uint32_t nks_S_ = 2;              // polynomials stored per power (largest size, rounded up to even)
+    PowerSizes sizes_;                // polynomials per target power; .products: no key switching AND the PowersDag has products
     uint32_t result_polys_ = 2;
 
     HeParams hp_;
@@ -520,15 +517,9 @@ private:
     void *wire_pinned_ = nullptr;
     size_t wire_pinned_bytes_ = 0;
 
-    // PowersDag schedule (slot order = depth, parents first, power)
-    struct Sched {
-        std::vector<uint32_t> slot_power;                 // slot -> power
-        std::vector<int> slot_of;                         // power -> slot (-1 if absent)
-        struct Level { int s0, s1, sp; };                 // slots [s0,s1) ; [s0,sp) are parents of later nodes
-        std::vector<Level> levels;
-        std::vector<std::array<int, 3>> nodes;           // per non-source slot: {slot, slot_p1, slot_p2}
-        std::vector<uint32_t> low_powers, high_powers;    // target powers by final form
-    } sched_, sched_low_, sched_high_;
+    // PowersDag schedules (powers_sched.h): the whole DAG's and, where split_ok_, its two halves' (empty where the
+    // walk does not split)
+    PowersSched sched_, sched_low_, sched_high_;
     void mask_generate_impl(uint32_t count, u64 *masks_dev, u64 *values_host, u64 *blocks_host, const std::function<void(u64 *, size_t)> &fill);
     bool fuse_tensor_ = true;         // BEHZ step 4 is formed by the inverse transform's load (k_intt_tensor); off only for n = 32768, whose limb does not fit one workgroup
     bool tier1_device_ = false;       // tier-1 operands are device memory and calls do not synchronise
@@ -544,14 +535,16 @@ private:
     void d_mac(const MacPlan &p, const MacJob *jobs = nullptr);
     bool split_ok_ = false;           // the low-power and high-power halves of the PowersDag share no node
     int two_stream_mode_ = -1;        // apsu_he_set_two_stream (-1: EngineSwitches::two_stream_default)
-    void build_schedule();
-    void build_schedule_for(Sched &s, const std::vector<char> &member);
     struct DagRun;                    // per-call state of one walk over a schedule
     void dag_sources(DagRun &run, const u64 *const *src, bool on_device);
     void dag_level(DagRun &run, size_t d, const RelinKeys *rk);
     void dag_outputs(DagRun &run, Powers &pw, bool do_low, bool do_high);
-    void dag_walk(const Sched &s, int nb, const u64 *const *src, bool on_device, const RelinKeys *rk, Powers &pw);
-    // eval_bundles in pieces (engine.cpp): per-call context and Paterson-Stockmeyer batch; the plan: eval_plan.h
+    void dag_walk(const PowersSched &s, int nb, const u64 *const *src, bool on_device, const RelinKeys *rk, Powers &pw);
+    // what compute_powers and compute_powers_nks share: the Powers header of a new query (its sequence number included), and the
+    // ComputePowers phase span around the walk -- body(span) runs inside WITH_ARENA and stamps the span's end(s) (engine_impl.h)
+    void powers_header(Powers &pw, const uint32_t *bundle_indices, int nb, int low_level, int high_level);
+    template <class F> void with_powers_span(F &&body);
+    // eval_bundles in pieces (engine_eval.cpp): per-call context and Paterson-Stockmeyer batch; the plan: eval_plan.h
     struct EvalCall;
     void eval_plain(EvalCall &c, const std::vector<int> &pl_ids);
     void eval_patstock(EvalCall &c, const std::vector<int> &ps_ids);

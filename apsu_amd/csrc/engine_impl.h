@@ -1,6 +1,10 @@
-// What the Engine's three translation units share and nobody else sees: engine.cpp (contexts, tier 1, ComputePowers, the evaluation,
-// the querier's side), engine_bundles.cpp (what makes, stores and converts a BinBundle: upload, build, encode and decode, images) and
-// engine_db.cpp (the calls on a resident database: update, lookup, bins, merge and compaction, export, plaintext evaluation, self-test).
+// What the Engine's translation units share and nobody else sees.  engine.cpp: the context (construction, waits, lanes, profiling and
+// phase timers, the arena, the device building blocks, tier 1); engine_powers.cpp: ComputePowers; engine_eval.cpp: the BinBundle
+// evaluation; engine_query.cpp: seeded expansion, masks and packing, the querier's side; engine_nks.cpp: both paths without key
+// switching; engine_bundles.cpp: what makes, stores and converts a BinBundle (upload, build, encode and decode, images); engine_db.cpp: the
+// calls on a resident database (update, lookup, bins, merge and compaction, export, plaintext evaluation, self-test); engine_cuckoo.cpp and
+// the engine_*_steps.cpp test hooks.  The arena's allocator and the job-table upload are defined HERE, not in a unit: a launch path
+// then crosses no unit boundary for them.
 #pragma once
 #include "engine.h"
 
@@ -56,8 +60,83 @@ struct EngineAccess {
 #define WITH_ARENA(...) EngineAccess::run(this, [&]() __VA_ARGS__)
 #define TIER1_SLOTS() job_seq_base_ = 512
 
+// ---- the arena and the job tables: defined here so that every unit's launch path allocates and uploads without leaving its unit
+inline u64 *Engine::ws(size_t words)
+{
+    size_t bytes = (words * sizeof(u64) + 255) & ~(size_t)255;
+    if (arena_off_ + bytes > arena_.bytes()) { overflow_lane_ = cur_lane_; throw ArenaOverflow{ arena_off_ + bytes }; }
+    u64 *p = reinterpret_cast<u64 *>(static_cast<char *>(arena_.p()) + arena_off_);
+    arena_off_ += bytes;
+    return p;
+}
+
 // `count` objects of type T from the arena (whole 64-bit words, rounded up) and `extra` words behind them
 template <class T> T *Engine::ws_as(size_t count, size_t extra) { return reinterpret_cast<T *>(ws((count * sizeof(T) + 7) / 8 + extra)); }
+
+template <class T> const T *Engine::upload_jobs(const std::vector<T> &v)
+{
+    if (v.empty()) return nullptr;
+    const size_t bytes = v.size() * sizeof(T);
+    // lanes 1 and 2 run next to other lanes' kernels: their tables must stay inside their own slot ranges (ws_reset; a pipelined
+    // ComputePowers uses 12 of lane 1's 112)
+    if ((cur_lane_ == 1 && job_seq_ >= job_seq_base_ + 240) || (cur_lane_ == 2 && job_seq_ >= job_seq_base_ + 256))
+        throw std::logic_error("job-table slots of a side lane exhausted");
+    if (job_seq_ >= job_slots_.size()) job_slots_.resize(job_seq_ + 1);
+    JobSlot &slot = job_slots_[job_seq_++];
+    for (JobWay &w : slot.way)
+        if (w.host.size() == bytes && std::memcmp(w.host.data(), v.data(), bytes) == 0) {
+            counters_[C_JOB_HIT]++;
+            w.stamp = ++job_stamp_;
+            return reinterpret_cast<const T *>(w.buf.p());                                            // unchanged since an earlier call
+        }
+    counters_[C_JOB_UPLOAD]++;
+    JobWay *lru = &slot.way[0];
+    for (JobWay &w : slot.way) if (w.stamp < lru->stamp) lru = &w;                                    // least recently used
+    JobWay &way = *lru;
+    way.stamp = ++job_stamp_;
+    if (way.buf.bytes() < bytes) {
+        counters_[C_JOB_REALLOC]++;
+        sync();                                   // the old buffer may still be read by queued kernels
+        way.buf.alloc(bytes + bytes / 2);
+    }
+    // through a pinned staging area so the copy is truly asynchronous and the std::vector may die
+    const size_t aligned = (bytes + 63) & ~(size_t)63;
+    if (stage_off_ + aligned > stage_bytes_) {
+        counters_[C_STAGE_WRAP]++;
+        sync();                                   // everything staged so far has been consumed
+        if (aligned > stage_bytes_) {
+            if (stage_) (void)hipHostFree(stage_);
+            stage_bytes_ = aligned * 2;
+            HIP_CHECK(hipHostMalloc(&stage_, stage_bytes_));
+        }
+        stage_off_ = 0;
+    }
+    char *hp = static_cast<char *>(stage_) + stage_off_;
+    std::memcpy(hp, v.data(), bytes);
+    stage_off_ += aligned;
+    HIP_CHECK(hipMemcpyAsync(way.buf.p(), hp, bytes, hipMemcpyHostToDevice, st_));
+    way.host.assign(reinterpret_cast<const unsigned char *>(v.data()), reinterpret_cast<const unsigned char *>(v.data()) + bytes);
+    return reinterpret_cast<const T *>(way.buf.p());
+}
+
+// The ComputePowers phase span around a walk (compute_powers, compute_powers_nks): opened on the current stream together with the
+// RunQuery span, closed when body(span), which runs inside WITH_ARENA, has stamped span.b (and span.b2 on a second stream).  A retry
+// after arena growth queues the walk again: the stamps of the attempt before go back to the pool first.
+template <class F> void Engine::with_powers_span(F &&body)
+{
+    PhaseSpan span;
+    if (phase_on_) {
+        phase_close_query();
+        span.phase = PH_COMPUTE_POWERS;
+        span.a = phase_event(st_);
+        query_start_ = phase_event(st_);
+    }
+    WITH_ARENA({
+        for (hipEvent_t *e : { &span.b, &span.b2 }) if (*e) { phase_pool_.push_back(*e); *e = nullptr; }
+        body(span);
+    });
+    if (phase_on_ && span.a && span.b) phase_spans_.push_back(span);
+}
 
 // Tier-1 operands are host pointers by default; with apsu_he_set_tier1_on_device they are device (or page-locked) memory and the
 // calls only queue their work -- unified addressing lets one copy kind serve both

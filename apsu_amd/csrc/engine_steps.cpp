@@ -5,6 +5,7 @@
 // anything is launched: sizes, levels, a RAW form the launcher does not have, a term count beyond the bound the engine checks on the
 // host, and a word that is not a canonical residue where the contract asks for one.  For the tests; nothing on the query path calls it.
 #include "engine_impl.h"
+#include "eval_plan.h"
 
 #include <string>
 

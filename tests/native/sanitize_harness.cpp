@@ -1,6 +1,6 @@
 // CPU tier, sanitizer build (AddressSanitizer + UndefinedBehaviorSanitizer) of the product's HOST code that parses untrusted or
 // structured input: the N3 framing reader (wire.cpp), the PSUParams JSON reader + constant derivation (params.cpp), the
-// constant blocks built from them (dev_consts.cpp), the PowersDag (powers_dag.cpp) and the partition rule (sharding.cpp).  Built and run by tests/test_host_sanitizers.py; any
+// constant blocks built from them (dev_consts.cpp), the PowersDag (powers_dag.cpp) with its schedules and sizes (powers_sched.h) and the partition rule (sharding.cpp).  Built and run by tests/test_host_sanitizers.py; any
 // out-of-bounds read in the verifier, signed overflow or misaligned access aborts the run.  Also the reads of k_mac, k_term_product and
 // packed_coeff (mac_core.h, the functions the kernels run) at the very end of a bit-packed buffer.
 #include <cstdio>
@@ -18,6 +18,7 @@
 #include "../../apsu_amd/csrc/bundle_layout.h"
 #include "../../apsu_amd/csrc/mac_core.h"
 #include "../../apsu_amd/csrc/powers_dag.h"
+#include "../../apsu_amd/csrc/powers_sched.h"
 #include "../../apsu_amd/csrc/sharding.h"
 #include "../../apsu_amd/csrc/wire.h"
 #include "../../apsu_amd/csrc/seal_codec.h"
@@ -220,7 +221,24 @@ int main(int argc, char **argv)
         }
         PowersDag dag;
         if (!dag.configure(p.query_params.query_powers, create_powers_set(p.query_params.ps_low_degree, p.table_params.max_items_per_bin))) return 20;
-        std::printf("%s: n=%zu K=%d t=%llu depth=%u\n", argv[i], hp.n, hp.K, (unsigned long long)hp.t, dag.depth());
+        // the walks over it and the polynomial counts (powers_sched.h), with and without key switching: every slot a node names lies inside
+        // the schedule, every size inside the table
+        const uint32_t ps = p.query_params.ps_low_degree;
+        const PowersScheds sc = powers_scheds(dag, ps);
+        for (const PowersSched *s : { &sc.all, &sc.low, &sc.high }) {
+            const int P = (int)s->slot_power.size();
+            if (s != &sc.all && !sc.split_ok) { if (P) return 24; continue; }
+            for (const auto &nd : s->nodes) for (int slot : nd) if (slot < 0 || slot >= P) return 24;
+            for (const PowersSched::Level &lv : s->levels) if (lv.s0 < 0 || lv.s0 > lv.sp || lv.sp > lv.s1 || lv.s1 > P) return 24;
+            for (uint32_t pw : s->low_powers) if (s->slot_of.at(pw) < 0) return 24;
+            for (uint32_t pw : s->high_powers) if (s->slot_of.at(pw) < 0) return 24;
+        }
+        for (bool ks : { true, false }) {
+            const PowerSizes z = power_sizes(sc.all, ks, dag.depth());
+            const uint32_t rp = result_polys(z, ps, ks, p.table_params.max_items_per_bin);
+            if (z.size.size() != sc.all.slot_of.size() || z.stored < 2 || z.stored > CT_SIZE_MAX || rp < 2 || rp > CT_SIZE_MAX || (ks && rp != 2)) return 25;
+        }
+        std::printf("%s: n=%zu K=%d t=%llu depth=%u split=%d\n", argv[i], hp.n, hp.K, (unsigned long long)hp.t, dag.depth(), (int)sc.split_ok);
         // truncated / garbled JSON must throw, not crash
         const std::string js = ss.str();
         for (int r = 0; r < 300; r++) {

@@ -41,6 +41,25 @@ def test_family_header_spares_the_transform_emulation(header, units):
     assert "build/emu/ntt.o" not in got and "build/kernels_ntt.o" not in got, got
 
 
+def kernel_objects(got):
+    return {t for t in got if t.startswith("build/kernels_")}
+
+
+def test_evaluation_plan_spares_the_other_engine_units():
+    """the Engine is in units by section (engine_impl.h): the evaluation's plan is read by the evaluation, not by ComputePowers, the
+    querier's side or the paths without key switching"""
+    got = remade("eval_plan.h")
+    assert {"build/engine_eval.o", "build/kernels_behz.o", "build/emu/rules.o"} <= got, got
+    assert not {"build/engine_powers.o", "build/engine_query.o", "build/engine_nks.o"} & got, got
+    assert "build/kernels_ntt.o" not in got, got
+
+
+def test_powers_schedule_reaches_its_users_and_no_kernel():
+    got = remade("powers_sched.h")
+    assert {"build/engine.o", "build/engine_powers.o", "build/engine_nks.o", "build/emu/rules.o", EMU} <= got, got
+    assert not kernel_objects(got), got
+
+
 def test_transform_header_reaches_every_user():
     got = remade("ntt_core.h")
     assert {"build/kernels_ntt.o", "build/kernels_roots.o", EMU} <= got, got
