@@ -279,6 +279,7 @@ EngineSwitches read_switches()
     size("APSU_HE_EVAL_WS_BYTES", s.eval_ws_bytes);
     size("APSU_HE_ARENA_BYTES", s.arena_bytes);
     size("APSU_HE_NTT_LATENCY_LIMBS", s.ntt_latency_limbs);
+    size("APSU_HE_SEED_REJ_CAP", s.seed_rej_cap);
     return s;
 }
 

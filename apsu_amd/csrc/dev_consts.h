@@ -17,6 +17,7 @@ constexpr int EW_T = 256;           // threads per workgroup of the coefficient-
 constexpr int DMAXL = 8;            // limbs of q at a data level
 constexpr int DMAXB = DMAXL + 2;    // |Bsk|
 constexpr int DMAXE = DMAXL + DMAXB; // limbs of an extended (q u Bsk) polynomial
+constexpr u32 SEED_REJ_CAP = 8192;  // rejected positions per object that the seed expansion's fix-up pass can hold (kernels_ew.hip: k_seed_fix)
 
 struct ShoupConst { u64 w, wq; };
 
@@ -177,6 +178,8 @@ struct EngineSwitches {
     bool force_per_term = false;                 // APSU_HE_EVAL_PER_TERM=1    eval_patstock's products finished one by one (the fallback of the summed finish)
     int mac_kara = -1;                           // APSU_HE_MAC_KARA=0/1       three-product k_mac forced off / on (default: by chain length)
     bool seed_expand_host = false;               // APSU_HE_SEED_EXPAND_HOST=1 seeded objects expanded by the host codec (the fallback of the device sampler)
+    // (values outside 1 .. SEED_REJ_CAP are refused at create; the compiled list stride and LDS array stay SEED_REJ_CAP)
+    size_t seed_rej_cap = SEED_REJ_CAP;          // APSU_HE_SEED_REJ_CAP=n     rejected words per seeded object the device list takes before the host redoes the object (tests: the fallback at small sizes)
     bool fuse_tail = true;                       // APSU_HE_FUSE_TAIL=0        eval_patstock's last mod-down as its own launch instead of inside the epilogue kernel (round 6)
     // The latency form of the LDS-resident transform (ntt_core.h plan_k, c = 8): a limb's workgroup has twice the waves, so a launch
     // that gives a CU at most one limb hides that limb's LDS turnarounds and table loads behind three other waves per SIMD.

@@ -74,5 +74,14 @@ int emu_qs_pow_mod(uint64_t t, const uint64_t *x, const uint32_t *e, uint64_t *o
     for (int i = 0; i < count; i++) out[i] = qs_pow_mod(x[i], e[i], m);
     return 0;
 }
+// decrypt_round_coeff (the code k_decrypt_round and k_decrypt_round_budget run) on `count` values x < q0: out = round(t x / q0) mod t,
+// rem = (t x + floor(q0 / 2)) mod q0.  -1 for what the kernels' range argument does not cover (q0 >= 2^62, t >= 2^61, t < 2, t >= q0, x >= q0).
+int emu_qs_decrypt_round(uint64_t q0, uint64_t t, const uint64_t *x, uint64_t *out, uint64_t *rem, int count)
+{
+    if (q0 >> 62 || t >> 61 || t < 2 || t >= q0) return -1;
+    for (int i = 0; i < count; i++) if (x[i] >= q0) return -1;
+    for (int i = 0; i < count; i++) out[i] = decrypt_round_coeff(x[i], q0, t, rem[i]);
+    return 0;
+}
 
 } // extern "C"

@@ -153,13 +153,23 @@ int64_t emu_device_constants(const char *json, uint64_t n, const uint64_t *prime
 void emu_dev_layout(uint64_t *out) { out[0] = sizeof(NttTable); out[1] = sizeof(DevLevel); out[2] = sizeof(DevKey); out[3] = DMAXL; out[4] = DMAXB; }
 
 // read_switches() under the caller's environment: two_stream_default, eval_side, packed_rows, eval_ws_bytes, arena_bytes, force_per_term,
-// mac_kara, seed_expand_host, fuse_tail, ntt_latency_limbs (signed values as int64)
+// mac_kara, seed_expand_host, fuse_tail, ntt_latency_limbs (signed values as int64).  Ten values: callers size their buffer for ten, so a
+// switch added later gets an entry of its own below.
 void emu_switches(int64_t *out)
 {
     const EngineSwitches s = read_switches();
     const int64_t v[10] = { s.two_stream_default, s.eval_side, s.packed_rows, (int64_t)s.eval_ws_bytes, (int64_t)s.arena_bytes, s.force_per_term,
                             s.mac_kara, s.seed_expand_host, s.fuse_tail, (int64_t)s.ntt_latency_limbs };
     for (int i = 0; i < 10; i++) out[i] = v[i];
+}
+// the switches added since: out[0] = seed_rej_cap (APSU_HE_SEED_REJ_CAP as read; a context refuses a value outside 1 .. SEED_REJ_CAP).
+// Returns their number (the first `cap` are written).
+int emu_switches_more(int64_t *out, int cap)
+{
+    const EngineSwitches s = read_switches();
+    const int64_t v[1] = { (int64_t)s.seed_rej_cap };
+    for (int i = 0; i < 1 && i < cap; i++) out[i] = v[i];
+    return 1;
 }
 
 // PowersDag::configure on explicit sets; nodes: [power, depth, p1, p2] ascending by power

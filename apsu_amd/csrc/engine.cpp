@@ -40,6 +40,7 @@ int Powers::slot_of(uint32_t bundle_idx) const
 Engine::Engine(const HeParams &hp, const PSUParams *psu, int device) : hp_(hp), device_(device)
 {
     if (psu) { psu_ = *psu; has_psu_ = true; }
+    if (sw_.seed_rej_cap < 1 || sw_.seed_rej_cap > SEED_REJ_CAP) throw std::invalid_argument("APSU_HE_SEED_REJ_CAP outside 1 .. 8192");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0)

@@ -383,7 +383,10 @@ public:
                 // the transforms (engine_ntt_steps.cpp): the launchers of launch_ntt.h with a caller-given limb-to-modulus map
                 STEP_NTT_INFO, STEP_NTT, STEP_NTT_GATHER, STEP_INTT_TENSOR,
                 // behind the existing ids, which stay: k_roots_split (engine_db_steps.cpp)
-                STEP_ROOTS_SPLIT, STEP_COUNT };
+                STEP_ROOTS_SPLIT,
+                // the querier's side and the decryption (engine_query_steps.cpp): the launchers engine_query.cpp calls
+                STEP_SEED_EXPAND, STEP_DECRYPT_ROUND, STEP_PLAIN_POWERS, STEP_SAMPLE_SMALL, STEP_SMALL_LIFT, STEP_ENC_FINISH, STEP_RLK_FINISH,
+                STEP_FLAG_MONOMIAL, STEP_COUNT };
     enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32, STEP_INVERSE = 64, STEP_NORED = 128 };
     struct StepArgs {
         int step, chain_idx;
@@ -397,6 +400,7 @@ public:
     void debug_run_step(const StepArgs &a);
     void debug_run_db_step(const StepArgs &a);                    // its database half (the caller holds the lock)
     void debug_run_ntt_step(const StepArgs &a);                   // its transform half (the caller holds the lock)
+    void debug_run_query_step(const StepArgs &a);                 // its querier-side half (the caller holds the lock)
     // Staging of apsu_he_run_query_request (c_api.cpp) kept across calls: a device buffer and a page-locked host buffer of at least
     // `bytes` (grown on demand; hipHostMalloc / hipMalloc per query cost milliseconds).  The caller holds wire_mutex() for the whole query.
     std::mutex &wire_mutex() { return wire_mu_; }
@@ -624,6 +628,7 @@ private:
     // sampler (seed_expand's rule) and nothing was queued; seeds_overflowed() after the final sync tells whether the device lists sufficed
     bool queue_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst);
     bool seeds_overflowed(int count);
+    const DevLevel *seed_level(int L);                // the level block an expansion of L limbs reads: a data level's, or the key level's view (uploaded by the first use)
     void host_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst);
     void check_key_residues(const u64 *sk_ntt_host, int limbs) const;
     // seed expansion: rejection lists; the DevLevel-shaped view of the key level and max_multiple per key prime as build_device_constants

@@ -19,9 +19,11 @@ void Engine::seed_expand(int chain_idx, int count, const u64 *seeds, u64 *const 
     const int L = key_level ? hp_.K : chain_idx + 1;
     TIER1_SLOTS();
     job_seq_ = job_seq_base_;
-    // The device list holds 8192 rejected words per object.  The rejection rate is ~q / 2^64 per word, so ~60-bit primes with a large
-    // L * n may legitimately exceed it (and L may exceed the device tables): those objects are expanded by the host's
-    // sample_poly_uniform (seal_codec.cpp) and uploaded -- slower, same words.  APSU_HE_SEED_EXPAND_HOST=1 forces that path (tests).
+    // The device list holds SEED_REJ_CAP = 8192 rejected words per object (APSU_HE_SEED_REJ_CAP lowers it: tests).  A word is refused
+    // with probability (2^64 mod q) / 2^64: below 2^-27 for the primes 2^b - c a parameter file gives, up to ~q / 2^64 for a caller's own
+    // primes (apsu_he_create_raw), so a large L * n of those may exceed the list (and L may exceed the device tables): such objects are
+    // expanded by the host's sample_poly_uniform (seal_codec.cpp) and uploaded -- slower, same words.
+    // APSU_HE_SEED_EXPAND_HOST=1 forces that path (tests).
     bool on_device = queue_seed_expand(L, count, seeds, dst);
     if (on_device) {
         sync();
@@ -135,7 +137,8 @@ void Engine::decrypt_decode(const u64 *sk_ntt_host, const u64 *cts, bool on_devi
         if (values_host) D2H(values_host, vals, (size_t)count * n);
         if (values_dev) D2D(values_dev, vals, (size_t)count * n);
         sync();
-        // Decryptor::invariant_noise_budget: floor(log2(q_0 / (2 |t x mod q_0|))), the whole of q_0 for a noiseless result
+        // Decryptor::invariant_noise_budget: the largest b with worst 2^b < q_0, worst = max |t x mod q_0| centred, i.e.
+        // ceil(log2(q_0 / (2 worst))); the bit count of q_0 for a noiseless result (worst = 0)
         for (uint32_t i = 0; budget_bits && i < count; i++) {
             const unsigned __int128 q0 = hp_.key_q[0], w = worst_host[i];
             int bits = 0;
@@ -170,31 +173,36 @@ void Engine::host_seed_expand(int L, int count, const u64 *seeds, u64 *const *ds
     }
 }
 
-bool Engine::queue_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst)
+const DevLevel *Engine::seed_level(int L)
 {
-    if (L > DMAXL || sw_.seed_expand_host) return false;
     const bool key_view = L == hp_.K && !key_level_.empty();     // the key level is not a data level: its moduli-only view (engine.h)
     if (key_view && !d_key_level_.p()) {
         d_key_level_.alloc(sizeof(DevLevel));
         HIP_CHECK(hipMemcpy(d_key_level_.p(), key_level_.data(), sizeof(DevLevel), hipMemcpyHostToDevice));
     }
-    const DevLevel *lv = key_view ? reinterpret_cast<const DevLevel *>(d_key_level_.p()) : dlevel(L - 1);
+    return key_view ? reinterpret_cast<const DevLevel *>(d_key_level_.p()) : dlevel(L - 1);
+}
+
+bool Engine::queue_seed_expand(int L, int count, const u64 *seeds, u64 *const *dst)
+{
+    if (L > DMAXL || sw_.seed_expand_host) return false;
+    const DevLevel *lv = seed_level(L);
     const std::vector<u64> mm(max_multiple_.begin(), max_multiple_.begin() + L);
     std::vector<SeedJob> jobs(count);
     for (int i = 0; i < count; i++) {
         for (int k = 0; k < 8; k++) jobs[i].seed.w[k] = seeds[(size_t)i * 8 + k];
         jobs[i].dst = dst[i];
     }
-    const size_t need = ((size_t)count * (1 + 8192) + 1) * sizeof(u32);
+    const size_t need = ((size_t)count * (1 + SEED_REJ_CAP) + 1) * sizeof(u32);
     if (d_seed_rej_.bytes() < need) {
         sync();
         d_seed_rej_.alloc(need * 2);
         HIP_CHECK(hipMemsetAsync(d_seed_rej_.p(), 0, d_seed_rej_.bytes(), st_));
     }
     u32 *rej = reinterpret_cast<u32 *>(d_seed_rej_.p());
-    int *overflow = reinterpret_cast<int *>(rej + (size_t)count * (1 + 8192));
+    int *overflow = reinterpret_cast<int *>(rej + (size_t)count * (1 + SEED_REJ_CAP));
     HIP_CHECK(hipMemsetAsync(overflow, 0, sizeof(int), st_));
-    { PROF(P_OTHER, 0); launch_seed_expand(upload_jobs(jobs), count, lv, L, upload_jobs(mm), hp_.n, rej, overflow, st_); }
+    { PROF(P_OTHER, 0); launch_seed_expand(upload_jobs(jobs), count, lv, L, upload_jobs(mm), hp_.n, rej, (u32)sw_.seed_rej_cap, overflow, st_); }
     return true;
 }
 
@@ -202,7 +210,7 @@ bool Engine::queue_seed_expand(int L, int count, const u64 *seeds, u64 *const *d
 bool Engine::seeds_overflowed(int count)
 {
     int h = 0;
-    HIP_CHECK(hipMemcpy(&h, reinterpret_cast<u32 *>(d_seed_rej_.p()) + (size_t)count * (1 + 8192), sizeof(int), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&h, reinterpret_cast<u32 *>(d_seed_rej_.p()) + (size_t)count * (1 + SEED_REJ_CAP), sizeof(int), hipMemcpyDeviceToHost));
     if (h) {
         HIP_CHECK(hipMemsetAsync(d_seed_rej_.p(), 0, d_seed_rej_.bytes(), st_));
         sync();

@@ -33,6 +33,7 @@ void Engine::debug_run_step(const StepArgs &a)
 {
     Enter g(this);
     TIER1_SLOTS();
+    if (a.step >= STEP_SEED_EXPAND) { debug_run_query_step(a); return; }      // the querier's side and the decryption
     if (a.step == STEP_ROOTS_SPLIT) { debug_run_db_step(a); return; }         // (a database step numbered behind the transforms)
     if (a.step >= STEP_NTT_INFO) { debug_run_ntt_step(a); return; }          // the transforms: a map of the caller's, no chain level
     if (a.step >= STEP_POLYN_WITH_ROOTS) { debug_run_db_step(a); return; }   // the mod-t kernels of a resident database: no chain level

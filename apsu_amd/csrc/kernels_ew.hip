@@ -309,9 +309,9 @@ void launch_fill_blake2xb(u64 *out, size_t words, const Blake2xbSeed &seed, u64 
 // Pass 2 (k_seed_fix, one wave per ciphertext): the rejected positions are put in stream order (rank sort in LDS) and
 // replaced one after the other by fresh draws that continue behind the bulk fill, exactly in SEAL's order; the wave
 // generates 64 stream blocks at a time, every lane follows the same (uniform) control flow and lane 0 writes.
-constexpr u32 SEED_REJ_CAP = 8192;                                // rejected positions per ciphertext the fix-up can hold
+// cap (1 .. SEED_REJ_CAP, dev_consts.h): the positions an object's list takes; the list stride and the LDS array stay as compiled.
 __global__ __launch_bounds__(EW_T) void k_seed_bulk(const SeedJob *__restrict__ jobs, const DevLevel *__restrict__ lv, const u64 *__restrict__ max_multiple,
-                                                    size_t n, u32 *__restrict__ rej)
+                                                    size_t n, u32 *__restrict__ rej, u32 cap)
 {
     const u64 sb = (u64)blockIdx.x * EW_T + threadIdx.x;
     const int L = lv->L;
@@ -326,13 +326,13 @@ __global__ __launch_bounds__(EW_T) void k_seed_bulk(const SeedJob *__restrict__ 
         const int j = (int)(w / n);
         if (blk[i] >= max_multiple[j]) {
             const u32 slot = atomicAdd(list, 1u);
-            if (slot < SEED_REJ_CAP) list[1 + slot] = (u32)w;
+            if (slot < cap) list[1 + slot] = (u32)w;
         } else job.dst[w] = barrett64(blk[i], lv->q[j]);
     }
 }
 
 __global__ __launch_bounds__(64) void k_seed_fix(const SeedJob *__restrict__ jobs, const DevLevel *__restrict__ lv, const u64 *__restrict__ max_multiple,
-                                                 size_t n, u32 *__restrict__ rej, int *__restrict__ overflow)
+                                                 size_t n, u32 *__restrict__ rej, u32 cap, int *__restrict__ overflow)
 {
     __shared__ u32 sorted[SEED_REJ_CAP];
     __shared__ u64 cache[64 * 8];
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(64) void k_seed_fix(const SeedJob *__restrict__ job
     u32 *list = rej + (size_t)blockIdx.x * (1 + SEED_REJ_CAP);
     const u32 cnt = list[0];
     const u32 lane = threadIdx.x;
-    if (cnt > SEED_REJ_CAP) { if (lane == 0) *overflow = 1; return; }
+    if (cnt > cap) { if (lane == 0) *overflow = 1; return; }
     for (u32 e = lane; e < cnt; e += 64) {                        // rank sort (positions are distinct)
         const u32 v = list[1 + e];
         u32 rank = 0;
@@ -374,36 +374,19 @@ __global__ __launch_bounds__(64) void k_seed_fix(const SeedJob *__restrict__ job
     if (lane == 0) list[0] = 0;                                   // ready for the next use of this list
 }
 
-void launch_seed_expand(const SeedJob *jobs, int njobs, const DevLevel *lv, int L, const u64 *max_multiple, size_t n, u32 *rej, int *overflow,
+void launch_seed_expand(const SeedJob *jobs, int njobs, const DevLevel *lv, int L, const u64 *max_multiple, size_t n, u32 *rej, u32 cap, int *overflow,
                         hipStream_t st)
 {
     if (!njobs) return;
     const u64 blocks = ((u64)L * n + 7) / 8;
-    hipLaunchKernelGGL(k_seed_bulk, dim3((unsigned)((blocks + EW_T - 1) / EW_T), (unsigned)njobs), dim3(EW_T), 0, st, jobs, lv, max_multiple, n, rej);
-    hipLaunchKernelGGL(k_seed_fix, dim3((unsigned)njobs), dim3(64), 0, st, jobs, lv, max_multiple, n, rej, overflow);
+    hipLaunchKernelGGL(k_seed_bulk, dim3((unsigned)((blocks + EW_T - 1) / EW_T), (unsigned)njobs), dim3(EW_T), 0, st, jobs, lv, max_multiple, n, rej, cap);
+    hipLaunchKernelGGL(k_seed_fix, dim3((unsigned)njobs), dim3(64), 0, st, jobs, lv, max_multiple, n, rej, cap, overflow);
     KERNEL_CHECK();
 }
 
 // N4: the querier's decryption of a result at the last level (result_package.cpp:175-213, Decryptor::decrypt):
 // x = c0 + v (v = INTT(NTT(c1) . s), one limb q0), m = round(t x / q0) mod t.
-// rem receives (t x + floor(q0 / 2)) mod q0
-__device__ __forceinline__ u64 decrypt_round_coeff(u64 x, u64 q0, u64 t, u64 &rem)
-{
-    u128p num = mul128(x, t);
-    add128(num, u128p{ q0 >> 1, 0 });
-    // floor(num / q0) mod t by restoring division, the quotient folded mod t on the fly (num < 2^124)
-    u64 quo = 0;
-    rem = 0;
-    for (int i = 127; i >= 0; i--) {
-        const u64 bit = i >= 64 ? (num.hi >> (i - 64)) & 1 : (num.lo >> i) & 1;
-        rem = (rem << 1) | bit;                                   // rem < q0 < 2^62 before the shift
-        quo <<= 1;                                                // quo < t < 2^61
-        if (rem >= q0) { rem -= q0; quo |= 1; }
-        if (quo >= t) quo -= t;
-    }
-    return quo;
-}
-
+// (decrypt_round_coeff: query_side.h)
 __global__ __launch_bounds__(EW_T) void k_decrypt_round(const u64 *__restrict__ ct, size_t ct_stride, const u64 *__restrict__ v,
                                                         u64 q0, u64 t, u64 *__restrict__ out, size_t n)
 {
@@ -416,7 +399,8 @@ __global__ __launch_bounds__(EW_T) void k_decrypt_round(const u64 *__restrict__ 
 }
 
 // The same with SEAL's invariant noise budget (result_package.cpp:175-213, Decryptor::invariant_noise_budget): worst[b] = the
-// largest centred |t x mod q0| over ciphertext b's coefficients; budget = floor(log2(q0 / (2 worst))) is formed on the host.
+// largest centred |t x mod q0| over ciphertext b's coefficients; the budget -- the largest b with worst 2^b < q0, i.e.
+// ceil(log2(q0 / (2 worst))), and the bit count of q0 for worst = 0 -- is formed on the host.
 // Wave maximum, then the workgroup's four waves through LDS and one atomic per workgroup.
 __global__ __launch_bounds__(EW_T) void k_decrypt_round_budget(const u64 *__restrict__ ct, size_t ct_stride, const u64 *__restrict__ v,
                                                                u64 q0, u64 t, u64 *__restrict__ out, size_t n, unsigned long long *__restrict__ worst)

@@ -42,10 +42,13 @@ void launch_fill_random(u64 *out, size_t words, u64 seed, u64 bound, hipStream_t
 // out[i] = (the (first + i)-th 32-bit output of SEAL's Blake2xb generator under `seed`) % bound
 void launch_fill_blake2xb(u64 *out, size_t words, const Blake2xbSeed &seed, u64 first, u64 bound, hipStream_t st);
 // N3: c1 of seeded ciphertexts / keys = util::sample_poly_uniform under SEAL's Blake2xb generator (seal_codec.h), dst[L][n] at level lv.
-// rej: [njobs][1 + 8192] u32, zeroed once (the kernels leave the counters at zero); *overflow is set when a ciphertext has more
-// rejected words than the list holds (a modulus within a factor 3 of 2^64: not a SEAL modulus).
+// rej: [njobs][1 + SEED_REJ_CAP] u32, zeroed once (the kernels leave the counter of every object they complete at zero); *overflow is
+// set when an object has more than `cap` rejected words: that object is left incomplete with its counter standing, the others are
+// complete.  A word is refused with probability (2^64 mod q) / 2^64: below 2^-27 for SEAL's primes 2^b - c, up to ~q / 2^64 otherwise.
+// contract: 1 <= cap <= SEED_REJ_CAP; every max_multiple[j] well above 0 -- the fix-up redraws until a word falls below it (SEAL's
+// own value exceeds 2^63 for q < 2^62); n a multiple of 8
 struct SeedJob { Blake2xbSeed seed; u64 *dst; };
-void launch_seed_expand(const SeedJob *jobs, int njobs, const DevLevel *lv, int L, const u64 *max_multiple, size_t n, u32 *rej, int *overflow,
+void launch_seed_expand(const SeedJob *jobs, int njobs, const DevLevel *lv, int L, const u64 *max_multiple, size_t n, u32 *rej, u32 cap, int *overflow,
                         hipStream_t st);
 // N4: the rounding step of the querier's decryption
 void launch_decrypt_round(const u64 *ct, size_t ct_stride, const u64 *v, u64 q0, u64 t, u64 *out, size_t n, int batch, hipStream_t st);

@@ -47,4 +47,23 @@ HD u64 qs_pow_mod(u64 x, u32 e, const Mod &t)
     return r;
 }
 
+// The rounding of the querier's decryption (k_decrypt_round, k_decrypt_round_budget): round(t x / q0) mod t for x < q0 < 2^62,
+// 2 <= t < 2^61; rem receives (t x + floor(q0 / 2)) mod q0
+HD u64 decrypt_round_coeff(u64 x, u64 q0, u64 t, u64 &rem)
+{
+    u128p num = mul128(x, t);
+    add128(num, u128p{ q0 >> 1, 0 });
+    // floor(num / q0) mod t by restoring division, the quotient folded mod t on the fly (num < 2^124)
+    u64 quo = 0;
+    rem = 0;
+    for (int i = 127; i >= 0; i--) {
+        const u64 bit = i >= 64 ? (num.hi >> (i - 64)) & 1 : (num.lo >> i) & 1;
+        rem = (rem << 1) | bit;                                   // rem < q0 < 2^62 before the shift
+        quo <<= 1;                                                // quo < t < 2^61
+        if (rem >= q0) { rem -= q0; quo |= 1; }
+        if (quo >= t) quo -= t;
+    }
+    return quo;
+}
+
 } // namespace apsu_he

@@ -349,7 +349,37 @@ int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_
  * Refused like the others, nothing launched: a modulus id out of range; MAP_RAW in a forward map; NORED at n = 32768, with a target
  * for which max_src + 4 log2(n) q exceeds 2^64 or which is not narrow, or with a source word at or above max_src; a word that is not
  * canonical where canonical is asked; the three outputs of one operand limb under different moduli; INTT_TENSOR at n = 32768; sizes
- * that do not match (at most 4096 limbs per launch). */
+ * that do not match (at most 4096 limbs per launch).
+ *
+ * The querier's side and the decryption, from SEED_EXPAND on (same entry, no new symbol): the launchers behind apsu_he_seed_expand,
+ * apsu_he_keygen, apsu_he_relin_keygen, apsu_he_query_create and apsu_he_decrypt_decode, with the context's own level and key blocks
+ * and its slot map.  `batch` is 1 .. 64.  A signed byte (the small polynomials) travels as one sign-extended 64-bit word.  out[0] is
+ * in/out everywhere: a word the kernel does not write comes back as it went.
+ *   SEED_EXPAND     chain_idx = the level (-1 or K - 1: the key level, L = K), terms = the list cap (1 .. 8192: the rejected positions an
+ *                   object's list takes); in[0] seeds [batch][8], in[1] thresholds [L]: a word at or above its limb's threshold is
+ *                   rejected (in place of SEAL's max_multiple) -> out[0] [batch][L][n]; out[1] [batch + 1]: every list's counter as the
+ *                   fix-up pass left it (0 for a completed object, its number of rejected words for one that overflowed), then the
+ *                   overflow word (1 when some object rejected more words than the cap; that object is incomplete, the others complete).
+ *                   The lists are fresh for every call.
+ *   DECRYPT_ROUND   in[0] ct [batch][2][n] (c0 is read, at stride 2 n), in[1] v [batch][n], in[2] q0, t (the launcher's arguments, need not
+ *                   be the context's) -> out[0] [batch][n] = round(t (c0 + v mod q0) / q0) mod t.  ACCUMULATE: the launcher with the noise
+ *                   budget's numerator, out[1] worst [batch] = max over the coefficients of min(r, q0 - r), r = t (c0 + v) mod q0
+ *   PLAIN_POWERS    in[0] values [batch][n] (any words), in[1] exponents [S] (32 bits each, S = 1 .. 64) -> out[0] [batch * S][n]:
+ *                   row b S + s holds values[b][i]^exponents[s] mod t at the slot BatchEncoder gives index i; a value >= t counts as 0
+ *                   and raises bit 0 of the flag word out[1] [1]
+ *   SAMPLE_SMALL    in[0] seed [8] -> out[0] [n] the secret's coefficients (batch 1, e0 0); KEY: out[0] [batch][n] the noise polynomials
+ *                   of objects e0 .. e0 + batch - 1 (N5's stream layout, below)
+ *   SMALL_LIFT      polys = limbs (1 .. K); in[0] small [batch][n] signed bytes -> out[0] [batch][limbs][n] residues of the key primes
+ *   ENC_FINISH      chain_idx = the level; in[0] pt [batch][n] mod t, in[1] v [batch][L][n], in[2] e [batch][n] signed bytes; out[0] cts
+ *                   [batch][2][L][n]: c0 = Delta(pt) - e - v per limb is written, the c1 halves are left alone
+ *   RLK_FINISH      (batch 1) in[0] s [K][n], in[1] e [K - 1][K][n]; out[0] ksk [K - 1][2][K][n]: ksk[i][0][j] = -(ksk[i][1][j] s_j + e[i][j])
+ *                   + [j == i] (p mod q_i) s_i^2 is written, the halves ksk[i][1] are read and left alone
+ *   FLAG_MONOMIAL   in[0] pt [batch][n] (any words) -> out[0] [batch]: 1 where exactly one word is non-zero, else 0
+ * Refused like the others, nothing launched: a list cap outside 1 .. 8192; a threshold below 2^62 (the fix-up redraws until a word
+ * falls below its threshold: a small one would not end; every real one exceeds 2^63); for DECRYPT_ROUND t >= q0, q0 >= 2^62,
+ * t >= 2^61, t < 2, a word of c0 or v that is not below q0; an exponent above 32 bits; PLAIN_POWERS without batching; a word that is
+ * no sign-extended signed byte; a word of pt, v, s, e or an a half that is not canonical; RLK_FINISH in a context with one prime;
+ * objects beyond the seed's range; sizes that do not match. */
 enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEHZ_EXT, APSU_HE_STEP_TENSOR, APSU_HE_STEP_TENSOR_CONV,
        APSU_HE_STEP_TENSOR_SUM, APSU_HE_STEP_BEHZ_FINISH, APSU_HE_STEP_BEHZ_FINISH_SUM, APSU_HE_STEP_KS_INNER, APSU_HE_STEP_KS_MODDOWN,
        APSU_HE_STEP_MODSWITCH, APSU_HE_STEP_MODSWITCH_JOBS, APSU_HE_STEP_I0_FINISH, APSU_HE_STEP_EVAL_EPILOGUE, APSU_HE_STEP_ADD_MANY,
@@ -357,7 +387,9 @@ enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEH
        APSU_HE_STEP_POLYN_WITH_ROOTS, APSU_HE_STEP_BINS_UPDATE, APSU_HE_STEP_BIN_COUNTS, APSU_HE_STEP_POLY_DEGREE, APSU_HE_STEP_BINS_LOOKUP,
        APSU_HE_STEP_BINS_MERGE, APSU_HE_STEP_BINS_ROWS, APSU_HE_STEP_BINS_EVAL, APSU_HE_STEP_EVAL_COMPARE, APSU_HE_STEP_ROOTS, APSU_HE_STEP_UNLIFT,
        APSU_HE_STEP_NTT_INFO, APSU_HE_STEP_NTT, APSU_HE_STEP_NTT_GATHER, APSU_HE_STEP_INTT_TENSOR,
-       APSU_HE_STEP_ROOTS_SPLIT };
+       APSU_HE_STEP_ROOTS_SPLIT,
+       APSU_HE_STEP_SEED_EXPAND, APSU_HE_STEP_DECRYPT_ROUND, APSU_HE_STEP_PLAIN_POWERS, APSU_HE_STEP_SAMPLE_SMALL, APSU_HE_STEP_SMALL_LIFT,
+       APSU_HE_STEP_ENC_FINISH, APSU_HE_STEP_RLK_FINISH, APSU_HE_STEP_FLAG_MONOMIAL };
 enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8, APSU_HE_STEP_PLAN = 16,
        APSU_HE_STEP_COMPOSED = 32, APSU_HE_STEP_INVERSE = 64, APSU_HE_STEP_NORED = 128 };
 #define APSU_HE_STEP_MAP_RAW ((uint64_t)1 << 30)   /* in a map entry of an inverse transform */

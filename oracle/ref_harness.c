@@ -151,7 +151,8 @@ int ref_decrypt(const ref_ctx *c, const uint64_t *sk, const uint64_t *ct, int po
     for (size_t k = 0; k < n; k++) {
         u128 num = (u128)ph[k] * t;
         uint64_t m = (uint64_t)((num + (q0 >> 1)) / q0);
-        /* invariant noise ~ |t*x - m*q0| / q0 ; budget = log2(q0 / (2 * |t x mod q0|_centred)) */
+        /* invariant noise ~ |t*x - m*q0| / q0 ; worst = the largest |t x mod q0|_centred; the budget formed below is the largest b
+         * with worst * 2^b < q0, i.e. ceil(log2(q0 / (2 * worst))), and the bit count of q0 for worst = 0 */
         u128 rem = num % q0;
         u128 dist = rem > (q0 >> 1) ? (u128)q0 - rem : rem;
         if (dist > worst) worst = dist;

@@ -26,7 +26,8 @@ def remade(header):
 
 
 @pytest.mark.parametrize("header, unit", [("bin_merge.h", "kernels_db.o"), ("bin_update.h", "kernels_db.o"),
-                                          ("mac_core.h", "kernels_mac.o"), ("query_side.h", "kernels_ew.o")])
+                                          ("mac_core.h", "kernels_mac.o"), ("query_side.h", "kernels_ew.o"),
+                                          ("query_side.h", "engine_query_steps.o"), ("query_side.h", "emu/query.o")])
 def test_family_header_spares_the_transforms(header, unit):
     got = remade(header)
     assert "build/" + unit in got, got
@@ -50,7 +51,7 @@ def test_evaluation_plan_spares_the_other_engine_units():
     querier's side or the paths without key switching"""
     got = remade("eval_plan.h")
     assert {"build/engine_eval.o", "build/kernels_behz.o", "build/emu/rules.o"} <= got, got
-    assert not {"build/engine_powers.o", "build/engine_query.o", "build/engine_nks.o"} & got, got
+    assert not {"build/engine_powers.o", "build/engine_query.o", "build/engine_query_steps.o", "build/engine_nks.o"} & got, got
     assert "build/kernels_ntt.o" not in got, got
 
 

@@ -404,6 +404,48 @@ print(json.dumps(res))
 """
 
 
+# a switch added after the ten above is read through emu_switches_more (emu_switches keeps writing ten values)
+MORE_FIELDS = ["seed_rej_cap"]
+MORE_DEFAULTS = dict(seed_rej_cap=8192)
+# (read as written; a context refuses a value outside 1 .. 8192 at create: tests/test_gpu_query_steps.py)
+MORE_SWITCHES = {"APSU_HE_SEED_REJ_CAP": ("seed_rej_cap", {"1": 1, "16": 16, "8192": 8192, "0": 0, "8193": 8193, "": 0})}
+CHILD_MORE = """
+import ctypes, json, os, sys
+sys.path.insert(0, sys.argv[1])
+import emu_lib
+lib = emu_lib.load()
+name, values = sys.argv[2], json.loads(sys.argv[3])
+out, ten = (ctypes.c_int64 * 4)(), (ctypes.c_int64 * 10)()
+res = {}
+for v in ([None] if not name else values):
+    if v is not None:
+        os.environ[name] = v
+    k = lib.emu_switches_more(out, 4)
+    lib.emu_switches(ten)
+    res[str(v)] = [list(out)[:k], list(ten)]
+print(json.dumps(res))
+"""
+
+
+def test_switches_added_later(emu):
+    """APSU_HE_SEED_REJ_CAP: its default, every documented value, and that it moves none of the ten older switches"""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("APSU_HE_")}
+
+    def read(name, values):
+        r = subprocess.run([sys.executable, "-c", CHILD_MORE, os.path.join(ROOT, "tests"), name, json.dumps(values)], capture_output=True, text=True, env=env, timeout=60)
+        assert r.returncode == 0, r.stderr
+        return json.loads(r.stdout)
+
+    more, ten = read("", [])["None"]
+    assert dict(zip(MORE_FIELDS, more)) == MORE_DEFAULTS and len(more) == len(MORE_FIELDS)
+    assert dict(zip(SWITCH_FIELDS, ten)) == SWITCH_DEFAULTS
+    for name, (field, values) in MORE_SWITCHES.items():
+        got = read(name, list(values))
+        for v, want in values.items():
+            assert dict(zip(MORE_FIELDS, got[v][0])) == dict(MORE_DEFAULTS, **{field: want}), (name, v)
+            assert dict(zip(SWITCH_FIELDS, got[v][1])) == SWITCH_DEFAULTS, (name, v)
+
+
 def read_in_child(name, values):
     env = {k: v for k, v in os.environ.items() if not k.startswith("APSU_HE_")}
     r = subprocess.run([sys.executable, "-c", CHILD, os.path.join(ROOT, "tests"), name, json.dumps(values)], capture_output=True, text=True, env=env, timeout=60)

@@ -36,7 +36,7 @@ def test_return_types_cover_every_export():
     src = defined_in_sources()
     out = subprocess.run(["nm", "-D", "--defined-only", emu_lib.SO], check=True, capture_output=True, text=True).stdout
     exported = set(re.findall(r" T (emu_\w+)$", out, re.M))
-    assert set(src) == exported and len(exported) == 85, sorted(set(src) ^ exported)
+    assert set(src) == exported and len(exported) == 87, sorted(set(src) ^ exported)
     assert all(ret == "int" or ret in CTYPE for ret in src.values()), sorted(set(src.values()))
     assert {n: CTYPE[ret] for n, ret in src.items() if ret != "int"} == emu_lib.RESTYPES
     for name, restype in emu_lib.RESTYPES.items():

@@ -28,6 +28,8 @@ def params(name):
         return common.toy_json(ps_low=0, max_items=6, query_powers=(1, 2, 3, 5))
     if name == "n32768":
         return common.toy_json(n=32768, coeff_bits=(56, 56, 56, 50), plain_bits=20, ps_low=2, max_items=8, query_powers=(1, 3), felts=5)
+    if name == "n1024-60":
+        return common.toy_json(n=1024, coeff_bits=(60, 60, 60, 50), plain_bits=17)
     if name == "single-prime":
         return common.toy_json(n=64, coeff_bits=(60,), plain_bits=9, felts=10, ps_low=0, max_items=4)
     return common.param_json(name)
@@ -255,6 +257,51 @@ def test_seed_expansion_waiting_and_queued_agree_at_the_key_level(monkeypatch):
         words.append(waited)
         G.close()
     assert (words[0] == words[1]).all()
+
+
+@pytest.mark.parametrize("which", ["cap 16", "median"])
+def test_overflowing_seed_lists_give_the_words_of_a_context_without_the_switch(monkeypatch, which):
+    """relin_keygen queues the expansion of its public halves and runs the rest of its work behind it; when an object has refused more
+    words than its device list holds, the host redoes every object and the rest runs a second time.  Driven at a small size by
+    APSU_HE_SEED_REJ_CAP with primes that refuse one word in 17 (query_step_model.high_rejection_primes): about 240 per key at
+    n = 1024.  With a cap of 16 every key overflows, with the median of the keys' counts (the model's) one does.  Every word must be
+    what a context without the switch returns, and the same call again must be exact too: the lists were left clean.
+
+    query_create has the same fallback, but no context can take it: it needs a parameter file, a parameter file gives SEAL's primes
+    2^b - c, and those refuse 2^(64 - b) c words in 2^64 -- the objects of the 60-bit set below refuse none, so there the switch must
+    change nothing."""
+    import query_step_model as QS
+    n, t = 1024, 120833
+    q = QS.high_rejection_primes(n, 4)
+    plain = apsu_amd.HeContext(n=n, coeff_modulus=q, plain_modulus=t)
+    sk = plain.keygen(SEED)
+    ksk0, kseeds0 = plain.relin_keygen(sk, SEED, want_resident=False)[:2]
+    plain.close()
+    assert all((kseeds0[i] == M.public_seed(SEED, i)).all() for i in range(3))
+    counts = [QS.rejection_count(sd, q, n) for sd in kseeds0]
+    cap = 16 if which == "cap 16" else sorted(counts)[1]
+    over = [c > cap for c in counts]
+    assert min(counts) > 150 and any(over) and (which == "cap 16") == all(over), (counts, cap)
+    monkeypatch.setenv("APSU_HE_SEED_REJ_CAP", str(cap))
+    G = apsu_amd.HeContext(n=n, coeff_modulus=q, plain_modulus=t)
+    assert (G.keygen(SEED) == sk).all()
+    for _ in range(2):
+        ksk, kseeds = G.relin_keygen(sk, SEED, want_resident=False)[:2]
+        assert (kseeds == kseeds0).all() and (ksk == ksk0).all()
+    G.close()
+    # the 60-bit set of a parameter file: nothing is refused, with or without the switch
+    monkeypatch.delenv("APSU_HE_SEED_REJ_CAP")
+    base = Side("n1024-60")
+    sk = base.G.keygen(SEED)
+    idx, x = [1, 0], base.slot_values(2)
+    cts0, seeds0, _ = base.query(sk, idx, x)
+    assert [QS.rejection_count(sd, [int(v) for v in base.C.q[:base.L]], base.n) for sd in seeds0] == [0] * len(seeds0)
+    base.close()
+    monkeypatch.setenv("APSU_HE_SEED_REJ_CAP", "1")
+    sd = Side("n1024-60")
+    cts, seeds, _ = sd.query(sk, idx, x)
+    assert (seeds == seeds0).all() and (cts == cts0).all()
+    sd.close()
 
 
 # ---- 5 + 6: the loop closes without the oracle as producer, and over the wire

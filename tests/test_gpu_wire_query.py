@@ -160,7 +160,8 @@ def test_framed_seeded_query_runs_through_the_engine(compr):
 def test_seed_expansion_on_the_device_equals_the_host_codec(monkeypatch, bits, force_host):
     """apsu_he_seed_expand (k_seed_bulk + k_seed_fix: SEAL's sample_poly_uniform with its in-stream rejection sampling) against
     the host codec's expansion (itself held against the Python model in tests/test_seal_codec.py): data levels and the key
-    level, several ciphertexts per call, 60-bit primes for hundreds of rejections per limb.  Last case: the engine's own fallback
+    level, several ciphertexts per call, primes of 36 to 60 bits (SEAL's primes refuse next to nothing: the rejections themselves are
+    driven by tests/test_gpu_query_steps.py and the overflow test below).  Last case: the engine's own fallback
     for objects whose rejections overflow the device list -- expansion by the host codec, uploaded -- forced for every object
     (APSU_HE_SEED_EXPAND_HOST=1, read at apsu_he_create)"""
     import torch
@@ -185,6 +186,48 @@ def test_seed_expansion_on_the_device_equals_the_host_codec(monkeypatch, bits, f
         for _ in range(2):                                      # the rejection lists are left clean for the next call
             G.seed_expand(chain_idx, seeds[:2], [out.data_ptr() + i * L * n * 8 for i in range(2)])
         assert (out.cpu().numpy().view(np.uint64)[:2] == got[:2]).all()
+    G.close()
+    sc.close()
+
+
+@pytest.mark.parametrize("chain_idx", [-1, 2])
+@pytest.mark.parametrize("which", ["cap 16", "median"])
+def test_seed_expansion_overflow_falls_back_to_the_host_codec(monkeypatch, which, chain_idx):
+    """The engine's real fallback, driven at a small size by APSU_HE_SEED_REJ_CAP (read at apsu_he_create).  The primes are chosen to
+    refuse one word in 17 (query_step_model.high_rejection_primes; the primes a parameter file gives refuse fewer than one in 2^27):
+    about 60 words per limb at n = 1024.  With a cap of 16 every object overflows its list; with the median of the objects' counts (the
+    model's) some do and some do not.  Either way the call must give the host codec's words, the call after it too, and a call of only
+    the objects that fit -- which stays on the device -- must find the lists clean."""
+    import torch
+    import query_step_model as QS
+    n = 1024
+    q = QS.high_rejection_primes(n, 4)
+    t = 120833                                                       # the 17-bit batching prime of this ring
+    L = len(q) if chain_idx < 0 else chain_idx + 1
+    seeds = [QS.seed_of("overflow-%d" % i) for i in range(8)]
+    counts = [QS.rejection_count(sd, q[:L], n) for sd in seeds]
+    assert min(counts) > 150
+    cap = 16 if which == "cap 16" else sorted(counts[:5])[2]
+    over = [c > cap for c in counts]
+    assert any(over[:5]) and (which == "cap 16") == all(over) and (which == "cap 16" or sum(over[:5]) == 2), counts
+    monkeypatch.setenv("APSU_HE_SEED_REJ_CAP", str(cap))
+    G = apsu_amd.HeContext(n=n, coeff_modulus=q, plain_modulus=t)
+    sc = seal.SealContext(n=n, coeff_modulus=q, plain_modulus=t)
+    assert G.q == q and G.first_chain_idx == 2
+
+    def expand_and_check(some):
+        out = torch.full((len(some), L, n), -1, dtype=torch.int64, device="cuda")
+        G.seed_expand(chain_idx, np.array(some, dtype=np.uint64), [out.data_ptr() + i * L * n * 8 for i in range(len(some))])
+        got = out.cpu().numpy().view(np.uint64)
+        for i, sd in enumerate(some):
+            assert (got[i] == sc.sample_poly_uniform(chain_idx, sd, L, n)).all(), (which, chain_idx, i)
+
+    expand_and_check(seeds[:5])
+    expand_and_check(seeds[5:])                                      # the call after the overflowing one
+    fit = [sd for sd, o in zip(seeds, over) if not o]
+    if fit:
+        expand_and_check(fit[::-1])                                  # no overflow this time: the device's words, from lists left clean
+    expand_and_check(seeds[:5])
     G.close()
     sc.close()
 

@@ -15,7 +15,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import apsu_amd
 from apsu_amd import seal
-from oracle.blake2x import blake2xb
+from query_step_model import prng_words, sample_poly_uniform
 
 N = 64
 Q = [0xffffffffc001, 0xffffee001, 0x1ffc001]     # 48, 36, 25 bits: three key-level primes (1M-1024-com's)
@@ -113,38 +113,7 @@ def parms_id(n, q, t):
     return list(struct.unpack("<4Q", d))
 
 
-def prng_words(seed):
-    """SEAL's Blake2xb generator as a stream of 64-bit words"""
-    key = struct.pack("<8Q", *seed)
-    counter = 0
-    while True:
-        buf = blake2xb(4096, struct.pack("<Q", counter), key)
-        counter += 1
-        yield from struct.unpack("<512Q", buf)
-
-
-def shake_words(seed):
-    """SEAL's Shake256 generator [SEAL-recall]: 4096-byte buffer k = SHAKE256(seed || k as u64), python's hashlib as the pin of SHAKE256"""
-    key = struct.pack("<8Q", *seed)
-    counter = 0
-    while True:
-        buf = hashlib.shake_256(key + struct.pack("<Q", counter)).digest(4096)
-        counter += 1
-        yield from struct.unpack("<512Q", buf)
-
-
-def sample_poly_uniform(seed, q, n, shake=False):
-    g = shake_words(seed) if shake else prng_words(seed)
-    L = len(q)
-    out = np.array([next(g) for _ in range(L * n)], dtype=object).reshape(L, n)
-    for j, qj in enumerate(q):
-        max_multiple = (2**64 - 1) - ((2**64 - 1) % qj) - 1
-        for k in range(n):
-            r = out[j, k]
-            while r >= max_multiple:
-                r = next(g)
-            out[j, k] = r % qj
-    return out.astype(np.uint64)
+# (the generators as streams of 64-bit words and sample_poly_uniform: query_step_model.py, shared with the seed-expansion step's tests)
 
 
 @pytest.fixture(scope="module")
