@@ -59,8 +59,9 @@ int emu_term_product(int nl, const uint64_t *q, const uint32_t *shift, const uin
     return guarded([&]() -> int {
         const DevLevel lv = mac_level(nl, q, shift, chunk, chunk_k, bits, n);
         const TermJob *tj = static_cast<const TermJob *>(jobs);
-        const size_t lanes = (n / 2 + EW_T - 1) / EW_T * EW_T;                   // launch_term_product's grid
-        for (size_t u = 0; u < njobs; u++)
+        const size_t lanes = (n / 2 + EW_T - 1) / EW_T * EW_T;                   // launch_term_product's grid: x, and the jobs over y and z --
+        const size_t gy = njobs < 32768 ? njobs : 32768, gz = gy ? (njobs + gy - 1) / gy : 0;   // the last z slab is stepped whole, beyond njobs
+        for (size_t u = 0; u < gy * gz; u++)
             for (size_t t = 0; t < lanes; t++) {
                 if (packed) term_product_lane<true>(&lv, tj, njobs, n, limb, pw_poly_stride, out_poly_stride, t * 2, u);
                 else term_product_lane<false>(&lv, tj, njobs, n, limb, pw_poly_stride, out_poly_stride, t * 2, u);
@@ -68,10 +69,12 @@ int emu_term_product(int nl, const uint64_t *q, const uint32_t *shift, const uin
         return 0;
     });
 }
-// k_pack_rows / k_unpack_rows over `slots` slots of L limbs (the level's first L row widths)
+// k_pack_rows / k_unpack_rows over `slots` slots of L limbs (the level's first L row widths), behind the host check that stands in front
+// of every launch of them (pack_rows_grid_check, mac_plan.h: -1 with its refusal, before an array is touched)
 int emu_pack_rows(int L, const uint32_t *bits, uint64_t n, const uint64_t *dense, void *packed, uint64_t slot_bytes, uint64_t slots, int unpack, uint64_t *dense_out)
 {
     return guarded([&]() -> int {
+        pack_rows_grid_check(slots, L);
         std::vector<uint64_t> q(L, 3); std::vector<uint32_t> z(L, 1);
         const DevLevel lv = mac_level(L, q.data(), z.data(), z.data(), z.data(), bits, n);
         const size_t lanes = ((unpack ? n : n * 2) + EW_T - 1) / EW_T * EW_T;     // launch_pack_rows / launch_unpack_rows

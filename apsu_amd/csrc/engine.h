@@ -386,8 +386,11 @@ public:
                 STEP_ROOTS_SPLIT,
                 // the querier's side and the decryption (engine_query_steps.cpp): the launchers engine_query.cpp calls
                 STEP_SEED_EXPAND, STEP_DECRYPT_ROUND, STEP_PLAIN_POWERS, STEP_SAMPLE_SMALL, STEP_SMALL_LIFT, STEP_ENC_FINISH, STEP_RLK_FINISH,
-                STEP_FLAG_MONOMIAL, STEP_COUNT };
-    enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32, STEP_INVERSE = 64, STEP_NORED = 128 };
+                STEP_FLAG_MONOMIAL,
+                // the multiply-accumulate family (engine_mac_steps.cpp): the launchers of launch_mac.h and launch_limb0_rows
+                STEP_MAC_INFO, STEP_MAC, STEP_TERM_PRODUCT, STEP_PACK_ROWS, STEP_UNPACK_ROWS, STEP_LIMB0_ROWS, STEP_COUNT };
+    enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32, STEP_INVERSE = 64, STEP_NORED = 128,
+                      STEP_KARA = 256, STEP_PACKED = 512, STEP_LIMB_SLOW = 1024 };
     struct StepArgs {
         int step, chain_idx;
         uint32_t flags;
@@ -401,6 +404,7 @@ public:
     void debug_run_db_step(const StepArgs &a);                    // its database half (the caller holds the lock)
     void debug_run_ntt_step(const StepArgs &a);                   // its transform half (the caller holds the lock)
     void debug_run_query_step(const StepArgs &a);                 // its querier-side half (the caller holds the lock)
+    void debug_run_mac_step(const StepArgs &a);                   // its multiply-accumulate half (the caller holds the lock)
     // Staging of apsu_he_run_query_request (c_api.cpp) kept across calls: a device buffer and a page-locked host buffer of at least
     // `bytes` (grown on demand; hipHostMalloc / hipMalloc per query cost milliseconds).  The caller holds wire_mutex() for the whole query.
     std::mutex &wire_mutex() { return wire_mu_; }

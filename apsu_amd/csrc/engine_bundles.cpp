@@ -48,6 +48,7 @@ void Engine::pack_bundle(Bundle &b)
         DevBuf pk;
         pk.alloc(b.ntt_count * b.ntt_slot_bytes + 16);
         HIP_CHECK(hipMemsetAsync(static_cast<char *>(pk.p()) + b.ntt_count * b.ntt_slot_bytes, 0, 16, st_));
+        pack_rows_grid_check(b.ntt_count, b.pt_level + 1);
         launch_pack_rows(dlevel(b.pt_level), b.pt_level + 1, b.ntt.u(), pk.p(), b.ntt_slot_bytes, n, b.ntt_count, st_);
         sync();
         b.ntt = std::move(pk);
@@ -56,6 +57,7 @@ void Engine::pack_bundle(Bundle &b)
         DevBuf pk;
         pk.alloc(H * b.lifted_slot_bytes + 16);
         HIP_CHECK(hipMemsetAsync(static_cast<char *>(pk.p()) + H * b.lifted_slot_bytes, 0, 16, st_));
+        pack_rows_grid_check(H, high + 1);
         launch_pack_rows(dlevel(high), high + 1, b.lifted.u(), pk.p(), b.lifted_slot_bytes, n, H, st_);
         sync();
         b.lifted = std::move(pk);
@@ -71,6 +73,7 @@ void Engine::unpack_bundle(Bundle &b)
     if (b.ntt_count) {
         DevBuf dn;
         dn.alloc(b.ntt_count * (size_t)(b.pt_level + 1) * n * sizeof(u64));
+        pack_rows_grid_check(b.ntt_count, b.pt_level + 1);
         launch_unpack_rows(dlevel(b.pt_level), b.pt_level + 1, b.ntt.p(), b.ntt_slot_bytes, dn.u(), n, b.ntt_count, st_);
         sync();
         b.ntt = std::move(dn);
@@ -79,6 +82,7 @@ void Engine::unpack_bundle(Bundle &b)
     if (H && b.lifted.bytes()) {
         DevBuf dn;
         dn.alloc(H * (size_t)(high + 1) * n * sizeof(u64));
+        pack_rows_grid_check(H, high + 1);
         launch_unpack_rows(dlevel(high), high + 1, b.lifted.p(), b.lifted_slot_bytes, dn.u(), n, H, st_);
         sync();
         b.lifted = std::move(dn);

@@ -44,7 +44,7 @@ void Engine::debug_run_query_step(const StepArgs &a)
     const size_t batch = a.batch > 0 ? (size_t)a.batch : 0, terms = a.terms > 0 ? (size_t)a.terms : 0, polys = a.polys > 0 ? (size_t)a.polys : 0;
     auto in_is = [&](int i, size_t words, const char *what) { if (!a.in[i] || a.in_words[i] != words) refuse(std::string(what) + ": wrong size"); };
     auto out_is = [&](int i, size_t words, const char *what) { if (!a.out[i] || a.out_words[i] != words) refuse(std::string(what) + ": wrong size"); };
-    need(a.step >= STEP_SEED_EXPAND && a.step < STEP_COUNT, "unknown step");
+    need(a.step >= STEP_SEED_EXPAND && a.step < STEP_MAC_INFO, "unknown step");
     need(batch >= 1 && batch <= 64, "batch out of range (1 .. 64)");
 
     // ---- everything a launcher's contract does not admit is refused here, in front of the arena: nothing below can refuse

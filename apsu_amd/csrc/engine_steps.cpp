@@ -33,6 +33,7 @@ void Engine::debug_run_step(const StepArgs &a)
 {
     Enter g(this);
     TIER1_SLOTS();
+    if (a.step >= STEP_MAC_INFO) { debug_run_mac_step(a); return; }           // the multiply-accumulate family and the packed rows
     if (a.step >= STEP_SEED_EXPAND) { debug_run_query_step(a); return; }      // the querier's side and the decryption
     if (a.step == STEP_ROOTS_SPLIT) { debug_run_db_step(a); return; }         // (a database step numbered behind the transforms)
     if (a.step >= STEP_NTT_INFO) { debug_run_ntt_step(a); return; }          // the transforms: a map of the caller's, no chain level

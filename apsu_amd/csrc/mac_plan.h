@@ -4,6 +4,8 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <stdexcept>
+#include <string>
 #include <vector>
 #include "mac_core.h"
 
@@ -15,6 +17,16 @@ struct MacStream { const u64 *pt; const u64 *pw; u64 *out; u32 cnt, pt_stride, p
 // grid of k_mac: gx blocks of EW_T lanes along the coefficients; limb slowest (k_mac) unless the jobs do not fit grid dimension y
 struct MacGrid { unsigned gx; int limb_slow; };
 inline MacGrid mac_grid(size_t n, size_t njobs) { return MacGrid{ (unsigned)((n / MAC_C + EW_T - 1) / EW_T), njobs <= 65535u ? 1 : 0 }; }
+
+// k_pack_rows / k_unpack_rows take (slot, limb) from grid dimension y: slots * L rows is all a launch can address.  Every caller of
+// launch_pack_rows / launch_unpack_rows asks this first (a BinBundle of 8192 coefficients at 8 limbs would pass it)
+constexpr size_t PACK_ROWS_GRID_Y = 65535;
+inline void pack_rows_grid_check(size_t slots, int L)
+{
+    if (L < 1 || slots > PACK_ROWS_GRID_Y / (size_t)L)
+        throw std::invalid_argument("pack_rows / unpack_rows: " + std::to_string(slots) + " slots of " + std::to_string(L) +
+                                    " limbs exceed the 65535 rows of one launch (grid dimension y)");
+}
 
 struct MacPlan {
     std::vector<MacJob> jobs;

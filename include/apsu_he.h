@@ -379,7 +379,44 @@ int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_
  * falls below its threshold: a small one would not end; every real one exceeds 2^63); for DECRYPT_ROUND t >= q0, q0 >= 2^62,
  * t >= 2^61, t < 2, a word of c0 or v that is not below q0; an exponent above 32 bits; PLAIN_POWERS without batching; a word that is
  * no sign-extended signed byte; a word of pt, v, s, e or an a half that is not canonical; RLK_FINISH in a context with one prime;
- * objects beyond the seed's range; sizes that do not match. */
+ * objects beyond the seed's range; sizes that do not match.
+ *
+ * The multiply-accumulate family, from MAC_INFO on (same entry, no new symbol): launch_mac, launch_term_product, launch_pack_rows,
+ * launch_unpack_rows and launch_limb0_rows with the level block of chain_idx (L = chain_idx + 1 limbs).  A stored plaintext is a SLOT:
+ * dense, [L][n] words; or bit-packed (flag PACKED): limb j is a row of n coefficients of w_j = mac_bits[j] bits, coefficient c in bits
+ * [c w_j, (c + 1) w_j) of the little-endian bit string that starts at byte mac_row_off[j] of the slot, rows back to back, a slot of
+ * n (w_0 + .. + w_{L-1}) / 8 bytes.  Bit-packed bytes travel as 64-bit words (little-endian; n is a multiple of 64, so a slot is whole
+ * words).  Every bit-packed array a kernel READS is uploaded with 16 zero bytes behind it, as the engine keeps them.  out[0] is in/out
+ * everywhere: a word the kernel does not write comes back as it went.  The geometry is read back from the device's level block.
+ *   MAC_INFO        -> out[0] [2 + 7 L] = L, the bit-packed slot's bytes, then per limb mac_shift, mac_chunk, mac_chunk_k, mac_bits,
+ *                   mac_row_off, mac_mask_hi, mac_kara_usable (0 / 1)
+ *   MAC             ONE launch_mac over `batch` jobs (1 .. 64).  polys = streams per job (1 .. 4), terms = terms per chain (1 .. 4096),
+ *                   e0 = limb0, n_ext = nl: a job multiplies limbs limb0 .. limb0 + nl - 1 and writes them as limbs 0 .. nl - 1.
+ *                   Flags: KARA the three-product form, PACKED bit-packed plaintexts, LIMB_SLOW the grid order (block, job, limb)
+ *                   instead of (block, limb, job); the grid is MacGrid{ mac_grid(n, batch).gx, LIMB_SLOW }, so either order runs
+ *                   with a handful of jobs, and its limb extent is L as in the engine.
+ *                   in[0] powers [batch][terms][2][P][n], P read from the size, L <= P <= 18 (pw_poly_stride = P n, pw_stride = 2 P n);
+ *                   in[1] plaintexts [batch][polys][terms] slots (pt_stride = one slot); out[0] [batch][polys][2][n_ext][n]
+ *                   (out_poly_stride = n_ext n): stream g of job b = sum over the terms of plaintext (.) power, per polynomial.
+ *                   in[2] null, or a job table [batch][4] = limb0, nl, ng, cnt per job (nl <= n_ext, limb0 + nl <= L, 1 <= ng <= polys,
+ *                   1 <= cnt <= terms): the job takes its first ng streams and cnt terms and leaves every other word of its part
+ *                   of out[0] alone.  A stream the job does not have reads stream 0's plaintexts, as mac_plan sets it; its
+ *                   output pointer is that stream's own part of out[0] (g < polys), where a store the kernel must not make shows,
+ *                   and stream 0's beyond.
+ *   TERM_PRODUCT    ONE launch_term_product on limb e0, dense or PACKED: `batch` operand sets (1 .. 64), each repeated `terms`
+ *                   times -- job u < batch * terms (at most 2^17) reads set u % batch.  in[0] powers [batch][2][P][n], in[1]
+ *                   plaintexts [batch] slots -> out[0] [batch * terms + 1][2][n]: job u writes its own [2][n]; the last [2][n]
+ *                   is a guard behind the last job's output that no job owns.
+ *   PACK_ROWS       batch = slots; in[0] dense [slots][L][n] -> out[0] the bit-packed slots, then two words (16 bytes) that no row owns
+ *   UNPACK_ROWS     batch = slots; in[0] the bit-packed slots -> out[0] dense [slots][L][n]
+ *   LIMB0_ROWS      batch = count (1 .. 65535); in[0] [count] slots, dense or PACKED -> out[0] [count][n], limb 0 of every slot
+ * Refused like the others, nothing launched: a chain_idx that is no data level; n no multiple of 64; PACKED in a context whose rows
+ * are all 64 bits wide; for MAC polys outside 1 .. 4, terms 0 (or a cnt of 0), limb0 + nl beyond the level, P below L, KARA on a
+ * level with a prime that mac_kara_usable rejects (59 and 60 bits), a job-table entry outside the ranges above; for MAC and
+ * TERM_PRODUCT a word of the powers (limbs below L) or a coefficient of a plaintext -- a bit-packed one decoded on the host with
+ * packed_coeff -- that is not a canonical residue of its limb; for TERM_PRODUCT a limb beyond the level; for PACK_ROWS a word that is
+ * not canonical; for PACK_ROWS and UNPACK_ROWS slots * L above 65535, the y extent of their grid (the engine's own callers refuse the
+ * same: pack_rows_grid_check, mac_plan.h); sizes that do not match. */
 enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEHZ_EXT, APSU_HE_STEP_TENSOR, APSU_HE_STEP_TENSOR_CONV,
        APSU_HE_STEP_TENSOR_SUM, APSU_HE_STEP_BEHZ_FINISH, APSU_HE_STEP_BEHZ_FINISH_SUM, APSU_HE_STEP_KS_INNER, APSU_HE_STEP_KS_MODDOWN,
        APSU_HE_STEP_MODSWITCH, APSU_HE_STEP_MODSWITCH_JOBS, APSU_HE_STEP_I0_FINISH, APSU_HE_STEP_EVAL_EPILOGUE, APSU_HE_STEP_ADD_MANY,
@@ -389,9 +426,12 @@ enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEH
        APSU_HE_STEP_NTT_INFO, APSU_HE_STEP_NTT, APSU_HE_STEP_NTT_GATHER, APSU_HE_STEP_INTT_TENSOR,
        APSU_HE_STEP_ROOTS_SPLIT,
        APSU_HE_STEP_SEED_EXPAND, APSU_HE_STEP_DECRYPT_ROUND, APSU_HE_STEP_PLAIN_POWERS, APSU_HE_STEP_SAMPLE_SMALL, APSU_HE_STEP_SMALL_LIFT,
-       APSU_HE_STEP_ENC_FINISH, APSU_HE_STEP_RLK_FINISH, APSU_HE_STEP_FLAG_MONOMIAL };
+       APSU_HE_STEP_ENC_FINISH, APSU_HE_STEP_RLK_FINISH, APSU_HE_STEP_FLAG_MONOMIAL,
+       APSU_HE_STEP_MAC_INFO, APSU_HE_STEP_MAC, APSU_HE_STEP_TERM_PRODUCT, APSU_HE_STEP_PACK_ROWS, APSU_HE_STEP_UNPACK_ROWS,
+       APSU_HE_STEP_LIMB0_ROWS };
 enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8, APSU_HE_STEP_PLAN = 16,
-       APSU_HE_STEP_COMPOSED = 32, APSU_HE_STEP_INVERSE = 64, APSU_HE_STEP_NORED = 128 };
+       APSU_HE_STEP_COMPOSED = 32, APSU_HE_STEP_INVERSE = 64, APSU_HE_STEP_NORED = 128, APSU_HE_STEP_KARA = 256, APSU_HE_STEP_PACKED = 512,
+       APSU_HE_STEP_LIMB_SLOW = 1024 };
 #define APSU_HE_STEP_MAP_RAW ((uint64_t)1 << 30)   /* in a map entry of an inverse transform */
 typedef struct {
     int32_t step, chain_idx;

@@ -27,7 +27,9 @@ def remade(header):
 
 @pytest.mark.parametrize("header, unit", [("bin_merge.h", "kernels_db.o"), ("bin_update.h", "kernels_db.o"),
                                           ("mac_core.h", "kernels_mac.o"), ("query_side.h", "kernels_ew.o"),
-                                          ("query_side.h", "engine_query_steps.o"), ("query_side.h", "emu/query.o")])
+                                          ("query_side.h", "engine_query_steps.o"), ("query_side.h", "emu/query.o"),
+                                          ("mac_core.h", "engine_mac_steps.o"), ("mac_plan.h", "engine_mac_steps.o"),
+                                          ("mac_plan.h", "kernels_mac.o"), ("mac_plan.h", "emu/mac.o")])
 def test_family_header_spares_the_transforms(header, unit):
     got = remade(header)
     assert "build/" + unit in got, got

@@ -16,6 +16,7 @@ import pytest
 import edge_values as ev
 import emu_lib
 from emu_lib import vp
+from mac_step_model import exact_chain
 from oracle import ref
 from test_gpu_mac_edges import LONG_CHAIN, WIDTHS, chain_lengths
 
@@ -86,20 +87,6 @@ def pack(emu, lv, dense):
     buf = np.full(slots * lv.slot_bytes + PAD, 0xA5, dtype=np.uint8)
     assert emu.emu_pack_rows(len(lv.qs), vp(u32(lv.bits)), C.c_uint64(lv.n), vp(dense), vp(buf), C.c_uint64(lv.slot_bytes), C.c_uint64(slots), 0, None) == 0
     return buf
-
-
-def exact_chain(q, A, P):
-    """sum_t A[t] * P[t][p] mod q per coefficient and polynomial p, in Python integers (columns that repeat are computed once)"""
-    terms, n = A.shape
-    cols = np.concatenate([A, P[:, 0], P[:, 1]])
-    mix = np.random.default_rng(1).integers(1, 1 << 63, (3 * terms, 1), dtype=np.uint64) | np.uint64(1)
-    _, first, inv = np.unique((cols * mix).sum(axis=0, dtype=np.uint64), return_index=True, return_inverse=True)    # columns by a 64-bit mix ...
-    uniq = cols[:, first]
-    assert (uniq[:, inv] == cols).all()                   # ... which did not merge two different ones
-    a, p0, p1 = (uniq[i * terms:(i + 1) * terms].astype(object) for i in range(3))
-    r0 = np.array([int(v) % q for v in (a * p0).sum(axis=0)], dtype=np.uint64)
-    r1 = np.array([int(v) % q for v in (a * p1).sum(axis=0)], dtype=np.uint64)
-    return np.stack([r0[inv], r1[inv]])
 
 
 class Chains:
