@@ -378,6 +378,33 @@ int apsu_he_db_rebase(apsu_he_ctx *dst, apsu_he_ctx *src, const apsu_he_bundle *
     });
 }
 
+int apsu_he_db_entries_plan(const apsu_he_ctx *c, const uint64_t *offsets, uint32_t *bundles_per_index, uint32_t *total)
+{
+    return guarded([&] {
+        REQUIRE(c && offsets && total, "null argument");
+        const BulkPlan plan = c->eng->entries_plan(offsets);
+        REQUIRE(plan.total <= 0xFFFFFFFFull, "more than 2^32 - 1 BinBundles");
+        if (bundles_per_index) std::copy(plan.bundles.begin(), plan.bundles.end(), bundles_per_index);
+        *total = (uint32_t)plan.total;
+    });
+}
+
+int apsu_he_db_build_from_entries(apsu_he_ctx *c, const uint8_t *entries, int entries_on_device, const uint64_t *offsets, apsu_he_bundle **out,
+                                  uint32_t capacity, uint32_t *n_out)
+{
+    return guarded([&] {
+        REQUIRE(c && offsets && n_out && (out || !capacity), "null argument");
+        const BulkPlan plan = c->eng->entries_plan(offsets);            // every refusal of the plan, and the count, before anything is built
+        REQUIRE(plan.total <= 0xFFFFFFFFull, "more than 2^32 - 1 BinBundles");
+        *n_out = (uint32_t)plan.total;
+        if (plan.total > capacity)
+            throw std::invalid_argument("build_from_entries: " + std::to_string(plan.total) + " BinBundles come out, the caller has room for " + std::to_string(capacity));
+        REQUIRE(entries || !plan.total, "null argument");
+        auto made = c->eng->build_from_entries(entries, entries_on_device != 0, offsets);
+        wrap_bundles(made, out);
+    });
+}
+
 int apsu_he_bundle_bins(apsu_he_ctx *c, const apsu_he_bundle *b, uint64_t *roots, uint32_t *counts, uint32_t stride)
 { return guarded([&] { REQUIRE(c && b && b->b && counts, "null argument"); c->eng->bundle_bins(*b->b, roots, counts, stride); }); }
 int apsu_he_debug_bundle_bins_form(apsu_he_ctx *c, const apsu_he_bundle *b, uint64_t *roots, uint32_t *counts, uint32_t stride, int form)
@@ -392,7 +419,7 @@ int apsu_he_debug_run_step(apsu_he_ctx *c, const apsu_he_step_args *args)
 {
     return guarded([&] {
         REQUIRE(c && args, "null argument");
-        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT == (int)Engine::STEP_UNLIFT && (int)APSU_HE_STEP_INTT_TENSOR == (int)Engine::STEP_INTT_TENSOR && (int)APSU_HE_STEP_ROOTS_SPLIT == (int)Engine::STEP_ROOTS_SPLIT && (int)APSU_HE_STEP_SEED_EXPAND == (int)Engine::STEP_SEED_EXPAND && (int)APSU_HE_STEP_FLAG_MONOMIAL == (int)Engine::STEP_FLAG_MONOMIAL && (int)APSU_HE_STEP_MAC_INFO == (int)Engine::STEP_MAC_INFO && (int)APSU_HE_STEP_LIMB0_ROWS + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
+        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT == (int)Engine::STEP_UNLIFT && (int)APSU_HE_STEP_INTT_TENSOR == (int)Engine::STEP_INTT_TENSOR && (int)APSU_HE_STEP_ROOTS_SPLIT == (int)Engine::STEP_ROOTS_SPLIT && (int)APSU_HE_STEP_SEED_EXPAND == (int)Engine::STEP_SEED_EXPAND && (int)APSU_HE_STEP_FLAG_MONOMIAL == (int)Engine::STEP_FLAG_MONOMIAL && (int)APSU_HE_STEP_MAC_INFO == (int)Engine::STEP_MAC_INFO && (int)APSU_HE_STEP_LIMB0_ROWS == (int)Engine::STEP_LIMB0_ROWS && (int)APSU_HE_STEP_ENTRIES_SCATTER + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
                       (int)APSU_HE_STEP_KARA == (int)Engine::STEP_KARA && (int)APSU_HE_STEP_PACKED == (int)Engine::STEP_PACKED && (int)APSU_HE_STEP_LIMB_SLOW == (int)Engine::STEP_LIMB_SLOW &&
                       (int)APSU_HE_STEP_COMPOSED == (int)Engine::STEP_COMPOSED && (int)APSU_HE_STEP_NORED == (int)Engine::STEP_NORED, "step ids of the header and the engine");
         Engine::StepArgs a{};
@@ -403,7 +430,7 @@ int apsu_he_debug_run_step(apsu_he_ctx *c, const apsu_he_step_args *args)
         c->eng->debug_run_step(a);
     });
 }
-// the seven apsu_he_debug_*_times: the first spans of one entry of the context's clock (Engine::op_times), each to where the caller wants it
+// the eight apsu_he_debug_*_times: the first spans of one entry of the context's clock (Engine::op_times), each to where the caller wants it
 static int read_op_times(apsu_he_ctx *c, Engine::Op op, std::initializer_list<double *> out)
 {
     return guarded([&] {
@@ -420,6 +447,10 @@ int apsu_he_debug_split_times(apsu_he_ctx *c, double *decode_ms, double *roots_m
 { return read_op_times(c, Engine::OP_SPLIT, { decode_ms, roots_ms, split_ms, build_ms }); }
 int apsu_he_debug_merge_times(apsu_he_ctx *c, double *decode_ms, double *kernel_ms, double *encode_ms)
 { return read_op_times(c, Engine::OP_MERGE, { decode_ms, kernel_ms, encode_ms }); }
+int apsu_he_debug_build_from_entries_times(apsu_he_ctx *c, double *copy_ms, double *scatter_ms, double *build_ms)
+{ return read_op_times(c, Engine::OP_BUILD, { copy_ms, scatter_ms, build_ms }); }
+int apsu_he_debug_set_scatter_blocks(apsu_he_ctx *c, uint32_t blocks)
+{ return guarded([&] { REQUIRE(c, "null argument"); c->eng->set_scatter_blocks(blocks); }); }
 int apsu_he_debug_lookup_times(apsu_he_ctx *c, double *decode_ms, double *kernels_ms)
 { return read_op_times(c, Engine::OP_LOOKUP, { decode_ms, kernels_ms }); }
 int apsu_he_algebraize_items(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t *felts, int felts_on_device)
@@ -860,6 +891,15 @@ int apsu_he_multi_db_apply_entries(apsu_he_multi *m, uint32_t bundle_idx, const 
         if (rem_status) std::copy(p.rem_status.begin(), p.rem_status.end(), rem_status);
         if (ins_target) for (size_t e = 0; e < p.ins_target.size(); e++) ins_target[e] = as_id(p.ins_target[e]);
         if (rem_target) for (size_t e = 0; e < p.rem_target.size(); e++) rem_target[e] = as_id(p.rem_target[e]);
+    });
+}
+int apsu_he_multi_db_build_from_entries(apsu_he_multi *m, const uint8_t *entries, const uint64_t *offsets, int *first_id, uint32_t *n_built)
+{
+    return guarded([&] {
+        REQUIRE(m && offsets, "null argument");
+        const std::pair<int, uint32_t> r = m->m->build_from_entries(entries, offsets);
+        if (first_id) *first_id = r.first;
+        if (n_built) *n_built = r.second;
     });
 }
 int apsu_he_multi_db_merge_bundles(apsu_he_multi *m, const int *bundle_ids, uint32_t n_ids, int *new_id)

@@ -20,6 +20,7 @@
 #include "params.h"
 #include "db_place.h"
 #include "db_compact.h"
+#include "bulk_place.h"
 #include "powers_dag.h"
 #include "powers_sched.h"
 #include "bundle_layout.h"
@@ -191,7 +192,8 @@ public:
     //   OP_EXPORT     (export_saved) decode and counts, the root search and multiplicities, k_bins_rows (device, by events); the copies
     //                 to the host, the plaintexts' serialisation, the buffer's assembly (host clock)
     //   OP_SPLIT      (split_bundle) decode and counts, the root search and multiplicities, k_roots_split, the parts' builds
-    enum Op { OP_LOOKUP = 0, OP_BINS, OP_MERGE, OP_EVAL_PLAIN, OP_SELF_TEST, OP_EXPORT, OP_SPLIT, OP_COUNT };
+    //   OP_BUILD      (build_from_entries, summed over the bundle indices and BinBundles) the entries' copies, k_entries_scatter, the builds
+    enum Op { OP_LOOKUP = 0, OP_BINS, OP_MERGE, OP_EVAL_PLAIN, OP_SELF_TEST, OP_EXPORT, OP_SPLIT, OP_BUILD, OP_COUNT };
     static constexpr int OP_SPANS = 6;
     void op_times(Op op, double *ms, int count);
     struct ApplyResult {
@@ -203,6 +205,18 @@ public:
     // index given in cache order.  The given BinBundles are only read.
     ApplyResult apply_entries(uint32_t bundle_idx, const Bundle *const *bundles, uint32_t n_bundles, const u64 *ins_felts, const uint32_t *ins_start,
                               size_t n_ins, const u64 *rem_felts, const uint32_t *rem_start, size_t n_rem);
+    // N1, a whole database from its entries (include/apsu_he.h: apsu_he_db_build_from_entries; bulk_place.h): ReceiverDB::set_data on an
+    // empty database.  entries [offsets[table_size]][16]: the post-OPRF items in items_bucket's order, host or device; offsets
+    // [table_size + 1] (host).  Per bundle index with entries: its contiguous entry range is copied once, its kstart uploaded; per
+    // BinBundle k in cache order new_bundle(b, k, degree), k_entries_scatter into root lists from the arena, build_from_roots -- no
+    // entry touches the host.  cache_idx = k.  Out: bundle index by bundle index, in cache order within each; a bundle index without
+    // entries gets no BinBundle.  want (may be null: all): one byte per BinBundle of the plan in that order, 0 = not built here, a null
+    // pointer in its place (MultiEngine builds each on its device).  NO entry-level dedupe: two equal entries of one location put a
+    // double root into their bins.  All or nothing.
+    BulkPlan entries_plan(const u64 *offsets) const;
+    std::vector<std::unique_ptr<Bundle>> build_from_entries(const unsigned char *entries, bool on_device, const u64 *offsets, const unsigned char *want = nullptr);
+    // measurement hook: workgroups per location of k_entries_scatter in build_from_entries; 0 (the default) = scatter_blocks' choice
+    void set_scatter_blocks(uint32_t blocks) { std::lock_guard<std::mutex> g(mu_); scatter_blocks_ = blocks; }
     // N1, compaction (include/apsu_he.h: apsu_he_bundles_merge, apsu_he_db_compact): the union of two bins is the product of their
     // polynomials, so n >= 2 BinBundles of one bundle index become ONE new BinBundle without anybody's roots: decode each, per-slot
     // products pairwise (k_bins_merge, bin_merge.h), the tail of the build.  The given BinBundles are only read.
@@ -388,7 +402,9 @@ public:
                 STEP_SEED_EXPAND, STEP_DECRYPT_ROUND, STEP_PLAIN_POWERS, STEP_SAMPLE_SMALL, STEP_SMALL_LIFT, STEP_ENC_FINISH, STEP_RLK_FINISH,
                 STEP_FLAG_MONOMIAL,
                 // the multiply-accumulate family (engine_mac_steps.cpp): the launchers of launch_mac.h and launch_limb0_rows
-                STEP_MAC_INFO, STEP_MAC, STEP_TERM_PRODUCT, STEP_PACK_ROWS, STEP_UNPACK_ROWS, STEP_LIMB0_ROWS, STEP_COUNT };
+                STEP_MAC_INFO, STEP_MAC, STEP_TERM_PRODUCT, STEP_PACK_ROWS, STEP_UNPACK_ROWS, STEP_LIMB0_ROWS,
+                // behind the existing ids, which stay: k_entries_scatter (engine_db_steps.cpp)
+                STEP_ENTRIES_SCATTER, STEP_COUNT };
     enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32, STEP_INVERSE = 64, STEP_NORED = 128,
                       STEP_KARA = 256, STEP_PACKED = 512, STEP_LIMB_SLOW = 1024 };
     struct StepArgs {
@@ -619,6 +635,7 @@ private:
     void roots_tables();                             // the context's generator, step table and point table, made by the first bundle_bins
     u64 roots_g_ = 0;
     DevBuf d_roots_step_, d_roots_pts_;                // g^i (u32) and the forward transform mod t of the polynomial X, n words each
+    uint32_t scatter_blocks_ = 0;                      // set_scatter_blocks
     bool unlift_exact_ = false;                        // q_0 > 2 t (set at creation): a stored residue tells its value mod t (bin_update.h)
     DevBuf d_slot_map_;
     // ---- cuckoo hashing (engine_cuckoo.cpp)

@@ -1,6 +1,7 @@
-// See engine.h.  The calls on a resident database: a BinBundle updated, searched, listed, merged, split, moved to another context, exported
-// in the reference's saved format, evaluated in plaintext and self-tested.  Each decodes what engine_bundles.cpp stored (decode_counted) and, where it makes a new
-// BinBundle, ends in that file's encode_bundle.  One clock for all of them (op_times), one place for the context's refusals (lookup_check).
+// See engine.h.  The calls on a resident database: a BinBundle updated, searched, listed, merged, split, moved to another context, built
+// from the database's entries, exported in the reference's saved format, evaluated in plaintext and self-tested.  Each decodes what
+// engine_bundles.cpp stored (decode_counted) and, where it makes a new BinBundle, ends in that file's encode_bundle.  One clock for all of
+// them (op_times), one place for the context's refusals (lookup_check).
 #include "engine_impl.h"
 
 #include <chrono>
@@ -585,6 +586,73 @@ Engine::ApplyResult Engine::apply_entries(uint32_t bundle_idx, const Bundle *con
         res.appended.push_back(build_bundle(bundle_idx, next_cache + k, li.roots.data(), li.counts.data(), bins, li.stride));
     }
     return res;
+}
+
+// ---- N1, a whole database from its entries (bulk_place.h): per bundle index one copy of its entries, per BinBundle k_entries_scatter
+// and the tail of the build on the device-resident lists
+BulkPlan Engine::entries_plan(const u64 *offsets) const
+{
+    // the parameters never change: read without the lock
+    if (!has_psu_) throw std::logic_error("context was created without PSUParams");
+    return bulk_plan(offsets, psu_.table_params.table_size, psu_.items_per_bundle, psu_.table_params.max_items_per_bin);
+}
+
+std::vector<std::unique_ptr<Bundle>> Engine::build_from_entries(const unsigned char *entries, bool on_device, const u64 *offsets, const unsigned char *want)
+{
+    Enter g(this);
+    TIER1_SLOTS();
+    lookup_check("build_from_entries", NEED_BATCHING);
+    const size_t n = hp_.n;
+    const u32 ipb = psu_.items_per_bundle, F = psu_.item_params.felts_per_item, bins = psu_.bins_per_bundle, cap = psu_.table_params.max_items_per_bin - 1;
+    const BulkPlan plan = bulk_plan(offsets, psu_.table_params.table_size, ipb, psu_.table_params.max_items_per_bin);   // every refusal comes before any GPU work
+    if (plan.total > 0xFFFFFFFFull) throw std::invalid_argument("build_from_entries: more than 2^32 - 1 BinBundles");
+    OpClock &clk = clock_[OP_BUILD];
+    // stamps: per bundle index two around the copies, per BinBundle three: in front of the scatter, behind it, behind the build
+    clk.evs.reserve(2 * plan.bundles.size() + 3 * (size_t)plan.total);
+    for (double &m : clk.ms) m = 0;
+    std::vector<std::unique_ptr<Bundle>> out((size_t)plan.total);
+    size_t at = 0, stamp = 0;
+    for (u32 b = 0; b < plan.bundles.size(); at += plan.bundles[b], b++) {
+        const u32 K = plan.bundles[b];
+        bool any = false;
+        for (u32 k = 0; k < K; k++) any |= !want || want[at + k];
+        if (!any) continue;
+        const u64 *off = offsets + (size_t)b * ipb;
+        const u32 *kstart = plan.kstart.data() + (size_t)b * ipb;
+        const size_t count = off[ipb] - off[0];
+        const size_t first_stamp = stamp;
+        WITH_ARENA({
+            stamp = first_stamp;                                       // (the body runs again after an arena overflow)
+            clk.evs.record(stamp++, st_);
+            unsigned char *ditems = ws_as<unsigned char>(count * 16 + 16);
+            HIP_CHECK(hipMemcpyAsync(ditems, entries + off[0] * 16, count * 16, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st_));
+            u64 *doff = ws((size_t)ipb + 1);
+            u32 *dkstart = ws_as<u32>(ipb, 1);
+            HIP_CHECK(hipMemcpyAsync(doff, off, ((size_t)ipb + 1) * sizeof(u64), hipMemcpyHostToDevice, st_));
+            HIP_CHECK(hipMemcpyAsync(dkstart, kstart, (size_t)ipb * sizeof(u32), hipMemcpyHostToDevice, st_));
+            clk.evs.record(stamp++, st_);
+            const size_t mark = arena_off_;
+            for (u32 k = 0; k < K; k++) {
+                if (want && !want[at + k]) continue;
+                arena_off_ = mark;                                     // one BinBundle after the other through the same workspace (stream order)
+                const u32 degree = bulk_degree(off, kstart, ipb, k, cap), stride = std::max<u32>(1, degree);
+                out[at + k] = new_bundle(b, k, degree);
+                u64 *droots = ws((size_t)bins * stride + 1);
+                u32 *dcounts = ws_as<u32>(n, 1);
+                clk.evs.record(stamp++, st_);
+                launch_entries_scatter(ditems, doff, dkstart, ipb, F, psu_.item_bit_count_per_felt, psu_.item_bit_count, cap, k, stride, droots, dcounts, (u32)n, scatter_blocks_, st_);
+                clk.evs.record(stamp++, st_);
+                build_from_roots(*out[at + k], droots, dcounts, bins, stride);
+                clk.evs.record(stamp++, st_);
+            }
+            sync();
+        });
+        clk.ms[0] += clk.evs.ms(first_stamp, first_stamp + 1);
+        for (size_t s = first_stamp + 2; s < stamp; s += 3) { clk.ms[1] += clk.evs.ms(s, s + 1); clk.ms[2] += clk.evs.ms(s + 1, s + 2); }
+        for (u32 k = 0; k < K; k++)
+            if (out[at + k]) pack_bundle(*out[at + k]);
+    }
+    return out;
 }
 
 // ---- N1, compaction: several BinBundles of one bundle index into one (bin_merge.h, db_compact.h)

@@ -462,6 +462,36 @@ void Engine::debug_run_db_step(const StepArgs &a)
             down32(a.out[1], dco, k * n);
             down(a.out[1] + k * n, fail, 1);
         } break;
+        case STEP_ENTRIES_SCATTER: {
+            // batch = locations, polys = F, terms = stride, e0 = k; bits per felt, item_bit_count and cap = max_items_per_bin - 1 are the
+            // context's.  in[0] items [count][2] (count = offsets[batch] - offsets[0]; may be null when 0), in[1] offsets [batch + 1],
+            // in[2] kstart [batch] -> out[0] roots [bins][stride] (in: what the words nobody writes keep; bins from its size), out[1] counts [n]
+            const size_t locations = batch, F = polys, stride = terms, k = e0;
+            need(has_psu_, "entries_scatter: the context was created without PSUParams");
+            const u32 bpf = psu_.item_bit_count_per_felt, item_bits = psu_.item_bit_count, max_items = psu_.table_params.max_items_per_bin;
+            need(max_items >= 2, "entries_scatter: max_items_per_bin < 2");
+            need(locations >= 1 && F >= 1 && F <= SCATTER_MAX_F && (F - 1) * bpf < 128 && locations * F <= n, "entries_scatter: locations (batch) or F (polys) out of range");
+            need(stride >= 1 && stride < ROWS_MAX && k < ROWS_MAX, "entries_scatter: stride (terms) or k (e0) out of range");
+            in_is(1, locations + 1, "entries_scatter: in[1] offsets [locations + 1]");
+            in_is(2, locations, "entries_scatter: in[2] kstart [locations]");
+            fits32(a.in[2], locations, "entries_scatter: in[2]");
+            need(a.out[0] && a.out_words[0] % stride == 0 && a.out_words[0] / stride >= locations * F && a.out_words[0] / stride <= n, "entries_scatter: out[0] roots [bins][stride], locations * F <= bins <= n");
+            out_is(1, n, "entries_scatter: out[1] counts [n]");
+            for (size_t l = 0; l < locations; l++) {
+                need(a.in[1][l + 1] >= a.in[1][l] && a.in[1][l + 1] - a.in[1][l] <= 0xFFFFFFFFull, "entries_scatter: offsets decrease, or a location holds more than 2^32 - 1 entries");
+                need(bulk_chunk((u32)a.in[2][l], (u32)(a.in[1][l + 1] - a.in[1][l]), (u32)k, max_items - 1).len <= stride, "entries_scatter: a location's chunk is longer than stride");
+            }
+            const size_t count = a.in[1][locations] - a.in[1][0];
+            if (count) in_is(0, 2 * count, "entries_scatter: in[0] items [count][2]");
+            const u64 *ditems = up(a.in[0], 2 * count), *doff = up(a.in[1], locations + 1);
+            const u32 *dk = up32(a.in[2], locations);
+            u64 *droots = up(a.out[0], a.out_words[0]);
+            u32 *dc = ws_as<u32>(n, 1);
+            HIP_CHECK(hipMemsetAsync(dc, 0xee, n * sizeof(u32), st_));  // (the kernel writes every one)
+            launch_entries_scatter(ditems, doff, dk, (u32)locations, (u32)F, bpf, item_bits, max_items - 1, (u32)k, (u32)stride, droots, dc, (u32)n, 0, st_);
+            down(a.out[0], droots, a.out_words[0]);
+            down32(a.out[1], dc, n);
+        } break;
         default: refuse("unknown step");
         }
         sync();

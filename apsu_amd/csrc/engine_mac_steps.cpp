@@ -50,7 +50,7 @@ void canonical_packed(const std::vector<u64> &padded, size_t slots, size_t slot_
 void Engine::debug_run_mac_step(const StepArgs &a)
 {
     const size_t n = hp_.n;
-    need(a.step >= STEP_MAC_INFO && a.step < STEP_COUNT, "unknown step");
+    need(a.step >= STEP_MAC_INFO && a.step <= STEP_LIMB0_ROWS, "unknown step");
     check_level(a.chain_idx);
     const int L = a.chain_idx + 1;
     const bool kara = a.flags & STEP_KARA, packed = a.flags & STEP_PACKED, limb_slow = a.flags & STEP_LIMB_SLOW;

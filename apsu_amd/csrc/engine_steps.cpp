@@ -33,6 +33,7 @@ void Engine::debug_run_step(const StepArgs &a)
 {
     Enter g(this);
     TIER1_SLOTS();
+    if (a.step == STEP_ENTRIES_SCATTER) { debug_run_db_step(a); return; }     // (a database step numbered behind the multiply-accumulate family)
     if (a.step >= STEP_MAC_INFO) { debug_run_mac_step(a); return; }           // the multiply-accumulate family and the packed rows
     if (a.step >= STEP_SEED_EXPAND) { debug_run_query_step(a); return; }      // the querier's side and the decryption
     if (a.step == STEP_ROOTS_SPLIT) { debug_run_db_step(a); return; }         // (a database step numbered behind the transforms)

@@ -1,11 +1,12 @@
 // The resident-database kernels of the query-evaluation engine for gfx950: BinBundle build (polyn_with_roots), update, find and place,
-// merge, BatchEncoder's slot scatter and gather, algebraize and the PEQT block packing.  Rules and lane arithmetic: bin_update.h,
-// bin_lookup.h, bin_merge.h, which the CPU tier runs as well.  (Reading the bins back: kernels_roots.hip.)
+// merge, BatchEncoder's slot scatter and gather, algebraize, the entries' scatter and the PEQT block packing.  Rules and lane arithmetic:
+// bin_update.h, bin_lookup.h, bin_merge.h, bulk_place.h, which the CPU tier runs as well.  (Reading the bins back: kernels_roots.hip.)
 #include "launch_db.h"
 #include "kernel_launch.h"
 #include "bin_update.h"
 #include "bin_lookup.h"
 #include "bin_merge.h"
+#include "bulk_place.h"
 #include "mac_core.h"
 #include <stdexcept>
 #include <type_traits>
@@ -517,6 +518,31 @@ void launch_algebraize(const unsigned char *items, size_t count, u32 felts, u32 
 {
     if (!count) return;
     hipLaunchKernelGGL(k_algebraize, dim3((unsigned)((count * felts + EW_T - 1) / EW_T)), dim3(EW_T), 0, st, items, count, felts, bpf, item_bits, out);
+    KERNEL_CHECK();
+}
+
+// N1, a whole database from its entries (Engine::build_from_entries; bulk_place.h): the root lists of ONE target BinBundle (bundle
+// index, k) straight from the bundle index's post-OPRF items -- a streaming transposition, 16 bytes in and 8 F bytes out per entry.
+// Workgroup (location, block of entries): the lane is the entry (entries_scatter_lane).  Plain vector loads and stores: no atomics, no LDS.
+__global__ __launch_bounds__(SCATTER_T) void k_entries_scatter(const BulkItem *__restrict__ items, const u64 *__restrict__ offsets,
+                                                               const u32 *__restrict__ kstart, u32 locations, u32 F, u32 bpf, u32 item_bits, u32 cap,
+                                                               u32 k, u32 stride, u64 *__restrict__ roots, u32 *__restrict__ counts, u32 n_counts)
+{
+    entries_scatter_lane(items, offsets, kstart, locations, F, bpf, item_bits, cap, k, stride, roots, counts, n_counts, blockIdx.x, blockIdx.y,
+                         gridDim.y, threadIdx.x, SCATTER_T);
+}
+
+void launch_entries_scatter(const void *items, const u64 *offsets, const u32 *kstart, u32 locations, u32 F, u32 bpf, u32 item_bits, u32 cap, u32 k,
+                            u32 stride, u64 *roots, u32 *counts, u32 n_counts, u32 blocks, hipStream_t st)
+{
+    if (!F || F > SCATTER_MAX_F || !bpf || bpf > 64 || (u64)(F - 1) * bpf >= 128) throw std::invalid_argument("entries_scatter: felts_per_item or bits per felt out of range");
+    if (!cap || !stride || stride >= ((u32)1 << 30)) throw std::invalid_argument("entries_scatter: cap or stride out of range");
+    if ((u64)locations * F > n_counts) throw std::invalid_argument("entries_scatter: more bins than count words");
+    if ((uintptr_t)items & 15) throw std::invalid_argument("entries_scatter: the items are not 16-byte aligned");
+    if (!blocks) blocks = scatter_blocks(locations, cap);
+    if (blocks > 65535) throw std::invalid_argument("entries_scatter: more than 65535 workgroups per location");
+    hipLaunchKernelGGL(k_entries_scatter, dim3(locations + 1, blocks), dim3(SCATTER_T), 0, st, static_cast<const BulkItem *>(items), offsets, kstart, locations,
+                       F, bpf, item_bits, cap, k, stride, roots, counts, n_counts);
     KERNEL_CHECK();
 }
 

@@ -58,6 +58,14 @@ void launch_scatter_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n
 void launch_gather_slots(const u64 *in, const u32 *slot_map, u64 *out, size_t n, int batch, hipStream_t st);
 // N1: algebraize_item for `count` 16-byte items -> out[count][felts]; bpf = bits per field element, item_bits = felts * bpf
 void launch_algebraize(const unsigned char *items, size_t count, u32 felts, u32 bpf, u32 item_bits, u64 *out, hipStream_t st);
+// N1, a whole database from its entries (Engine::build_from_entries; bulk_place.h): the root lists of target BinBundle k of one bundle index.
+// contract (launch_entries_scatter): items 16-byte aligned, [offsets[locations] - offsets[0]][16] bytes; offsets [locations + 1] ascending;
+// kstart [locations], any words; 1 <= F <= SCATTER_MAX_F, 1 <= bpf <= 64, (F - 1) bpf < 128; cap >= 1; every location's chunk
+// bulk_chunk(kstart[l], c_l, k, cap).len <= stride < 2^30; locations F <= n_counts.  roots [bins][stride] with bins >= locations F:
+// words r < len of bins l F .. l F + F - 1 are written, no other; counts [n_counts]: all written, 0 from locations F on.
+// blocks: workgroups per location, 0 = scatter_blocks' choice.
+void launch_entries_scatter(const void *items, const u64 *offsets, const u32 *kstart, u32 locations, u32 F, u32 bpf, u32 item_bits, u32 cap, u32 k,
+                            u32 stride, u64 *roots, u32 *counts, u32 n_counts, u32 blocks, hipStream_t st);
 // N4: item -> 128-bit block packing for PEQT
 void launch_pack_blocks(const u64 *values, size_t n, u32 items, u32 felts, u32 len, u64 *out, int batch, hipStream_t st);
 

@@ -83,6 +83,10 @@ public:
     // the EMPTY BinBundles still counted; appended ones placed in order), EMPTY BinBundles dropped, ids renumbered
     ApplyOutcome apply_entries(uint32_t bundle_idx, const u64 *ins_felts, const uint32_t *ins_start, size_t n_ins, const u64 *rem_felts,
                                const uint32_t *rem_start, size_t n_rem);
+    // Engine::build_from_entries on the handle (host entries): the plan once on the host, BinBundle (b, k) on the slot place_new_unit gives
+    // it, in (b, k) order, the loads taken as each one registers; every device copies the entries of the bundle indices it builds for.
+    // Refuses a handle that holds a BinBundle of a bundle index that receives entries.  -> (first id, BinBundles built), ids dense
+    std::pair<int, uint32_t> build_from_entries(const unsigned char *entries, const u64 *offsets);
     // Engine::merge_bundles on the given BinBundles of one bundle index, wherever they lie: members that are not on merge_home travel
     // there as temporaries; the merged BinBundle takes the first member's (cache order) id slot and cache_idx, the others are dropped
     void merge_bundles(const int *ids, uint32_t n_ids, int *new_id);

@@ -309,6 +309,43 @@ MultiEngine::ApplyOutcome MultiEngine::apply_entries(uint32_t bundle_idx, const 
     return res;
 }
 
+std::pair<int, uint32_t> MultiEngine::build_from_entries(const unsigned char *entries, const u64 *offsets)
+{
+    std::lock_guard<std::mutex> g(mu_);
+    const uint32_t ipb = psu_.items_per_bundle, cap = psu_.table_params.max_items_per_bin - 1;
+    const BulkPlan plan = devs_[0]->eng->entries_plan(offsets);    // every refusal of the plan comes before any GPU work
+    if (plan.total > 0xFFFFFFFFull) throw std::invalid_argument("build_from_entries: more than 2^32 - 1 BinBundles");
+    const std::vector<RegUnit> reg = registry_locked();
+    for (const RegUnit &u : reg)
+        if (plan.bundles[u.bundle_idx])
+            throw std::invalid_argument("build_from_entries: bundle index " + std::to_string(u.bundle_idx) + " receives entries but holds a BinBundle already: "
+                                        "entries are added to a database that exists with apply_entries");
+    if (!entries && plan.total) throw std::invalid_argument("null argument");
+    // the slots, in (b, k) order, the loads as each one registers
+    std::vector<uint64_t> load = device_loads(reg, (int)devs_.size());
+    std::vector<int> slot((size_t)plan.total);
+    size_t at = 0;
+    for (uint32_t b = 0; b < plan.bundles.size(); b++)
+        for (uint32_t k = 0; k < plan.bundles[b]; k++, at++) {
+            slot[at] = place_new_unit(b, psu_.bundle_idx_count, (int)devs_.size(), load.data());
+            load[(size_t)slot[at]] += unit_cost(bulk_degree(offsets + (size_t)b * ipb, plan.kstart.data() + (size_t)b * ipb, ipb, k, cap));
+        }
+    std::vector<std::unique_ptr<Bundle>> built((size_t)plan.total);
+    run_all([&](Dev &d) {
+        std::vector<unsigned char> want((size_t)plan.total);
+        bool any = false;
+        for (size_t i = 0; i < want.size(); i++) any |= (want[i] = slot[i] == d.slot) != 0;
+        if (!any) return;
+        std::vector<std::unique_ptr<Bundle>> mine = d.eng->build_from_entries(entries, false, offsets, want.data());
+        for (size_t i = 0; i < want.size(); i++)
+            if (want[i]) built[i] = std::move(mine[i]);
+    });
+    Change c(reg.size());
+    for (size_t i = 0; i < built.size(); i++) c.appended.push_back({ slot[i], std::move(built[i]) });
+    commit(c, nullptr, nullptr);
+    return { (int)reg.size(), (uint32_t)plan.total };
+}
+
 // one merged BinBundle per group (ids in cache order), made on merge_home; groups with different homes run side by side
 std::vector<std::unique_ptr<Bundle>> MultiEngine::merge_groups(const std::vector<std::vector<int>> &groups)
 {

@@ -177,7 +177,7 @@ STEPS = {name: i for i, name in enumerate((
     "polyn_with_roots", "bins_update", "bin_counts", "poly_degree", "bins_lookup", "bins_merge", "bins_rows", "bins_eval", "eval_compare", "roots",
     "unlift", "ntt_info", "ntt", "ntt_gather", "intt_tensor", "roots_split",
     "seed_expand", "decrypt_round", "plain_powers", "sample_small", "small_lift", "enc_finish", "rlk_finish", "flag_monomial",
-    "mac_info", "mac", "term_product", "pack_rows", "unpack_rows", "limb0_rows"))}
+    "mac_info", "mac", "term_product", "pack_rows", "unpack_rows", "limb0_rows", "entries_scatter"))}
 STEP_RAW, STEP_ACCUMULATE, STEP_STORE, STEP_KEY, STEP_PLAN, STEP_COMPOSED, STEP_INVERSE, STEP_NORED = 1, 2, 4, 8, 16, 32, 64, 128
 STEP_KARA, STEP_PACKED, STEP_LIMB_SLOW = 256, 512, 1024      # the multiply-accumulate steps: three products, bit-packed plaintexts, grid order
 STEP_MAP_RAW = 1 << 30                 # in a map entry of an inverse transform step: that limb comes back RAW
@@ -779,6 +779,56 @@ class HeContext:
                 out[b] = self.apply_entries(list(bundles_by_index.get(b, [])), inserts=(felts[lo:hi], start), bundle_idx=b)
         return out
 
+    # ---- N1: a whole database from its entries (include/apsu_he.h: apsu_he_db_build_from_entries)
+    def _offsets(self, offsets):
+        T, _ = self._table_params()
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.shape != (T + 1,):
+            raise ValueError("offsets: table_size + 1 words, as bucket_items returns them")
+        return offsets
+
+    def entries_plan(self, offsets):
+        """offsets of bucket_items -> BinBundles per bundle index [bundle_idx_count] uint32, as build_database will make them
+        (apsu_he_db_entries_plan; the host half alone)"""
+        offsets = self._offsets(offsets)
+        per_index = np.zeros(self.bundle_idx_count, dtype=np.uint32)
+        total = C.c_uint32()
+        _check(load_library().apsu_he_db_entries_plan(self.h, _p(offsets), C.c_void_p(per_index.ctypes.data), C.byref(total)))
+        assert int(per_index.sum()) == total.value
+        return per_index
+
+    def build_database(self, entries, offsets, count=None):
+        """The resident database of the post-OPRF items entries [offsets[-1]][16] uint8, location by location in bucket_items' order ->
+        its Bundles, bundle index by bundle index, in cache order within each (apsu_he_db_build_from_entries).  ReceiverDB::set_data
+        on an empty database; no entry-level dedupe: two equal entries of one location are a double root of their bins.  entries
+        may be a device pointer (int).  All or nothing."""
+        offsets = self._offsets(offsets)
+        per_index = self.entries_plan(offsets)
+        total = int(per_index.sum())
+        on_dev = isinstance(entries, int)
+        if not on_dev:
+            entries = self._items16(entries)
+            if entries.shape[0] != int(offsets[-1]):
+                raise ValueError("build_database: %d entries, offsets name %d" % (entries.shape[0], int(offsets[-1])))
+        hs = (C.c_void_p * max(total, 1))()
+        n_out = C.c_uint32()
+        _check(load_library().apsu_he_db_build_from_entries(self.h, C.c_void_p(entries if on_dev else entries.ctypes.data), 1 if on_dev else 0, _p(offsets),
+                                                            hs, C.c_uint32(total if count is None else int(count)), C.byref(n_out)))
+        assert n_out.value == total
+        ids = [(b, k) for b in range(self.bundle_idx_count) for k in range(int(per_index[b]))]
+        return [self._wrap_new(hs[i], b, k) for i, (b, k) in enumerate(ids)]
+
+    def build_times(self):
+        """-> (the entries' copies, k_entries_scatter, the builds) ms: device time of the last build_database call, summed over its
+        bundle indices and BinBundles"""
+        v = [C.c_double() for _ in range(3)]
+        _check(load_library().apsu_he_debug_build_from_entries_times(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def set_scatter_blocks(self, blocks):
+        """measurements: workgroups per location of k_entries_scatter in the build_database calls that follow; 0 = the engine's choice"""
+        _check(load_library().apsu_he_debug_set_scatter_blocks(self.h, C.c_uint32(blocks)))
+
     def cuckoo_table(self, items, max_rounds=500):
         """the querier's table by the engine's deterministic rule -> (table_idx [table_size] uint32: item or 0xFFFFFFFF, item_loc
         [count] uint32: location, 0xFFFFFFFF for a repeated item, rounds); apsu_he_cuckoo_table.  An item without a slot after
@@ -1242,6 +1292,19 @@ class MultiContext:
             self.h, C.c_uint32(bundle_idx), _p(fi), u32(si), C.c_size_t(len(si)), _p(fr), u32(sr), C.c_size_t(len(sr)), p, C.byref(n_app),
             *[u32(a) for a in out])), extra=len(si))
         return MultiApplyResult(new_id[:len(new_id) - len(si) + n_app.value], n_app.value, *out)
+
+    def build_database(self, entries, offsets):
+        """HeContext.build_database on the handle (host entries): BinBundle (bundle index, k) on the slot the placement rule gives
+        it, in that order -> the new ids, appended densely.  Refused where the handle already holds a BinBundle of a bundle index
+        that receives entries.  All or nothing."""
+        entries = np.ascontiguousarray(entries, dtype=np.uint8).reshape(-1, 16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.ndim != 1 or not len(offsets) or entries.shape[0] != int(offsets[-1]):
+            raise ValueError("build_database: entries and offsets do not match")
+        first, built = C.c_int(), C.c_uint32()
+        _check(load_library().apsu_he_multi_db_build_from_entries(self.h, C.c_void_p(entries.ctypes.data), _p(offsets), C.byref(first), C.byref(built)))
+        self.bundle_count()
+        return list(range(first.value, first.value + built.value))
 
     def merge_bundles(self, bundle_ids):
         """HeContext.merge_bundles on BinBundles of one bundle index, wherever they lie -> new_id (the merged BinBundle takes the place

@@ -228,6 +228,41 @@ int apsu_he_db_apply_entries(apsu_he_ctx *ctx, uint32_t bundle_idx, const apsu_h
                              uint32_t *rem_status, uint32_t *rem_target);
 /* device time of the context's last call of the three above, summed over its BinBundles: the decode, and the kernels behind it */
 int apsu_he_debug_lookup_times(apsu_he_ctx *ctx, double *decode_ms, double *kernels_ms);
+/* N1, a whole database from its entries in one call: ReceiverDB::set_data, which is clear plus the insertion loop on an EMPTY database
+ * (receiver_db.cpp:349-434).  apsu_he_db_apply_entries is the incremental path: it looks every entry up and places it on the host, one
+ * by one.  From empty that loop has a closed form, because the bins of two cuckoo locations of one bundle index never overlap (location
+ * l owns bins (l % items_per_bundle) F .. + F - 1): "BinBundles newest first, strictly below max_items_per_bin, else a new one"
+ * reduces to one running number per bundle index.
+ *  - cap = max_items_per_bin - 1 entries of one location fit one BinBundle.  K_l = the BinBundles of l's bundle index when location l
+ *    begins = the largest ceil(c_l' / cap) over the earlier locations l' of that index (c = entries of a location).  Entry i of
+ *    location l, 0-based in list order, is in chunk m = i / cap; it goes to BinBundle K_l - 1 - m if m < K_l, else to BinBundle m, at
+ *    position i - m cap of its bins.  The BinBundles of an index are numbered from 0 in the order the loop opens them: cache_idx = k, as
+ *    apsu_he_db_apply_entries numbers BinBundles appended to an empty index.
+ *  - entries [offsets[table_size]][16]: the post-OPRF items in apsu_he_items_bucket's order (the OPRF runs per location between the
+ *    bucketing and this call, receiver_db.cpp:290-299), host memory or, with entries_on_device, device memory of the context's device;
+ *    offsets [table_size + 1]: host.  Per bundle index its entries are copied once; per BinBundle one kernel (k_entries_scatter) splits
+ *    every item into its field elements (apsu_he_algebraize_items' rule) and writes them into the BinBundle's root lists on the device,
+ *    which the build consumes there.  No entry is touched on the host and no host-side copy of the bins exists.
+ *  - NO entry-level dedupe: the reference's loop has none (hashed_items_ dedupes ITEMS before the OPRF).  Two equal entries of one
+ *    location put a double root into their bins, and the result is apsu_he_db_build_bundle of bins that hold that root twice.  For
+ *    lists whose entries are distinct per location the result is, byte for byte (apsu_he_bundle_save), what apsu_he_db_apply_entries
+ *    appends per bundle index when it starts from no BinBundle.
+ *  - apsu_he_db_entries_plan: the host half alone.  bundles_per_index [bundle_idx_count] (may be NULL), *total their sum.
+ *  - apsu_he_db_build_from_entries: out[i], i < *n_out = the plan's total, bundle index by bundle index, in cache order within each; a
+ *    bundle index without entries gets no BinBundle.  capacity below the total: APSU_HE_INVALID_ARGUMENT with the needed count in the
+ *    error text (and in *n_out), nothing built.  All or nothing: on any failure no handle is produced.
+ *  - Refused (APSU_HE_INVALID_ARGUMENT): offsets that decrease, a location with more than 2^32 - 1 entries, max_items_per_bin < 2
+ *    (cap would be 0).  Preconditions: PSUParams and batching.  Synchronous.
+ * Out of scope: building onto a bundle index that already has BinBundles (the incremental call's), and bucketing on the device.
+ * apsu_he_debug_build_from_entries_times: device time of the context's last such call, summed over bundle indices and BinBundles: the
+ * entries' copies, k_entries_scatter, the builds.
+ * apsu_he_debug_set_scatter_blocks (measurements): workgroups per location of k_entries_scatter in the calls that follow; 0, the
+ * default, = one per 256 entries of a full chunk, fewer where the grid would pass about 16384 workgroups.  The results do not depend on it. */
+int apsu_he_db_entries_plan(const apsu_he_ctx *ctx, const uint64_t *offsets, uint32_t *bundles_per_index, uint32_t *total);
+int apsu_he_db_build_from_entries(apsu_he_ctx *ctx, const uint8_t *entries, int entries_on_device, const uint64_t *offsets,
+                                  apsu_he_bundle **out, uint32_t capacity, uint32_t *n_out);
+int apsu_he_debug_build_from_entries_times(apsu_he_ctx *ctx, double *copy_ms, double *scatter_ms, double *build_ms);
+int apsu_he_debug_set_scatter_blocks(apsu_he_ctx *ctx, uint32_t blocks);
 /* N1, reading the bins back: the items of a resident BinBundle, read from its polynomials -- the one question apsu_he_bundles_lookup
  * cannot answer, since it takes values the caller already knows.  With it a database that came from an image, a DB file or a
  * reference-saved cache can be rebuilt for other parameters (apsu_he_db_build_bundle of the bins in another context), audited, or counted
@@ -410,6 +445,12 @@ int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_
  *   PACK_ROWS       batch = slots; in[0] dense [slots][L][n] -> out[0] the bit-packed slots, then two words (16 bytes) that no row owns
  *   UNPACK_ROWS     batch = slots; in[0] the bit-packed slots -> out[0] dense [slots][L][n]
  *   LIMB0_ROWS      batch = count (1 .. 65535); in[0] [count] slots, dense or PACKED -> out[0] [count][n], limb 0 of every slot
+ *   ENTRIES_SCATTER (a database step, no chain level) ONE launch_entries_scatter for target BinBundle k = e0 of one bundle index:
+ *                   batch = locations, polys = F, terms = stride; bits per field element, item_bit_count and cap = max_items_per_bin
+ *                   - 1 are the context's.  in[0] items [count][2] words, count = offsets[batch] - offsets[0]; in[1] offsets [batch + 1];
+ *                   in[2] kstart [batch], one word each -> out[0] roots [bins][stride], in/out (bins from its size, locations * F <=
+ *                   bins <= n; the words nobody writes keep what they held), out[1] counts [n].  Refused: a chunk longer than stride,
+ *                   offsets that decrease, F above 64 or (F - 1) * bits per field element >= 128, sizes that do not match.
  * Refused like the others, nothing launched: a chain_idx that is no data level; n no multiple of 64; PACKED in a context whose rows
  * are all 64 bits wide; for MAC polys outside 1 .. 4, terms 0 (or a cnt of 0), limb0 + nl beyond the level, P below L, KARA on a
  * level with a prime that mac_kara_usable rejects (59 and 60 bits), a job-table entry outside the ranges above; for MAC and
@@ -428,7 +469,8 @@ enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEH
        APSU_HE_STEP_SEED_EXPAND, APSU_HE_STEP_DECRYPT_ROUND, APSU_HE_STEP_PLAIN_POWERS, APSU_HE_STEP_SAMPLE_SMALL, APSU_HE_STEP_SMALL_LIFT,
        APSU_HE_STEP_ENC_FINISH, APSU_HE_STEP_RLK_FINISH, APSU_HE_STEP_FLAG_MONOMIAL,
        APSU_HE_STEP_MAC_INFO, APSU_HE_STEP_MAC, APSU_HE_STEP_TERM_PRODUCT, APSU_HE_STEP_PACK_ROWS, APSU_HE_STEP_UNPACK_ROWS,
-       APSU_HE_STEP_LIMB0_ROWS };
+       APSU_HE_STEP_LIMB0_ROWS,
+       APSU_HE_STEP_ENTRIES_SCATTER };
 enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8, APSU_HE_STEP_PLAN = 16,
        APSU_HE_STEP_COMPOSED = 32, APSU_HE_STEP_INVERSE = 64, APSU_HE_STEP_NORED = 128, APSU_HE_STEP_KARA = 256, APSU_HE_STEP_PACKED = 512,
        APSU_HE_STEP_LIMB_SLOW = 1024 };
@@ -855,6 +897,10 @@ int apsu_he_multi_db_update_bundle(apsu_he_multi *m, int bundle_id, const uint64
  *   are OLD ids: the id a BinBundle had before the call, and (count before the call) + k for the k-th appended BinBundle; new_id
  *   [count before the call + *n_appended, at most + n_ins] translates them.  EMPTY BinBundles are dropped by the call itself.  Appended
  *   BinBundles are placed one after the other, against the loads as the call's updates left them (an EMPTY BinBundle still counts).
+ * apsu_he_multi_db_build_from_entries: apsu_he_db_build_from_entries on the handle (host entries only).  The plan is computed once on
+ *   the host; BinBundle (bundle index b, k) is built on the slot the placement rule gives it, in (b, k) order, the loads taken as each one
+ *   registers; ids are appended densely: *first_id = the count before the call, *n_built the plan's total.  Refused if the handle
+ *   already holds a BinBundle of a bundle index that receives entries (that case is apsu_he_multi_db_apply_entries').  All or nothing.
  * apsu_he_multi_db_merge_bundles: apsu_he_bundles_merge on n_ids >= 2 BinBundles of one bundle index, wherever they lie.  The merged
  *   BinBundle takes the id slot and the cache_idx of the first member in cache order; the others are dropped.  new_id[count before the call].
  * apsu_he_multi_db_compact: apsu_he_db_compact's rule on apsu_he_multi_db_index_bundles(bundle_idx), one merge per group of two or more;
@@ -874,6 +920,7 @@ int apsu_he_multi_db_lookup(apsu_he_multi *m, uint32_t bundle_idx, const uint64_
 int apsu_he_multi_db_apply_entries(apsu_he_multi *m, uint32_t bundle_idx, const uint64_t *ins_felts, const uint32_t *ins_start, size_t n_ins,
                                    const uint64_t *rem_felts, const uint32_t *rem_start, size_t n_rem, int *new_id, uint32_t *n_appended,
                                    uint32_t *ins_status, uint32_t *ins_target, uint32_t *rem_status, uint32_t *rem_target);
+int apsu_he_multi_db_build_from_entries(apsu_he_multi *m, const uint8_t *entries, const uint64_t *offsets, int *first_id, uint32_t *n_built);
 int apsu_he_multi_db_merge_bundles(apsu_he_multi *m, const int *bundle_ids, uint32_t n_ids, int *new_id);
 int apsu_he_multi_db_compact(apsu_he_multi *m, uint32_t bundle_idx, int *new_id, uint32_t *n_merged);
 /* One query on all devices (receiver_osn.cpp:304-364): src_cts[b * source_power_count + s] = host ciphertext of source
