@@ -474,6 +474,24 @@ int apsu_he_items_bucket(apsu_he_ctx *c, const uint8_t *items, size_t count, int
         c->eng->items_bucket(items, count, items_on_device != 0, offsets, order, total);
     });
 }
+int apsu_he_items_bucket_device(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t *offsets, uint32_t *order,
+                                int order_on_device, uint8_t *entries, int entries_on_device, uint64_t *total)
+{
+    return guarded([&] {
+        REQUIRE(c && offsets && total && (!count || items), "null argument");
+        c->eng->items_bucket_device(items, count, items_on_device != 0, offsets, order, order_on_device != 0, entries, entries_on_device != 0, total);
+    });
+}
+int apsu_he_debug_bucket_locs(apsu_he_ctx *c, const uint32_t *locs, size_t count, uint32_t hash_func_count, uint32_t table_size, uint32_t tile_entries,
+                              uint64_t *offsets, uint32_t *order, uint64_t *total)
+{
+    return guarded([&] {
+        REQUIRE(c && offsets && total && (!count || (locs && order)), "null argument");
+        c->eng->debug_bucket_locs(locs, count, hash_func_count, table_size, tile_entries, offsets, order, total);
+    });
+}
+int apsu_he_debug_bucket_times(apsu_he_ctx *c, double *locs_ms, double *sort_ms, double *gather_ms)
+{ return read_op_times(c, Engine::OP_BUCKET, { locs_ms, sort_ms, gather_ms }); }
 int apsu_he_cuckoo_table(apsu_he_ctx *c, const uint8_t *items, size_t count, int items_on_device, uint64_t max_rounds, uint32_t *table_idx,
                          uint32_t *item_loc, uint64_t *rounds)
 {

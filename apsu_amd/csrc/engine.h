@@ -193,7 +193,8 @@ public:
     //                 to the host, the plaintexts' serialisation, the buffer's assembly (host clock)
     //   OP_SPLIT      (split_bundle) decode and counts, the root search and multiplicities, k_roots_split, the parts' builds
     //   OP_BUILD      (build_from_entries, summed over the bundle indices and BinBundles) the entries' copies, k_entries_scatter, the builds
-    enum Op { OP_LOOKUP = 0, OP_BINS, OP_MERGE, OP_EVAL_PLAIN, OP_SELF_TEST, OP_EXPORT, OP_SPLIT, OP_BUILD, OP_COUNT };
+    //   OP_BUCKET     (items_bucket_device) k_cuckoo_locations, the grouping (keys, passes, offsets and order), k_entries_gather
+    enum Op { OP_LOOKUP = 0, OP_BINS, OP_MERGE, OP_EVAL_PLAIN, OP_SELF_TEST, OP_EXPORT, OP_SPLIT, OP_BUILD, OP_BUCKET, OP_COUNT };
     static constexpr int OP_SPANS = 6;
     void op_times(Op op, double *ms, int count);
     struct ApplyResult {
@@ -282,6 +283,14 @@ public:
     void items_bucket(const unsigned char *items, size_t count, bool items_on_device, u64 *offsets, uint32_t *order, u64 *total);
     void cuckoo_table(const unsigned char *items, size_t count, bool items_on_device, u64 max_rounds, uint32_t *table_idx, uint32_t *item_loc, u64 *rounds);
     void query_values(const unsigned char *table_items, bool on_device, u64 *values, bool values_on_device);
+    // items_bucket with the grouping and the gather on the device (include/apsu_he.h: apsu_he_items_bucket_device; bucket_plan.h,
+    // kernels_bucket.hip): the same offsets (host) and order, and entries[k] = items[order[k]] as build_from_entries reads them.  order
+    // and entries may be null, and host or device memory as flagged; only offsets must visit the host.
+    void items_bucket_device(const unsigned char *items, size_t count, bool items_on_device, u64 *offsets, uint32_t *order, bool order_on_device,
+                             unsigned char *entries, bool entries_on_device, u64 *total);
+    // test hook: the grouping alone on caller-given locations locs[count][H] (host) in tiles of `tile` keys (0: BUCKET_TILE_DEFAULT), any
+    // context; offsets [T + 1] and order (count * H words of room, host).  A location >= T: std::invalid_argument, nothing written.
+    void debug_bucket_locs(const uint32_t *locs, size_t count, uint32_t H, uint32_t T, uint32_t tile, u64 *offsets, uint32_t *order, u64 *total);
     // test hook: k_cuckoo_insert alone on caller-given items and locations locs[count][H] (host), any context.  form: where the table
     // lives -- the engine's choice, LDS (std::logic_error where table_size slots do not fit), or device memory
     enum { CUCKOO_FORM_AUTO = 0, CUCKOO_FORM_LDS = 1, CUCKOO_FORM_GLOBAL = 2 };
@@ -642,6 +651,8 @@ private:
     DevBuf d_cuckoo_tabs_;                             // [hash_func_count][16][256] words, made by the first call that hashes
     void cuckoo_tables_ready();
     const unsigned char *cuckoo_items(const unsigned char *items, size_t count, bool on_device);     // 16-byte aligned device memory (inside WITH_ARENA)
+    struct BucketOut { u64 *offsets, *total; };        // device: [T + 1] and one word
+    BucketOut bucket_run(const uint32_t *dlocs, size_t count, uint32_t H, uint32_t T, uint32_t tile, uint32_t *dorder);   // (inside WITH_ARENA)
     // inside the caller's WITH_ARENA: the launch, the status, then the copies to the host; throws for an unplaced item before any copy
     void cuckoo_insert_run(const unsigned char *ditems, const uint32_t *dlocs, uint32_t count, uint32_t H, uint32_t T, u64 max_rounds, int form,
                            uint32_t *table_idx, uint32_t *item_loc, u64 *rounds);

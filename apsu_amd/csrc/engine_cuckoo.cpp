@@ -2,6 +2,7 @@
 // querier's table and its slot values.  Shares the arena and the stream with the other calls (engine_impl.h).
 #include "engine_impl.h"
 #include "launch_cuckoo.h"
+#include "launch_bucket.h"
 
 namespace apsu_he {
 
@@ -74,6 +75,100 @@ void Engine::items_bucket(const unsigned char *items, size_t count, bool items_o
     std::vector<u32> locs(count * H);
     item_locations(items, count, items_on_device, locs.data(), false);
     if (!cuckoo_bucket(locs.data(), count, H, T, offsets, order, total)) throw std::runtime_error("items_bucket: a location outside the table");
+}
+
+// ---- the grouping on the device (bucket_plan.h, kernels_bucket.hip).  Inside WITH_ARENA: dlocs [count][H] -> offsets [T + 1] and the
+// total in the arena, order [count * H] where the caller says; everything is queued, nothing waited for
+Engine::BucketOut Engine::bucket_run(const u32 *dlocs, size_t count, u32 H, u32 T, u32 tile, u32 *dorder)
+{
+    const BucketSizes s = bucket_sizes(count, H, T, tile);
+    BucketWork w{};
+    w.keys[0] = ws(s.keys);
+    w.keys[1] = ws(s.keys);
+    w.tile_cnt = ws_as<u32>(s.tile_cnt);
+    w.tile_base = ws(s.tile_base);
+    w.hist = ws_as<u32>(s.hist);
+    w.wave_cnt = ws_as<u32>(s.wave_cnt);
+    w.scanned = ws(s.scanned);
+    w.total = ws(1);
+    BucketOut out{};
+    out.offsets = ws((size_t)T + 1);
+    out.total = w.total;
+    { PROF(P_OTHER, 0); launch_bucket_sort(dlocs, count, H, T, tile, w, out.offsets, dorder, st_); }
+    return out;
+}
+
+void Engine::items_bucket_device(const unsigned char *items, size_t count, bool items_on_device, u64 *offsets, uint32_t *order, bool order_on_device,
+                                 unsigned char *entries, bool entries_on_device, u64 *total)
+{
+    if (count >= CUCKOO_NONE) throw std::invalid_argument("items_bucket_device: more items than a 32-bit index names");
+    Enter g(this);
+    lookup_check(nullptr, NEED_PSU);
+    const u32 H = psu_.table_params.hash_func_count, T = psu_.table_params.table_size;
+    OpClock &clk = clock_[OP_BUCKET];
+    for (double &m : clk.ms) m = 0;
+    for (size_t l = 0; l <= T; l++) offsets[l] = 0;
+    *total = 0;
+    if (!count) return;
+    cuckoo_tables_ready();
+    TIER1_SLOTS();
+    clk.evs.reserve(4);                                                // around the locations, the grouping and the gather
+    const u64 room = (u64)count * H;
+    WITH_ARENA({
+        const unsigned char *src = cuckoo_items(items, count, items_on_device);
+        u32 *dlocs = ws_as<u32>(room);
+        u32 *dorder = order && order_on_device ? order : ws_as<u32>(room);
+        unsigned char *dent = !entries ? nullptr : entries_on_device && !((uintptr_t)entries & 15) ? entries : ws_as<unsigned char>(room * 16 + 16);
+        clk.evs.record(0, st_);
+        { PROF(P_OTHER, 0); launch_cuckoo_locations(src, count, reinterpret_cast<const u32 *>(d_cuckoo_tabs_.p()), H, T, dlocs, 0, st_); }
+        clk.evs.record(1, st_);
+        const BucketOut out = bucket_run(dlocs, count, H, T, BUCKET_TILE_DEFAULT, dorder);
+        clk.evs.record(2, st_);
+        if (dent) { PROF(P_OTHER, 0); launch_entries_gather(src, dorder, out.total, room, dent, st_); }
+        clk.evs.record(3, st_);
+        HIP_CHECK(hipMemcpyAsync(offsets, out.offsets, ((size_t)T + 1) * sizeof(u64), hipMemcpyDeviceToHost, st_));
+        sync();
+        const u64 n = offsets[T];
+        if (order && !order_on_device && n) HIP_CHECK(hipMemcpyAsync(order, dorder, n * sizeof(u32), hipMemcpyDeviceToHost, st_));
+        if (entries && dent != entries && n) HIP_CHECK(hipMemcpyAsync(entries, dent, n * 16, entries_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st_));
+        sync();
+    });
+    *total = offsets[T];
+    for (int k = 0; k < 3; k++) clk.ms[k] = clk.evs.ms(k, k + 1);
+}
+
+void Engine::debug_bucket_locs(const uint32_t *locs, size_t count, uint32_t H, uint32_t T, uint32_t tile, u64 *offsets, uint32_t *order, u64 *total)
+{
+    Enter g(this);
+    if (!H || H > CUCKOO_MAX_FUNCS || !T) throw std::invalid_argument("debug_bucket_locs: 1 <= H <= 8 and T >= 1");
+    if (count >= CUCKOO_NONE) throw std::invalid_argument("debug_bucket_locs: more items than a 32-bit index names");
+    if (!tile) tile = BUCKET_TILE_DEFAULT;
+    if (!bucket_tile_ok(tile))
+        throw std::invalid_argument("debug_bucket_locs: tile_entries must be a multiple of " + std::to_string(BUCKET_TILE_STEP) + " in [" +
+                                    std::to_string(BUCKET_TILE_MIN) + ", " + std::to_string(BUCKET_TILE_MAX) + "]");
+    for (size_t k = 0; k < count * H; k++)
+        if (locs[k] >= T) throw std::invalid_argument("debug_bucket_locs: location " + std::to_string(k) + " is outside the table");
+    OpClock &clk = clock_[OP_BUCKET];
+    for (double &m : clk.ms) m = 0;
+    for (size_t l = 0; l <= T; l++) offsets[l] = 0;
+    *total = 0;
+    if (!count) return;
+    TIER1_SLOTS();
+    clk.evs.reserve(4);
+    WITH_ARENA({
+        u32 *dlocs = ws_as<u32>(count * H);
+        u32 *dorder = ws_as<u32>(count * H);
+        HIP_CHECK(hipMemcpyAsync(dlocs, locs, count * H * sizeof(u32), hipMemcpyHostToDevice, st_));
+        clk.evs.record(1, st_);
+        const BucketOut out = bucket_run(dlocs, count, H, T, tile, dorder);
+        clk.evs.record(2, st_);
+        HIP_CHECK(hipMemcpyAsync(offsets, out.offsets, ((size_t)T + 1) * sizeof(u64), hipMemcpyDeviceToHost, st_));
+        sync();
+        if (offsets[T]) HIP_CHECK(hipMemcpyAsync(order, dorder, offsets[T] * sizeof(u32), hipMemcpyDeviceToHost, st_));
+        sync();
+    });
+    *total = offsets[T];
+    clk.ms[1] = clk.evs.ms(1, 2);
 }
 
 void Engine::cuckoo_insert_run(const unsigned char *ditems, const u32 *dlocs, u32 count, u32 H, u32 T, u64 max_rounds, int form, uint32_t *table_idx,

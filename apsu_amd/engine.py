@@ -268,6 +268,7 @@ class HeContext:
             q = np.array(coeff_modulus, dtype=np.uint64)
             _check(L.apsu_he_create_raw(C.c_uint64(n), _p(q), len(q), C.c_uint64(plain_modulus), device, C.byref(h)))
         self.h = h
+        self.device = int(device)
         info = _Info()
         _check(L.apsu_he_get_info(self.h, C.byref(info)))
         self.info = info
@@ -745,6 +746,75 @@ class HeContext:
         _check(load_library().apsu_he_items_bucket(self.h, C.c_void_p(items.ctypes.data), C.c_size_t(items.shape[0]), 0, _p(offsets),
                                                    C.c_void_p(order.ctypes.data), C.byref(total)))
         return offsets, order[:total.value].copy()
+
+    def bucket_items_device(self, items, count=None, order=None, entries=None):
+        """bucket_items with the grouping and the gather on the device (apsu_he_items_bucket_device) -> (offsets [table_size + 1] uint64,
+        order [total] uint32, entries [total][16] uint8 = items[order], total).  items may be a device pointer (int; `count` then says how
+        many items).  order / entries: True (the default, None, too) returns the array; False leaves it out (None in its place); a device
+        pointer (int) with room for count * hash_func_count words / 16-byte entries is written to instead, and None is returned in its
+        place.  Only offsets visit the host then."""
+        T, H = self._table_params()
+        on_dev = isinstance(items, int) and not isinstance(items, bool)
+        if not on_dev:
+            items = self._items16(items)
+            count = items.shape[0]
+        elif count is None:
+            raise ValueError("bucket_items_device: a device pointer needs its count")
+        is_ptr = lambda x: isinstance(x, int) and not isinstance(x, bool)
+        want = lambda x: x is None or x is True
+        room = max(count * H, 1)
+        h_order = np.zeros(room, dtype=np.uint32) if want(order) else None
+        h_entries = np.zeros((room, 16), dtype=np.uint8) if want(entries) else None
+        offsets = np.zeros(T + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        arg = lambda host, given: C.c_void_p(host.ctypes.data) if host is not None else C.c_void_p(int(given) if is_ptr(given) else None)
+        _check(load_library().apsu_he_items_bucket_device(self.h, C.c_void_p(items if on_dev else items.ctypes.data), C.c_size_t(count), 1 if on_dev else 0,
+                                                          _p(offsets), arg(h_order, order), 1 if is_ptr(order) else 0,
+                                                          arg(h_entries, entries), 1 if is_ptr(entries) else 0, C.byref(total)))
+        n = total.value
+        return (offsets, None if h_order is None else h_order[:n].copy(), None if h_entries is None else h_entries[:n].copy(), n)
+
+    def bucket_times(self):
+        """-> (k_cuckoo_locations, the grouping, k_entries_gather) ms: device time of the last bucket_items_device call"""
+        v = [C.c_double() for _ in range(3)]
+        _check(load_library().apsu_he_debug_bucket_times(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def debug_bucket_locs(self, locs, table_size, tile_entries=0, order=None, offsets=None):
+        """test hook: the device grouping alone on caller-given locations locs [count][H] -> (offsets [table_size + 1], order, total).
+        order, offsets: arrays of count * H uint32 / table_size + 1 uint64 words to write into (the whole arrays are returned, so that a
+        test sees the words past total, and what a refusal left)"""
+        locs = np.ascontiguousarray(locs, dtype=np.uint32)
+        if locs.ndim != 2 or not locs.shape[1]:
+            raise ValueError("debug_bucket_locs: locs must be [count][H]")
+        count, H = locs.shape
+        if offsets is None:
+            offsets = np.zeros(max(table_size, 0) + 1, dtype=np.uint64)
+        if order is None:
+            order = np.zeros(max(count * H, 1), dtype=np.uint32)
+        assert order.dtype == np.uint32 and order.flags["C_CONTIGUOUS"] and order.size >= count * H
+        total = C.c_uint64()
+        _check(load_library().apsu_he_debug_bucket_locs(self.h, C.c_void_p(locs.ctypes.data), C.c_size_t(count), C.c_uint32(H), C.c_uint32(table_size),
+                                                        C.c_uint32(tile_entries), _p(offsets), C.c_void_p(order.ctypes.data), C.byref(total)))
+        return offsets, order, total.value
+
+    def build_database_from_items(self, items, oprf=None):
+        """The resident database of `items` [count][16]: bucket_items_device with gathered entries, then build_database.  oprf None: the
+        entries stay on the device between the two calls.  Otherwise they are downloaded, oprf(entries [total][16], offsets) returns
+        the post-OPRF entries [total][16], and the database is built from those.  -> the Bundles, as build_database returns them."""
+        import torch
+        T, H = self._table_params()
+        items = self._items16(items)
+        if oprf is None:
+            buf = torch.empty(max(items.shape[0] * H, 1) * 16, dtype=torch.uint8, device="cuda:%d" % self.device)
+            torch.cuda.synchronize(buf.device)
+            offsets, _, _, total = self.bucket_items_device(items, order=False, entries=buf.data_ptr())
+            return self.build_database(buf.data_ptr(), offsets)
+        offsets, _, entries, total = self.bucket_items_device(items, order=False)
+        hashed = self._items16(oprf(entries, offsets))
+        if hashed.shape[0] != total:
+            raise ValueError("build_database_from_items: oprf must return one entry per entry it was given")
+        return self.build_database(hashed, offsets)
 
     def bucket_entries(self, offsets):
         """offsets of bucket_items -> per bundle index (lo, hi, start_bins): its entries are order[lo:hi] (contiguous, location by

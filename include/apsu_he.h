@@ -253,7 +253,10 @@ int apsu_he_debug_lookup_times(apsu_he_ctx *ctx, double *decode_ms, double *kern
  *    error text (and in *n_out), nothing built.  All or nothing: on any failure no handle is produced.
  *  - Refused (APSU_HE_INVALID_ARGUMENT): offsets that decrease, a location with more than 2^32 - 1 entries, max_items_per_bin < 2
  *    (cap would be 0).  Preconditions: PSUParams and batching.  Synchronous.
- * Out of scope: building onto a bundle index that already has BinBundles (the incremental call's), and bucketing on the device.
+ *  - The step in front of this call on the device as well: apsu_he_items_bucket_device leaves the entries in device memory in exactly
+ *    the order this call reads, so that with an OPRF that runs on the device (or none) a database goes from items to resident
+ *    BinBundles with nothing but offsets visiting the host.
+ * Out of scope: building onto a bundle index that already has BinBundles (the incremental call's).
  * apsu_he_debug_build_from_entries_times: device time of the context's last such call, summed over bundle indices and BinBundles: the
  * entries' copies, k_entries_scatter, the builds.
  * apsu_he_debug_set_scatter_blocks (measurements): workgroups per location of k_entries_scatter in the calls that follow; 0, the
@@ -670,6 +673,26 @@ int apsu_he_algebraize_items(apsu_he_ctx *ctx, const uint8_t *items, size_t coun
  *   order in which the reference emits entries.  Every listed item is one ENTRY of apsu_he_db_apply_entries: its (OPRF'd) item through
  *   apsu_he_algebraize_items, bundle index l / items_per_bundle, start bin (l % items_per_bundle) * felts_per_item.  The buckets of
  *   one bundle index are contiguous in order: offsets[b * items_per_bundle] .. offsets[(b + 1) * items_per_bundle].
+ * apsu_he_items_bucket_device (added after ABI 7, additive): the same offsets and order with the grouping on the device too, and the
+ *   entries gathered there.  apsu_he_items_bucket stays as it is: the second implementation of the same contract.
+ *   - offsets[table_size + 1]: host, always.  order (may be NULL): count * hash_func_count words of room, host or, with order_on_device,
+ *     device memory; *total = offsets[table_size] words are written, the words behind them are not.  entries (may be NULL):
+ *     [count * hash_func_count][16] of room, host or, with entries_on_device, device memory of any alignment; entries[k] =
+ *     items[order[k]] for k < *total, which is exactly what apsu_he_db_build_from_entries reads (after the caller's OPRF).
+ *   - The output is the sequence of the surviving pairs (location, item) in ascending (location, item) order, a pure function of
+ *     the input: the words are the same on every run.  Method: keys location << 32 | item of the surviving entries, compacted in
+ *     input order by a prefix sum; a stable least-significant-digit radix sort on the ceil(log2 table_size) bits of the location, in
+ *     digits of at most 8 bits (two passes for every shipped parameter file), each pass a histogram per tile, one exclusive scan over
+ *     (digit, tile) and a stable scatter whose ranks come from ballots within a wave and counts across waves -- never from the return
+ *     value of an atomic; offsets by bisection of the sorted keys; one 16-byte load and store per gathered entry (k_entries_gather).
+ *     No workgroup waits for another: every pass over the data is a launch of its own on the context's stream.
+ *   - count = 0: offsets all zero, *total = 0, nothing is launched.  count >= 2^32 - 1: APSU_HE_INVALID_ARGUMENT.  Synchronous.
+ * apsu_he_debug_bucket_locs (test hook, any context): the grouping alone on caller-given locs[count][hash_func_count] (host) for a
+ *   caller-given function count (1 .. 8) and table size (>= 1), offsets and order on the host.  tile_entries: the keys per tile of the
+ *   passes, a multiple of 256 from 256 to 2^20, or 0 for the engine's choice (8192); the result does not depend on it.  Anything else,
+ *   and a location >= table_size (the message names its index): APSU_HE_INVALID_ARGUMENT, nothing written.
+ * apsu_he_debug_bucket_times: device time of the context's last apsu_he_items_bucket_device: the locations, the grouping (keys, passes,
+ *   offsets and order), the gather.
  *
  * apsu_he_cuckoo_table (the querier's side).  The reference inserts sequentially with a random walk under its own generator; the
  * protocol needs only that every item sits at one of its own locations, so the table is built by the engine's own deterministic,
@@ -698,6 +721,15 @@ int apsu_he_algebraize_items(apsu_he_ctx *ctx, const uint8_t *items, size_t coun
 int apsu_he_item_locations(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint32_t *locs, int locs_on_device);
 int apsu_he_items_bucket(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint64_t *offsets, uint32_t *order,
                          uint64_t *total);
+int apsu_he_items_bucket_device(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device,
+                                uint64_t *offsets,                       /* host, table_size + 1 */
+                                uint32_t *order, int order_on_device,    /* count * hash_func_count words of room; may be NULL */
+                                uint8_t *entries, int entries_on_device, /* [count * hash_func_count][16] of room; may be NULL */
+                                uint64_t *total);
+int apsu_he_debug_bucket_locs(apsu_he_ctx *ctx, const uint32_t *locs, size_t count, uint32_t hash_func_count, uint32_t table_size,
+                              uint32_t tile_entries,                     /* 0: the engine's choice */
+                              uint64_t *offsets, uint32_t *order, uint64_t *total);   /* host arrays */
+int apsu_he_debug_bucket_times(apsu_he_ctx *ctx, double *locs_ms, double *sort_ms, double *gather_ms);
 int apsu_he_cuckoo_table(apsu_he_ctx *ctx, const uint8_t *items, size_t count, int items_on_device, uint64_t max_rounds, uint32_t *table_idx,
                          uint32_t *item_loc, uint64_t *rounds);
 int apsu_he_query_values(apsu_he_ctx *ctx, const uint8_t *table_items, int table_items_on_device, uint64_t *values, int values_on_device);
