@@ -419,7 +419,7 @@ int apsu_he_debug_run_step(apsu_he_ctx *c, const apsu_he_step_args *args)
 {
     return guarded([&] {
         REQUIRE(c && args, "null argument");
-        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT == (int)Engine::STEP_UNLIFT && (int)APSU_HE_STEP_INTT_TENSOR == (int)Engine::STEP_INTT_TENSOR && (int)APSU_HE_STEP_ROOTS_SPLIT == (int)Engine::STEP_ROOTS_SPLIT && (int)APSU_HE_STEP_SEED_EXPAND == (int)Engine::STEP_SEED_EXPAND && (int)APSU_HE_STEP_FLAG_MONOMIAL == (int)Engine::STEP_FLAG_MONOMIAL && (int)APSU_HE_STEP_MAC_INFO == (int)Engine::STEP_MAC_INFO && (int)APSU_HE_STEP_LIMB0_ROWS == (int)Engine::STEP_LIMB0_ROWS && (int)APSU_HE_STEP_ENTRIES_SCATTER + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
+        static_assert((int)APSU_HE_STEP_LIFT == (int)Engine::STEP_LIFT && (int)APSU_HE_STEP_UNLIFT == (int)Engine::STEP_UNLIFT && (int)APSU_HE_STEP_INTT_TENSOR == (int)Engine::STEP_INTT_TENSOR && (int)APSU_HE_STEP_ROOTS_SPLIT == (int)Engine::STEP_ROOTS_SPLIT && (int)APSU_HE_STEP_SEED_EXPAND == (int)Engine::STEP_SEED_EXPAND && (int)APSU_HE_STEP_FLAG_MONOMIAL == (int)Engine::STEP_FLAG_MONOMIAL && (int)APSU_HE_STEP_MAC_INFO == (int)Engine::STEP_MAC_INFO && (int)APSU_HE_STEP_LIMB0_ROWS == (int)Engine::STEP_LIMB0_ROWS && (int)APSU_HE_STEP_ENTRIES_SCATTER == (int)Engine::STEP_ENTRIES_SCATTER && (int)APSU_HE_STEP_BUCKET_COUNT == (int)Engine::STEP_BUCKET_COUNT && (int)APSU_HE_STEP_ENTRIES_GATHER == (int)Engine::STEP_ENTRIES_GATHER && (int)APSU_HE_STEP_ADD == (int)Engine::STEP_ADD && (int)APSU_HE_STEP_PACK_BLOCKS + 1 == (int)Engine::STEP_COUNT && (int)APSU_HE_STEP_KEY == (int)Engine::STEP_KEY &&
                       (int)APSU_HE_STEP_KARA == (int)Engine::STEP_KARA && (int)APSU_HE_STEP_PACKED == (int)Engine::STEP_PACKED && (int)APSU_HE_STEP_LIMB_SLOW == (int)Engine::STEP_LIMB_SLOW &&
                       (int)APSU_HE_STEP_COMPOSED == (int)Engine::STEP_COMPOSED && (int)APSU_HE_STEP_NORED == (int)Engine::STEP_NORED, "step ids of the header and the engine");
         Engine::StepArgs a{};

@@ -413,7 +413,13 @@ public:
                 // the multiply-accumulate family (engine_mac_steps.cpp): the launchers of launch_mac.h and launch_limb0_rows
                 STEP_MAC_INFO, STEP_MAC, STEP_TERM_PRODUCT, STEP_PACK_ROWS, STEP_UNPACK_ROWS, STEP_LIMB0_ROWS,
                 // behind the existing ids, which stay: k_entries_scatter (engine_db_steps.cpp)
-                STEP_ENTRIES_SCATTER, STEP_COUNT };
+                STEP_ENTRIES_SCATTER,
+                // the grouping by location (engine_bucket_steps.cpp): the per-kernel launchers of launch_bucket.h
+                STEP_BUCKET_COUNT, STEP_BUCKET_KEYS, STEP_BUCKET_SCAN, STEP_BUCKET_HIST, STEP_BUCKET_SCATTER, STEP_BUCKET_OFFSETS, STEP_BUCKET_ORDER,
+                STEP_ENTRIES_GATHER,
+                // the launchers no other family reaches (engine_misc_steps.cpp): launch_ew.h's and launch_db.h's small ones
+                STEP_ADD, STEP_CLEAR_BITS, STEP_COPY_JOBS, STEP_COPY_SOURCES, STEP_FILL_RANDOM, STEP_FILL_BLAKE2XB, STEP_SCATTER_SLOTS,
+                STEP_GATHER_SLOTS, STEP_ALGEBRAIZE, STEP_PACK_BLOCKS, STEP_COUNT };
     enum : uint32_t { STEP_RAW = 1, STEP_ACCUMULATE = 2, STEP_STORE = 4, STEP_KEY = 8, STEP_PLAN = 16, STEP_COMPOSED = 32, STEP_INVERSE = 64, STEP_NORED = 128,
                       STEP_KARA = 256, STEP_PACKED = 512, STEP_LIMB_SLOW = 1024 };
     struct StepArgs {
@@ -430,6 +436,8 @@ public:
     void debug_run_ntt_step(const StepArgs &a);                   // its transform half (the caller holds the lock)
     void debug_run_query_step(const StepArgs &a);                 // its querier-side half (the caller holds the lock)
     void debug_run_mac_step(const StepArgs &a);                   // its multiply-accumulate half (the caller holds the lock)
+    void debug_run_bucket_step(const StepArgs &a);                // its grouping half (the caller holds the lock)
+    void debug_run_misc_step(const StepArgs &a);                  // the remaining launchers (the caller holds the lock)
     // Staging of apsu_he_run_query_request (c_api.cpp) kept across calls: a device buffer and a page-locked host buffer of at least
     // `bytes` (grown on demand; hipHostMalloc / hipMalloc per query cost milliseconds).  The caller holds wire_mutex() for the whole query.
     std::mutex &wire_mutex() { return wire_mu_; }

@@ -33,6 +33,8 @@ void Engine::debug_run_step(const StepArgs &a)
 {
     Enter g(this);
     TIER1_SLOTS();
+    if (a.step >= STEP_ADD) { debug_run_misc_step(a); return; }               // the launchers no other family reaches
+    if (a.step >= STEP_BUCKET_COUNT) { debug_run_bucket_step(a); return; }    // the grouping by location: no chain level
     if (a.step == STEP_ENTRIES_SCATTER) { debug_run_db_step(a); return; }     // (a database step numbered behind the multiply-accumulate family)
     if (a.step >= STEP_MAC_INFO) { debug_run_mac_step(a); return; }           // the multiply-accumulate family and the packed rows
     if (a.step >= STEP_SEED_EXPAND) { debug_run_query_step(a); return; }      // the querier's side and the decryption

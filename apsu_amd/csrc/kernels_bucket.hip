@@ -7,6 +7,7 @@
 #include "kernel_launch.h"
 
 #include <stdexcept>
+#include <string>
 
 namespace apsu_he {
 
@@ -223,27 +224,82 @@ __global__ __launch_bounds__(BUCKET_T) void k_entries_gather(const uint4 *__rest
 // a grid of BUCKET_T lanes for `n` elements under a stride loop: one lane each up to 2^20 workgroups
 static dim3 stride_grid(u64 n) { return dim3((unsigned)std::min<u64>((n + BUCKET_T - 1) / BUCKET_T, (u64)1 << 20)); }
 
+// ---- one launcher per kernel (contracts: launch_bucket.h): launch_bucket_sort below and the steps of engine_bucket_steps.cpp run these
+static void key_contract(size_t count, u32 H, u32 tile, const char *who)
+{
+    if (!count || count >= 0xFFFFFFFFull || !H || H > BUCKET_MAX_FUNCS || !bucket_tile_ok(tile)) throw std::logic_error(std::string(who) + ": outside its contract");
+}
+static void pass_contract(u64 tiles, u32 tile, u32 shift, u32 width, const char *who)
+{
+    if (!tiles || tiles > 0x7FFFFFFFull || !bucket_tile_ok(tile) || !width || width > BUCKET_DIGIT_BITS || shift < 32 || shift + width > 64)
+        throw std::logic_error(std::string(who) + ": outside its contract");
+}
+
+void launch_bucket_count(const u32 *locs, size_t count, u32 H, u32 tile, u32 *tile_cnt, hipStream_t st)
+{
+    key_contract(count, H, tile, "launch_bucket_count");
+    hipLaunchKernelGGL(k_bucket_count, dim3((unsigned)bucket_tiles(count, tile)), dim3(BUCKET_T), 0, st, locs, count, H, tile, tile_cnt);
+    KERNEL_CHECK();
+}
+
+void launch_bucket_keys(const u32 *locs, size_t count, u32 H, u32 tile, const u64 *tile_base, u64 *keys, hipStream_t st)
+{
+    key_contract(count, H, tile, "launch_bucket_keys");
+    hipLaunchKernelGGL(k_bucket_keys, dim3((unsigned)bucket_tiles(count, tile)), dim3(BUCKET_T), 0, st, locs, count, H, tile, tile_base, keys);
+    KERNEL_CHECK();
+}
+
+void launch_bucket_scan(const u32 *in, u64 n, u64 *out, u64 *sum, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(BUCKET_SCAN_T), 0, st, in, n, out, sum);
+    KERNEL_CHECK();
+}
+
+void launch_bucket_hist(const u64 *keys, const u64 *total, u64 tiles, u32 tile, u32 shift, u32 width, u32 *hist, u32 *wave_cnt, hipStream_t st)
+{
+    pass_contract(tiles, tile, shift, width, "launch_bucket_hist");
+    hipLaunchKernelGGL(k_bucket_hist, dim3((unsigned)tiles), dim3(BUCKET_T), 0, st, keys, total, tile, shift, width, hist, wave_cnt);
+    KERNEL_CHECK();
+}
+
+void launch_bucket_scatter(const u64 *keys, const u64 *total, u64 tiles, u32 tile, u32 shift, u32 width, const u64 *scanned, const u32 *wave_cnt, u64 *out,
+                           hipStream_t st)
+{
+    pass_contract(tiles, tile, shift, width, "launch_bucket_scatter");
+    hipLaunchKernelGGL(k_bucket_scatter, dim3((unsigned)tiles), dim3(BUCKET_T), 0, st, keys, total, tile, shift, width, scanned, wave_cnt, out);
+    KERNEL_CHECK();
+}
+
+void launch_bucket_offsets(const u64 *keys, const u64 *total, u32 T, u64 *offsets, hipStream_t st)
+{
+    if (!T) throw std::logic_error("launch_bucket_offsets: outside its contract");
+    hipLaunchKernelGGL(k_bucket_offsets, stride_grid((u64)T + 1), dim3(BUCKET_T), 0, st, keys, total, T, offsets);
+    KERNEL_CHECK();
+}
+
+void launch_bucket_order(const u64 *keys, const u64 *total, u64 room, u32 *order, hipStream_t st)
+{
+    if (!room) return;
+    hipLaunchKernelGGL(k_bucket_order, stride_grid(room), dim3(BUCKET_T), 0, st, keys, total, order);
+    KERNEL_CHECK();
+}
+
 const u64 *launch_bucket_sort(const u32 *locs, size_t count, u32 H, u32 T, u32 tile, const BucketWork &w, u64 *offsets, u32 *order, hipStream_t st)
 {
     if (!count || count >= 0xFFFFFFFFull || !H || H > BUCKET_MAX_FUNCS || !T || !bucket_tile_ok(tile)) throw std::logic_error("launch_bucket_sort: outside its contract");
     const BucketSizes s = bucket_sizes(count, H, T, tile);
     const BucketDigits plan = bucket_digit_plan(T);
-    const dim3 wg(BUCKET_T), key_grid((unsigned)s.key_tiles), grid((unsigned)s.tiles);
-    hipLaunchKernelGGL(k_bucket_count, key_grid, wg, 0, st, locs, count, H, tile, w.tile_cnt);
-    hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(BUCKET_SCAN_T), 0, st, w.tile_cnt, s.key_tiles, w.tile_base, w.total);
-    hipLaunchKernelGGL(k_bucket_keys, key_grid, wg, 0, st, locs, count, H, tile, w.tile_base, w.keys[0]);
-    KERNEL_CHECK();
+    launch_bucket_count(locs, count, H, tile, w.tile_cnt, st);
+    launch_bucket_scan(w.tile_cnt, s.key_tiles, w.tile_base, w.total, st);
+    launch_bucket_keys(locs, count, H, tile, w.tile_base, w.keys[0], st);
     u32 at = 0;
     for (u32 p = 0; p < plan.passes; p++, at ^= 1) {
-        const u64 n = (u64)s.tiles << plan.width[p];
-        hipLaunchKernelGGL(k_bucket_hist, grid, wg, 0, st, w.keys[at], w.total, tile, plan.shift[p], plan.width[p], w.hist, w.wave_cnt);
-        hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(BUCKET_SCAN_T), 0, st, w.hist, n, w.scanned, (u64 *)nullptr);
-        hipLaunchKernelGGL(k_bucket_scatter, grid, wg, 0, st, w.keys[at], w.total, tile, plan.shift[p], plan.width[p], w.scanned, w.wave_cnt, w.keys[at ^ 1]);
-        KERNEL_CHECK();
+        launch_bucket_hist(w.keys[at], w.total, s.tiles, tile, plan.shift[p], plan.width[p], w.hist, w.wave_cnt, st);
+        launch_bucket_scan(w.hist, (u64)s.tiles << plan.width[p], w.scanned, nullptr, st);
+        launch_bucket_scatter(w.keys[at], w.total, s.tiles, tile, plan.shift[p], plan.width[p], w.scanned, w.wave_cnt, w.keys[at ^ 1], st);
     }
-    hipLaunchKernelGGL(k_bucket_offsets, stride_grid((u64)T + 1), wg, 0, st, w.keys[at], w.total, T, offsets);
-    hipLaunchKernelGGL(k_bucket_order, stride_grid(s.entries), wg, 0, st, w.keys[at], w.total, order);
-    KERNEL_CHECK();
+    launch_bucket_offsets(w.keys[at], w.total, T, offsets, st);
+    launch_bucket_order(w.keys[at], w.total, s.entries, order, st);
     return w.keys[at];
 }
 

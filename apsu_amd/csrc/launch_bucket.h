@@ -41,6 +41,26 @@ struct BucketWork {
 // -> the sorted keys (one of w.keys).
 const u64 *launch_bucket_sort(const u32 *locs, size_t count, u32 H, u32 T, u32 tile, const BucketWork &w, u64 *offsets, u32 *order, hipStream_t st);
 
+// The launches of launch_bucket_sort one by one, each with the grid and block it has there (the sort calls these; so do the steps of
+// engine_bucket_steps.cpp).  All pointers are device memory, nothing is waited for.  std::logic_error outside the contracts.
+// tile_cnt[t] = the surviving entries of items t tile .. of locs [count][H], t < bucket_tiles(count, tile).  contract: 1 <= count <
+// 2^32 - 1, 1 <= H <= BUCKET_MAX_FUNCS, bucket_tile_ok(tile) -- for the keys as well:
+void launch_bucket_count(const u32 *locs, size_t count, u32 H, u32 tile, u32 *tile_cnt, hipStream_t st);
+// keys[tile_base[t] ..] = the keys of tile t's surviving entries in (i, h) order; no other word of keys is written
+void launch_bucket_keys(const u32 *locs, size_t count, u32 H, u32 tile, const u64 *tile_base, u64 *keys, hipStream_t st);
+// out[k] = in[0] + .. + in[k - 1] for k < n, *sum = the sum of all n (sum may be null); one workgroup, n = 0 writes *sum alone
+void launch_bucket_scan(const u32 *in, u64 n, u64 *out, u64 *sum, hipStream_t st);
+// one pass over keys [tiles * tile] of which the first *total count: hist [1 << width][tiles], wave_cnt [tiles][BUCKET_WAVES][1 << width]
+// (every word written, zeros for a tile beyond *total); the scatter writes out[scanned[d][t] + ..] for the keys below *total alone.
+// contract: 1 <= tiles < 2^31, bucket_tile_ok(tile), 1 <= width <= BUCKET_DIGIT_BITS, 32 <= shift, shift + width <= 64, *total <= tiles * tile
+void launch_bucket_hist(const u64 *keys, const u64 *total, u64 tiles, u32 tile, u32 shift, u32 width, u32 *hist, u32 *wave_cnt, hipStream_t st);
+void launch_bucket_scatter(const u64 *keys, const u64 *total, u64 tiles, u32 tile, u32 shift, u32 width, const u64 *scanned, const u32 *wave_cnt, u64 *out,
+                           hipStream_t st);
+// offsets[l] = the first of the *total ascending keys that is >= l << 32, l <= T (T >= 1); order[k] = the low half of keys[k], k < *total
+// (`room` >= *total words of order sizes the grid; 0: nothing is launched)
+void launch_bucket_offsets(const u64 *keys, const u64 *total, u32 T, u64 *offsets, hipStream_t st);
+void launch_bucket_order(const u64 *keys, const u64 *total, u64 room, u32 *order, hipStream_t st);
+
 // entries[k] = items[order[k]] for k < *total: one 16-byte load and one 16-byte store per lane.  items and entries 16-byte aligned.
 void launch_entries_gather(const unsigned char *items, const u32 *order, const u64 *total, u64 room, unsigned char *entries, hipStream_t st);
 

@@ -177,7 +177,9 @@ STEPS = {name: i for i, name in enumerate((
     "polyn_with_roots", "bins_update", "bin_counts", "poly_degree", "bins_lookup", "bins_merge", "bins_rows", "bins_eval", "eval_compare", "roots",
     "unlift", "ntt_info", "ntt", "ntt_gather", "intt_tensor", "roots_split",
     "seed_expand", "decrypt_round", "plain_powers", "sample_small", "small_lift", "enc_finish", "rlk_finish", "flag_monomial",
-    "mac_info", "mac", "term_product", "pack_rows", "unpack_rows", "limb0_rows", "entries_scatter"))}
+    "mac_info", "mac", "term_product", "pack_rows", "unpack_rows", "limb0_rows", "entries_scatter",
+    "bucket_count", "bucket_keys", "bucket_scan", "bucket_hist", "bucket_scatter", "bucket_offsets", "bucket_order", "entries_gather",
+    "add", "clear_bits", "copy_jobs", "copy_sources", "fill_random", "fill_blake2xb", "scatter_slots", "gather_slots", "algebraize", "pack_blocks"))}
 STEP_RAW, STEP_ACCUMULATE, STEP_STORE, STEP_KEY, STEP_PLAN, STEP_COMPOSED, STEP_INVERSE, STEP_NORED = 1, 2, 4, 8, 16, 32, 64, 128
 STEP_KARA, STEP_PACKED, STEP_LIMB_SLOW = 256, 512, 1024      # the multiply-accumulate steps: three products, bit-packed plaintexts, grid order
 STEP_MAP_RAW = 1 << 30                 # in a map entry of an inverse transform step: that limb comes back RAW

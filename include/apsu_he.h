@@ -460,7 +460,61 @@ int apsu_he_debug_bins_times(apsu_he_ctx *ctx, double *decode_ms, double *roots_
  * TERM_PRODUCT a word of the powers (limbs below L) or a coefficient of a plaintext -- a bit-packed one decoded on the host with
  * packed_coeff -- that is not a canonical residue of its limb; for TERM_PRODUCT a limb beyond the level; for PACK_ROWS a word that is
  * not canonical; for PACK_ROWS and UNPACK_ROWS slots * L above 65535, the y extent of their grid (the engine's own callers refuse the
- * same: pack_rows_grid_check, mac_plan.h); sizes that do not match. */
+ * same: pack_rows_grid_check, mac_plan.h); sizes that do not match.
+ *
+ * The grouping by location, from BUCKET_COUNT on (same entry, no new symbol; chain_idx is not used): the kernels behind
+ * apsu_he_items_bucket_device one at a time, each through the launcher that the whole sort calls for it (launch_bucket.h), so grid and
+ * block are the sort's.  A 32-bit array (locs, tile_cnt, hist, wave_cnt, order) travels one value per 64-bit word.  Every out[] is in/out:
+ * a word the kernel does not write comes back as it went.  tile = keys (or items) per workgroup, a multiple of 256 in [256, 2^20];
+ * waves = 4; D = 1 << width.
+ *   BUCKET_COUNT    polys = H, terms = tile; in[0] locs [count][H] -> out[0] tile_cnt [key_tiles], key_tiles = ceil(count / tile): the entries
+ *                   (i, h) of the tile's items with no g < h where locs[i][g] == locs[i][h]
+ *   BUCKET_KEYS     the same geometry; in[1] the CALLER's tile_base [key_tiles] -> out[0] keys [room] (room from its size): tile t's keys
+ *                   loc << 32 | i in (i, h) order from tile_base[t] on, no other word
+ *   BUCKET_SCAN     in[0] [n] 32-bit values (null: n = 0) -> out[0] [n + 1]: out[k] = in[0] + .. + in[k - 1] for k < n, the last word a
+ *                   guard.  STORE: out[1], one word, the sum of all; without the flag the launcher gets a null sum pointer, as in the
+ *                   passes, and out[1] must be null
+ *   BUCKET_HIST     terms = tile, e0 = shift, n_ext = width, batch = the tiles of the grid; in[0] keys [batch * tile], any 64-bit words;
+ *                   in[1] total, one word -> out[0] hist [D][batch]: the keys of tile t below total with digit d = bits [shift, shift +
+ *                   width) of the key; out[1] wave_cnt [batch][4][D]: the same over wave w's run, keys [w tile / 4, (w + 1) tile / 4) of the
+ *                   tile cut at the tile's keys
+ *   BUCKET_SCATTER  the same geometry; in[2] the CALLER's scanned [D][batch], in[3] the CALLER's wave_cnt [batch][4][D] -> out[0] [room]:
+ *                   key -> place scanned[d][t] + wave_cnt[t][ww][d] over ww < w + its rank among the equal digits earlier in its
+ *                   wave's run; no other word
+ *   BUCKET_OFFSETS  terms = T; in[0] keys, ascending below total (null with a total of 0), in[1] total -> out[0] [T + 2]: offsets[l] =
+ *                   the keys below total that are below l << 32, l <= T; the last word a guard
+ *   BUCKET_ORDER    in[0], in[1] as for BUCKET_OFFSETS -> out[0] [room]: the low halves of the keys below total
+ *   ENTRIES_GATHER  batch = room; in[0] items [count][2], in[1] order [room], in[2] total -> out[0] [room][2]: entry k = item order[k], k < total
+ * Refused like the others, nothing launched: a tile size outside the rule; H outside 1 .. 8; count 0; T = 0; a width outside 1 .. 8; a
+ * shift below 32 or shift + width above 64; a total above the keys given (or above the room); a 32-bit value that does not fit; for
+ * BUCKET_KEYS a tile whose keys would reach beyond the room, for BUCKET_SCATTER a place at or beyond the room -- both worked out on the
+ * host from the arrays given, so no step stores out of bounds; for BUCKET_OFFSETS keys below total that do not ascend; for
+ * ENTRIES_GATHER an order word below total that names no item; sizes that do not match.
+ *
+ * The remaining launchers, from ADD on (same entry, no new symbol): the small kernels of the query path and the database-build path
+ * that no step above reaches.  Every out[] is in/out; a guard is a word behind (or in front of) what the kernel owns.
+ *   ADD             chain_idx = the level; in[0] x [batch][polys][L][n] added into out[0] acc [batch][polys][L][n] per limb (batch 1 .. 64,
+ *                   polys 1 .. 8), both canonical
+ *   CLEAR_BITS      e0 = bits (0 .. 63); out[0] [words + 1]: the low `bits` bits of the first `words` words are cleared, the last a guard
+ *   COPY_JOBS       terms = words per job (even, >= 2), batch = jobs (1 .. 64); in[0] sources [jobs][words] -> out[0] [jobs][words + 2]:
+ *                   job j's words, then two guard words
+ *   COPY_SOURCES    chain_idx = the level, L = chain_idx + 1, words = 2 L n; batch = jobs; in[0] sources [jobs][2][L][n], or null: the
+ *                   check in place, out[0] is source and destination; in[1] = the report word before the launch, seq (32 bits each)
+ *                   -> out[0] [jobs][2][L][n]; out[1], one word: the report word after -- max(before, seq) when some word of some job
+ *                   is at or above the prime of its limb, else as before
+ *   FILL_RANDOM     in[0] = seed, bound (>= 1) -> out[0] [words + 1]: word i = splitmix64(seed + i) % bound (64-bit wrap), the last a guard
+ *   FILL_BLAKE2XB   in[0] seed [8], in[1] = first, bound (>= 1) -> out[0] [1 + words + 1]: word 1 + i = the (first + i)-th 32-bit output of
+ *                   SEAL's Blake2xb generator under the seed, % bound; a guard on both sides
+ *   SCATTER_SLOTS   in[0] [batch][n], in[1] a permutation [n] or null: the context's slot map -> out[0] [batch][n]: out[b][map[i]] = in[b][i]
+ *   GATHER_SLOTS    the same arguments: out[b][i] = in[b][map[i]]
+ *   ALGEBRAIZE      polys = felts, terms = bits per felt, e0 = item_bit_count; in[0] items [count][2] (16 bytes, little-endian) -> out[0]
+ *                   [count * felts + 1]: felt j = bits [j bpf, j bpf + bpf) of the item's first item_bit_count bits; the last a guard
+ *   PACK_BLOCKS     polys = felts, terms = len (2 .. 63), e0 = items (items * felts <= n); in[0] values [batch][n] -> out[0] [batch][items][2]
+ *                   + 1: (lower, higher) of the reference's vec_to_oc_block, the last word a guard
+ * Refused like the others, nothing launched: a chain_idx that is no data level; a word of ADD's operands that is not canonical; bits
+ * outside 0 .. 63; an odd word count for COPY_JOBS; a bound of 0; a map word >= n or a map that is no permutation, a null map in a
+ * context without batching; felts outside 1 .. 64, bits per felt outside 1 .. 64, (felts - 1) * bits per felt >= 128, item_bit_count
+ * outside 1 .. 128; len outside 2 .. 63; items * felts above n; batch outside 1 .. 64; sizes that do not match. */
 enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEHZ_EXT, APSU_HE_STEP_TENSOR, APSU_HE_STEP_TENSOR_CONV,
        APSU_HE_STEP_TENSOR_SUM, APSU_HE_STEP_BEHZ_FINISH, APSU_HE_STEP_BEHZ_FINISH_SUM, APSU_HE_STEP_KS_INNER, APSU_HE_STEP_KS_MODDOWN,
        APSU_HE_STEP_MODSWITCH, APSU_HE_STEP_MODSWITCH_JOBS, APSU_HE_STEP_I0_FINISH, APSU_HE_STEP_EVAL_EPILOGUE, APSU_HE_STEP_ADD_MANY,
@@ -473,7 +527,11 @@ enum { APSU_HE_STEP_LEVEL_INFO = 0, APSU_HE_STEP_BEHZ_EXT, APSU_HE_STEP_DROP_BEH
        APSU_HE_STEP_ENC_FINISH, APSU_HE_STEP_RLK_FINISH, APSU_HE_STEP_FLAG_MONOMIAL,
        APSU_HE_STEP_MAC_INFO, APSU_HE_STEP_MAC, APSU_HE_STEP_TERM_PRODUCT, APSU_HE_STEP_PACK_ROWS, APSU_HE_STEP_UNPACK_ROWS,
        APSU_HE_STEP_LIMB0_ROWS,
-       APSU_HE_STEP_ENTRIES_SCATTER };
+       APSU_HE_STEP_ENTRIES_SCATTER,
+       APSU_HE_STEP_BUCKET_COUNT, APSU_HE_STEP_BUCKET_KEYS, APSU_HE_STEP_BUCKET_SCAN, APSU_HE_STEP_BUCKET_HIST, APSU_HE_STEP_BUCKET_SCATTER,
+       APSU_HE_STEP_BUCKET_OFFSETS, APSU_HE_STEP_BUCKET_ORDER, APSU_HE_STEP_ENTRIES_GATHER,
+       APSU_HE_STEP_ADD, APSU_HE_STEP_CLEAR_BITS, APSU_HE_STEP_COPY_JOBS, APSU_HE_STEP_COPY_SOURCES, APSU_HE_STEP_FILL_RANDOM,
+       APSU_HE_STEP_FILL_BLAKE2XB, APSU_HE_STEP_SCATTER_SLOTS, APSU_HE_STEP_GATHER_SLOTS, APSU_HE_STEP_ALGEBRAIZE, APSU_HE_STEP_PACK_BLOCKS };
 enum { APSU_HE_STEP_RAW = 1, APSU_HE_STEP_ACCUMULATE = 2, APSU_HE_STEP_STORE = 4, APSU_HE_STEP_KEY = 8, APSU_HE_STEP_PLAN = 16,
        APSU_HE_STEP_COMPOSED = 32, APSU_HE_STEP_INVERSE = 64, APSU_HE_STEP_NORED = 128, APSU_HE_STEP_KARA = 256, APSU_HE_STEP_PACKED = 512,
        APSU_HE_STEP_LIMB_SLOW = 1024 };

@@ -78,6 +78,18 @@ def test_two_runs_give_the_same_words(toy):
     assert (first[0] == want_off).all() and (first[1][:first[2]] == want_order).all() and (first[1][first[2]:] == POISON).all()
 
 
+def test_whole_call_crosses_the_scans_step(toy):
+    """3000 items under 3 functions in 256 slots at tile 256: 36 tiles x 256 digits = 9216 words for the pass's scan, which takes 8192 a
+    step -- the carry and the second step's tail inside the whole call"""
+    locs = np.random.default_rng(3000).integers(0, 256, (3000, 3)).astype(np.uint32)
+    assert -(-locs.size // 256) * 256 == 9216 > 8192 and bucket_cases.digit_plan(256) == (8, [8])
+    want_off, want_order = bucket_cases.reference(locs, 256)
+    assert 8192 < len(want_order) <= 9000                                          # collisions inside an item drop a few entries
+    offsets, order, total = run(toy, locs, 256, 256)
+    assert total == len(want_order) and (offsets == want_off).all()
+    assert (order[:total] == want_order).all() and (order[total:] == POISON).all()
+
+
 def test_hook_refusals_write_nothing(toy):
     locs = np.array([[0, 1, 2], [2, 3, 1]], dtype=np.uint32)
     with pytest.raises(ValueError, match="location 4 is outside the table"):       # a location equal to T

@@ -284,6 +284,27 @@ def test_ntt_workgroup_emulation_61_bit_primes(emu, n):
         assert int(prod[k]) == want
 
 
+def ordering_violations(pending, plan, evaluated):
+    """The ordering rule of the scheduler test below on one state.  pending: what may still be queued on the buffer, "writer@main",
+    "writer@side", "reader@main"; plan: emu_plan_walk's bits; evaluated: whether an evaluation really read the buffer since its last
+    walk, so that a `last_use` mark lies behind every writer.  -> the (writing stream, pending operation) pairs that nothing orders"""
+    ONE, SPLIT, PIPE = 0, 1, 2
+    walk, main_hr, side_lu, side_main = plan & 3, bool(plan & 4), bool(plan & 8), bool(plan & 16)
+    out = []
+    for x in {ONE: ["main"], SPLIT: ["main", "side"], PIPE: ["side"]}[walk]:
+        for a in sorted(pending):
+            kind, y = a.split("@")
+            if x == y:
+                continue                                          # stream order
+            if x == "main":                                       # the second stream's writers: only high_ready orders the main stream behind them
+                covered = main_hr
+            else:                                                 # main-stream writers / readers in front of the second stream
+                covered = side_main or (side_lu and evaluated)    # last_use lies behind the evaluation, which lies behind every writer
+            if not covered:
+                out.append((x, a))
+    return out
+
+
 def test_scheduler_ordering_rules_hold_in_every_state(emu):
     """round 6: the decision block of Engine::compute_powers is a pure function (apsu_amd/csrc/sched_policy.h, plan_walk) and is held, in
     EVERY state, to the invariant the project's one real race violated (a pooled buffer kept an older evaluation's `last_use` mark):
@@ -323,17 +344,7 @@ def test_scheduler_ordering_rules_hold_in_every_state(emu):
                     pending.add("writer@main")
                 if prev in (SPLIT, PIPE):
                     pending.add("writer@side")
-        writers = {ONE: ["main"], SPLIT: ["main", "side"], PIPE: ["side"]}[walk]
-        for x in writers:
-            for a in pending:
-                kind, y = a.split("@")
-                if x == y:
-                    continue                                      # stream order
-                if x == "main":                                   # the second stream's writers: only high_ready orders the main stream behind them
-                    assert main_hr, state
-                else:                                             # main-stream writers / readers in front of the second stream
-                    covered = side_main or (side_lu and evaluated)   # last_use lies behind the evaluation, which lies behind every writer
-                    assert covered, state
+        assert not ordering_violations(pending, r, evaluated), state
         # the walks themselves
         if walk != ONE:
             assert split_ok and not prof_on and split_mode != 0, state
@@ -352,7 +363,9 @@ def test_scheduler_ordering_rules_hold_in_every_state(emu):
     # main stream's pending writers
     r = emu.emu_plan_walk(1 | 1 << 1 | 1 << 2 | 1 << 3 | 1 << 4 | 1 << 8 | 1 << 9, -1)
     assert (r & 3) == SPLIT and not (r & 16), r                   # second stream does not wait for the main stream ...
-    assert not ((r & 16) or ((r & 8) and False))                  # ... and the mark it waits for is not behind those writers: a violation
+    # ... and the mark it waits for is not behind those writers (no evaluation ran, whatever the engine believed): a violation
+    assert ordering_violations({"writer@main"}, r, evaluated=False) == [("side", "writer@main")]
+    assert ordering_violations({"writer@main"}, r | 16, evaluated=False) == []     # (waiting for the main stream would have covered it)
     # (Engine::compute_powers therefore consumes last_use_set on every walk and only eval_bundles sets it: consumes_last_use above)
 
 
